@@ -117,6 +117,26 @@ def cpu_baseline(budget_s=25.0, max_threads=64):
 
 
 SPLIT_LINE = os.environ.get('LANEMAP_WINO_SPLIT', '0') != '0'        # this process IS a second-line run
+DUMP_BYTES = 64 << 20             # --dump-outputs: size budget of all files together
+
+
+def dump_outputs(out_dir, results):
+    """--dump-outputs: what the timed path handed its caller for the last timed step, per tile in tile order ((lanes, kept endpoints) as
+    TilePipeline returns them), as float64 .npy files: lanes.npy [T, 72, 144, 2]; endpoints.npy [N, 3] = (position in lanes.npy, row,
+    column) of every kept endpoint; tiles.npy [T] = the step's tile index of each entry.  Over the budget, a fixed seeded sample of the
+    tiles is written.  -> the names written"""
+    tile_bytes = 72 * 144 * 2 * 8 + 500 * 3 * 8        # lanes + room for the endpoints of one tile
+    keep = np.arange(len(results))
+    if len(keep) * tile_bytes > DUMP_BYTES:
+        keep = np.sort(np.random.RandomState(2021).choice(len(keep), DUMP_BYTES // tile_bytes, replace=False))
+    lanes = np.stack([np.asarray(results[t][0], dtype=np.float64) for t in keep])
+    endp = [np.asarray(results[t][1], dtype=np.float64).reshape(-1, 2) for t in keep]
+    endp = np.concatenate([np.concatenate([np.full((len(e), 1), float(i)), e], axis=1) for i, e in enumerate(endp)])
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {'lanes': lanes, 'endpoints': endp, 'tiles': keep.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return sorted(arrays)
 
 
 def second_line(args):
@@ -283,10 +303,15 @@ def main():
     ap.add_argument('--graphs', action='store_true', help='replay the device part of every sub-batch as one HIP graph (TilePipeline use_graph); the default since '
                     'round 5 for the workloads that can be captured (fused, tiles, rowref): +1.4 %% on the headline in four interleaved 100-step runs, '
                     'profiles/r5_graphs_ab.txt')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the timed path computed in its last step to DIR/<name>.npy (float64): the lanes and '
+                         'kept endpoints of every tile (N > 1: of every rank, from the last all-gather); rank 0 writes')
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit('--gpus must be >= 1')
+    if args.steps < 1:
+        raise SystemExit('--steps must be >= 1')
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         ndev = torch.cuda.device_count()        # (counting devices does not initialise the GPU)
         if ndev < args.gpus and 'LANEMAP_BENCH_DEVICE' not in os.environ:
@@ -578,6 +603,10 @@ def main():
             raise SystemExit(f'gather check FAILED on rank {rank}: the all-gathered block does not hold world x batch valid tiles equal to the per-rank results')
         gather_check = (f'last all-gather: {world * batch} valid tiles in one [{world * batch}, {shard.TILE_BYTES}] byte block; on every rank its own slice '
                         f'is bitwise the block it sent and unpacks to the lanes / endpoints of its last batch')
+    # ---- what the timed path delivered in its last step (N > 1: every rank's tiles, as the last all-gather delivered them), before any
+    # checker leg below runs the pipelines again
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, shard.unpack_gathered(inflight[-1][1]) if world > 1 else last)
 
     # ---- fused workload: the rasteriser's tiles of the last timed step against the scalar C oracle (oracle/raster_ref.c) - the first
     # and the last tile of the 16-tile launch (a wrong record slot at a high chunk index, or in the last BatchArgs entry, shows here).

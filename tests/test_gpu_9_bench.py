@@ -108,42 +108,44 @@ def test_bench_two_ranks_code_path(dev):
     assert d['config']['raster_check'].startswith('tiles 0 and 15 of the last timed 16 x 4194304-point launch equal oracle/raster_ref.c')
 
 
-def test_bench_eight_ranks_on_one_gpu(dev):
-    """Readiness of the 8-GPU line (no 8-GPU node is available to the builder): `bench.py --gpus 8 --workload tiles` with EIGHT ranks
-    sharing this box's GPU over gloo - the code path the driver runs one rank per GPU over RCCL.  Every rank takes its slice of the host
-    cores by itself (usable cores / 8, HIP graphs on at <= 4 cores per rank), the slices are disjoint, ONE all-gather per batch delivers
-    8 x 8 valid tiles to every rank, rank 0 prints the only line (with the CPU baseline measured while the other ranks are parked)."""
+def test_bench_four_ranks_on_one_gpu(dev):
+    """Readiness of the multi-GPU lines beyond two ranks (no multi-GPU node is available to the builder): `bench.py --gpus 4 --workload
+    tiles` with FOUR ranks sharing this box's GPU over gloo - the code path the driver runs one rank per GPU over RCCL.  (Four, not the
+    node's eight: with this test process, eight ranks would put nine processes on one shared GPU.)  Every rank takes its slice of the
+    host cores by itself (usable cores / 4, HIP graphs on), the slices are disjoint, ONE all-gather per batch delivers 4 x 8 valid tiles
+    to every rank, rank 0 prints the only line (with the CPU baseline measured while the other ranks are parked)."""
     import json
     import socket
     import subprocess
     import sys
     import bench as bench_mod
+    n = 4
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     s = socket.socket()
     s.bind(('127.0.0.1', 0))
     port = s.getsockname()[1]
     s.close()
     env = dict(os.environ, LANEMAP_BENCH_DEVICE='0', LANEMAP_BENCH_BACKEND='gloo')
-    r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '8', '--master-addr', '127.0.0.1',
-                        '--master-port', str(port), os.path.join(root, 'bench.py'), '--gpus', '8', '--workload', 'tiles', '--steps', '2', '--warmup', '1',
-                        '--cpu-budget-s', '4'], capture_output=True, text=True, timeout=1500, cwd=root, env=env)
+    r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(n), '--master-addr', '127.0.0.1',
+                        '--master-port', str(port), os.path.join(root, 'bench.py'), '--gpus', str(n), '--workload', 'tiles', '--steps', '2',
+                        '--warmup', '1', '--cpu-budget-s', '4'], capture_output=True, text=True, timeout=1500, cwd=root, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     lines = [l for l in r.stdout.strip().split('\n') if l.startswith('{')]
     assert len(lines) == 1                                           # rank 0 only
     d = json.loads(lines[0])
-    assert d['n_gpus'] == 8 and d['steps'] == 2 and d['scaling'] == 'weak' and d['value'] > 10
-    assert d['config']['gather_check'].startswith('last all-gather: 64 valid tiles in one [64, 169992] byte block'), d['config']['gather_check']
+    assert d['n_gpus'] == n and d['steps'] == 2 and d['scaling'] == 'weak' and d['value'] > 10
+    assert d['config']['gather_check'].startswith(f'last all-gather: {n * 8} valid tiles in one [{n * 8}, 169992] byte block'), d['config']['gather_check']
     cores = bench_mod.usable_cores()
-    if cores // 8 <= 8:              # the ranks split the node's cores: on the pool's 16-core boxes 2 per rank, graphs on
+    if cores // n <= 8:              # the ranks split the node's cores
         assert d['config']['host_cores_auto'] is True and d['config']['host_cores_pinned'] is True
-        assert d['config']['host_cores_per_rank'] == max(1, cores // 8)
+        assert d['config']['host_cores_per_rank'] == max(1, cores // n)
         assert d['config']['hip_graphs'] is True                     # (the default of the capturable workloads since round 5)
         allowed = sorted(os.sched_getaffinity(0))
-        slices = [bench_mod.host_budget(8, 8, lr, cores, allowed, None, False, 'tiles')['cores'] for lr in range(8)]
-        if 8 * (cores // 8) <= len(allowed):
+        slices = [bench_mod.host_budget(n, n, lr, cores, allowed, None, False, 'tiles')['cores'] for lr in range(n)]
+        if n * (cores // n) <= len(allowed):
             flat = [c for sl in slices for c in sl]
-            assert len(flat) == len(set(flat)) == 8 * max(1, cores // 8)          # disjoint
-    assert d['cpu_baseline'] is not None and d['cpu_baseline']['value'] > 0 and '7 other rank(s)' in d['cpu_baseline']['measured_with']
+            assert len(flat) == len(set(flat)) == n * max(1, cores // n)          # disjoint
+    assert d['cpu_baseline'] is not None and d['cpu_baseline']['value'] > 0 and f'{n - 1} other rank(s)' in d['cpu_baseline']['measured_with']
 
 
 @pytest.mark.parametrize('workload', ['tiles', 'rowref', 'lidar'])
@@ -175,6 +177,28 @@ def test_bench_hip_graphs_four_streams(dev):
     assert 'bitwise equal' in d['config']['stream_check'] and 0.0 < d['roofline']['frac'] <= 1.0
 
 
+def test_bench_dump_outputs(dev, net, tmp_path):
+    """`bench.py --dump-outputs DIR`: the lanes and kept endpoints of the last timed step (tiles workload: tile seeds 2021..2028, weight
+    seed 2021 - the `net` fixture) are, bit for bit, what TilePipeline returns for the same tiles in this process."""
+    import json
+    import subprocess
+    import sys
+    from lanemapping_amd.pipeline import TilePipeline
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / 'out'
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--workload', 'tiles', '--steps', '3', '--warmup', '1', '--no-cpu-baseline',
+                        '--dump-outputs', str(out)], capture_output=True, text=True, timeout=900, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.strip().split('\n') if l.startswith('{')][-1])
+    assert d['steps'] == 3 and abs(d['ms_per_step'] - 1e3 * 8 / d['value']) < 1e-6 * d['ms_per_step']
+    got = {n: np.load(out / f'{n}.npy') for n in ('lanes', 'endpoints', 'tiles')}
+    assert sorted(os.listdir(out)) == ['endpoints.npy', 'lanes.npy', 'tiles.npy'] and all(a.dtype == np.float64 for a in got.values())
+    want = TilePipeline(net).run_batch(torch.from_numpy(synth.bev_batch([2021 + i for i in range(8)], 1152)).to(dev))
+    assert np.array_equal(got['tiles'], np.arange(8)) and np.array_equal(got['lanes'], np.stack([l for l, _ in want]))
+    want_e = np.concatenate([np.concatenate([np.full((len(e), 1), t), np.asarray(e).reshape(-1, 2)], axis=1) for t, (_, e) in enumerate(want)])
+    assert np.array_equal(got['endpoints'], want_e)
+
+
 @pytest.mark.parametrize('points', ['host', 'las'])
 def test_bench_input_inclusive_variants(dev, points):
     """`bench.py --points host` / `--points las`: the headline step with its 16 x 4,194,304 points arriving from PINNED HOST memory every
@@ -198,27 +222,39 @@ def test_bench_input_inclusive_variants(dev, points):
     assert d['config']['stream_check'].startswith('lanes and endpoints')
 
 
-# ------------------------------------------------------------------------------------------------ waiting for a multi-GPU box
-@pytest.mark.skipif(torch.cuda.device_count() < 2, reason='needs two distinct MI355X (the builder\'s and the round-end GPU boxes have one): '
-                    'the first multi-GPU GPUTEST turns this into scaling evidence')
+# ------------------------------------------------------------------------------------------------ multi-GPU lines over RCCL
+# Two distinct devices are needed for the RCCL lines themselves; on a one-GPU box the same tests run the one-rank half and check that a
+# two-GPU request is refused before any rank starts (no two-GPU number or file set is ever produced on one device).
 def test_bench_two_real_gpus_over_rccl(dev):
-    """UNMEASURED ON HARDWARE until a box with >= 2 GPUs runs it: `python bench.py --gpus 2` with the default `nccl` (= RCCL) backend on
-    two DISTINCT devices.  Asserts the collective really was RCCL over two ranks, the gathered content was verified on every rank, and
-    the whole-job rate is >= 1.8 x a 1-rank run of the same command in the same test (north_star: >= 0.9 linear)."""
+    """`python bench.py --gpus 2` with the default `nccl` (= RCCL) backend and no test hooks.  Always: the 1-rank run of the same command
+    prints its line (one rank, no process group, device 0).  With >= 2 GPUs (UNMEASURED ON HARDWARE until such a box runs it): two
+    DISTINCT devices, the collective really was RCCL over two ranks, the gathered content was verified on every rank, and the whole-job
+    rate is >= 1.8 x the 1-rank run (north_star: >= 0.9 linear).  With one GPU: `--gpus 2` exits non-zero without a result line."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'LANEMAP_BENCH_DEVICE', 'LANEMAP_BENCH_BACKEND')}
 
+    def launch(n):
+        return subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', str(n), '--steps', '20', '--warmup', '3', '--no-cpu-baseline'],
+                              capture_output=True, text=True, timeout=1500, cwd=root, env=env)
+
     def run(n):
-        r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', str(n), '--steps', '20', '--warmup', '3', '--no-cpu-baseline'],
-                           capture_output=True, text=True, timeout=1500, cwd=root, env=env)
+        r = launch(n)
         assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
         lines = [l for l in r.stdout.strip().split('\n') if l.startswith('{')]
         assert len(lines) == 1
         return json.loads(lines[0])
-    one, two = run(1), run(2)
+    one = run(1)
+    assert one['n_gpus'] == 1 and one['steps'] == 20 and one['value'] > 10
+    assert one['config']['dist_ranks'] == 1 and one['config']['dist_backend'] is None and one['config']['rank_devices'] == [0]
+    if torch.cuda.device_count() < 2:
+        r = launch(2)
+        assert r.returncode != 0 and not any(l.startswith('{') for l in r.stdout.split('\n')), (r.stdout + r.stderr)[-3000:]
+        assert '--gpus 2 but only 1 GPU(s) are visible' in r.stderr, r.stderr[-3000:]
+        return
+    two = run(2)
     assert two['n_gpus'] == 2 and two['config']['dist_ranks'] == 2 and two['config']['dist_backend'] == 'nccl' and two['config']['rccl_ranks'] == 2
     assert two['config']['gather_check'].startswith('last all-gather: 32 valid tiles in one [32, 169992] byte block'), two['config']['gather_check']
     assert two['config']['rank_devices'] == [0, 1], two['config']['rank_devices']
@@ -226,10 +262,10 @@ def test_bench_two_real_gpus_over_rccl(dev):
     assert two['value'] >= 1.8 * one['value'], (one['value'], two['value'])
 
 
-@pytest.mark.skipif(torch.cuda.device_count() < 2, reason='needs two distinct MI355X')
 def test_runner_two_real_gpus_over_rccl(dev, synth_sd, tmp_path):
-    """UNMEASURED ON HARDWARE until a multi-GPU box runs it: load_config_and_runner(path, '0,1') without the one-GPU test hook - one
-    fresh process per GPU, RCCL all-gather - writes the files of the one-id run byte for byte."""
+    """load_config_and_runner(path, '0,1') without the one-GPU test hook.  Always: the one-id run writes one file per tile.  With >= 2
+    GPUs (UNMEASURED ON HARDWARE until a multi-GPU box runs it): one fresh process per GPU, RCCL all-gather, the files of the one-id run
+    byte for byte.  With one GPU: the two-id runner is refused when it is built, before any rank process starts."""
     from PIL import Image
     from lanemapping_amd.runner import load_config_and_runner
     tiles = tmp_path / 'tiles'
@@ -241,6 +277,11 @@ def test_runner_two_real_gpus_over_rccl(dev, synth_sd, tmp_path):
     for ids in ('0', '0,1'):
         path = tmp_path / f'configs_{len(ids)}.py'
         path.write_text(src.replace("log_dir = './logs'", f"log_dir = {str(tmp_path / ('logs' + str(len(ids))))!r}"))
+        if ids == '0,1' and torch.cuda.device_count() < 2:
+            with pytest.raises(RuntimeError, match=r"gpus='0,1' names 2 GPUs \(device indices \[0, 1\]\) but this process sees 1"):
+                load_config_and_runner(str(path), ids)
+            assert len(os.listdir(outs['0'][1])) == 7
+            return
         cfg, runner = load_config_and_runner(str(path), ids)
         runner.net.load_state_dict(synth_sd)
         outs[ids] = (runner.infer_lane_coordinate_endpoint_semantics(tiles=str(tiles), batch_size=2, write_lane_vertex=True), cfg.work_dirs)

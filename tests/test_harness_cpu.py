@@ -1,13 +1,14 @@
 """CPU: the entry-point contract of the harness and the evaluation loop's bookkeeping (f3).
 
-  * the reference's four unmodified configs/Proj_*.py load through the boundary and give the repo configs' state-dict layout
-    (skipped where /root/reference does not exist, i.e. on the GPU box);
+  * the repo configs give the state-dict layout and entry-point keys that the reference's four unmodified configs/Proj_*.py give
+    through the boundary (golden G20);
   * the dataset listing and the evaluation ground truth equal golden G18 (the imported reference's LaserLaneProposal on a synthetic
     <data_root> that cases.write_dataset re-creates here);
   * the test loop's counter sums and P / R / F1 formulas equal golden G19;
   * Runner's entry points carry the reference's signatures, refuse unknown keywords and refuse an empty tile list.
 """
 import inspect
+import json
 import os
 
 import numpy as np
@@ -17,22 +18,25 @@ import cases
 from lanemapping_amd import datasets, metric_utils
 from lanemapping_amd.boundary import load_config, build_net_from_config
 
-REF = '/root/reference'
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 CONFIGS = ('Proj_polyline_fpn_vit_vertex_2', 'Proj_FPN_Seg', 'Proj28_GFC-T3_RowRef_82_73_laser', 'Proj_polyline_lidarconv_vit_vertex_2')
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='the reference tree only exists in the build container')
 @pytest.mark.parametrize('name', CONFIGS)
 def test_unmodified_reference_configs_build_the_same_layout(name):
-    ref_net = build_net_from_config(f'{REF}/configs/{name}.py', device='cpu')
+    """Golden G20 (make_golden.py g20) holds what the reference's unmodified configs build through the boundary: the state-dict
+    layout (keys in order, shapes) and the config keys the entry points read.  The repo's trimmed configs must give the same."""
+    with open(os.path.join(GOLDEN, 'g20_config_layout.json')) as f:
+        ref = json.load(f)[name]
     own_net = build_net_from_config(name, device='cpu')
-    a = {k: tuple(v.shape) for k, v in ref_net.state_dict().items()}
-    b = {k: tuple(v.shape) for k, v in own_net.state_dict().items()}
-    assert a == b and list(a) == list(b) and len(a) > 300
-    rc, oc = load_config(f'{REF}/configs/{name}.py'), load_config(name)
+    a = [(k, tuple(s)) for k, s in ref['state_dict']]
+    b = [(k, tuple(v.shape)) for k, v in own_net.state_dict().items()]
+    assert a == b and len(a) > 300
+    oc = load_config(name)
     # the keys the entry points read (runner.py:57-66, :690-697, :755) agree between the trimmed configs and the published ones
-    assert dict(rc.dataset.test) == dict(oc.dataset.test) and rc.dataset.train.type == oc.dataset.train.type
-    assert (rc.log_dir, rc.batch_size, rc.seed, rc.validate_buffer) == (oc.log_dir, oc.batch_size, oc.seed, oc.validate_buffer)
+    assert ref['dataset_test'] == dict(oc.dataset.test) and ref['train_type'] == oc.dataset.train.type
+    e = ref['entry']
+    assert (e['log_dir'], e['batch_size'], e['seed'], e['validate_buffer']) == (oc.log_dir, oc.batch_size, oc.seed, oc.validate_buffer)
 
 
 @pytest.fixture(scope='module')
@@ -287,3 +291,28 @@ def test_multi_gpu_runner_facade_and_rank_failure(tmp_path, monkeypatch, synth_s
     if not torch.cuda.is_available():
         with pytest.raises(RuntimeError, match=r'2 of 2 GPU ranks failed(.|\n)*rank 1 \(GPU 1, exit code 1\)(.|\n)*GPU index 0 is not visible'):
             r.infer_lane_coordinate_endpoint_semantics(tiles=str(tmp_path), write_lane_vertex=True)
+
+
+def test_bench_dump_outputs_files(tmp_path):
+    """bench.py --dump-outputs: the per-tile results of the last timed step as float64 .npy files (lanes, kept endpoints tagged with their
+    tile, tile indices), bit for bit; an output over the 64 MB budget is cut to a fixed seeded sample of whole tiles."""
+    import bench
+    rng = np.random.RandomState(5)
+    res = []
+    for t in range(5):
+        lanes = np.full((72, 144, 2), -1.0)
+        lanes[t, :, 0] = rng.rand(144) * 1152
+        res.append((lanes, rng.randint(0, 1152, (t % 3, 2)).astype(np.int32)))
+    assert bench.dump_outputs(str(tmp_path / 'a'), res) == ['endpoints', 'lanes', 'tiles']
+    got = {n: np.load(tmp_path / 'a' / f'{n}.npy') for n in ('lanes', 'endpoints', 'tiles')}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got['lanes'], np.stack([l for l, _ in res])) and np.array_equal(got['tiles'], np.arange(5))
+    want = np.concatenate([np.concatenate([np.full((len(e), 1), t), e], axis=1) for t, (_, e) in enumerate(res)])
+    assert got['endpoints'].shape == (0 + 1 + 2 + 0 + 1, 3) and np.array_equal(got['endpoints'], want)
+    big = [res[0]] * 400                                               # 400 tiles: over the budget
+    bench.dump_outputs(str(tmp_path / 'b'), big)
+    bench.dump_outputs(str(tmp_path / 'c'), big)
+    total = sum(os.path.getsize(tmp_path / 'b' / f) for f in os.listdir(tmp_path / 'b'))
+    tiles = np.load(tmp_path / 'b' / 'tiles.npy')
+    assert total <= 64 << 20 and 0 < len(tiles) < 400 and np.array_equal(tiles, np.load(tmp_path / 'c' / 'tiles.npy'))
+    assert np.load(tmp_path / 'b' / 'lanes.npy').shape == (len(tiles), 72, 144, 2)
