@@ -127,6 +127,12 @@ int lm_upsample_bilinear_to_chw(void* stream, const float* x, int ldx, float* y_
 int lm_layernorm_rows(void* stream, const float* x, const float* gamma, const float* beta, float* y,
                       long rows, int D, float eps);
 int lm_unpatchify(void* stream, const float* tokens, float* y_nhwc, int B, int G, int P, int C);
+/* MLP-Mixer token mixing (mixsegnet.py:24-31,55-58: Conv1d(K -> M, kernel 1) over the token axis of every channel):
+ * y[b] = act(W x[b] + bias) (+ res[b]) for b < B.  x [B*K][N], res / y [B*M][N] row-major (N % 4 == 0, 16-byte aligned);
+ * wt = W^T zero padded to [ceil(K/16)*16][ldw], ldw = M rounded up to a multiple of 128; bias [M] (one value per output token);
+ * act LM_ACT_NONE or LM_ACT_GELU (erf); res may be NULL.  Exact fp32 (v_mfma_f32_32x32x2_f32). */
+int lm_token_mix_mfma_f32(void* stream, const float* x, const float* wt, int ldw, const float* bias, const float* res, float* y,
+                          int B, int M, int K, int N, int act);
 
 /* ---- attention core: softmax(q k^T * scale) v per (batch, head); qkv = [B*N][3*heads*64] (vitsegnet.py:58-68) */
 int lm_attention_f32(void* stream, const float* qkv, float* out, int B, int N, int heads, int dim_head, float scale);
@@ -139,6 +145,8 @@ int lm_attention_masked_f32(void* stream, const float* qkv, float* out, const in
  * stage2: second Conv1d of ext2/cls2/offset2 (:210,218,226); proposal_conf: Linear(23040 -> 2) (:200-204) */
 int lm_head_tokens(void* stream, const float* seg, const float* row_nhwc16, float* tok, float seg_bias,
                    int B, int P, int Hr, int Wr, int prop_width, int half_buff);
+/* spatial_att=False (polyline_fpn_vit_vertex_2.py:403-404): the tokens are the raw zero-padded row window, no seg map */
+int lm_head_tokens_window(void* stream, const float* row_nhwc16, float* tok, int B, int P, int Hr, int Wr, int prop_width, int half_buff);
 int lm_head_stage2(void* stream, const float* hid, int ldh, int D, const float* w2, const float* b2,
                    float* ext2, float* cls2, float* off2, long M);
 int lm_head_proposal_conf(void* stream, const float* tok, const float* wt, const float* bias, float* conf,

@@ -60,10 +60,12 @@ SIGNATURES = {
     'lm_upsample_bilinear_nhwc': (i32, [vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32]),
     'lm_upsample_bilinear_to_chw': (i32, [vp, vp, i32, vp, i32, i32, i32, i32, i32, i32]),
     'lm_layernorm_rows': (i32, [vp, vp, vp, vp, vp, i64, i32, f32]),
+    'lm_token_mix_mfma_f32': (i32, [vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32]),
     'lm_unpatchify': (i32, [vp, vp, vp, i32, i32, i32, i32]),
     'lm_attention_f32': (i32, [vp, vp, vp, i32, i32, i32, i32, f32]),
     'lm_attention_masked_f32': (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32]),
     'lm_head_tokens': (i32, [vp, vp, vp, vp, f32, i32, i32, i32, i32, i32, i32]),
+    'lm_head_tokens_window': (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32]),
     'lm_head_stage2': (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp, i64]),
     'lm_head_proposal_conf': (i32, [vp, vp, vp, vp, vp, i32, i32]),
     'lm_decode_proposals': (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32]),

@@ -1,10 +1,15 @@
-"""GFC-T / ViT block behind the reference's BACKBONE registry name ``VitSegNet``.
+"""GFC-T / ViT block behind the reference's BACKBONE registry name ``VitSegNet``, and its MLP-Mixer variant ``MixSegNet``.
 
 Drop-in for baseline/models/backbone/vitsegnet.py:132-214 (same kwargs, same state-dict keys:
 ``to_patch_embedding.1``, ``pos_embedding``, ``transformer.layers.{l}.{0,1}.{norm,fn...}``).
 Kernels: patch embedding = 8x8/stride-8 implicit GEMM straight from the NHWC feature map (no patchify
 copy) with the positional embedding added in the epilogue; LayerNorm rows; QKV / out-proj / MLP GEMMs
 on lm_conv2d_nhwc_mfma_f32 with bias + residual + erf-GELU epilogues; lm_attention_f32.
+
+MixSegNet: drop-in for baseline/models/backbone/mixsegnet.py:34-76 (same kwargs, same state-dict keys
+``mixsegnet.{1, 2..depth+1, depth+2, depth+4}``).  Same patch embedding (no positional embedding), channel mixing on the
+ViT's GEMM epilogues, token mixing (Conv1d over the token axis, weight on the left) on lm_token_mix_mfma_f32 straight from
+the [B*tokens, dim] rows, final LayerNorm, un-patchify, the 1x1 output conv on lm_conv2d_nhwc_small.
 """
 import torch
 import torch.nn as nn
@@ -124,3 +129,98 @@ class VitSegNet(PackedModule):
         if self.is_with_shared_mlp:
             x = ops.conv_mfma(x, P['mlp.w'], self.shared_mlp.out_channels, shift=P['mlp.b'])
         return x
+
+
+class _PreNormResidual(nn.Module):
+    """mixsegnet.py:15-22: x + fn(norm(x)) (fn registered first: the reference's state-dict order)."""
+
+    def __init__(self, dim, fn):
+        super().__init__()
+        self.fn = fn
+        self.norm = nn.LayerNorm(dim)
+
+
+def _mixer_ff(dim, expansion_factor, dense):
+    return nn.Sequential(dense(dim, dim * expansion_factor), nn.GELU(), nn.Dropout(0.), dense(dim * expansion_factor, dim), nn.Dropout(0.))
+
+
+def _conv1d_k1(cin, cout):
+    return nn.Conv1d(cin, cout, kernel_size=1)
+
+
+@BACKBONE.register_module
+class MixSegNet(PackedModule):
+    def __init__(self, image_size=144, channels=64, patch_size=8, dim=512, depth=5, output_channels=1024, expansion_factor=4,
+                 dropout=0., cfg=None):
+        super().__init__()
+        assert (image_size % patch_size) == 0, 'image must be divisible by patch size'
+        self.cfg = cfg
+        self.patch, self.grid, self.channels, self.dim = patch_size, image_size // patch_size, channels, dim
+        self.num_patches = self.grid * self.grid
+        self.out_c = dim // (patch_size * patch_size)
+        self.output_channels = output_channels
+        self.depth = depth
+        self.mixsegnet = nn.Sequential(
+            nn.Identity(),                                                  # patchify 'b c (h p1) (w p2) -> b (h w) (p1 p2 c)'
+            nn.Linear(patch_size * patch_size * channels, dim),
+            *[nn.Sequential(_PreNormResidual(dim, _mixer_ff(self.num_patches, expansion_factor, _conv1d_k1)),
+                            _PreNormResidual(dim, _mixer_ff(dim, expansion_factor, nn.Linear))) for _ in range(depth)],
+            nn.LayerNorm(dim),
+            nn.Identity(),                                                  # un-patchify
+            nn.Conv2d(self.out_c, output_channels, kernel_size=1))
+
+    @property
+    def blocks(self):
+        return [self.mixsegnet[2 + l] for l in range(self.depth)]
+
+    def _pack(self):
+        P = {}
+        lin = self.mixsegnet[1]
+        p = self.patch
+        # Linear weight columns are ordered (p1 p2 c) == (kh kw cin) of an 8x8/stride-8 conv over NHWC
+        P['embed.w'] = ops.pack_mfma(lin.weight.reshape(self.dim, p, p, self.channels).permute(0, 3, 1, 2))
+        P['embed.b'] = lin.bias.float().contiguous()
+        for l, (tok, ch) in enumerate(self.blocks):
+            k = f'L{l}'
+            P[k + '.ln1.g'], P[k + '.ln1.b'] = tok.norm.weight.float().contiguous(), tok.norm.bias.float().contiguous()
+            P[k + '.tm1'] = ops.pack_token_mix(tok.fn[0].weight)
+            P[k + '.tm1.b'] = tok.fn[0].bias.float().contiguous()
+            P[k + '.tm2'] = ops.pack_token_mix(tok.fn[3].weight)
+            P[k + '.tm2.b'] = tok.fn[3].bias.float().contiguous()
+            P[k + '.ln2.g'], P[k + '.ln2.b'] = ch.norm.weight.float().contiguous(), ch.norm.bias.float().contiguous()
+            P[k + '.fc1'] = ops.pack_mfma(ch.fn[0].weight)
+            P[k + '.fc1.b'] = ch.fn[0].bias.float().contiguous()
+            P[k + '.fc2'] = ops.pack_mfma(ch.fn[3].weight)
+            P[k + '.fc2.b'] = ch.fn[3].bias.float().contiguous()
+        ln = self.mixsegnet[2 + self.depth]
+        P['ln.g'], P['ln.b'] = ln.weight.float().contiguous(), ln.bias.float().contiguous()
+        conv = self.mixsegnet[4 + self.depth]
+        P['out.w'] = ops.pack_small(conv.weight)
+        P['out.b'] = conv.bias.float().contiguous()
+        return P
+
+    def forward(self, img):
+        """Goes through the dispatcher: torch.ops.lanemap_hip.mixer_backbone (torch_ops.py)."""
+        from . import torch_ops
+        return torch_ops.mixer_backbone(img, torch_ops.stage_weights(self), torch_ops.stage_name(self))
+
+    def _forward_impl(self, img):
+        if self.output_channels > 16 or self.out_c % 4:
+            raise NotImplementedError(f'MixSegNet output conv {self.out_c}->{self.output_channels}: the hot path covers <= 16 outputs '
+                                      'from a multiple of 4 channels')
+        P = self.packed()
+        B = img.shape[0]
+        N = self.num_patches
+        tok = ops.conv_mfma(img, P['embed.w'], self.dim, self.patch, self.patch, self.patch, 0, 1, shift=P['embed.b'])
+        t = tok.permute(0, 2, 3, 1).reshape(B * N, self.dim)                # [B,dim,G,G] NHWC == [B*N, dim]
+        for l, (tm, cm) in enumerate(self.blocks):
+            k = f'L{l}'
+            y = ops.layernorm(t, P[k + '.ln1.g'], P[k + '.ln1.b'], tm.norm.eps)
+            h = ops.token_mix(y, P[k + '.tm1'], tm.fn[0].out_channels, P[k + '.tm1.b'], B, act=ops.ACT_GELU)
+            t = ops.token_mix(h, P[k + '.tm2'], N, P[k + '.tm2.b'], B, res=t)
+            y = ops.layernorm(t, P[k + '.ln2.g'], P[k + '.ln2.b'], cm.norm.eps)
+            y = ops.linear_mfma(y, P[k + '.fc1'], cm.fn[0].out_features, shift=P[k + '.fc1.b'], act=ops.ACT_GELU)
+            t = ops.linear_mfma(y, P[k + '.fc2'], self.dim, shift=P[k + '.fc2.b'], res=t)
+        t = ops.layernorm(t, P['ln.g'], P['ln.b'], self.mixsegnet[2 + self.depth].eps)
+        x = ops.unpatchify(t, B, self.grid, self.patch, self.out_c)
+        return ops.conv_small(x, P['out.w'], self.output_channels, shift=P['out.b'])

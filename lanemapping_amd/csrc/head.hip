@@ -1,11 +1,12 @@
 // Column-proposal head glue kernels (ColumnProposal2.forward, live branch only:
-// column_att=False, spatial_att=True; baseline/models/heads/polyline_fpn_vit_vertex_2.py:390-421).
+// column_att=False, spatial_att=True or False; baseline/models/heads/polyline_fpn_vit_vertex_2.py:390-421).
 //
 //  lm_head_tokens       : for every proposal p, row h, window column w and channel c
 //                           tok[(b,p,h), c*10+w] = avg_pool8x8( up_{(288,20)->(1152,80)}( seg_p ) )[h,w] * row_fea_pad[b,c,h,2p+w]
 //                         (:392-405).  seg = bi_seg_proposal(relu(col_fea_up)) is computed once for the whole
 //                         288x288 map; zero-padded columns (:383) evaluate to the conv bias.  The 1152x80
 //                         per-proposal map (prop_bi_seg, 26.5 MB/tile) is never materialised.
+//  lm_head_tokens_window: spatial_att=False (:403-404): tok[(b,p,h), c*10+w] = row_fea_pad[b,c,h,2p+w], no seg map
 //  lm_head_stage2       : second Conv1d of ext2 / cls2 / offset2 (:210,218,226) on the BN'd hidden rows
 //  lm_head_proposal_conf: proposal_confidence Linear(23040 -> 2) (:200-204)
 #include "common.h"
@@ -70,6 +71,8 @@ __device__ __forceinline__ void write_tokens(const float* __restrict__ row, floa
 // seg [B,Hs,Ws] (Hs=Ws=288), row [B,Hr,Wr,16] NHWC (Hr=Wr=144), tok [B*P*Hr, 160]
 // (rounds 1-3: one thread per token, its 256 taps gathered from global memory - the vector-memory path serves a 64-lane gather of
 // 4-byte elements at a fraction of its line rate: 0.275 ms per 16 tiles; kept behind LM_HEAD_TOKENS_GATHER=1)
+// SPATIAL = false: spatial_att=False (:403-404), the tokens are the raw zero-padded row window, seg is not read (1 * v is exact)
+template <bool SPATIAL>
 __global__ __launch_bounds__(256) void head_tokens_kernel(const float* __restrict__ seg, const float* __restrict__ row,
                                                           float* __restrict__ tok, float seg_bias, int P, int Hr, int Wr,
                                                           int prop_width, int half_buff, long total) {
@@ -84,8 +87,11 @@ __global__ __launch_bounds__(256) void head_tokens_kernel(const float* __restric
     const int Hs = 2 * Hr, Ws = 2 * Wr;
     const int win = 2 * FW;                             // 20 source columns per proposal
     const int col0 = 2 * prop_width * p - 2 * half_buff;   // first source column of the window (may be < 0)
-    const float* sb = seg + (long)b * Hs * Ws;
-    const float pooled = pooled_window(h, w, Hs, Hr, win, col0, Ws, seg_bias, [&](int y, int, int c) { return sb[(long)y * Ws + c]; });
+    float pooled = 1.f;
+    if (SPATIAL) {
+        const float* sb = seg + (long)b * Hs * Ws;
+        pooled = pooled_window(h, w, Hs, Hr, win, col0, Ws, seg_bias, [&](int y, int, int c) { return sb[(long)y * Ws + c]; });
+    }
     write_tokens(row, tok, pooled, b, p, h, w, P, Hr, Wr, prop_width, half_buff);
 }
 
@@ -260,8 +266,20 @@ LM_API int lm_head_tokens(void* stream, const float* seg, const float* row_nhwc1
         LM_LAUNCH_CHECK();
         return LM_OK;
     }
-    hipLaunchKernelGGL(head_tokens_kernel, dim3(lm_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(head_tokens_kernel<true>, dim3(lm_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream,
                        seg, row_nhwc16, tok, seg_bias, P, Hr, Wr, prop_width, half_buff, total);
+    LM_LAUNCH_CHECK();
+    return LM_OK;
+}
+
+// spatial_att=False: tok[(b,p,h), c*10+w] = row_fea_pad[b,c,h,2p+w] (:403-404)
+LM_API int lm_head_tokens_window(void* stream, const float* row_nhwc16, float* tok, int B, int P, int Hr, int Wr, int prop_width,
+                                 int half_buff) {
+    LM_REQUIRE(row_nhwc16 && tok, "head_tokens_window: null pointer");
+    LM_REQUIRE(prop_width + 2 * half_buff == FW, "head_tokens_window: prop_fea_width must be %d", FW);
+    const long total = (long)B * P * Hr * FW;
+    hipLaunchKernelGGL(head_tokens_kernel<false>, dim3(lm_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream,
+                       nullptr, row_nhwc16, tok, 0.f, P, Hr, Wr, prop_width, half_buff, total);
     LM_LAUNCH_CHECK();
     return LM_OK;
 }

@@ -10,6 +10,8 @@ are kept so checkpoints load strictly), same method names and output dictionarie
   get_lane_map_numpy_with_label(...)       :761-886  -> lane_maps {coor_label, cls_offset_smooth, endp_by_cls, semantic_line}
   get_lane_map_on_source_image(...)        :926-1083 -> pred_smooth_lane_vertex (vertex packing only, no cv2 overlays)
 
+spatial_att=False (the MixSeg config): the tokens are the raw zero-padded row windows, the bi_seg_proposal conv is skipped
+(its parameters stay for strict loading).
 Not supported (raise): column_att / column_transformer_decoder branches, endp_mode == 'endpoint',
 view_detail=True (the reference itself raises NameError there).  `prop_bi_seg`
 ([B,72,1,1152,80], unused downstream) and the dead `endpoint` map are not produced.
@@ -129,8 +131,6 @@ class ColumnProposal2(PackedModule):
         cfg = self.cfg
         if cfg.column_att or cfg.column_transformer_decoder:
             raise NotImplementedError('column_att / column_transformer_decoder are off in every BASELINE config')
-        if not cfg.spatial_att:
-            raise NotImplementedError('spatial_att=False is not on the hot path')
         if self.prop_fea_width != 10 or self.dim_shared * 3 > 320:
             raise NotImplementedError('hot path covers prop_fea_width == 10 and dim_shared <= 106')
         P = self.packed()
@@ -145,8 +145,11 @@ class ColumnProposal2(PackedModule):
         row = ops.conv_small(r, P['hc2.w'], hd, 3, 3, 2, 1, scale=P['hc2.s'], shift=P['hc2.b'])   # :376
         o = ops.conv_small(row, P['or0.w'], hd // 2, 3, 3, 1, 1, scale=P['or0.s'], shift=P['or0.b'])
         orient = ops.conv_small(o, P['or2.w'], self.num_orients, 3, 3, 1, 1, shift=P['or2.b'])      # :380
-        seg = ops.conv_small(col, P['seg.w'], 1, shift=P['seg.b'], pre_relu=True)                   # :400 (once)
-        tok = ops.head_tokens(seg, row, self.num_prop, self.prop_width, self.prop_half_buff, P['seg.bias_value'])
+        if cfg.spatial_att:
+            seg = ops.conv_small(col, P['seg.w'], 1, shift=P['seg.b'], pre_relu=True)               # :400 (once)
+            tok = ops.head_tokens(seg, row, self.num_prop, self.prop_width, self.prop_half_buff, P['seg.bias_value'])
+        else:                                                                                       # :403-404 raw row window
+            tok = ops.head_tokens(None, row, self.num_prop, self.prop_width, self.prop_half_buff, 0.)
         D = self.dim_shared
         hid = torch.empty((tok.shape[0], 320), device=x.device, dtype=torch.float32)
         ops.linear_mfma(tok, P['w1'], 3 * D, scale=P['s1'], shift=P['b1'], out=hid)

@@ -137,6 +137,16 @@ def pack_small(w):
     return p.contiguous()
 
 
+def pack_token_mix(w):
+    """Token-mixing weight [M,K] (or Conv1d [M,K,1]) -> W^T zero padded to [ceil(K/16)*16, ceil(M/128)*128] (lm_token_mix_mfma_f32)."""
+    if w.dim() == 3:
+        w = w[:, :, 0]
+    m, k = w.shape
+    p = torch.zeros(((k + 15) // 16 * 16, (m + 127) // 128 * 128), device=w.device, dtype=torch.float32)
+    p[:k, :m] = w.t()
+    return p.contiguous()
+
+
 # ------------------------------------------------------------------------------- convolutions / GEMM
 _conv_hook = None   # optional profiler hook: called as hook(kind, algorithmic_flops, launch_fn[, executed_flops])
 
@@ -296,6 +306,27 @@ def linear_mfma(x2d, wp, n_out, scale=None, shift=None, res=None, res_rows=0, ac
     return out
 
 
+def token_mix(x2d, wt, M, bias, B, res=None, act=ACT_NONE, out=None):
+    """MLP-Mixer token mixing: y[b] = act(W @ x[b] + bias[:, None]) (+ res[b]) for each of the B batch elements.
+    x2d [B*K, N] row-major (token rows, channels contiguous), wt = pack_token_mix(W) of W [M, K], bias [M] -> [B*M, N]."""
+    assert x2d.dim() == 2 and x2d.is_contiguous() and x2d.shape[0] % B == 0
+    K, N = x2d.shape[0] // B, x2d.shape[1]
+    assert wt.shape[0] >= K and wt.shape[1] >= M and bias.numel() == M
+    if out is None:
+        out = torch.empty((B * M, N), device=x2d.device, dtype=torch.float32)
+    assert out.is_contiguous() and tuple(out.shape) == (B * M, N)
+    if res is not None:
+        assert res.is_contiguous() and tuple(res.shape) == (B * M, N)
+    def launch():
+        check(lib().lm_token_mix_mfma_f32(_stream(), _ptr(x2d), _ptr(wt), wt.shape[1], _ptr(bias), _ptr(res), _ptr(out),
+                                          B, M, K, N, act))
+    if _conv_hook is not None:
+        _conv_hook(f'token_mix M{M} K{K} N{N} B{B}', 2.0 * B * M * K * N, launch)
+    else:
+        launch()
+    return out
+
+
 def conv_small(x, w16, cout, kh=1, kw=1, stride=1, pad=0, scale=None, shift=None, pre_relu=False, act=ACT_NONE, out=None):
     x, ldx = as_nhwc(x)
     B, cin, H, W = x.shape
@@ -443,12 +474,16 @@ def attention(qkv, B, N, heads, dim_head, scale, valid=None):
 
 # ------------------------------------------------------------------------------- head
 def head_tokens(seg, row, P, prop_width, half_buff, seg_bias):
-    """seg [B,1,288,288], row [B,16,144,144] (NHWC-stored) -> tok [B*P*144, 160]."""
+    """seg [B,1,288,288], row [B,16,144,144] (NHWC-stored) -> tok [B*P*144, 160].
+    seg None: spatial_att=False, the tokens are the raw row windows."""
     row, ld = as_nhwc(row)
     B, C_, Hr, Wr = row.shape
     assert C_ == 16 and ld == 16
-    seg = seg.reshape(B, 2 * Hr, 2 * Wr).contiguous()
     tok = torch.empty((B * P * Hr, 160), device=row.device, dtype=torch.float32)
+    if seg is None:
+        check(lib().lm_head_tokens_window(_stream(), _ptr(row), _ptr(tok), B, P, Hr, Wr, prop_width, half_buff))
+        return tok
+    seg = seg.reshape(B, 2 * Hr, 2 * Wr).contiguous()
     check(lib().lm_head_tokens(_stream(), _ptr(seg), _ptr(row), _ptr(tok), float(seg_bias), B, P, Hr, Wr, prop_width, half_buff))
     return tok
 

@@ -9,14 +9,15 @@ liblanemap_hip.so, registered for the ``cuda`` (HIP) device only - calling an op
 same library and are registered for ``cpu`` because that is where their inputs live.
 
 Two levels:
-  * stage ops - what the modules' ``forward`` go through: ``bev_raster``, ``fpn_encoder``, ``vit_backbone``, ``colprop_head``
+  * stage ops - what the modules' ``forward`` go through: ``bev_raster``, ``fpn_encoder``, ``vit_backbone`` / ``mixer_backbone``,
+    ``colprop_head``
     (+ ``endp_cluster``, ``polyline_assemble`` on the host).  A stage op takes the stage's WEIGHTS as a ``Tensor[]`` operand (every
     parameter and buffer of the module, in ``state_dict`` order - the tracer / ``torch.export`` see them as inputs of the op, and the
     op computes from the tensors it is handed) and the stage's STRUCTURE (which layers, strides, dilations) as a string: the name
     under which the module registered itself (``stage_name``: class name + a process-wide counter, never recycled).  Round 2 passed
     ``id(module)``: a process-local integer that could alias a recycled id and hid the weights from the graph.
   * kernel ops - one per device kernel family (``conv2d_mfma``, ``conv3x3_winograd44``, ``stem_conv7x7``, ``gn_relu_upsample``,
-    ``layernorm_rows``, ``attention``, ``linear_mfma``, ``decode_proposals``, ``decode_semantic``, ``endp_topk``, ``tile_ingest``, ...).
+    ``layernorm_rows``, ``attention``, ``linear_mfma``, ``token_mix``, ``decode_proposals``, ``decode_semantic``, ``endp_topk``, ``tile_ingest``, ...).
 Activations are logically NCHW, stored channels-last (ops.new_act); fake kernels return the same strides.
 """
 import itertools
@@ -168,6 +169,10 @@ def _linear_mfma(x: Tensor, w_packed: Tensor, n_out: int, scale: Optional[Tensor
     return _ops.linear_mfma(x, w_packed, n_out, scale=scale, shift=shift, res=res, res_rows=res_rows, act=act)
 
 
+def _token_mix(x: Tensor, wt: Tensor, M: int, bias: Tensor, B: int, res: Optional[Tensor], act: int) -> Tensor:
+    return _ops.token_mix(x, wt, M, bias, B, res=res, act=act)
+
+
 def _tile_ingest(u8_hwc: Tensor) -> Tensor:
     return _ops.tile_ingest(u8_hwc)
 
@@ -216,6 +221,7 @@ layernorm_rows = _define('layernorm_rows', _layernorm_rows, lambda x, gamma, bet
 attention = _define('attention', _attention, lambda qkv, B, N, heads, dim_head, scale: qkv.new_empty((B * N, heads * dim_head)))
 linear_mfma = _define('linear_mfma', _linear_mfma,
                       lambda x, w_packed, n_out, scale, shift, res, res_rows, act: x.new_empty((x.shape[0], n_out)))
+token_mix = _define('token_mix', _token_mix, lambda x, wt, M, bias, B, res, act: x.new_empty((B * M, x.shape[1])))
 tile_ingest = _define('tile_ingest', _tile_ingest,
                       lambda u8: u8.new_empty((u8.shape[0], 3, u8.shape[1], u8.shape[2]), dtype=torch.float32))
 decode_proposals = _define('decode_proposals', _decode_proposals, _decode_proposals_fake)
@@ -279,6 +285,19 @@ def _vit_backbone_fake(fea, weights, stage):
 vit_backbone = _define('vit_backbone', _vit_backbone, _vit_backbone_fake)
 
 
+def _mixer_backbone(fea: Tensor, weights: List[Tensor], stage: str) -> Tensor:
+    with _with_weights(stage, weights) as m:
+        return m._forward_impl(fea)
+
+
+def _mixer_backbone_fake(fea, weights, stage):
+    m = _stage(stage)
+    return _fake_act(fea, fea.shape[0], m.output_channels, m.grid * m.patch, m.grid * m.patch)
+
+
+mixer_backbone = _define('mixer_backbone', _mixer_backbone, _mixer_backbone_fake)
+
+
 def _colprop_head(x: Tensor, col: Tensor, weights: List[Tensor], stage: str) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
     """Column-proposal head stage (heads.ColumnProposal2): x [B,8,144,144], col [B,16,288,288] whose channels 8..15 hold fea_up
     (channels 0..7 are filled here) -> (proposal_conf, ext2, cls2, offset2, orient logits)."""
@@ -329,5 +348,5 @@ def _polyline_assemble_fake(prop_conf, prop_v_ext, cls_offset, bi_seg_rows, endp
 polyline_assemble = _define('polyline_assemble', _polyline_assemble, _polyline_assemble_fake, device='cpu')
 
 OP_NAMES = ['conv2d_mfma', 'conv3x3_winograd44', 'stem_conv7x7', 'maxpool3x3s2', 'gn_stats', 'gn_relu_upsample',
-            'upsample_bilinear', 'layernorm_rows', 'attention', 'linear_mfma', 'tile_ingest', 'decode_proposals', 'decode_semantic',
-            'decode_orient', 'endp_topk', 'bev_raster', 'fpn_encoder', 'vit_backbone', 'colprop_head', 'endp_cluster', 'polyline_assemble']
+            'upsample_bilinear', 'layernorm_rows', 'attention', 'linear_mfma', 'token_mix', 'tile_ingest', 'decode_proposals', 'decode_semantic',
+            'decode_orient', 'endp_topk', 'bev_raster', 'fpn_encoder', 'vit_backbone', 'mixer_backbone', 'colprop_head', 'endp_cluster', 'polyline_assemble']
