@@ -423,6 +423,9 @@ __global__ __launch_bounds__(512) void lateral_mfma_kernel(ConvParams p) {
             __builtin_amdgcn_global_load_lds((gptr_t*)(xt + xoff[i]), (lptr_t*)(smem + buf * XBUF + (i * 8 + wave) * 256), 16, 0, 0);
     };
     load_x(tile, 0);
+    // the first tile's pixels have landed before the loop (the loop's vmcnt(4) assumes four stores behind each prefetch, and the first
+    // tile has none).  The builtin, not inline asm: the compiler's wait-count pass sees it and merges its own wait for the weights into it
+    __builtin_amdgcn_s_waitcnt(0x0F70);                            // gfx9 encoding: vmcnt(0), expcnt / lgkmcnt not waited on
     const int fswz = (j >> 1) & 7;
     // the weights are complete before the loop (their first use is inside it, where the compiler's wait would also drain the pixel
     // prefetch of every later iteration)

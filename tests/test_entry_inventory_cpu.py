@@ -9,10 +9,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # queries (workspace sizes, chunk / tile counts): their results size the launches that the tests do check
 NOT_DIRECTLY_TESTED = {
-    'lm_winograd44_gn_chunks': 'query: statistics chunks per image of the Winograd epilogue (sizes conv_wino44\'s partial buffer)',
     'lm_winograd44_tiles': 'query: Winograd tile count (profiling FLOP count in conv_wino44)',
-    'lm_winograd44_twin_workspace_bytes': 'query: workspace size of the Winograd twin',
-    'lm_gn_stats_workspace_bytes': 'query: workspace size of lm_gn_stats',
     'lm_endp_topk_workspace_bytes': 'query: workspace size of lm_endp_topk',
     'lm_voxelize_workspace_bytes': 'query: workspace size of the voxeliser',
     'lm_scan_workspace_bytes': 'query: workspace size of the exclusive scan',
