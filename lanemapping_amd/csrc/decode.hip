@@ -4,7 +4,8 @@
 // (baseline/models/pcencoder/postprojector.py:115-183).
 //
 //  lm_decode_proposals : :610 (prop_conf softmax), :694-697 (existence 3-way softmax + thresholds),
-//                        :701-702 (10-way softmax + argmax), :726-738 (idx + offset, clamp, + 2p-4).
+//                        :701-702 (FW-way softmax + argmax), :726-738 (idx + offset, clamp at FW, + pw*p - half_buff);
+//                        FW = prop_fea_width in {10, 12, 16} (num_prop 72 / 36 / 18).
 //                        Replaces the 10 368-iteration Python loop per tile by one lane per (b,p,h).
 //  lm_decode_orient    : :615 argmax over the 11 orientation channels.
 //  lm_decode_semantic  : :627-632 3-way softmax over the 1152x1152 map, class thresholds, s1+s2.
@@ -41,6 +42,7 @@ __device__ __forceinline__ int softmax_argmax(const float* in, float* out) {
     return best;
 }
 
+template <int FW>
 __global__ __launch_bounds__(256) void decode_proposals_kernel(
     const float* __restrict__ pconf, const float* __restrict__ ext2, const float* __restrict__ cls2,
     const float* __restrict__ off2, float* __restrict__ prop_conf, float* __restrict__ v_ext,
@@ -63,14 +65,14 @@ __global__ __launch_bounds__(256) void decode_proposals_kernel(
     if (e[1] > e[2] && e[1] > exist_thre) v = 1.f;
     if (e[2] > e[1] && e[2] > exist_thre) v = 2.f;
     v_ext[i] = v;
-    float c[10];
-    const int idx = softmax_argmax<10>(cls2 + i * 10, c);
+    float c[FW];
+    const int idx = softmax_argmax<FW>(cls2 + i * FW, c);
 #pragma unroll
-    for (int k = 0; k < 10; ++k) cls_conf[i * 10 + k] = c[k];
+    for (int k = 0; k < FW; ++k) cls_conf[i * FW + k] = c[k];
     cls_idx[i] = idx;
-    const float fsum = (float)idx + off2[i * 10 + idx];   // fp32 sum stored in f64 (:726)
+    const float fsum = (float)idx + off2[i * FW + idx];   // fp32 sum stored in f64 (:726)
     double co = (double)fsum;
-    if (co > 10.0) co = 10.0;                             // :732 (prop_w = 10)
+    if (co > (double)FW) co = (double)FW;                 // :732 (prop_w = cls2.shape[-1] = FW)
     cls_offset[i] = co + (double)(prop_width * p - half_buff);
 }
 
@@ -361,8 +363,11 @@ LM_API int lm_decode_proposals(void* stream, const float* pconf, const float* ex
                                float* prop_conf, float* v_ext, float* cls_conf, int* cls_idx, double* cls_offset,
                                int B, int P, int R, float exist_thre, int prop_width, int half_buff) {
     LM_REQUIRE(pconf && ext2 && cls2 && off2 && prop_conf && v_ext && cls_conf && cls_idx && cls_offset, "decode_proposals: null pointer");
+    const int fw = prop_width + 2 * half_buff;
+    LM_REQUIRE(fw == 10 || fw == 12 || fw == 16, "decode_proposals: prop_fea_width must be 10, 12 or 16 (got %d)", fw);
     const long total = (long)B * P * R;
-    hipLaunchKernelGGL(decode_proposals_kernel, dim3(lm_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, pconf, ext2, cls2,
+    auto kernel = fw == 10 ? decode_proposals_kernel<10> : fw == 12 ? decode_proposals_kernel<12> : decode_proposals_kernel<16>;
+    hipLaunchKernelGGL(kernel, dim3(lm_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, pconf, ext2, cls2,
                        off2, prop_conf, v_ext, cls_conf, cls_idx, cls_offset, P, R, exist_thre, prop_width, half_buff, total);
     LM_LAUNCH_CHECK();
     return LM_OK;

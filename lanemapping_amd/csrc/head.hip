@@ -2,12 +2,14 @@
 // column_att=False, spatial_att=True or False; baseline/models/heads/polyline_fpn_vit_vertex_2.py:390-421).
 //
 //  lm_head_tokens       : for every proposal p, row h, window column w and channel c
-//                           tok[(b,p,h), c*10+w] = avg_pool8x8( up_{(288,20)->(1152,80)}( seg_p ) )[h,w] * row_fea_pad[b,c,h,2p+w]
-//                         (:392-405).  seg = bi_seg_proposal(relu(col_fea_up)) is computed once for the whole
+//                           tok[(b,p,h), c*FW+w] = avg_pool8x8( up_{(288,2FW)->(1152,8FW)}( seg_p ) )[h,w] * row_fea_pad[b,c,h,pw*p+w]
+//                         (:392-405), FW = prop_fea_width = prop_width + 2*half_buff in {10, 12, 16} (num_prop 72 / 36 / 18).
+//                         seg = bi_seg_proposal(relu(col_fea_up)) is computed once for the whole
 //                         288x288 map; zero-padded columns (:383) evaluate to the conv bias.  The 1152x80
 //                         per-proposal map (prop_bi_seg, 26.5 MB/tile) is never materialised.
-//  lm_head_tokens_window: spatial_att=False (:403-404): tok[(b,p,h), c*10+w] = row_fea_pad[b,c,h,2p+w], no seg map
-//  lm_head_stage2       : second Conv1d of ext2 / cls2 / offset2 (:210,218,226) on the BN'd hidden rows
+//  lm_head_tokens_window: spatial_att=False (:403-404): tok[(b,p,h), c*FW+w] = row_fea_pad[b,c,h,pw*p+w], no seg map
+//  lm_head_stage2       : second Conv1d of ext2 / cls2 / offset2 (:210,218,226) on the BN'd hidden rows (FW = 10; the other widths run
+//                         it as three 1x1 lm_conv2d_nhwc_small calls, heads.py)
 //  lm_head_proposal_conf: proposal_confidence Linear(23040 -> 2) (:200-204)
 #include "common.h"
 
@@ -15,7 +17,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
-constexpr int FW = 10;      // prop_fea_width = prop_width + 2*half_buff
 constexpr int NCH = 16;     // header_fea_dim
 
 __device__ __forceinline__ void bilin_axis(int o, int in, int out, int& i0, int& i1, float& w0, float& w1) {
@@ -31,7 +32,7 @@ __device__ __forceinline__ void bilin_axis(int o, int in, int out, int& i0, int&
 // 8 x 8 average of the bilinearly up-sampled (x 4 rows, x 4 columns) proposal window at token (h, w): `tap(y, x, ok)` returns the
 // segmentation value of source row y, window column x (ok: inside the un-padded map, else the conv bias).  ONE expression for both
 // kernels below, so the compiler forms the same multiply-adds in both: identical bits.
-template <typename Tap>
+template <int FW, typename Tap>
 __device__ __forceinline__ float pooled_window(int h, int w, int Hs, int Hr, int win, int col0, int Ws, float seg_bias, Tap tap) {
     float sum = 0.f;
     for (int r = 0; r < 8; ++r) {
@@ -54,6 +55,7 @@ __device__ __forceinline__ float pooled_window(int h, int w, int Hs, int Hr, int
     return sum * (1.0f / 64.0f);
 }
 
+template <int FW>
 __device__ __forceinline__ void write_tokens(const float* __restrict__ row, float* __restrict__ tok, float pooled, int b, int p, int h, int w,
                                              int P, int Hr, int Wr, int prop_width, int half_buff) {
     const int rc = prop_width * p + w - half_buff;      // column in the un-padded row feature map
@@ -68,11 +70,11 @@ __device__ __forceinline__ void write_tokens(const float* __restrict__ row, floa
     }
 }
 
-// seg [B,Hs,Ws] (Hs=Ws=288), row [B,Hr,Wr,16] NHWC (Hr=Wr=144), tok [B*P*Hr, 160]
+// seg [B,Hs,Ws] (Hs=Ws=288), row [B,Hr,Wr,16] NHWC (Hr=Wr=144), tok [B*P*Hr, 16*FW]
 // (rounds 1-3: one thread per token, its 256 taps gathered from global memory - the vector-memory path serves a 64-lane gather of
 // 4-byte elements at a fraction of its line rate: 0.275 ms per 16 tiles; kept behind LM_HEAD_TOKENS_GATHER=1)
 // SPATIAL = false: spatial_att=False (:403-404), the tokens are the raw zero-padded row window, seg is not read (1 * v is exact)
-template <bool SPATIAL>
+template <int FW, bool SPATIAL>
 __global__ __launch_bounds__(256) void head_tokens_kernel(const float* __restrict__ seg, const float* __restrict__ row,
                                                           float* __restrict__ tok, float seg_bias, int P, int Hr, int Wr,
                                                           int prop_width, int half_buff, long total) {
@@ -85,24 +87,28 @@ __global__ __launch_bounds__(256) void head_tokens_kernel(const float* __restric
     const int p = (int)(t % P);
     const int b = (int)(t / P);
     const int Hs = 2 * Hr, Ws = 2 * Wr;
-    const int win = 2 * FW;                             // 20 source columns per proposal
+    const int win = 2 * FW;                             // 2*FW source columns per proposal (20 at FW = 10)
     const int col0 = 2 * prop_width * p - 2 * half_buff;   // first source column of the window (may be < 0)
     float pooled = 1.f;
     if (SPATIAL) {
         const float* sb = seg + (long)b * Hs * Ws;
-        pooled = pooled_window(h, w, Hs, Hr, win, col0, Ws, seg_bias, [&](int y, int, int c) { return sb[(long)y * Ws + c]; });
+        pooled = pooled_window<FW>(h, w, Hs, Hr, win, col0, Ws, seg_bias, [&](int y, int, int c) { return sb[(long)y * Ws + c]; });
     }
-    write_tokens(row, tok, pooled, b, p, h, w, P, Hr, Wr, prop_width, half_buff);
+    write_tokens<FW>(row, tok, pooled, b, p, h, w, P, Hr, Wr, prop_width, half_buff);
 }
 
-// Round 4: one workgroup per (image, proposal, block of HT token rows); the source rows its tokens touch x the proposal's 20 window
-// columns are staged in LDS once (<= HT_ROWS x 20 floats), the 256 taps per token come from there.  Same expression, same order
+// Round 4: one workgroup per (image, proposal, block of HT token rows); the source rows its tokens touch x the proposal's 2*FW window
+// columns are staged in LDS once (<= HT_ROWS x 2*FW floats), the 256 taps per token come from there.  Same expression, same order
 // (pooled_window): bit-identical to the gather kernel.
-constexpr int HT = 24;             // token rows per workgroup (x 10 window columns = 240 of 256 threads)
-constexpr int HT_ROWS = 64;        // source rows staged at most (24 token rows span 8 * 24 / 4 + 2 = 50)
+// Token rows per workgroup: HT x FW threads of 256 - 24 x 10 = 240 (as before the width became a parameter), 21 x 12 = 252, 16 x 16.
+template <int FW>
+constexpr int head_tile_rows() { return FW == 10 ? 24 : 256 / FW; }
+constexpr int HT_ROWS = 64;        // source rows staged at most (HT token rows span 8 * HT / 4 + 2 <= 50)
+template <int FW>
 __global__ __launch_bounds__(256) void head_tokens_lds_kernel(const float* __restrict__ seg, const float* __restrict__ row,
                                                               float* __restrict__ tok, float seg_bias, int P, int Hr, int Wr,
                                                               int prop_width, int half_buff, int hblocks) {
+    constexpr int HT = head_tile_rows<FW>();
     __shared__ float win_s[HT_ROWS * 2 * FW];
     const int tid = threadIdx.x;
     const int hb = blockIdx.x % hblocks, bp = blockIdx.x / hblocks;
@@ -126,8 +132,8 @@ __global__ __launch_bounds__(256) void head_tokens_lds_kernel(const float* __res
     const int hl = tid / FW, w = tid - hl * FW;
     const int h = h0 + hl;
     if (hl >= HT || h >= h1) return;
-    const float pooled = pooled_window(h, w, Hs, Hr, win, col0, Ws, seg_bias, [&](int y, int x, int) { return win_s[(y - ya) * win + x]; });
-    write_tokens(row, tok, pooled, b, p, h, w, P, Hr, Wr, prop_width, half_buff);
+    const float pooled = pooled_window<FW>(h, w, Hs, Hr, win, col0, Ws, seg_bias, [&](int y, int x, int) { return win_s[(y - ya) * win + x]; });
+    write_tokens<FW>(row, tok, pooled, b, p, h, w, P, Hr, Wr, prop_width, half_buff);
 }
 
 // hid [M, ldh] (ext | cls | off hidden, D each) -> ext2 [M,3], cls2 [M,10], off2 [M,10]
@@ -224,7 +230,7 @@ __global__ __launch_bounds__(S2R) void head_stage2_lds_kernel(const float* __res
     else stage2_rows_lds<10>(hl, D, w2 + 13L * D, b2 + 13, off2 + m * 10);
 }
 
-// tok [B*P, L] (L = Hr*160, already in (h, cw) order), wt [2][L] -> conf [B*P, 2]
+// tok [B*P, L] (L = Hr*16*FW, already in (h, cw) order), wt [2][L] -> conf [B*P, 2]
 __global__ __launch_bounds__(256) void head_conf_kernel(const float* __restrict__ tok, const float* __restrict__ wt,
                                                         const float* __restrict__ bias, float* __restrict__ conf, int L) {
     __shared__ float red[2][256];
@@ -249,39 +255,66 @@ __global__ __launch_bounds__(256) void head_conf_kernel(const float* __restrict_
     if (threadIdx.x < 2) conf[bp * 2 + threadIdx.x] = red[threadIdx.x][0] + bias[threadIdx.x];
 }
 
-}  // namespace
-
-LM_API int lm_head_tokens(void* stream, const float* seg, const float* row_nhwc16, float* tok, float seg_bias,
-                          int B, int P, int Hr, int Wr, int prop_width, int half_buff) {
-    LM_REQUIRE(seg && row_nhwc16 && tok, "head_tokens: null pointer");
-    LM_REQUIRE(prop_width + 2 * half_buff == FW, "head_tokens: prop_fea_width must be %d", FW);
+template <int FW>
+int launch_head_tokens(hipStream_t stream, const float* seg, const float* row, float* tok, float seg_bias, int B, int P, int Hr, int Wr,
+                       int prop_width, int half_buff) {
+    constexpr int HT = head_tile_rows<FW>();
     const long total = (long)B * P * Hr * FW;
     static const bool gather = [] { const char* e = getenv("LM_HEAD_TOKENS_GATHER"); return e && atoi(e) != 0; }();
     const int hblocks = lm_cdiv(Hr, HT);
     // source rows a block of HT token rows can touch: (8 HT - 1) * (2 Hr - 1) / (8 Hr - 1) + 3
     const bool fits = (long)(8 * HT - 1) * (2 * Hr - 1) / (8 * Hr - 1) + 3 <= HT_ROWS && (long)B * P * hblocks < (1L << 31);
     if (!gather && fits) {
-        hipLaunchKernelGGL(head_tokens_lds_kernel, dim3((unsigned)((long)B * P * hblocks)), dim3(256), 0, (hipStream_t)stream, seg, row_nhwc16, tok,
+        hipLaunchKernelGGL(head_tokens_lds_kernel<FW>, dim3((unsigned)((long)B * P * hblocks)), dim3(256), 0, stream, seg, row, tok,
                            seg_bias, P, Hr, Wr, prop_width, half_buff, hblocks);
         LM_LAUNCH_CHECK();
         return LM_OK;
     }
-    hipLaunchKernelGGL(head_tokens_kernel<true>, dim3(lm_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       seg, row_nhwc16, tok, seg_bias, P, Hr, Wr, prop_width, half_buff, total);
+    hipLaunchKernelGGL((head_tokens_kernel<FW, true>), dim3(lm_cdiv(total, 256)), dim3(256), 0, stream,
+                       seg, row, tok, seg_bias, P, Hr, Wr, prop_width, half_buff, total);
     LM_LAUNCH_CHECK();
     return LM_OK;
 }
 
-// spatial_att=False: tok[(b,p,h), c*10+w] = row_fea_pad[b,c,h,2p+w] (:403-404)
+template <int FW>
+int launch_head_tokens_window(hipStream_t stream, const float* row, float* tok, int B, int P, int Hr, int Wr, int prop_width,
+                              int half_buff) {
+    const long total = (long)B * P * Hr * FW;
+    hipLaunchKernelGGL((head_tokens_kernel<FW, false>), dim3(lm_cdiv(total, 256)), dim3(256), 0, stream,
+                       nullptr, row, tok, 0.f, P, Hr, Wr, prop_width, half_buff, total);
+    LM_LAUNCH_CHECK();
+    return LM_OK;
+}
+
+}  // namespace
+
+LM_API int lm_head_tokens(void* stream, const float* seg, const float* row_nhwc16, float* tok, float seg_bias,
+                          int B, int P, int Hr, int Wr, int prop_width, int half_buff) {
+    LM_REQUIRE(seg && row_nhwc16 && tok, "head_tokens: null pointer");
+    const int fw = prop_width + 2 * half_buff;
+    hipStream_t s = (hipStream_t)stream;
+    switch (fw) {
+        case 10: return launch_head_tokens<10>(s, seg, row_nhwc16, tok, seg_bias, B, P, Hr, Wr, prop_width, half_buff);
+        case 12: return launch_head_tokens<12>(s, seg, row_nhwc16, tok, seg_bias, B, P, Hr, Wr, prop_width, half_buff);
+        case 16: return launch_head_tokens<16>(s, seg, row_nhwc16, tok, seg_bias, B, P, Hr, Wr, prop_width, half_buff);
+    }
+    lm_set_error("head_tokens: prop_fea_width must be 10, 12 or 16 (got %d)", fw);
+    return LM_ERR_ARG;
+}
+
+// spatial_att=False: tok[(b,p,h), c*FW+w] = row_fea_pad[b,c,h,pw*p+w] (:403-404)
 LM_API int lm_head_tokens_window(void* stream, const float* row_nhwc16, float* tok, int B, int P, int Hr, int Wr, int prop_width,
                                  int half_buff) {
     LM_REQUIRE(row_nhwc16 && tok, "head_tokens_window: null pointer");
-    LM_REQUIRE(prop_width + 2 * half_buff == FW, "head_tokens_window: prop_fea_width must be %d", FW);
-    const long total = (long)B * P * Hr * FW;
-    hipLaunchKernelGGL(head_tokens_kernel<false>, dim3(lm_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       nullptr, row_nhwc16, tok, 0.f, P, Hr, Wr, prop_width, half_buff, total);
-    LM_LAUNCH_CHECK();
-    return LM_OK;
+    const int fw = prop_width + 2 * half_buff;
+    hipStream_t s = (hipStream_t)stream;
+    switch (fw) {
+        case 10: return launch_head_tokens_window<10>(s, row_nhwc16, tok, B, P, Hr, Wr, prop_width, half_buff);
+        case 12: return launch_head_tokens_window<12>(s, row_nhwc16, tok, B, P, Hr, Wr, prop_width, half_buff);
+        case 16: return launch_head_tokens_window<16>(s, row_nhwc16, tok, B, P, Hr, Wr, prop_width, half_buff);
+    }
+    lm_set_error("head_tokens_window: prop_fea_width must be 10, 12 or 16 (got %d)", fw);
+    return LM_ERR_ARG;
 }
 
 LM_API int lm_head_stage2(void* stream, const float* hid, int ldh, int D, const float* w2, const float* b2,

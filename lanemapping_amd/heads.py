@@ -12,7 +12,9 @@ are kept so checkpoints load strictly), same method names and output dictionarie
 
 spatial_att=False (the MixSeg config): the tokens are the raw zero-padded row windows, the bi_seg_proposal conv is skipped
 (its parameters stay for strict loading).
-Not supported (raise): column_att / column_transformer_decoder branches, endp_mode == 'endpoint',
+Proposal geometries (the reference config's `num_prop = 72, 36, 18` / `prop_width = 2, 4, 8`): SUPPORTED_GEOMETRIES with
+prop_half_buff = 4, i.e. prop_fea_width FW = 10, 12 or 16, and dim_shared any multiple of 4 up to 512.
+Not supported (raise): other geometries, column_att / column_transformer_decoder branches, endp_mode == 'endpoint',
 view_detail=True (the reference itself raises NameError there).  `prop_bi_seg`
 ([B,72,1,1152,80], unused downstream) and the dead `endpoint` map are not produced.
 """
@@ -35,6 +37,21 @@ class _ConvPool2d(nn.Module):
         for a, b in zip([cin] + hidden, hidden + [cout]):
             layers.append(nn.Sequential(nn.ReLU(inplace=True), nn.BatchNorm2d(a), nn.Conv2d(a, b, 3, 2, 1)))
         self.layers = nn.ModuleList(layers)
+
+
+SUPPORTED_GEOMETRIES = ((72, 2), (36, 4), (18, 8))     # (num_prop, prop_width); prop_half_buff = 4, num_prop * prop_width = 144
+SUPPORTED_HALF_BUFF = 4
+MAX_DIM_SHARED = 512
+
+
+def check_geometry(num_prop, prop_width, prop_half_buff, dim_shared):
+    """Raise NotImplementedError unless the device path covers this head geometry."""
+    if ((num_prop, prop_width) not in SUPPORTED_GEOMETRIES or prop_half_buff != SUPPORTED_HALF_BUFF
+            or dim_shared % 4 or not 0 < dim_shared <= MAX_DIM_SHARED):
+        raise NotImplementedError(
+            f'ColumnProposal2 geometry num_prop={num_prop}, prop_width={prop_width}, prop_half_buff={prop_half_buff}, '
+            f'dim_shared={dim_shared}: the device path covers (num_prop, prop_width) in {list(SUPPORTED_GEOMETRIES)} with '
+            f'prop_half_buff={SUPPORTED_HALF_BUFF} and dim_shared a multiple of 4 up to {MAX_DIM_SHARED}')
 
 
 def _conv1d_stack(cin, hidden, cout):
@@ -108,6 +125,8 @@ class ColumnProposal2(PackedModule):
         P['s1'], P['b1'] = torch.cat(sc).contiguous(), torch.cat(sh).contiguous()
         P['w2'] = torch.cat([s[2].weight[:, :, 0] for s in stacks], dim=0).float().contiguous()
         P['b2'] = torch.cat([s[2].bias for s in stacks]).float().contiguous()
+        if self.prop_fea_width != 10:        # stage 2 as three 1x1 small convs (ops.head_stage2)
+            P['w2.small'] = [ops.pack_small(s[2].weight[:, :, :, None]) for s in stacks]
         lin = self.proposal_confidence[1]
         cw = lin.in_features // self.row_size
         P['conf.w'] = lin.weight.reshape(2, cw, self.row_size).permute(0, 2, 1).reshape(2, -1).float().contiguous()
@@ -131,8 +150,7 @@ class ColumnProposal2(PackedModule):
         cfg = self.cfg
         if cfg.column_att or cfg.column_transformer_decoder:
             raise NotImplementedError('column_att / column_transformer_decoder are off in every BASELINE config')
-        if self.prop_fea_width != 10 or self.dim_shared * 3 > 320:
-            raise NotImplementedError('hot path covers prop_fea_width == 10 and dim_shared <= 106')
+        check_geometry(self.num_prop, self.prop_width, self.prop_half_buff, self.dim_shared)
         P = self.packed()
         B, _, h, w = x.shape
         self.b_size = B
@@ -151,9 +169,9 @@ class ColumnProposal2(PackedModule):
         else:                                                                                       # :403-404 raw row window
             tok = ops.head_tokens(None, row, self.num_prop, self.prop_width, self.prop_half_buff, 0.)
         D = self.dim_shared
-        hid = torch.empty((tok.shape[0], 320), device=x.device, dtype=torch.float32)
+        hid = torch.empty((tok.shape[0], -(-3 * D // 64) * 64), device=x.device, dtype=torch.float32)   # 320 columns at D = 100
         ops.linear_mfma(tok, P['w1'], 3 * D, scale=P['s1'], shift=P['b1'], out=hid)
-        ext2, cls2, off2 = ops.head_stage2(hid, D, P['w2'], P['b2'], B, self.num_prop, h)
+        ext2, cls2, off2 = ops.head_stage2(hid, D, P['w2'], P['b2'], B, self.num_prop, h, w_small=P.get('w2.small'))
         conf = ops.head_proposal_conf(tok, P['conf.w'], P['conf.b'], B, self.num_prop)
         return {'proposal_conf': conf, 'ext2': ext2, 'cls2': cls2, 'offset2': off2, 'orient': orient}
 

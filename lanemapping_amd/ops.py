@@ -474,12 +474,12 @@ def attention(qkv, B, N, heads, dim_head, scale, valid=None):
 
 # ------------------------------------------------------------------------------- head
 def head_tokens(seg, row, P, prop_width, half_buff, seg_bias):
-    """seg [B,1,288,288], row [B,16,144,144] (NHWC-stored) -> tok [B*P*144, 160].
+    """seg [B,1,288,288], row [B,16,144,144] (NHWC-stored) -> tok [B*P*144, 16*FW], FW = prop_width + 2*half_buff (10, 12 or 16).
     seg None: spatial_att=False, the tokens are the raw row windows."""
     row, ld = as_nhwc(row)
     B, C_, Hr, Wr = row.shape
     assert C_ == 16 and ld == 16
-    tok = torch.empty((B * P * Hr, 160), device=row.device, dtype=torch.float32)
+    tok = torch.empty((B * P * Hr, 16 * (prop_width + 2 * half_buff)), device=row.device, dtype=torch.float32)
     if seg is None:
         check(lib().lm_head_tokens_window(_stream(), _ptr(row), _ptr(tok), B, P, Hr, Wr, prop_width, half_buff))
         return tok
@@ -488,12 +488,29 @@ def head_tokens(seg, row, P, prop_width, half_buff, seg_bias):
     return tok
 
 
-def head_stage2(hid, D, w2, b2, B, P, R):
+def head_stage2(hid, D, w2, b2, B, P, R, w_small=None):
+    """Second Conv1d of ext2 / cls2 / offset2 on the hidden rows hid [M, >= 3D] (ext | cls | off, D each): w2 [3 + 2 FW, D], b2 [3 + 2 FW]
+    -> ext2 [B,P,R,3], cls2 / off2 [B,P,R,FW].  FW = 10: lm_head_stage2.  Other widths: w_small = the three branches' weights packed by
+    pack_small, each branch one 1x1 lm_conv2d_nhwc_small over its slice of the hidden rows (row pitch hid.stride(0), bias as shift)."""
     M = hid.shape[0]
+    FW = (w2.shape[0] - 3) // 2
+    assert w2.shape == (3 + 2 * FW, D) and b2.numel() == 3 + 2 * FW and hid.shape[1] >= 3 * D and hid.stride(1) == 1
     ext2 = torch.empty((B, P, R, 3), device=hid.device, dtype=torch.float32)
-    cls2 = torch.empty((B, P, R, 10), device=hid.device, dtype=torch.float32)
-    off2 = torch.empty((B, P, R, 10), device=hid.device, dtype=torch.float32)
-    check(lib().lm_head_stage2(_stream(), _ptr(hid), hid.stride(0), D, _ptr(w2), _ptr(b2), _ptr(ext2), _ptr(cls2), _ptr(off2), M))
+    cls2 = torch.empty((B, P, R, FW), device=hid.device, dtype=torch.float32)
+    off2 = torch.empty((B, P, R, FW), device=hid.device, dtype=torch.float32)
+    if FW == 10:
+        check(lib().lm_head_stage2(_stream(), _ptr(hid), hid.stride(0), D, _ptr(w2), _ptr(b2), _ptr(ext2), _ptr(cls2), _ptr(off2), M))
+        return ext2, cls2, off2
+    if w_small is None:
+        raise ValueError(f'head_stage2: prop_fea_width {FW} runs through lm_conv2d_nhwc_small and needs the pack_small weights')
+    bounds = (0, 3, 3 + FW, 3 + 2 * FW)
+    for br, (y, w16) in enumerate(zip((ext2, cls2, off2), w_small)):
+        n = bounds[br + 1] - bounds[br]
+        assert tuple(w16.shape) == (1, D, 16)
+        x = hid[:, br * D:(br + 1) * D]
+        shift = b2[bounds[br]:bounds[br + 1]]
+        check(lib().lm_conv2d_nhwc_small(_stream(), _ptr(x), hid.stride(0), _ptr(w16), None, _ptr(shift), _ptr(y), n,
+                                         1, 1, M, D, n, 1, 1, 1, 0, 0, 0, ACT_NONE))
     return ext2, cls2, off2
 
 
@@ -527,11 +544,12 @@ def pack_readback(tensors, block=None):
 
 
 def decode_proposals(pconf, ext2, cls2, off2, exist_thre, prop_width, half_buff):
-    B, P, R, _ = cls2.shape
+    B, P, R, FW = cls2.shape
+    assert FW == prop_width + 2 * half_buff and off2.shape[-1] == FW, 'cls2 / offset2 are prop_fea_width wide'
     dev = cls2.device
     prop_conf = torch.empty((B, P, 2), device=dev, dtype=torch.float32)
     v_ext = torch.empty((B, P, R), device=dev, dtype=torch.float32)
-    cls_conf = torch.empty((B, P, R, 10), device=dev, dtype=torch.float32)
+    cls_conf = torch.empty((B, P, R, FW), device=dev, dtype=torch.float32)
     cls_idx = torch.empty((B, P, R), device=dev, dtype=torch.int32)
     cls_offset = torch.empty((B, P, R), device=dev, dtype=torch.float64)
     check(lib().lm_decode_proposals(_stream(), _ptr(pconf.contiguous()), _ptr(ext2.contiguous()), _ptr(cls2.contiguous()),

@@ -169,6 +169,10 @@ class TilePipeline:
             lanes, kept = hostpost.assemble_polylines(host['prop_conf'][b].numpy(), host['v_ext'][b].numpy(),
                                                       host['cls_offset'][b].numpy(), host['rows'][b].numpy(), pts,
                                                       self.cfg.proposal_obj_thre)
+            if lanes.shape[0] < 72:                             # num_prop 36 / 18: padded into the same [72,144,2] block
+                pad = np.full((72 - lanes.shape[0],) + lanes.shape[1:], -1.0)
+                pad[:, :, 1] = 0.0
+                lanes = np.concatenate([lanes, pad])
         dt = time.perf_counter() - t0
         with self._stats_lock:                              # pool threads finish tiles concurrently
             self.host_seconds += dt

@@ -183,8 +183,8 @@ def _decode_proposals(pconf: Tensor, ext2: Tensor, cls2: Tensor, off2: Tensor, e
 
 
 def _decode_proposals_fake(pconf, ext2, cls2, off2, exist_thre, prop_width, half_buff):
-    B, P, R, _ = cls2.shape
-    return (cls2.new_empty((B, P, 2)), cls2.new_empty((B, P, R)), cls2.new_empty((B, P, R, 10)),
+    B, P, R, FW = cls2.shape
+    return (cls2.new_empty((B, P, 2)), cls2.new_empty((B, P, R)), cls2.new_empty((B, P, R, FW)),
             cls2.new_empty((B, P, R), dtype=torch.int32), cls2.new_empty((B, P, R), dtype=torch.float64))
 
 
@@ -308,8 +308,8 @@ def _colprop_head(x: Tensor, col: Tensor, weights: List[Tensor], stage: str) -> 
 
 def _colprop_head_fake(x, col, weights, stage):
     m = _stage(stage)
-    B, R, P = x.shape[0], x.shape[2], m.num_prop
-    return (x.new_empty((B, P, 2)), x.new_empty((B, P, R, 3)), x.new_empty((B, P, R, 10)), x.new_empty((B, P, R, 10)),
+    B, R, P, FW = x.shape[0], x.shape[2], m.num_prop, m.prop_fea_width
+    return (x.new_empty((B, P, 2)), x.new_empty((B, P, R, 3)), x.new_empty((B, P, R, FW)), x.new_empty((B, P, R, FW)),
             _fake_act(x, B, m.num_orients, x.shape[2], x.shape[3]))
 
 
