@@ -124,6 +124,7 @@ int lm_upsample_bilinear_nhwc(void* stream, const float* x, int ldx, const float
                               int B, int Hi, int Wi, int Ho, int Wo, int C);
 int lm_upsample_bilinear_to_chw(void* stream, const float* x, int ldx, float* y_chw, int B, int Hi, int Wi,
                                 int Ho, int Wo, int C);
+/* nn.LayerNorm over rows of D floats: D % 32 == 0, 32 <= D <= 4096, D != 768 */
 int lm_layernorm_rows(void* stream, const float* x, const float* gamma, const float* beta, float* y,
                       long rows, int D, float eps);
 int lm_unpatchify(void* stream, const float* tokens, float* y_nhwc, int B, int G, int P, int C);
@@ -134,7 +135,8 @@ int lm_unpatchify(void* stream, const float* tokens, float* y_nhwc, int B, int G
 int lm_token_mix_mfma_f32(void* stream, const float* x, const float* wt, int ldw, const float* bias, const float* res, float* y,
                           int B, int M, int K, int N, int act);
 
-/* ---- attention core: softmax(q k^T * scale) v per (batch, head); qkv = [B*N][3*heads*64] (vitsegnet.py:58-68) */
+/* ---- attention core: softmax(q k^T * scale) v per (batch, head); qkv = [B*N][3*heads*64] (vitsegnet.py:58-68).  Any N >= 1: N >= 382
+ * (ViT patches 6 / 4) streams K / V through LDS with an online softmax; deterministic, no workspace. */
 int lm_attention_f32(void* stream, const float* qkv, float* out, int B, int N, int heads, int dim_head, float scale);
 /* the same with a key mask, valid [B][N] ints (N <= 64): per batch element only the flagged tokens are keys, compacted in token order
  * (row_shared_not_reduc_ref.py:199-215: the transformer runs over the data-dependent subset of the lane tokens) */

@@ -2,7 +2,8 @@
 
 Drop-in for baseline/models/backbone/vitsegnet.py:132-214 (same kwargs, same state-dict keys:
 ``to_patch_embedding.1``, ``pos_embedding``, ``transformer.layers.{l}.{0,1}.{norm,fn...}``).
-Kernels: patch embedding = 8x8/stride-8 implicit GEMM straight from the NHWC feature map (no patchify
+Geometries: square patches 4 / 6 / 8 / 12 / 16 (check_vit_geometry).
+Kernels: patch embedding = pxp/stride-p implicit GEMM straight from the NHWC feature map (no patchify
 copy) with the positional embedding added in the epilogue; LayerNorm rows; QKV / out-proj / MLP GEMMs
 on lm_conv2d_nhwc_mfma_f32 with bias + residual + erf-GELU epilogues; lm_attention_f32.
 
@@ -77,6 +78,26 @@ def pack_transformer(layers, P, prefix):
         P[k + '.fc2.b'] = ff.fn.net[3].bias.float().contiguous()
 
 
+SUPPORTED_PATCHES = (4, 6, 8, 12, 16)
+MAX_DIM = 4096
+
+
+def check_vit_geometry(patch, dim, shared_mlp, blocks=()):
+    """Raise NotImplementedError unless the device path covers this VitSegNet geometry; blocks: (heads, dim_head, mlp_dim) per
+    transformer block.  The multiples of 32 are the GEMMs' k-slab (every K that lm_conv2d_nhwc_mfma_f32 sees); LayerNorm takes
+    D % 32 == 0 up to 4096 except 768, attention dim_head 64."""
+    ok = patch in SUPPORTED_PATCHES and dim % (patch * patch) == 0 and dim % 32 == 0 and 0 < dim <= MAX_DIM and dim != 768
+    ok = ok and not (shared_mlp and dim // (patch * patch) % 32)
+    ok = ok and all(dim_head == 64 and heads >= 1 and not (heads == 1 and dim_head == dim) and mlp_dim > 0 and mlp_dim % 32 == 0
+                    for heads, dim_head, mlp_dim in blocks)
+    if not ok:
+        raise NotImplementedError(
+            f'VitSegNet geometry patch={patch}, dim={dim}, is_with_shared_mlp={bool(shared_mlp)}, (heads, dim_head, mlp_dim)='
+            f'{sorted(set(blocks))}: the device path covers square patches in {list(SUPPORTED_PATCHES)}, dim a multiple of 32 and of '
+            f'patch^2 up to {MAX_DIM} (not 768), dim_head=64 with heads >= 1 (not heads=1 with dim_head=dim), int(dim * expansion_factor) a '
+            f'multiple of 32, and with is_with_shared_mlp dim / patch^2 a multiple of 32')
+
+
 @BACKBONE.register_module
 class VitSegNet(PackedModule):
     def __init__(self, image_size=144, patch_h_size=8, patch_w_size=8, channels=64, dim=512, depth=5, heads=16,
@@ -101,7 +122,7 @@ class VitSegNet(PackedModule):
         P = {}
         lin = self.to_patch_embedding[1]
         p = self.patch
-        # Linear weight columns are ordered (p1 p2 c) == (kh kw cin) of an 8x8/stride-8 conv over NHWC
+        # Linear weight columns are ordered (p1 p2 c) == (kh kw cin) of a pxp/stride-p conv over NHWC
         w = lin.weight.reshape(self.dim, p, p, self.channels).permute(0, 3, 1, 2)
         P['embed.w'] = ops.pack_mfma(w)
         P['embed.b'] = lin.bias.float().contiguous()
@@ -118,6 +139,8 @@ class VitSegNet(PackedModule):
         return torch_ops.vit_backbone(img, torch_ops.stage_weights(self), torch_ops.stage_name(self))
 
     def _forward_impl(self, img):
+        check_vit_geometry(self.patch, self.dim, self.is_with_shared_mlp,
+                           [(a.fn.heads, a.fn.dim_head, f.fn.net[0].out_features) for a, f in self.transformer.layers])
         P = self.packed()
         B = img.shape[0]
         N = self.grid * self.grid

@@ -8,7 +8,7 @@
 //  lm_upsample_bilinear_nhwc  : F.interpolate(mode='bilinear', align_corners=True) (+ optional add)
 //                               (postprojector.py:541-561; heads/polyline_fpn_vit_vertex_2.py:298-300)
 //  lm_upsample_bilinear_to_chw: same, NHWC source -> planar [B,C,Ho,Wo] destination (bi_seg / endp maps)
-//  lm_layernorm_rows          : nn.LayerNorm(dim) eps 1e-5 over rows (vitsegnet.py:20-26)
+//  lm_layernorm_rows          : nn.LayerNorm(dim) eps 1e-5 over rows (vitsegnet.py:20-26), D % 32 == 0 up to 4096 but 768
 //  lm_unpatchify              : 'b (h w) (p1 p2 c) -> b c (h p1) (w p2)' into NHWC (vitsegnet.py:180)
 //
 // Bilinear source index follows ATen: scale = (in-1)/(out-1) in fp32, src = scale*dst,
@@ -658,6 +658,43 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     }
 }
 
+// The other widths (D % 32 == 0, 32 <= D <= 4096, not 768; the ViT at patch sizes 4 / 6 / 12 / 16 has D = 128 / 288 / 1152 / 2048): the same
+// one-wave-per-row, two-pass arithmetic with PER * 64 >= D columns per lane slot and the columns >= D masked out.  A masked column
+// holds 0 and adds 0 to the lane's sum, so each lane's sums and the butterfly run in the same order as in layernorm_kernel.
+template <int PER>
+__global__ __launch_bounds__(256) void layernorm_masked_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                               const float* __restrict__ beta, float* __restrict__ y, long rows, int D,
+                                                               float eps) {
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const float* xr = x + row * D;
+    float v[PER];
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const int c = k * 64 + lane;
+        v[k] = c < D ? xr[c] : 0.f;
+        s += v[k];
+    }
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    const float mean = s / (float)D;
+    float q = 0.f;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const float d = k * 64 + lane < D ? v[k] - mean : 0.f;
+        q += d * d;
+    }
+    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
+    const float rstd = 1.0f / sqrtf(q / (float)D + eps);
+    float* yr = y + row * D;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const int c = k * 64 + lane;
+        if (c < D) yr[c] = (v[k] - mean) * rstd * gamma[c] + beta[c];
+    }
+}
+
 __global__ __launch_bounds__(256) void unpatchify_kernel(const float* __restrict__ t, float* __restrict__ y, int G, int P,
                                                          int C, long total) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;   // index into NHWC output [B, G*P, G*P, C]
@@ -851,11 +888,18 @@ LM_API int lm_upsample_bilinear_to_chw(void* stream, const float* x, int ldx, fl
 
 LM_API int lm_layernorm_rows(void* stream, const float* x, const float* gamma, const float* beta, float* y,
                              long rows, int D, float eps) {
-    LM_REQUIRE(x && gamma && beta && y && (D == 512 || D == 1024), "layernorm: D=%d must be 512 or 1024", D);
+    // D = 768 stays refused as it always was: the entry-point tests pin that refusal, and no reference config uses it
+    LM_REQUIRE(x && gamma && beta && y && D >= 32 && D <= 4096 && D % 32 == 0 && D != 768,
+               "layernorm: D=%d must be 512 or 1024, or another multiple of 32 in [32, 4096] except 768", D);
+    const dim3 grid(lm_cdiv(rows, 4));
+    hipStream_t s = (hipStream_t)stream;
     if (D == 512)
-        hipLaunchKernelGGL(layernorm_kernel<8>, dim3(lm_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, rows, eps);
-    else
-        hipLaunchKernelGGL(layernorm_kernel<16>, dim3(lm_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, rows, eps);
+        hipLaunchKernelGGL(layernorm_kernel<8>, grid, dim3(256), 0, s, x, gamma, beta, y, rows, eps);
+    else if (D == 1024)
+        hipLaunchKernelGGL(layernorm_kernel<16>, grid, dim3(256), 0, s, x, gamma, beta, y, rows, eps);
+#define LM_LN_MASKED(PER) else if (D <= PER * 64) hipLaunchKernelGGL(layernorm_masked_kernel<PER>, grid, dim3(256), 0, s, x, gamma, beta, y, rows, D, eps);
+    LM_LN_MASKED(1) LM_LN_MASKED(2) LM_LN_MASKED(4) LM_LN_MASKED(8) LM_LN_MASKED(16) LM_LN_MASKED(32) LM_LN_MASKED(64)
+#undef LM_LN_MASKED
     LM_LAUNCH_CHECK();
     return LM_OK;
 }

@@ -4,8 +4,9 @@
 // to_qkv output [B*N, 3*H*64] (q | k | v, each laid out 'b n (h d)'), out is 'b n (h d)'.
 // The projections themselves run on lm_conv2d_nhwc_mfma_f32.
 //
-// Two kernels: attention_mfma_kernel (below) for the ViT block's 324 tokens, and this VALU kernel for every other
-// sequence length (the RowRef head's few lane tokens).
+// Three kernels: attention_mfma_kernel (below) for the ViT block's 324 tokens at patch 8, attention_flash_kernel (below) for the
+// longer sequences of patches 6 / 4 / 2 (N >= 382), and this VALU kernel for every other sequence length (the RowRef head's few lane
+// tokens, the 144 / 81 tokens of patches 12 / 16).
 // VALU kernel: one workgroup = one (batch, head, 36-query chunk).  K (then V, re-using the same LDS) for the
 // whole head is staged once: 324 x 64 fp32 = 83 KB of the CU's 160 KB LDS; the 36 x 324 score
 // block stays in LDS as well, so scores never touch HBM.  Fixed summation order => deterministic.
@@ -223,6 +224,110 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(const float* __rest
     }
 }
 
+// ---- Flash-style MFMA kernel for long sequences (every N the two kernels above cannot hold: N >= 382) --------------------------
+// One workgroup = (batch, head, 4 query tiles of 32), one wave per query tile, Q fragments in registers exactly as in
+// attention_mfma_kernel.  K and V stream through LDS in stages of FKB = 64 keys (two MFMA key blocks of 32; keys >= N are zero rows
+// and masked to -inf), and the softmax is online: per 32-key block the lane's query takes the block max (its 16 registers plus
+// lane ^ 32), rescales its running sum and its 32 output registers by exp(m_old - m_new) and adds the block's P V^T.  Each output row
+// is reduced over the key blocks in ascending order, whatever B, the grid or the schedule; no atomics.  LDS: 35 KB per workgroup
+// (four per CU), never a whole head; no score matrix.
+constexpr int FKB = 64;            // keys per LDS stage
+constexpr int VP = DH + 8;         // padded V row (floats): rows r and r + 4 of one PV read land on disjoint banks
+
+// 125 VGPRs with amdgpu_waves_per_eu(4), no spills: the LDS allows four workgroups per CU and the registers now do as well (the default
+// allocation, 122 VGPRs + 48 AGPRs, held the CU to two), so a wave waiting at a stage barrier leaves three to feed the matrix core.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void attention_flash_kernel(
+    const float* __restrict__ qkv, float* __restrict__ out, int N, int heads, float scale) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];      // K: [FKB][KP], V: [FKB][VP]
+    float* Ks = smem;
+    float* Vs = smem + FKB * KP;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int h = blockIdx.y, b = blockIdx.z;
+    const int inner = heads * DH, ld = 3 * inner;
+    const long row0 = (long)b * N;
+    const int col = lane & 31, half = lane >> 5;
+    const int q = (blockIdx.x * 4 + wave) * 32 + col;                 // this lane's query (MFMA column)
+    f32x4 qf[8];
+#pragma unroll
+    for (int g = 0; g < 8; ++g) {
+        qf[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (q < N) qf[g] = *reinterpret_cast<const f32x4*>(qkv + (row0 + q) * ld + h * DH + 8 * g + 4 * half);
+    }
+    f32x16 o[2];
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
+    float m = -INFINITY, l = 0.f;      // running max (shared with lane ^ 32) and this lane's share of the running sum
+    for (int k0 = 0; k0 < N; k0 += FKB) {
+        __syncthreads();               // every wave is done with the previous stage
+        for (int i = tid; i < FKB * (DH / 4); i += 256) {
+            const int n = i >> 4, c4 = (i & 15) * 4;
+            f32x4 kv = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
+            if (k0 + n < N) {
+                const float* src = qkv + (row0 + k0 + n) * ld + inner + h * DH + c4;
+                kv = *reinterpret_cast<const f32x4*>(src);
+                vv = *reinterpret_cast<const f32x4*>(src + inner);
+            }
+            *reinterpret_cast<f32x4*>(Ks + n * KP + c4) = kv;
+            *reinterpret_cast<f32x4*>(Vs + n * VP + c4) = vv;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int sb = 0; sb < FKB / 32; ++sb) {
+            const int kb0 = k0 + sb * 32;
+            if (kb0 >= N) break;       // workgroup-uniform: a ragged last stage has one key block
+            f32x16 s;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[r] = 0.f;
+#pragma unroll
+            for (int g = 0; g < 8; ++g) {
+                const f32x4 kf = *reinterpret_cast<const f32x4*>(Ks + (sb * 32 + col) * KP + 8 * g + 4 * half);
+#pragma unroll
+                for (int t = 0; t < 4; ++t) s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[t], qf[g][t], s, 0, 0, 0);
+            }
+            // register r is key kb0 + (r&3) + 8(r>>2) + 4*half; key kb0 < N, so the block max is finite
+            float mb = m;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int key = kb0 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                s[r] = key < N ? s[r] * scale : -INFINITY;
+                mb = fmaxf(mb, s[r]);
+            }
+            mb = fmaxf(mb, __shfl_xor(mb, 32));
+            const float alpha = expf(m - mb);                          // 0 on the first block (m = -inf), 1 while the max holds
+            m = mb;
+            float ps = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                s[r] = expf(s[r] - m);
+                ps += s[r];
+            }
+            l = l * alpha + ps;
+            o[0] *= alpha;
+            o[1] *= alpha;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float* vrow = Vs + (sb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * VP + col;
+                o[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(vrow[0], s[r], o[0], 0, 0, 0);
+                o[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(vrow[32], s[r], o[1], 0, 0, 0);
+            }
+        }
+    }
+    l += __shfl_xor(l, 32);
+    if (q < N) {
+        const float inv = 1.0f / l;
+        float* orow = out + (row0 + q) * inner + h * DH;
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+            for (int r4 = 0; r4 < 4; ++r4) {
+                f32x4 v = {o[dt][4 * r4] * inv, o[dt][4 * r4 + 1] * inv, o[dt][4 * r4 + 2] * inv, o[dt][4 * r4 + 3] * inv};
+                *reinterpret_cast<f32x4*>(orow + dt * 32 + 8 * r4 + 4 * half) = v;
+            }
+    }
+}
+
 }  // namespace
 
 LM_API int lm_attention_f32(void* stream, const float* qkv, float* out, int B, int N, int heads, int dim_head, float scale) {
@@ -237,7 +342,14 @@ LM_API int lm_attention_f32(void* stream, const float* qkv, float* out, int B, i
         return LM_OK;
     }
     const size_t lds = ((size_t)N * KLD + (size_t)QC * (N + 4) + QC * DH) * sizeof(float);
-    LM_REQUIRE(lds <= 160 * 1024, "attention: N=%d does not fit LDS", N);
+    if (lds > 160 * 1024) {                 // N >= 382 (patch sizes 6, 4, 2: 576, 1296, 5184 tokens): stream K / V
+        const size_t lds_f = (size_t)FKB * (KP + VP) * sizeof(float);
+        if (int e = lm_ensure_dynamic_lds((const void*)attention_flash_kernel, lds_f)) return e;
+        hipLaunchKernelGGL(attention_flash_kernel, dim3(lm_cdiv(lm_cdiv(N, 32), 4), heads, B), dim3(256), lds_f, (hipStream_t)stream, qkv,
+                           out, N, heads, scale);
+        LM_LAUNCH_CHECK();
+        return LM_OK;
+    }
     if (int e = lm_ensure_dynamic_lds((const void*)attention_kernel, lds)) return e;
     hipLaunchKernelGGL(attention_kernel, dim3(lm_cdiv(N, QC), heads, B), dim3(256), lds, (hipStream_t)stream, qkv, out, N, heads, scale,
                        (const int*)nullptr);
