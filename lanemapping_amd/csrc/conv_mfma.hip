@@ -655,11 +655,7 @@ static int conv_dispatch(void* stream, const float* x, int ldx, const float* wp,
     // 64 x 64 tiles (78 -> 92 TFLOP/s); N = 3072 (984 big tiles, 3.84 rounds) is better left on 128 x 128: 0.463 vs 0.476.  LM_CONV_SMALLM overrides)
     static const long small_m = [] { const char* e = getenv("LM_CONV_SMALLM"); return e ? atol(e) : 700L; }();
     if (big_blocks < small_m) return launch<64, 64, 32, 32>(p, s);
-#ifdef LM_CONV_8WAVES
-    return launch<128, 128, 64, 32>(p, s);
-#else
     return launch<128, 128, 64, 64>(p, s);
-#endif
 }
 
 LM_API int lm_conv2d_nhwc_mfma_f32(void* stream, const float* x, int ldx, const float* wp, int CoutP,

@@ -76,11 +76,7 @@ constexpr int QGRP = 256 + 8;                   // floats between the 16-cell gr
                                                 // bytes move consecutive groups by 8 banks - see roff in wino44_kernel
 constexpr int QRAWF = QLPW * 4 * QGRP;          // floats of one raw buffer (57.75 KB; cells 864.. are zero-source padding)
 constexpr int QVF = 36 * 256;                   // floats of the V buffer: 36 planes x [4 channel pairs][32 tiles][2]
-#ifndef LM_QBD
-#define LM_QBD 5
-#define LM_QRING 6
-#endif
-constexpr int QBD = LM_QBD, QRING = LM_QRING;   // B fragments run QBD steps ahead in a ring of QRING register sets
+constexpr int QBD = 5, QRING = 6;               // B fragments run QBD steps ahead in a ring of QRING register sets
 static_assert(6 * (QNCELL / 16) * QGRP <= QRAWF && QNCELL % 16 == 0, "patch loads cover the unit");
 
 __device__ __attribute__((aligned(16))) float g_w44_zeros[1024 + 32];   // zero source for padding cells, any channel unit (Cin <= 1024)
@@ -294,34 +290,6 @@ struct W44Params {
 
 // packed fp32 pairs (two channels of a lane).  Plain asm (not volatile): the scheduler may move them, the arithmetic is fixed.
 // (the multiplier b is one of three wave-uniform constant pairs: an SGPR-pair operand - with a "v" constraint every use cost a v_mov_b64)
-#ifdef LM_W44_SCALAR_XF
-// experiment: the same operations as plain (unpacked) f32 VALU instructions, two per pair (MI355X_MICROARCH.md: packed f32 VALU beside MFMAs
-// costs ~11-13 cycles beyond its issue slot, plain v_fma_f32 / v_add_f32 are hidden fillers)
-__device__ __forceinline__ float sc_fma(float a, float b, float c) {
-    float r;
-    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(b), "v"(c));
-    return r;
-}
-__device__ __forceinline__ float sc_fnma(float a, float b, float c) {
-    float r;
-    asm("v_fma_f32 %0, -%1, %2, %3" : "=v"(r) : "v"(a), "s"(b), "v"(c));
-    return r;
-}
-__device__ __forceinline__ float sc_add(float a, float b) {
-    float r;
-    asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float sc_sub(float a, float b) {
-    float r;
-    asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ f32x2 pk_fma(const f32x2 a, const f32x2 b, const f32x2 c) { return f32x2{sc_fma(a[0], b[0], c[0]), sc_fma(a[1], b[0], c[1])}; }
-__device__ __forceinline__ f32x2 pk_fnma(const f32x2 a, const f32x2 b, const f32x2 c) { return f32x2{sc_fnma(a[0], b[0], c[0]), sc_fnma(a[1], b[0], c[1])}; }
-__device__ __forceinline__ f32x2 pk_add(const f32x2 a, const f32x2 b) { return f32x2{sc_add(a[0], b[0]), sc_add(a[1], b[1])}; }
-__device__ __forceinline__ f32x2 pk_sub(const f32x2 a, const f32x2 b) { return f32x2{sc_sub(a[0], b[0]), sc_sub(a[1], b[1])}; }
-#else
 __device__ __forceinline__ f32x2 pk_fma(const f32x2 a, const f32x2 b, const f32x2 c) {          // a b + c
     f32x2 r;
     asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(b), "v"(c));
@@ -342,7 +310,6 @@ __device__ __forceinline__ f32x2 pk_sub(const f32x2 a, const f32x2 b) {
     asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
-#endif
 
 struct W44K {
     f32x2 c2, c4, c5;
@@ -431,11 +398,7 @@ __device__ __forceinline__ void w44_vstore(float* v, int j, const f32x2 t) {
 }
 template <int K, bool SPLIT>
 __device__ __forceinline__ void w44_xf_lds(W44Xf& d, const float* rawrow, const int (&roff)[6], float* vA, float* vB, float* vC) {
-#ifdef LM_QABL_NOVST                         // (PMC ablation: the transform without its V stores - whose LDS bank conflicts are they?)
-    auto st = [](float* v, int j, const f32x2 t) { asm volatile("" :: "v"(v), "v"(t)); };
-#else
     auto st = [](float* v, int j, const f32x2 t) { w44_vstore<SPLIT>(v, j, t); };
-#endif
     if constexpr (K == 0) {
         st(vB, 2, d.tB[2]); st(vB, 5, d.tB[5]);
         w44_preread<0>(d, rawrow, roff); w44_preread<1>(d, rawrow, roff);
@@ -499,20 +462,6 @@ __device__ __forceinline__ void q_bwait(f32x4 (&b)[2]) {
     asm volatile("s_waitcnt vmcnt(%2)" : "+v"(b[0]), "+v"(b[1]) : "n"(N) : "memory");
 }
 
-#ifdef LM_QPROF                             // (tools/build_variant.sh probe: per-phase shader-clock cycles of wave 0, one record per workgroup)
-constexpr int QPROF_WG = 16384;
-__device__ unsigned long long g_qprof[QPROF_WG][16];
-__device__ unsigned long long g_qgap[QPROF_WG][3];      // first / last clock of the workgroup and the CU it ran on (lm_qgap_report: idle gaps between workgroups)
-#define LM_QTICK(slot)                                       \
-    {                                                        \
-        const long long t_now = clock64();                   \
-        qprof[slot] += t_now - t_last;                       \
-        t_last = t_now;                                      \
-    }
-#else
-#define LM_QTICK(slot)
-#endif
-
 // The wave's 288 accumulator registers exceed the 256 AGPRs: the compiler keeps 32 of them in VGPRs and, left to itself, swaps
 // accumulators between the two files inside the loop (48 v_accvgpr_read + 48 v_accvgpr_write per phase, 8 cycles of matrix time each).
 // The ninth xi therefore accumulates through this wrapper, which pins its two blocks to VGPRs; the other eight fill the AGPRs exactly.
@@ -568,22 +517,14 @@ __device__ __forceinline__ void w44_step(f32x16& acc0, f32x16& acc1, f32x4 (&bq)
     typedef __attribute__((address_space(1))) const void gptr_t;
     typedef __attribute__((address_space(3))) void lptr_t;
     constexpr int K = S % 9;
-#ifndef LM_QABL_NOB
     q_bload2(bq[(S + QBD) % QRING], bvoff, bpre);
-#endif
-#ifndef LM_QABL_NOGLDS
 #pragma unroll
     for (int i = 0; i < q_ndma(S); ++i) {
         constexpr int L0 = q_dma0(S);
         __builtin_amdgcn_global_load_lds((gptr_t*)(gsrc[L0 + i] + goff), (lptr_t*)(rawld + ((L0 + i) * 4 + wave) * QGRP), 16, 0, 0);
     }
-#endif
     f32x4 (&b)[2] = bq[S % QRING];
-#if !defined(LM_QABL_NOB) && !defined(LM_QABL_NOGLDS)
     q_bwait<q_nwait(S)>(b);
-#else
-    q_bwait<0>(b);
-#endif
     constexpr bool VACC = K == 8;
     // SPLIT: a_cur = {hi 01, hi 23, lo 01, lo 23} of the tile's four channels, b[blk] likewise for the output channel: hi hi, hi lo, lo hi
     const f32x2 a_hi = {a_cur[0], a_cur[1]}, a_lo = {a_cur[2], a_cur[3]};
@@ -594,11 +535,9 @@ __device__ __forceinline__ void w44_step(f32x16& acc0, f32x16& acc1, f32x4 (&bq)
     //  its six MFMAs (192 cycles): the scheduler interleaves them - see the group pattern at the end of the step)
     if constexpr (!SPLIT) __builtin_amdgcn_sched_barrier(0);
     if constexpr (K != 4 && K != 8) a_nxt = q_aread<SPLIT>(anext);
-#ifndef LM_QABL_NOT
     w44_xf_lds<K, SPLIT>(xf, prerow, roff, vA, vB, vC);
     if constexpr (!SPLIT) __builtin_amdgcn_sched_barrier(0);
     w44_xf_valu<K>(xf, lower, kk);
-#endif
     if constexpr (!SPLIT) __builtin_amdgcn_sched_barrier(0);
     if constexpr (SPLIT) {
         q_mfma16<VACC>(acc1, a_hi, f32x2{b[1][0], b[1][1]});
@@ -606,7 +545,6 @@ __device__ __forceinline__ void w44_step(f32x16& acc0, f32x16& acc1, f32x4 (&bq)
         q_mfma16<VACC>(acc1, a_hi, f32x2{b[1][2], b[1][3]});
         q_mfma16<VACC>(acc0, a_lo, f32x2{b[0][0], b[0][1]});
         q_mfma16<VACC>(acc1, a_lo, f32x2{b[1][0], b[1][1]});
-#ifndef LM_SPLIT_NOGROUPS
         if constexpr (!VACC) {           // one MFMA, then a share of the step's VALU / LDS instructions, six times (leftovers follow)
 #pragma unroll
             for (int i = 0; i < 6; ++i) {
@@ -615,7 +553,6 @@ __device__ __forceinline__ void w44_step(f32x16& acc0, f32x16& acc1, f32x4 (&bq)
                 __builtin_amdgcn_sched_group_barrier(0x300, 3, 0);
             }
         }
-#endif
     } else {
         q_mfma<VACC>(acc1, a_cur[0], b[1][0]);
 #pragma unroll
@@ -659,23 +596,13 @@ __device__ __forceinline__ void w44_tail_vec(const f32x4 (&z)[4][6], const f32x4
             if (has_res) v += rpre[yy * 4 + xx];
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = w44_vmax(v[e], relu_lo);
-#ifdef LM_QABL_NOSTORE                       // (timing ablation: keep the values alive, store one of sixteen)
-            if (yy + xx == 0) *reinterpret_cast<f32x4*>(yp + yy * rowstep + xx * colstep) = v;
-            else asm volatile("" :: "v"(v));
-#else
             *reinterpret_cast<f32x4*>(yp + yy * rowstep + xx * colstep) = v;
-#endif
         }
     }
 }
 
 template <bool SPLIT>
 __global__ __launch_bounds__(256) void wino44_kernel(W44Params p) {
-#ifdef LM_QPROF
-    long long qprof[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    long long t_last = clock64();
-    const long long t_first = t_last;
-#endif
     extern __shared__ __attribute__((aligned(16))) float smem[];      // raw[2][QRAWF] | V[QVF]; the epilogue's exchange buffer over all of it
     float* const raw0 = smem;
     float* const Vbuf = smem + 2 * QRAWF;
@@ -747,8 +674,8 @@ __global__ __launch_bounds__(256) void wino44_kernel(W44Params p) {
     // one column of consecutive tiles needs are neighbours in LDS; the 16 cells of a load are contiguous, consecutive loads QGRP floats apart
     const float* gsrc[QLPW];
     const int img_pix0 = bi * g.H * g.W;
-    // Round 5: the set-up was 7.6 k cycles of address arithmetic per workgroup (tools/r4/qprof.py; 7.0 k with every cell served from the
-    // zero block: not memory) - the run search, nine run-time divisions and four exec-masked regions per load.  Now lane l describes
+    // Round 5: the set-up was 7.6 k cycles of address arithmetic per workgroup (profiles/r4_wino44_phase_profile_final.txt,
+    // profiles/r5_wino44_fixed_costs_experiments.txt; 7.0 k with every cell served from the zero block: not memory) - the run search, nine run-time divisions and four exec-masked regions per load.  Now lane l describes
     // tile SLOT l once (x / y pixel of its patch cell (0, 0), patch columns it may fetch: 4 (tiles left in its run) + 2, 0 without a run);
     // a load covers the four slots 4 gq .. 4 gq + 3 of one patch row (q = 4 s + wave = 9 r + gq: wave-uniform) and looks its slot up
     // with three ds_bpermute_b32; masks instead of selects keep the 64-bit offset out of divergent branches.
@@ -778,14 +705,10 @@ __global__ __launch_bounds__(256) void wino44_kernel(W44Params p) {
         const int nn = __builtin_amdgcn_ds_bpermute(idx, tab_n);
         const int yy = y0 + r * g.dil, xx = x0 + gccd;
         const bool ok = (r < 6) & (gcc < nn) & ((unsigned)yy < (unsigned)g.H) & ((unsigned)xx < (unsigned)g.W);
-#ifdef LM_QABL_ZEROSRC                        // (timing ablation: every patch cell comes from the zero block - what do the scattered input lines cost?)
-        gsrc[s_] = p.zeros + (ok ? 0 : 16) + gcq4;
-#else
         const long m = -(long)ok;                         // all ones: the cell exists
         const long eoff = ((long)(img_pix0 + yy * g.W + xx) * p.ldx) & m;
         const unsigned long base = (unsigned long)p.zeros + (((unsigned long)p.x - (unsigned long)p.zeros) & (unsigned long)m);
         gsrc[s_] = (const float*)base + eoff + gcq4;
-#endif
         // unit 0's patch load s goes out as soon as its source is known: issuing a load of cold, scattered lines stalls ~140 cycles
         // (profiles/r4_wino44_residual_issue_experiment.txt) - the address arithmetic of load s + 1 runs meanwhile
         __builtin_amdgcn_global_load_lds((gptr_t*)gsrc[s_], (lptr_t*)(raw0 + (s_ * 4 + wave) * QGRP), 16, 0, 0);
@@ -811,10 +734,6 @@ __global__ __launch_bounds__(256) void wino44_kernel(W44Params p) {
             const int pos = c < 4 ? pos0 + 4 * c : pos1 + 4 * (c - 4);
             roff[c] = (pos >> 4) * QGRP + (pos & 15) * 16 + 2 * cp;
         }
-#ifdef LM_QABL_LINREAD                        // (timing / PMC ablation: conflict-free raw reads by construction - wrong data; the most a better layout can buy)
-#pragma unroll
-        for (int c = 0; c < 6; ++c) roff[c] = c * 64 + tl * 2;
-#endif
         tvoff = SPLIT ? cp * 32 + tl : cp * 64 + tl * 2;
     }
     const bool lower = (wave >> 1) != 0;
@@ -844,7 +763,6 @@ __global__ __launch_bounds__(256) void wino44_kernel(W44Params p) {
     f32x4 bq[QRING][2];
     W44Xf xf;
     const int lowoff = lower ? (QNCELL / 16) * QGRP : 0;               // LOWER threads read patch rows 1..5
-    LM_QTICK(0)
     // prologue: (raw unit 0 was requested while the sources were computed,) B of steps 0 .. QBD-1, THEN raw unit 1: the wait below leaves unit 1's loads (the youngest) in flight - they
     // are only needed before the second slot, and being older than every load of the loop they do not enter its wait counts
 #define LM_QXI(K) (6 * ((K) / 3) + (K) % 3)
@@ -858,15 +776,10 @@ __global__ __launch_bounds__(256) void wino44_kernel(W44Params p) {
     }
     q_bwait<QLPW>(bq[0]);                      // unit 0 and the first B fragments have landed (this wave's part; the barrier collects all parts)
     __builtin_amdgcn_s_barrier();
-    LM_QTICK(1)
     // V(0): the only transform with nothing to hide behind
-#ifndef LM_QABL_NOT
     w44_xf_all<SPLIT>(xf, raw0 + lowoff, roff, vA, vB, vC, lower, kk);
-#endif
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    LM_QTICK(2)
     __builtin_amdgcn_s_barrier();
-    LM_QTICK(3)
 
     // B fragments of step S5 = S + QBD of the unit (S5 >= 18: first slot of the next unit)
 #define LM_QBPRE(S5) ((S5) < 18 ? bu + (long)((S5) / 9) * ustride + (long)LM_QXI((S5) % 9) * xstride : bu_next + (long)LM_QXI((S5) - 18) * xstride)
@@ -875,16 +788,10 @@ __global__ __launch_bounds__(256) void wino44_kernel(W44Params p) {
                 AC, AN, gsrc, goff, rawc_w, wave, xf, (S) < 9 ? rawc + 8 + lowoff : rawn + lowoff, roff, vA, vB, vC, lower, kk)
     // the barrier in the middle of a slot: this wave's late stores (steps 0..3) are done; behind it every wave's are, and the early
     // planes are free (every wave has read V(s)'s in steps 0..4)
-#ifdef LM_QABL_NOMID                          // (timing ablation: what the barrier in the middle of a slot costs; results are wrong)
-#define LM_QMID(AN) AN = q_aread<SPLIT>(Vq + LM_QXI(5) * 256);
-#else
 #define LM_QMID(AN)                                          \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       \
-    LM_QTICK(4)                                              \
     __builtin_amdgcn_s_barrier();                            \
-    LM_QTICK(5)                                              \
     AN = q_aread<SPLIT>(Vq + LM_QXI(5) * 256);
-#endif
     for (int u = 0; u < nun; ++u) {
         const float* const rawc = raw0 + (u & 1) * QRAWF;              // unit u
         float* const rawc_w = raw0 + (u & 1) * QRAWF;                  // ... and the destination of unit u + 2's patch loads (second slot)
@@ -899,22 +806,17 @@ __global__ __launch_bounds__(256) void wino44_kernel(W44Params p) {
         LM_QMID(a1)
         LM_QSTEP(5, a1, a0); LM_QSTEP(6, a0, a1); LM_QSTEP(7, a1, a0); LM_QSTEP(8, a0, a1);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        LM_QTICK(4)
         // unit u + 1 (patch loads of the previous unit's second slot, or of the prologue) is pre-read in the slot that follows: every
         // load older than the 18 B loads of the slot just finished has landed
         q_bwait<2 * 9>(bq[0]);
-        LM_QTICK(6)
         __builtin_amdgcn_s_barrier();          // V(2 u + 1)'s early planes complete
-        LM_QTICK(5)
         // ---- slot 2 u + 1: channels 16 u + 8 .. multiplied, the next unit's first half transformed, unit u + 2's patches requested
         a0 = q_aread<SPLIT>(Vq);
         LM_QSTEP(9, a0, a1);  LM_QSTEP(10, a1, a0); LM_QSTEP(11, a0, a1); LM_QSTEP(12, a1, a0); LM_QSTEP(13, a0, a1);
         LM_QMID(a1)
         LM_QSTEP(14, a1, a0); LM_QSTEP(15, a0, a1); LM_QSTEP(16, a1, a0); LM_QSTEP(17, a0, a1);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        LM_QTICK(4)
         __builtin_amdgcn_s_barrier();
-        LM_QTICK(5)
     }
 #undef LM_QMID
 #undef LM_QSTEP
@@ -924,10 +826,6 @@ __global__ __launch_bounds__(256) void wino44_kernel(W44Params p) {
 #pragma unroll
     for (int k = 0; k < QRING; ++k) q_bwait<0>(bq[k]);
 
-    LM_QTICK(7)
-#ifdef LM_QABL_NOEPI
-    if (p.act != 12345) return;
-#endif
     // ---- epilogue: the products of one 32-channel block go to LDS as M[xi][tile][32 channels] (144 KB; straight from the accumulator
     // registers), every thread takes one (tile, channel quad): 36 ds_read_b128, A^T M A (rows first, then columns: w44_at), tail, 16 stores
     const int etile = tid >> 3, ecq = tid & 7;
@@ -955,7 +853,6 @@ __global__ __launch_bounds__(256) void wino44_kernel(W44Params p) {
     const int ey1 = max(eny - 1, 0), ex1 = max(enx - 1, 0);
     const float relu_lo = p.act == LM_ACT_RELU ? 0.f : -__builtin_inff();               // fmaxf(v, -inf) = v
     const bool has_res = p.res != nullptr, gn = p.gn_part != nullptr;
-    LM_QTICK(8)
 #pragma unroll
     for (int blk = 0; blk < 2; ++blk) {
         const int n = n0 + blk * 32 + ecq * 4;
@@ -983,18 +880,12 @@ __global__ __launch_bounds__(256) void wino44_kernel(W44Params p) {
         // each would be a memory round trip of its own in front of a store (y may alias res as far as the compiler knows).
         // Branch-free: offsets clamped into the tile's valid part (equal to the true offsets wherever an output exists)
         f32x4 rpre[16];
-#ifdef LM_QABL_NORES
-        const bool load_res = false;
-#else
         const bool load_res = vec && has_res;
-#endif
         const float* const rp = p.res + (long)ebase * p.ldr + n;
         const int rs = g.W * g.dil * p.ldr, cs = g.dil * p.ldr;
         // (LDS-only barriers: __syncthreads() would also wait for the previous block's global stores to be acknowledged)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        LM_QTICK(9)
         __builtin_amdgcn_s_barrier();          // patch / V buffers (blk 0) or the previous block's products are no longer read
-        LM_QTICK(10)
 #pragma unroll
         for (int k = 0; k < 9; ++k) {
 #pragma unroll
@@ -1007,9 +898,7 @@ __global__ __launch_bounds__(256) void wino44_kernel(W44Params p) {
             __builtin_amdgcn_sched_barrier(0);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        LM_QTICK(12)
         __builtin_amdgcn_s_barrier();
-        LM_QTICK(13)
         if (n < p.Cout && eny > 0) {
             f32x4 z[4][6];
 #pragma unroll
@@ -1051,20 +940,7 @@ __global__ __launch_bounds__(256) void wino44_kernel(W44Params p) {
                 }
             }
         }
-        LM_QTICK(14)
     }
-#ifdef LM_QPROF
-    if (tid == 0) {
-#pragma unroll
-        for (int k = 0; k < 15; ++k) g_qprof[blockIdx.x % QPROF_WG][k] = (unsigned long long)qprof[k];
-        const long long t_end = clock64();
-        g_qprof[blockIdx.x % QPROF_WG][11] = (unsigned long long)(t_end - t_first);
-        g_qgap[blockIdx.x % QPROF_WG][0] = (unsigned long long)t_first;
-        g_qgap[blockIdx.x % QPROF_WG][1] = (unsigned long long)t_end;
-        g_qgap[blockIdx.x % QPROF_WG][2] = ((unsigned long long)__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) << 16) |     // XCC_ID
-                                           (__builtin_amdgcn_s_getreg((15 << 11) | (0 << 6) | 4) & 0xff00u);                     // HW_ID: cu, sh, se
-    }
-#endif
     if (p.gn_part) {      // fixed-order reduction: the 8 lanes of a wave that share a channel quad, then the four waves through LDS
 #pragma unroll
         for (int blk = 0; blk < 2; ++blk)
@@ -1127,57 +1003,6 @@ int w44_zeros(const float** out) {      // per device (a process may drive sever
 }
 
 }  // namespace
-
-#ifdef LM_QPROF
-extern "C" __attribute__((visibility("default"))) int lm_qprof_read(unsigned long long* out, int reset) {
-    static unsigned long long host[QPROF_WG][16];
-    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_qprof), sizeof(host)) != hipSuccess) return 1;
-    for (int k = 0; k < 17; ++k) out[k] = 0;
-    for (int w = 0; w < QPROF_WG; ++w) {
-        for (int k = 0; k < 16; ++k) out[k] += host[w][k];
-        if (host[w][11]) ++out[16];
-    }
-    if (reset) {
-        static unsigned long long zero[QPROF_WG][16];
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_qprof), zero, sizeof(zero)) != hipSuccess) return 1;
-    }
-    return 0;
-}
-// idle time of a CU between two workgroups of the LAST launch (<= QPROF_WG workgroups): out = {workgroups, CUs seen, mean workgroup cycles,
-// mean gap, median gap, 90th percentile gap, cycles from the first start to the last end, sum of workgroup cycles / (CUs x that span)}
-extern "C" __attribute__((visibility("default"))) int lm_qgap_report(double* out) {
-    static unsigned long long host[QPROF_WG][3];
-    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_qgap), sizeof(host)) != hipSuccess) return 1;
-    struct Rec { unsigned long long id, t0, t1; };
-    static Rec recs[QPROF_WG];
-    int n = 0;
-    for (int w = 0; w < QPROF_WG; ++w)
-        if (host[w][1]) recs[n++] = Rec{host[w][2], host[w][0], host[w][1]};
-    qsort(recs, n, sizeof(Rec), [](const void* a, const void* b) {
-        const Rec* x = (const Rec*)a; const Rec* y = (const Rec*)b;
-        if (x->id != y->id) return x->id < y->id ? -1 : 1;
-        return x->t0 < y->t0 ? -1 : (x->t0 > y->t0 ? 1 : 0);
-    });
-    static double gaps[QPROF_WG];
-    int ng = 0, ncu = 0;
-    double sumd = 0, sumg = 0;
-    unsigned long long tmin = ~0ull, tmax = 0;
-    for (int i = 0; i < n; ++i) {
-        sumd += (double)(recs[i].t1 - recs[i].t0);
-        if (recs[i].t0 < tmin) tmin = recs[i].t0;
-        if (recs[i].t1 > tmax) tmax = recs[i].t1;
-        if (i == 0 || recs[i].id != recs[i - 1].id) { ++ncu; continue; }
-        gaps[ng] = (double)recs[i].t0 - (double)recs[i - 1].t1;
-        sumg += gaps[ng++];
-    }
-    qsort(gaps, ng, sizeof(double), [](const void* a, const void* b) { return *(const double*)a < *(const double*)b ? -1 : (*(const double*)a > *(const double*)b ? 1 : 0); });
-    out[0] = n; out[1] = ncu; out[2] = n ? sumd / n : 0; out[3] = ng ? sumg / ng : 0; out[4] = ng ? gaps[ng / 2] : 0; out[5] = ng ? gaps[(int)(0.9 * ng)] : 0;
-    out[6] = (double)(tmax - tmin); out[7] = (ncu && tmax > tmin) ? sumd / ((double)ncu * (double)(tmax - tmin)) : 0;
-    static unsigned long long zero[QPROF_WG][3];
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_qgap), zero, sizeof(zero)) != hipSuccess) return 1;
-    return 0;
-}
-#endif
 
 // 1 if lm_conv3x3_winograd44_f32 covers the shape
 LM_API int lm_winograd44_supported(int H, int W, int Cin, int dil) {

@@ -53,18 +53,12 @@ namespace {
 // long record runs, half the count rows; 71 KB of LDS = two workgroups per CU) with 3 quads per lane measured 24.3 us per tile against
 // 25.4-25.7 for 256 / 2 on the same box; 1024 threads (one workgroup per CU: its load, sort and write-out phases no longer overlap
 // with another workgroup's) 41 us.
-#ifndef LM_RASTER_NT
-#define LM_RASTER_NT 512
-#endif
-#ifndef LM_RASTER_BQ
-#define LM_RASTER_BQ 3
-#endif
-constexpr int NT = LM_RASTER_NT;       // threads per pass-1 workgroup
+constexpr int NT = 512;                // threads per pass-1 workgroup
 constexpr int PER_THREAD = 32;
 constexpr int CHUNK = NT * PER_THREAD; // points per pass-1 workgroup = record capacity of one (tile, band, workgroup) slot
 constexpr int PART_CAPQ = (NT * 32 + 96 * 3 + 3) / 4;       // quads of the sorted buffer: every band's run is padded to 16 bytes
 constexpr size_t PART_LDS = (size_t)PART_CAPQ * 16 + ((PART_CAPQ + 15) / 16) * 16;
-constexpr int BQ = LM_RASTER_BQ;       // quads per lane of a 16-lane group fetched with a run's first round trip (pass 2)
+constexpr int BQ = 3;                  // quads per lane of a 16-lane group fetched with a run's first round trip (pass 2)
 constexpr int MAX_BANDS = 96;             // (12-row bands of a 1152-row tile)
 constexpr int MAX_TILES = 16;          // tiles per launch (kernel-argument block)
 constexpr int REP = 8;                 // replication of the LDS rank counters (fewer same-address collisions)

@@ -1,6 +1,7 @@
 """Inventory guard (CPU): every `lm_*` entry point declared in include/lanemap_hip.h is exercised by the suite - named directly in a
 tests/ file, or called from the body of a lanemapping_amd/ function that a tests/ file calls - or is listed below with the reason it
-is not.  A new entry point cannot land without a test or a written reason."""
+is not.  A new entry point cannot land without a test or a written reason.  Also: the kernel sources carry no compile-time build
+switches."""
 import ast
 import os
 import re
@@ -84,3 +85,25 @@ def test_every_entry_point_is_tested_or_listed():
     # the exemptions are for queries only: an entry that is tested after all must leave the list
     stale = [n for n in NOT_DIRECTLY_TESTED if re.search(r'\b' + n + r'\b', tests)]
     assert not stale, f'named in tests/ but still listed as not directly tested: {stale}'
+
+
+# the one build of every kernel source is the product build: no compile-time probe or ablation switch may come back.  A conditional may
+# only test __HIPCC__ (host / device split of shared headers), __SSE2__ (host SIMD paths) or be a header's include guard
+PREPROCESSOR_ALLOWED = {'__HIPCC__', '__SSE2__'}
+
+
+def test_kernel_sources_have_no_build_switches():
+    csrc = os.path.join(ROOT, 'lanemapping_amd', 'csrc')
+    bad = []
+    for f in sorted(os.listdir(csrc)):
+        lines = open(os.path.join(csrc, f)).read().splitlines()
+        for i, line in enumerate(lines):
+            m = re.match(r'\s*#\s*(if|ifdef|ifndef|elif)\b(.*)', line)
+            if not m:
+                continue
+            names = set(re.findall(r'[A-Za-z_]\w*', m.group(2).split('//')[0])) - {'defined'}
+            guard = (f.endswith('.h') and m.group(1) == 'ifndef' and i + 1 < len(lines)
+                     and re.match(r'\s*#\s*define\s+' + re.escape(m.group(2).strip()) + r'\s*$', lines[i + 1]))
+            if not guard and not (names and names <= PREPROCESSOR_ALLOWED):
+                bad.append(f'{f}:{i + 1}: {line.strip()}')
+    assert not bad, f'compile-time switches in lanemapping_amd/csrc: {bad}'

@@ -1,11 +1,14 @@
 #!/bin/bash
 # GPU busy fraction and kernel concurrency inside the timed region of the default (two-stream) bench command, from a rocprofv3 kernel
-# trace.  Run through gpurun: tools/gr.sh <dir> 900 'bash tools/r4/timeline_busy.sh'   ($O = gpurun_out/<dir>)
+# trace.  Usage: bash tools/r4/timeline_busy.sh OUTDIR   (OUTDIR relative to the repository root)
+R=$(cd "$(dirname "$0")/../.." && pwd)
+O=${1:?usage: timeline_busy.sh OUTDIR}
+mkdir -p $R/$O
 cd /tmp && export TMPDIR=/tmp
 K=6; W=2
-rocprofv3 --kernel-trace --output-format csv -d $GRAFT_REPO_ROOT/$O/tr -o t -- python3 $GRAFT_REPO_ROOT/bench.py --steps $K --warmup $W --cpu-budget-s 1 > $GRAFT_REPO_ROOT/$O/bench_traced.json 2>/dev/null
-cd $GRAFT_REPO_ROOT
-K=$K W=$W python3 - <<'PY'
+rocprofv3 --kernel-trace --output-format csv -d $R/$O/tr -o t -- python3 $R/bench.py --steps $K --warmup $W --cpu-budget-s 1 > $R/$O/bench_traced.json 2>/dev/null
+cd $R
+O=$O K=$K W=$W python3 - <<'PY'
 import csv, glob, os, collections
 K, W = int(os.environ['K']), int(os.environ['W'])
 f = glob.glob(os.environ['O'] + '/tr/**/*kernel_trace.csv', recursive=True)[0]
