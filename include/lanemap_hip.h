@@ -89,7 +89,8 @@ int lm_gn_finalize_split(void* stream, const double* partial, float* stats, int 
  * (postprojector.py:458-460,566).  maxpool: 3x3 stride 2 pad 1 (:461,567).
  * small: direct conv for Cout <= 16 (feature_layer/output_layer_* :509-511,628-651; head_common_layers,
  * orient, bi_seg_proposal heads/polyline_fpn_vit_vertex_2.py:183-189,232-237,249); w_tc16 = [KH*KW][Cin][16];
- * y = act(conv(pre_relu ? relu(x) : x) * scale + shift). */
+ * y = act(conv(pre_relu ? relu(x) : x) * scale + shift).  Cout = 32, 48 or 64 (generate_line_proposal :48-61):
+ * w_tc16 = Cout/16 consecutive [KH*KW][Cin][16] blocks, block i holding outputs 16 i .. 16 i + 15. */
 int lm_stem_conv7x7_bn_relu(void* stream, const float* x_chw, const float* w_k64, const float* scale,
                             const float* shift, float* y_nhwc, int B, int H, int W);
 /* The stem on a u8 HWC tile [B][H][W][3] as the rasteriser / PNG reader emit it (u8 / 255 = the reference's to_tensor,

@@ -3,8 +3,8 @@
 //  lm_stem_conv7x7_bn_relu : FPNWrapper.conv1 + bn1 + relu      (postprojector.py:458-460,566)  3 -> 64, 7x7 s2 p3
 //  lm_maxpool3x3s2_nhwc    : FPNWrapper.maxpool                  (postprojector.py:461,567)
 //  lm_conv2d_nhwc_small    : feature_layer / output_layer_* 1x1  (postprojector.py:509-511,628-651),
-//                            head_common_layers, orient, bi_seg_proposal
-//                            (heads/polyline_fpn_vit_vertex_2.py:183-189,232-237,249)
+//                            head_common_layers, orient, bi_seg_proposal, generate_line_proposal (column_att)
+//                            (heads/polyline_fpn_vit_vertex_2.py:48-61,183-189,232-237,249)
 #include "common.h"
 
 #include <type_traits>
@@ -427,6 +427,144 @@ int launch_small_mfma(const SmallConvParams& p, hipStream_t stream) {
     return LM_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// 3x3 pad-1 convolutions with Cout = 32, 48 or 64 (16 NB) and Cin = 8, 16 or 32 on the matrix cores: the stride-2 stages of
+// generate_line_proposal (Conv_Pool_2d, heads/polyline_fpn_vit_vertex_2.py:48-61: 8 -> 16(+16 zero), 16 -> 32, 32 -> 64).  The kernel
+// above generalised: the input channels go through LDS in chunks of CC = 8 or 16 (position (c % 4) * CC/4 + c / 4 inside a pixel, so a
+// lane's k slot h = lane / 16 reads channels h, 4 + h, ... of the chunk as ONE ds_read_b64 / b128), the weights - NB consecutive
+// [3 x 3][Cin][16] blocks, the packed layout for Cout > 16 - are staged into LDS once per persistent workgroup, and every wave keeps
+// 4 rows x NB channel blocks of accumulators.  Per output: (chunk, tap, channel)-ascending fp32 fmaf chain.
+// ---------------------------------------------------------------------------------------------
+template <int STRIDE, int CC, int NB>
+__global__ __launch_bounds__(256) void small_conv3x3_mfma_wide_kernel(SmallConvParams p, LmFastDiv div_tx, LmFastDiv div_ty, int ntiles) {
+    constexpr int R = 15 * STRIDE + 3;                                 // patch edge (pixels)
+    constexpr int G = CC / 4;                                          // k = 4 channel groups per chunk
+    typedef float fgv __attribute__((ext_vector_type(G)));
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float* const patch = lds;                                          // [R][R][CC permuted channels]
+    float* const wl = lds + R * R * CC;                                // [NB][9][Cin][16]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int l16 = lane & 15, h = lane >> 4;
+    const int nchunk = p.Cin / CC;
+    const int wsize = NB * 9 * p.Cin * 16;
+    for (int i = tid; i < wsize; i += 256) wl[i] = p.w[i];
+    float sc[NB], sh[NB];
+    const bool has_sc = p.scale != nullptr, has_sh = p.shift != nullptr;
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+        sc[nb] = has_sc ? p.scale[nb * 16 + l16] : 1.f;
+        sh[nb] = has_sh ? p.shift[nb * 16 + l16] : 0.f;
+    }
+    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const unsigned trow = lm_fastdiv((unsigned)t, div_tx);
+        const int b = (int)lm_fastdiv(trow, div_ty);
+        const int oy0 = (int)(trow - (unsigned)b * div_ty.d) * 16, ox0 = (int)((unsigned)t - trow * div_tx.d) * 16;
+        const int iy0 = oy0 * STRIDE - 1, ix0 = ox0 * STRIDE - 1;
+        f32x4 acc[4][NB];
+#pragma unroll
+        for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) acc[mb][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int ch = 0; ch < nchunk; ++ch) {
+            __syncthreads();                                           // the previous chunk's / tile's reads (and the weight stage) are done
+            constexpr int NCH = R * R * G;                             // channel quads of the patch
+            for (int i0 = 0; i0 < NCH; i0 += 256 * 4) {
+                f32x4 v[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int i = i0 + u * 256 + tid;
+                    const int pix = i / G, g = i - pix * G;
+                    const int r = pix / R, q = pix - r * R;
+                    const int iy = iy0 + r, ix = ix0 + q;
+                    const bool ok = (i < NCH) & ((unsigned)iy < (unsigned)p.H) & ((unsigned)ix < (unsigned)p.W);
+                    const long src = ok ? (((long)b * p.H + iy) * p.W + ix) * p.ldx + ch * CC + 4 * g : 0;
+                    const f32x4 ld = *reinterpret_cast<const f32x4*>(p.x + src);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[u][e] = ok ? (p.pre_relu ? fmaxf(ld[e], 0.f) : ld[e]) : 0.f;
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int i = i0 + u * 256 + tid;
+                    if (i < NCH) {
+                        const int pix = i / G, g = i - pix * G;
+                        float* d = patch + pix * CC + g;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) d[e * G] = v[u][e];
+                    }
+                }
+            }
+            __syncthreads();
+            const float* const wc = wl + (ch * CC + h) * 16 + l16;     // B operand of (nb, tap, group j): wc[((nb * 9 + tap) * Cin + 4 j) * 16]
+#pragma unroll
+            for (int tp = 0; tp < 9; ++tp) {
+                const int ky = tp / 3, kx = tp % 3;
+                fgv a[4];
+#pragma unroll
+                for (int mb = 0; mb < 4; ++mb)
+                    a[mb] = *reinterpret_cast<const fgv*>(patch + (((4 * wave + mb) * STRIDE + ky) * R + l16 * STRIDE + kx) * CC + G * h);
+#pragma unroll
+                for (int j = 0; j < G; ++j)
+#pragma unroll
+                    for (int nb = 0; nb < NB; ++nb) {
+                        const float bw = wc[((nb * 9 + tp) * p.Cin + 4 * j) * 16];
+#pragma unroll
+                        for (int mb = 0; mb < 4; ++mb) acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mb][j], bw, acc[mb][nb], 0, 0, 0);
+                    }
+            }
+        }
+        // accumulator register r of (mb, nb): pixel 4 h + r of tile row 4 wave + mb, output channel 16 nb + l16
+#pragma unroll
+        for (int mb = 0; mb < 4; ++mb) {
+            const int oy = oy0 + 4 * wave + mb;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int ox = ox0 + 4 * h + r;
+                if (oy < p.Ho && ox < p.Wo) {
+                    float* const yp = p.y + (((long)b * p.Ho + oy) * p.Wo + ox) * p.ldy + l16;
+#pragma unroll
+                    for (int nb = 0; nb < NB; ++nb) {
+                        float v = acc[mb][nb][r];
+                        if (has_sc) v *= sc[nb];
+                        if (has_sh) v += sh[nb];
+                        if (p.act == LM_ACT_RELU) v = fmaxf(v, 0.f);
+                        yp[nb * 16] = v;
+                    }
+                }
+            }
+        }
+    }
+}
+
+template <int STRIDE, int CC, int NB>
+int launch_small_mfma_wide(const SmallConvParams& p, hipStream_t stream) {
+    constexpr int R = 15 * STRIDE + 3;
+    const size_t lds = ((size_t)R * R * CC + (size_t)NB * 9 * p.Cin * 16) * sizeof(float);     // <= 140 KB (stride 2, Cin 32, Cout 64)
+    if (int e = lm_ensure_dynamic_lds((const void*)small_conv3x3_mfma_wide_kernel<STRIDE, CC, NB>, lds)) return e;
+    const int tx = lm_cdiv(p.Wo, 16), ty = lm_cdiv(p.Ho, 16);
+    const long ntiles = (long)tx * ty * p.B;
+    LM_REQUIRE(ntiles < (1L << 31), "small_conv: too many tiles");
+    const int grid = (int)(ntiles < 256 ? ntiles : 256);              // one workgroup per CU (LDS), weights staged once per workgroup
+    hipLaunchKernelGGL((small_conv3x3_mfma_wide_kernel<STRIDE, CC, NB>), dim3(grid), dim3(256), lds, stream, p,
+                       lm_fastdiv_make((unsigned)tx), lm_fastdiv_make((unsigned)ty), (int)ntiles);
+    LM_LAUNCH_CHECK();
+    return LM_OK;
+}
+
+template <int STRIDE, int CC>
+int launch_small_mfma_wide_nb(const SmallConvParams& p, hipStream_t stream) {
+    switch (p.Cout / 16) {
+        case 2: return launch_small_mfma_wide<STRIDE, CC, 2>(p, stream);
+        case 3: return launch_small_mfma_wide<STRIDE, CC, 3>(p, stream);
+        default: return launch_small_mfma_wide<STRIDE, CC, 4>(p, stream);
+    }
+}
+
+int launch_small_wide(const SmallConvParams& p, hipStream_t stream) {
+    const bool s1 = p.stride == 1;
+    if (p.Cin == 8) return s1 ? launch_small_mfma_wide_nb<1, 8>(p, stream) : launch_small_mfma_wide_nb<2, 8>(p, stream);
+    return s1 ? launch_small_mfma_wide_nb<1, 16>(p, stream) : launch_small_mfma_wide_nb<2, 16>(p, stream);
+}
+
 }  // namespace
 
 LM_API int lm_stem_conv7x7_bn_relu(void* stream, const float* x_chw, const float* w_k64, const float* scale,
@@ -458,7 +596,8 @@ LM_API int lm_conv2d_nhwc_small(void* stream, const float* x, int ldx, const flo
                                 const float* shift, float* y, int ldy, int B, int H, int W, int Cin, int Cout,
                                 int KH, int KW, int stride, int pad_h, int pad_w, int pre_relu, int act) {
     LM_REQUIRE(x && w_tc16 && y, "small_conv: null pointer");
-    LM_REQUIRE(Cin % 4 == 0 && ldx % 4 == 0 && Cout >= 1 && Cout <= 16, "small_conv: Cin=%d (mult of 4) Cout=%d (<=16)", Cin, Cout);
+    LM_REQUIRE(Cin % 4 == 0 && ldx % 4 == 0 && Cout >= 1 && (Cout <= 16 || (Cout <= 64 && Cout % 16 == 0)),
+               "small_conv: Cin=%d (mult of 4) Cout=%d (<= 16, or 32 / 48 / 64)", Cin, Cout);
     SmallConvParams p;
     p.x = x; p.w = w_tc16; p.scale = scale; p.shift = shift; p.y = y;
     p.ldx = ldx; p.ldy = ldy; p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
@@ -466,11 +605,27 @@ LM_API int lm_conv2d_nhwc_small(void* stream, const float* x, int ldx, const flo
     p.Ho = (H + 2 * pad_h - KH) / stride + 1;
     p.Wo = (W + 2 * pad_w - KW) / stride + 1;
     p.M = (long)B * p.Ho * p.Wo;
-    if (Cin == 16 && KH == 3 && KW == 3 && pad_h == 1 && pad_w == 1 && (stride == 1 || stride == 2) && act != LM_ACT_GELU) {
-        // LM_SMALL_CONV_VALU=1: the VALU kernel for these shapes too
-        static const bool valu = [] { const char* e = getenv("LM_SMALL_CONV_VALU"); return e && atoi(e) != 0; }();
-        if (!valu) return stride == 1 ? launch_small_mfma<1>(p, (hipStream_t)stream) : launch_small_mfma<2>(p, (hipStream_t)stream);
+    // LM_SMALL_CONV_VALU=1: the VALU kernel for the matrix-core shapes too
+    static const bool valu = [] { const char* e = getenv("LM_SMALL_CONV_VALU"); return e && atoi(e) != 0; }();
+    const bool mfma_shape = KH == 3 && KW == 3 && pad_h == 1 && pad_w == 1 && (stride == 1 || stride == 2) && act != LM_ACT_GELU;
+    if (Cout > 16) {
+        // w_tc16 holds Cout / 16 consecutive [KH*KW][Cin][16] blocks
+        if (mfma_shape && (Cin == 8 || Cin == 16 || Cin == 32) && !valu) return launch_small_wide(p, (hipStream_t)stream);
+        const long wblock = (long)KH * KW * Cin * 16;
+        for (int nb = 0; nb < Cout / 16; ++nb) {          // the VALU kernel once per 16-channel block
+            SmallConvParams q = p;
+            q.w = w_tc16 + nb * wblock;
+            q.scale = scale ? scale + nb * 16 : nullptr;
+            q.shift = shift ? shift + nb * 16 : nullptr;
+            q.y = y + nb * 16;
+            q.Cout = 16;
+            hipLaunchKernelGGL(small_conv_kernel, dim3(lm_cdiv(p.M, 256)), dim3(256), 0, (hipStream_t)stream, q);
+            LM_LAUNCH_CHECK();
+        }
+        return LM_OK;
     }
+    if (Cin == 16 && mfma_shape && !valu)
+        return stride == 1 ? launch_small_mfma<1>(p, (hipStream_t)stream) : launch_small_mfma<2>(p, (hipStream_t)stream);
     hipLaunchKernelGGL(small_conv_kernel, dim3(lm_cdiv(p.M, 256)), dim3(256), 0, (hipStream_t)stream, p);
     LM_LAUNCH_CHECK();
     return LM_OK;

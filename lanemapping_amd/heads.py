@@ -14,8 +14,16 @@ spatial_att=False (the MixSeg config): the tokens are the raw zero-padded row wi
 (its parameters stay for strict loading).
 Proposal geometries (the reference config's `num_prop = 72, 36, 18` / `prop_width = 2, 4, 8`): SUPPORTED_GEOMETRIES with
 prop_half_buff = 4, i.e. prop_fea_width FW = 10, 12 or 16, and dim_shared any multiple of 4 up to 512.
-Not supported (raise): other geometries, column_att / column_transformer_decoder branches, endp_mode == 'endpoint',
-view_detail=True (the reference itself raises NameError there).  `prop_bi_seg`
+column_att=True (the proposal-attention branch, :317-345; check_column_att): generate_line_proposal, to_token + emb_*,
+tr_lane_correlator and line_expand turn the P column proposals into tokens, run the lane transformer across them and expand them
+back into a [B,8,144,P] column feature whose bilinear upsampling replaces that of x in the head's concat buffer.  Device route:
+the 5x3 conv and each stage's BatchNorm (a diagonal 1x1 conv: it sits between the ReLU and a zero-padded conv, so it cannot be
+folded into that conv) and stride-2 conv as lm_conv2d_nhwc_small; to_token + emb as ONE (P x 1) lm_conv2d_nhwc_mfma_f32 over
+feat_down (output pixel (b, 0, w) = token row b P + w, emb through res_rows = P); the ViT transformer kernels and LayerNorm;
+line_expand as a GEMM whose rows are permuted to (h c); lm_sparse_to_dense_nhwc moves [b][p][h][c] to NHWC [b][h][p][c].
+Not supported (raise): other geometries, column_att with spatial_att=False or outside check_column_att, the
+column_transformer_decoder branch (broken upstream: it uses self.pe / self.line_decoder, which are never built),
+endp_mode == 'endpoint', view_detail=True (the reference itself raises NameError there).  `prop_bi_seg`
 ([B,72,1,1152,80], unused downstream) and the dead `endpoint` map are not produced.
 """
 import numpy as np
@@ -23,7 +31,7 @@ import torch
 import torch.nn as nn
 
 from . import ops, decode, hostpost
-from .backbone import _Transformer, _FeedForward, pack_transformer
+from .backbone import _Transformer, _FeedForward, pack_transformer, transformer_forward
 from .registry import HEADS
 from .packing import PackedModule
 
@@ -54,6 +62,32 @@ def check_geometry(num_prop, prop_width, prop_half_buff, dim_shared):
             f'prop_half_buff={SUPPORTED_HALF_BUFF} and dim_shared a multiple of 4 up to {MAX_DIM_SHARED}')
 
 
+COLUMN_ATT_MAX_DIM_TOKEN = 4096
+
+
+def check_column_att(spatial_att, dim_token, tr_heads, tr_dim_head, tr_mlp_dim, tr_depth):
+    """Raise NotImplementedError, naming the parameter at fault, unless the device path covers this column_att=True head (on top of
+    check_geometry).  The multiples of 32 are the GEMMs' k-slab; LayerNorm takes dim_token % 32 == 0 up to 4096 except 768; the
+    attention kernels take dim_head 64; heads=1 with dim_head=dim_token has no output projection (to_out is the identity)."""
+    bad = None
+    if not spatial_att:
+        bad = 'spatial_att=False (the proposal tokens without the segmentation attention)'
+    elif dim_token % 32 or not 0 < dim_token <= COLUMN_ATT_MAX_DIM_TOKEN or dim_token == 768:
+        bad = f'dim_token={dim_token} (a multiple of 32 up to {COLUMN_ATT_MAX_DIM_TOKEN}, not 768)'
+    elif tr_dim_head != 64:
+        bad = f'tr_dim_head={tr_dim_head} (64)'
+    elif tr_heads < 1 or (tr_heads == 1 and tr_dim_head == dim_token):
+        bad = f'tr_heads={tr_heads} (>= 1, not 1 with tr_dim_head = dim_token)'
+    elif tr_mlp_dim <= 0 or tr_mlp_dim % 32:
+        bad = f'tr_mlp_dim={tr_mlp_dim} (a positive multiple of 32)'
+    elif tr_depth < 0:
+        bad = f'tr_depth={tr_depth} (>= 0)'
+    if bad is not None:
+        raise NotImplementedError(f'ColumnProposal2 column_att=True with {bad}: the device path covers spatial_att=True, dim_token a '
+                                  f'multiple of 32 up to {COLUMN_ATT_MAX_DIM_TOKEN} except 768, tr_dim_head=64, any tr_heads / tr_depth '
+                                  'and tr_mlp_dim a multiple of 32')
+
+
 def _conv1d_stack(cin, hidden, cout):
     return nn.Sequential(nn.Conv1d(cin, hidden, 1), nn.BatchNorm1d(hidden), nn.Conv1d(hidden, cout, 1), nn.Identity())
 
@@ -76,8 +110,12 @@ class ColumnProposal2(PackedModule):
         self.N_s = prop_width
         self.prop_fea_width = prop_width + 2 * prop_half_buff
         self.dim_shared = dim_shared
+        self.dim_feat = dim_feat
+        self.dim_token, self.tr_depth, self.tr_heads, self.tr_dim_head, self.tr_mlp_dim = dim_token, tr_depth, tr_heads, tr_dim_head, tr_mlp_dim
+        self._ca_coords = {}
         hd = dim_feat * 2
-        # ---- dead-at-inference parameters (column_att branch), kept for strict checkpoint loading ----
+        # ---- column_att branch (live only with cfg.column_att); reg_ffn / head_upsample_layers / endpoint are dead, kept for strict
+        # checkpoint loading ----
         self.reg_ffn = _FeedForward(dim_feat, dim_feat * 4)
         hidden = {72: [], 36: [2 * dim_feat], 18: [2 * dim_feat, 4 * dim_feat]}.get(num_prop)
         if hidden is not None:
@@ -133,6 +171,80 @@ class ColumnProposal2(PackedModule):
         P['conf.b'] = lin.bias.float().contiguous()
         return P
 
+    def _pack_column_att(self):
+        """Weights of the column_att branch (:317-345), packed on first use: the branch is off in every BASELINE config."""
+        P = {}
+        layers = self.generate_line_proposal[0].layers
+        conv0 = layers[0]
+        P['ca.f0.w'] = ops.pack_small(conv0.weight)
+        P['ca.f0.b'] = conv0.bias.float().contiguous()
+        S = len(layers) - 1
+        for i, (_, bn, conv) in enumerate(layers[1:]):
+            # BN_i as a 1x1 conv with diagonal weights: a * r + beta once per element, the zero padding of the next conv stays zero
+            a, beta = ops.fold_bn(bn)
+            P[f'ca.bn{i}.w'] = ops.pack_small(torch.diag(a)[:, :, None, None])
+            P[f'ca.bn{i}.b'] = beta
+            w, b = conv.weight, conv.bias
+            if i == S - 1 and w.shape[0] < 32:      # feat_down feeds a GEMM whose K slab is 32 channels: outputs 16..31 are exact zeros
+                w = torch.cat([w, w.new_zeros((32 - w.shape[0],) + tuple(w.shape[1:]))])
+                b = torch.cat([b, b.new_zeros(32 - b.shape[0])])
+            P[f'ca.s{i}.w'] = ops.pack_small(w)
+            P[f'ca.s{i}.b'] = b.float().contiguous()
+        cd = layers[-1][2].out_channels
+        cdp = max(cd, 32)
+        lin = self.to_token[1]
+        # Linear over (c h) of feat_down[b, :, :, w] -> a (P x 1) convolution weight [n][c][h][1], channels zero padded to cdp
+        wt = lin.weight.reshape(lin.out_features, cd, self.num_prop)
+        wt = torch.cat([wt, wt.new_zeros(lin.out_features, cdp - cd, self.num_prop)], dim=1)
+        P['ca.tok.w'] = ops.pack_mfma(wt[:, :, :, None])
+        P['ca.tok.b'] = lin.bias.float().contiguous()
+        P['ca.emb'] = torch.stack([getattr(self, f'emb_{i}') for i in range(self.num_prop)]).float().contiguous()
+        pack_transformer(self.tr_lane_correlator[0].layers, P, 'ca.T')
+        ln = self.tr_lane_correlator[1]
+        P['ca.ln.g'], P['ca.ln.b'] = ln.weight.float().contiguous(), ln.bias.float().contiguous()
+        ex = self.line_expand[0]
+        C_, R = self.dim_feat, self.row_size
+        # rows (c h) -> (h c): the GEMM output row of token (b, p) is then [h][c], one NHWC pixel per h
+        P['ca.exp.w'] = ops.pack_mfma(ex.weight.reshape(C_, R, -1).permute(1, 0, 2).reshape(C_ * R, -1))
+        P['ca.exp.b'] = ex.bias.reshape(C_, R).t().reshape(-1).float().contiguous()
+        return P
+
+    def _column_coords(self, B, device):
+        """lm_sparse_to_dense_nhwc coordinates (b, 0, h, p) of the line_expand row (b P + p) 144 + h; built once per (B, device)
+        with device arange, outside any graph capture (TilePipeline runs a batch shape eagerly before it captures it)."""
+        key = (B, str(device))
+        t = self._ca_coords.get(key)
+        if t is None:
+            P_, R = self.num_prop, self.row_size
+            b = torch.arange(B, device=device, dtype=torch.int32).view(B, 1, 1).expand(B, P_, R)
+            p = torch.arange(P_, device=device, dtype=torch.int32).view(1, P_, 1).expand(B, P_, R)
+            h = torch.arange(R, device=device, dtype=torch.int32).view(1, 1, R).expand(B, P_, R)
+            t = torch.stack([b, torch.zeros_like(b), h, p], dim=-1).reshape(-1, 4).contiguous()
+            self._ca_coords[key] = t
+        return t
+
+    def _column_att_features(self, x, P):
+        """:317-341 -> colfeat [B,8,144,P] (NHWC-stored) and the intermediates (feat_down, tokens) for the tests."""
+        B = x.shape[0]
+        Np, R, C_ = self.num_prop, self.row_size, self.dim_feat
+        f = ops.conv_small(x, P['ca.f0.w'], C_, 5, 3, 1, (2, 1), shift=P['ca.f0.b'], act=ops.ACT_RELU)   # read only through the ReLU
+        S = len(self.generate_line_proposal[0].layers) - 1
+        for i in range(S):
+            cin = f.shape[1]
+            f = ops.conv_small(f, P[f'ca.bn{i}.w'], cin, shift=P[f'ca.bn{i}.b'])
+            cout = P[f'ca.s{i}.b'].numel()
+            f = ops.conv_small(f, P[f'ca.s{i}.w'], cout, 3, 3, 2, 1, shift=P[f'ca.s{i}.b'],
+                               act=ops.ACT_RELU if i < S - 1 else ops.ACT_NONE)
+        feat_down = f                                                                    # [B, max(Cd, 32), P, P]
+        D = P['ca.tok.b'].numel()
+        tok = ops.conv_mfma(feat_down, P['ca.tok.w'], D, kh=Np, kw=1, shift=P['ca.tok.b'], res=P['ca.emb'], res_rows=Np)
+        t = tok.permute(0, 2, 3, 1).reshape(B * Np, D)                                  # [B,1,P,D] NHWC = token rows b P + w
+        t = transformer_forward(self.tr_lane_correlator[0].layers, P, 'ca.T', t, B, Np)
+        t = ops.layernorm(t, P['ca.ln.g'], P['ca.ln.b'], self.tr_lane_correlator[1].eps)
+        e = ops.linear_mfma(t, P['ca.exp.w'], C_ * R, shift=P['ca.exp.b'])              # [B*P, (h c)]
+        colfeat = ops.sparse_to_dense(e.view(B * Np * R, C_), self._column_coords(B, x.device), B, (1, R, Np), C_, False)
+        return colfeat, feat_down, t
+
     # -------------------------------------------------------------------------------- forward
     def forward(self, x, x_up, x_endp=None, col=None):
         """x [B,8,144,144], x_up [B,8,288,288] -> raw head outputs (live sub-graph).
@@ -148,17 +260,27 @@ class ColumnProposal2(PackedModule):
 
     def _forward_impl(self, x, x_up, x_endp=None, col=None):
         cfg = self.cfg
-        if cfg.column_att or cfg.column_transformer_decoder:
-            raise NotImplementedError('column_att / column_transformer_decoder are off in every BASELINE config')
+        if cfg.column_transformer_decoder:
+            raise NotImplementedError('column_transformer_decoder is broken upstream (it uses self.pe / self.line_decoder, which the '
+                                      'reference never builds)')
         check_geometry(self.num_prop, self.prop_width, self.prop_half_buff, self.dim_shared)
+        if cfg.column_att:
+            check_column_att(cfg.spatial_att, self.dim_token, self.tr_heads, self.tr_dim_head, self.tr_mlp_dim, self.tr_depth)
         P = self.packed()
+        if cfg.column_att and 'ca.tok.w' not in P:
+            with torch.no_grad():
+                P.update(self._pack_column_att())
         B, _, h, w = x.shape
         self.b_size = B
         hd = 16
         if col is None:
             col = ops.new_act(B, hd, x_up.shape[2], x_up.shape[3], x.device)
             col[:, 8:16].copy_(x_up)
-        ops.upsample_nhwc(x, col.shape[2:], out=col[:, 0:8])                                   # :359
+        if cfg.column_att:
+            colfeat = self._column_att_features(x, P)[0]
+            ops.upsample_nhwc(colfeat, col.shape[2:], out=col[:, 0:8])                         # :341
+        else:
+            ops.upsample_nhwc(x, col.shape[2:], out=col[:, 0:8])                               # :359
         r = ops.conv_small(col, P['hc0.w'], hd, 3, 3, 1, 1, scale=P['hc0.s'], shift=P['hc0.b'])
         row = ops.conv_small(r, P['hc2.w'], hd, 3, 3, 2, 1, scale=P['hc2.s'], shift=P['hc2.b'])   # :376
         o = ops.conv_small(row, P['or0.w'], hd // 2, 3, 3, 1, 1, scale=P['or0.s'], shift=P['or0.b'])

@@ -130,8 +130,12 @@ def pack_wino44_fragments_split(wu):
 
 
 def pack_small(w):
-    """[Cout<=16,Cin,KH,KW] -> [KH*KW, Cin, 16]."""
+    """[Cout<=16,Cin,KH,KW] -> [KH*KW, Cin, 16].  Cout = 32, 48 or 64 -> [Cout/16, KH*KW, Cin, 16]: one 16-wide block per 16 outputs
+    (lm_conv2d_nhwc_small)."""
     co, ci, kh, kw = w.shape
+    if co > 16:
+        assert co % 16 == 0 and co <= 64, f'pack_small: Cout={co} must be <= 16 or 32 / 48 / 64'
+        return torch.stack([pack_small(w[16 * i:16 * (i + 1)]) for i in range(co // 16)]).contiguous()
     p = torch.zeros((kh * kw, ci, 16), device=w.device, dtype=torch.float32)
     p[:, :, :co] = w.permute(2, 3, 1, 0).reshape(kh * kw, ci, co)
     return p.contiguous()
