@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """Throughput bench of the lane-mapping hot path on MI355X (contract: see DESIGN.md §Measurement).
 
-    python bench.py [--gpus N --steps K --warmup W]          (N > 1 without torchrun: spawns the N ranks itself)
+    python bench.py [--gpus N --steps K --warmup W] [--full]          (N > 1 without torchrun: spawns the N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints its line.  `--full` adds what takes runs or
+work of its own: the checks against the oracles and a single-stream run, the instrumented roofline steps, the resident-points
+window of `--points host / las`, the split-precision second line and the CPU baseline.
 
 Default workload = BASELINE.json's headline, configs[2]: on-GPU LAS -> BEV raster of 16 x 4,194,304 points resident in HBM +
 configs/Proj_polyline_fpn_vit_vertex_2.py at batch 16, all the way to lane polylines: raster -> FPN -> ViT -> column-proposal
@@ -145,7 +149,8 @@ def second_line(args):
     (csrc/conv_wino44.hip w44_split2).  fp32-accurate, not bit-identical; held to the same goldens by the every-switch test.  Never `value`."""
     import subprocess
     steps = max(10, min(args.steps, 40))
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', str(steps), '--warmup', '3', '--no-cpu-baseline', '--no-second-line']
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', str(steps), '--warmup', '3', '--full', '--no-cpu-baseline',
+           '--no-second-line']
     if args.no_graphs:
         cmd.append('--no-graphs')
     if args.streams is not None:
@@ -272,8 +277,12 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=100, help='timed steps (default 100: a >= 4 s timed region; windows of 20 steps are also reported)')
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--cpu-budget-s', type=float, default=25.0)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run what a plain run leaves out: the raster check against oracle/raster_ref.c, the bitwise '
+                         'multi-stream == single-stream check, the instrumented roofline steps (several streams or HIP graphs), the '
+                         'resident-points window of --points host / las, the second line and the CPU baseline')
+    ap.add_argument('--cpu-budget-s', type=float, default=25.0, help='--full: time budget of the CPU baseline')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
     ap.add_argument('--host-threads', type=int, default=None, help='post-processing pool threads per pipeline (default 8; max(1, K - 1) under --host-cores K)')
     ap.add_argument('--host-cores', type=int, default=None,
                     help='per-rank host budget: pin this process (rank r) to K of the cores it may use, cores [r*K, (r+1)*K), BEFORE any GPU call - '
@@ -292,14 +301,15 @@ def main():
                          "host: 16 x 4,194,304 x 16 B of [x,y,z,intensity] f32 in PINNED HOST memory, uploaded every step on a copy stream into one of "
                          "two device buffers while the previous step computes (the reference's read_las -> to_cuda, laserlane_proposals.py:618-636, "
                          "runner.py:125-152).  las: the pinned host memory holds raw LAS point records (format 0, 20 B per point); they are uploaded "
-                         "the same way and decoded on the GPU (lm_las_decode_points) in front of the raster.  Both report the achieved H2D rate and "
-                         "the fraction of a resident-points window measured in the same run")
+                         "the same way and decoded on the GPU (lm_las_decode_points) in front of the raster.  Both report the achieved H2D rate; with --full "
+                         "also the fraction of a resident-points window measured in the same run")
     ap.add_argument('--no-second-line', action='store_true',
-                    help='skip the second line (fused workload, 1 GPU: the same command once more in a child process under LANEMAP_WINO_SPLIT=1 - '
+                    help='--full: skip the second line (fused workload, 1 GPU: the same command once more in a child process under LANEMAP_WINO_SPLIT=1 - '
                          'the Winograd products as fp16 x 2 split terms, fp32-accurate, NOT bit-identical to the exact path; reported as `second_line`, '
                          'never as `value`)')
-    ap.add_argument('--conv-detail', action='store_true', help='per-shape table of the MFMA launches on stderr')
-    ap.add_argument('--no-stream-check', action='store_true', help='skip the bitwise multi-stream == single-stream check')
+    ap.add_argument('--conv-detail', action='store_true', help='per-shape table of the MFMA launches on stderr (several streams or HIP graphs: '
+                    'from the instrumented steps of --full)')
+    ap.add_argument('--no-stream-check', action='store_true', help='--full: skip the bitwise multi-stream == single-stream check and the raster check')
     ap.add_argument('--graphs', action='store_true', help='replay the device part of every sub-batch as one HIP graph (TilePipeline use_graph); the default since '
                     'round 5 for the workloads that can be captured (fused, tiles, rowref): +1.4 %% on the headline in four interleaved 100-step runs, '
                     'profiles/r5_graphs_ab.txt')
@@ -610,9 +620,9 @@ def main():
 
     # ---- fused workload: the rasteriser's tiles of the last timed step against the scalar C oracle (oracle/raster_ref.c) - the first
     # and the last tile of the 16-tile launch (a wrong record slot at a high chunk index, or in the last BatchArgs entry, shows here).
-    # Checker leg, outside the clock.
-    raster_check = 'n/a'
-    if args.workload == 'fused' and args.steps > 0 and not args.no_stream_check:
+    # Checker leg, outside the clock; this and every leg below that runs work of its own belong to --full.
+    raster_check = 'n/a' if args.workload != 'fused' else 'not run (--full runs it)'
+    if args.full and args.workload == 'fused' and args.steps > 0 and not args.no_stream_check:
         from oracle import raster_ref
         lb = tile_bufs[(state['i'] - 1) & 1]
         rp = raster_ref.params(local_min_ele=-0.5, ele_reso=0.02)
@@ -630,8 +640,8 @@ def main():
     # ---- the product path the clock just timed splits each batch over `nstream` streams / pipelines: its outputs for the last step
     # must equal a single-stream run on the same tiles BITWISE (a cross-stream race on workspaces or packed weights would show here)
     last_buf = tile_bufs[(state['i'] - 1) & 1] if args.steps > 0 else tiles
-    stream_check = 'skipped'
-    if nstream > 1 and not args.no_stream_check and last:
+    stream_check = 'skipped' if args.full or nstream == 1 else 'not run (--full runs it)'
+    if args.full and nstream > 1 and not args.no_stream_check and last:
         ref = single_stream(last_buf)
         if len(ref) != len(last):
             raise SystemExit(f'stream check: {len(last)} results from the {nstream}-stream step, {len(ref)} from the single-stream run')
@@ -643,7 +653,9 @@ def main():
 
     roof_steps = args.steps
     roof_scope = 'HIP events around every launch inside the timed region (single stream)'
-    if nstream > 1 or args.graphs:
+    # single stream, no graphs: the timed steps themselves were instrumented; otherwise only --full measures the roofline
+    roofline_measured = args.full or (nstream == 1 and not args.graphs)
+    if args.full and (nstream > 1 or args.graphs):
         # per-launch durations are only meaningful when launches do not share the GPU: instrumented single-stream steps
         roof_steps = 2
         roof_scope = (f'{roof_steps} instrumented single-stream steps right after the timed region (in the timed region the batch is '
@@ -680,16 +692,18 @@ def main():
         feed['on'] = False
         torch.cuda.synchronize()
         n_res = min(40, max(10, args.steps))
-        for _ in range(3):
-            step()
-        drain()
-        torch.cuda.synchronize()
-        t_r = time.perf_counter()
-        for _ in range(n_res):
-            step()
-        drain()
-        torch.cuda.synchronize()
-        res_rate = batch * n_res / (time.perf_counter() - t_r)
+        res_rate = None
+        if args.full:
+            for _ in range(3):
+                step()
+            drain()
+            torch.cuda.synchronize()
+            t_r = time.perf_counter()
+            for _ in range(n_res):
+                step()
+            drain()
+            torch.cuda.synchronize()
+            res_rate = batch * n_res / (time.perf_counter() - t_r)
         my_rate = batch * args.steps / dt
         feed_report = {'source': {'host': 'pinned host memory, [x,y,z,intensity] f32 (16 B per point)',
                                   'las': 'pinned host memory, LAS 1.2 point format 0 records (20 B per point), decoded on the GPU by lm_las_decode_points'}[args.points],
@@ -698,8 +712,8 @@ def main():
                        'h2d_GBps': feed['bytes'] / (float(np.mean(up_ms)) * 1e-3) / 1e9 if up_ms else None,      # while the compute streams run
                        'h2d_GBps_needed_at_this_rate': feed['bytes'] * my_rate / batch / 1e9,
                        'double_buffered': True, 'copy_stream': True,
-                       'resident_window': {'steps': n_res, 'tiles_per_s_this_rank': res_rate},
-                       'fraction_of_resident': my_rate / res_rate}
+                       'resident_window': {'steps': n_res, 'tiles_per_s_this_rank': res_rate} if res_rate else None,
+                       'fraction_of_resident': my_rate / res_rate if res_rate else None}
 
     # ---- aggregate per kernel class.  kind strings: 'wino44 ...', 'conv ...', 'gemm ...', 'spconv ...'
     def kclass(kind):
@@ -799,9 +813,10 @@ def main():
                      'dominant_kernel': dominant, 'per_kernel': per_class,
                      'note': 'achieved / frac = executed MFMA FLOPs / launch time / fp32 MFMA peak (always <= 1). algorithmic_equiv_tflops = '
                              'direct-convolution FLOPs (SURVEY 8d: 2 per MAC of the 3x3 sums) / the same time: it exceeds the executed figure '
-                             'because Winograd F(4x4,3x3) does 36 multiplies where the direct sum does 144; frac_survey_8d = algorithmic_equiv_tflops / peak (SURVEY 8(d)\'s definition: it can exceed 1 for the same reason)'},
+                             'because Winograd F(4x4,3x3) does 36 multiplies where the direct sum does 144; frac_survey_8d = algorithmic_equiv_tflops / peak (SURVEY 8(d)\'s definition: it can exceed 1 for the same reason)'}
+        if roofline_measured else None,
     }
-    if args.workload == 'fused' and rast['pairs']:
+    if args.workload == 'fused' and rast['pairs'] and roofline_measured:
         rms = sum(a.elapsed_time(b) for a, b in rast['pairs']) / len(rast['pairs'])
         algb = (16.0 * N_PTS + 3 * 1152 * 1152 * 4) * batch
         movedb = (16.0 * N_PTS + 3 * 1152 * 1152) * batch          # what this design has to move: the tile leaves as u8
@@ -826,12 +841,14 @@ def main():
         dist.barrier()
         torch.cuda.synchronize()
         store = dist.distributed_c10d._get_default_store()
-    if rank == 0 and world == 1 and args.workload == 'fused' and args.points == 'resident' and not args.no_second_line and not SPLIT_LINE:
+    if (args.full and rank == 0 and world == 1 and args.workload == 'fused' and args.points == 'resident' and not args.no_second_line
+            and not SPLIT_LINE):
         result['second_line'] = second_line(args)
     if rank == 0:
-        if not args.no_cpu_baseline and affinity0 is not None and args.host_cores is not None:
+        with_cpu = args.full and not args.no_cpu_baseline
+        if with_cpu and affinity0 is not None and args.host_cores is not None:
             os.sched_setaffinity(0, affinity0)          # the CPU path gets the node's cores back, not this rank's slice
-        result['cpu_baseline'] = None if args.no_cpu_baseline else cpu_baseline(args.cpu_budget_s)
+        result['cpu_baseline'] = cpu_baseline(args.cpu_budget_s) if with_cpu else None
         if result['cpu_baseline'] is not None and world > 1:
             result['cpu_baseline']['measured_with'] = f'{world - 1} other rank(s) of this job idle on the node (blocked on a store key, not spinning)'
         print(json.dumps(result), flush=True)

@@ -14,15 +14,44 @@ from lanemapping_amd import synth
 pytestmark = pytest.mark.gpu
 
 
+def test_bench_plain_command(dev):
+    """The driver's plain command line (`python bench.py` with its defaults, shortened) prints ONE JSON line with the contract's keys for
+    the headline workload and runs nothing the headline does not need: no CPU baseline, no second line, no checker legs (`--full` runs
+    them).  What it spends outside its steps - set-up, priming batch, teardown - stays within 30 s."""
+    import json
+    import subprocess
+    import sys
+    import time
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '2', '--warmup', '1'],
+                       capture_output=True, text=True, timeout=900, cwd=root)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.strip().split('\n') if l.startswith('{')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline', 'dtype',
+              'data', 'config', 'roofline', 'cpu_baseline'):
+        assert k in d, k
+    assert 'LAS points' in d['metric'] and d['unit'] == 'tiles/s' and d['higher_is_better'] is True and d['dtype'] == 'f32'
+    assert d['steps'] == 2 and d['warmup'] == 1 and d['n_gpus'] == 1 and d['value'] > 10
+    assert abs(d['ms_per_step'] - 1e3 * d['config']['tiles_per_step_per_gpu'] / d['value']) < 1e-6 * d['ms_per_step']
+    assert d['cpu_baseline'] is None and 'second_line' not in d
+    assert d['config']['raster_check'].startswith('not run') and not d['config']['stream_check'].startswith('lanes and endpoints')
+    outside = wall - (d['steps'] + d['warmup']) * d['ms_per_step'] * 1e-3
+    assert outside <= 30.0, f'{outside:.1f} s outside the warm-up and timed steps'
+
+
 def test_bench_default_command(dev):
-    """The driver's command line (`python bench.py` with its defaults, shortened) prints ONE JSON line with the contract's
+    """The driver's full command line (`python bench.py --full` with its defaults, shortened) prints ONE JSON line with the contract's
     keys: the headline workload (BASELINE configs[2]: LAS points -> polylines, batch 16), a roofline whose fraction is the EXECUTED
     MFMA view (<= 1), the raster's HBM roofline, the bitwise multi-stream check and the CPU baseline."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '2', '--warmup', '1', '--cpu-budget-s', '3'],
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '2', '--warmup', '1', '--full', '--cpu-budget-s', '3'],
                        capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.strip().split('\n') if l.startswith('{')]
@@ -65,7 +94,7 @@ def test_bench_self_launch_two_ranks(dev):
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
     env.update(LANEMAP_BENCH_DEVICE='0', LANEMAP_BENCH_BACKEND='gloo')
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--workload', 'tiles', '--steps', '2', '--warmup', '1',
-                        '--cpu-budget-s', '6'], capture_output=True, text=True, timeout=900, cwd=root, env=env)
+                        '--full', '--cpu-budget-s', '6'], capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     lines = [l for l in r.stdout.strip().split('\n') if l.startswith('{')]
     assert len(lines) == 1
@@ -93,7 +122,8 @@ def test_bench_two_ranks_code_path(dev):
     s.close()
     env = dict(os.environ, LANEMAP_BENCH_DEVICE='0', LANEMAP_BENCH_BACKEND='gloo')
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
-                        '--master-port', str(port), os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--cpu-budget-s', '6'],
+                        '--master-port', str(port), os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--full',
+                        '--cpu-budget-s', '6'],
                        capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     lines = [l for l in r.stdout.strip().split('\n') if l.startswith('{')]
@@ -128,7 +158,7 @@ def test_bench_four_ranks_on_one_gpu(dev):
     env = dict(os.environ, LANEMAP_BENCH_DEVICE='0', LANEMAP_BENCH_BACKEND='gloo')
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(n), '--master-addr', '127.0.0.1',
                         '--master-port', str(port), os.path.join(root, 'bench.py'), '--gpus', str(n), '--workload', 'tiles', '--steps', '2',
-                        '--warmup', '1', '--cpu-budget-s', '4'], capture_output=True, text=True, timeout=1500, cwd=root, env=env)
+                        '--warmup', '1', '--full', '--cpu-budget-s', '4'], capture_output=True, text=True, timeout=1500, cwd=root, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     lines = [l for l in r.stdout.strip().split('\n') if l.startswith('{')]
     assert len(lines) == 1                                           # rank 0 only
@@ -156,7 +186,7 @@ def test_bench_other_workloads(dev, workload):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--workload', workload, '--steps', '2', '--warmup', '1',
-                        '--no-cpu-baseline'], capture_output=True, text=True, timeout=900, cwd=root)
+                        '--full', '--no-cpu-baseline'], capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.strip().split('\n') if l.startswith('{')][-1])
     assert d['value'] > 10 and 0.0 < d['roofline']['frac'] <= 1.0 and d['config']['tiles_per_step_per_gpu'] == 8
@@ -170,7 +200,7 @@ def test_bench_hip_graphs_four_streams(dev):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--workload', 'tiles', '--graphs', '--streams', '4', '--steps', '3', '--warmup', '1',
-                        '--no-cpu-baseline'], capture_output=True, text=True, timeout=900, cwd=root)
+                        '--full', '--no-cpu-baseline'], capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.strip().split('\n') if l.startswith('{')][-1])
     assert d['value'] > 10 and d['config']['hip_graphs'] is True and d['config']['streams'] == 4
@@ -209,7 +239,8 @@ def test_bench_input_inclusive_variants(dev, points):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--points', points, '--steps', '4', '--warmup', '1', '--no-cpu-baseline'],
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--points', points, '--steps', '4', '--warmup', '1', '--full',
+                        '--no-cpu-baseline'],
                        capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     d = json.loads([l for l in r.stdout.strip().split('\n') if l.startswith('{')][-1])
