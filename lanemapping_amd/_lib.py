@@ -27,6 +27,11 @@ class LmLasHeader(C.Structure):
                 ('min_xyz', C.c_double * 3), ('max_xyz', C.c_double * 3)]
 
 
+class LmStripGrid(C.Structure):
+    """Point-to-tile lookup grid of the strip binning (include/lanemap_hip.h)."""
+    _fields_ = [('x0', C.c_double), ('y0', C.c_double), ('cell', C.c_double), ('nx', C.c_int), ('ny', C.c_int)]
+
+
 # name -> (restype, argtypes); every entry must be declared in include/lanemap_hip.h
 SIGNATURES = {
     'lm_abi_version': (i32, []),
@@ -77,6 +82,10 @@ SIGNATURES = {
     'lm_bev_raster_workspace_bytes': (i64, [i32, i64, i32, i32]),
     'lm_bev_raster_batch': (i32, [vp, vp, C.POINTER(i64), C.POINTER(LmRasterParams), i32, vp, i64, vp, vp, i32, i32]),
     'lm_tile_ingest_u8': (i32, [vp, vp, vp, i32, i32, i32, i32]),
+    'lm_strip_build_grid': (i32, [C.POINTER(LmRasterParams), i32, i32, i32, C.c_double, C.c_double, C.POINTER(LmStripGrid), vp, i64]),
+    'lm_strip_bin_workspace_bytes': (i64, [i64, i32]),
+    'lm_strip_bin_points': (i32, [vp, vp, i64, C.POINTER(LmRasterParams), i32, i32, i32, C.c_double, C.c_double, vp, i64, vp, vp,
+                                  C.POINTER(i64), vp, i64]),
     'lm_endp_cluster': (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp]),
     'lm_polyline_assemble': (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp]),
     'lm_raster_polylines': (i32, [vp, i32, i32, vp]),

@@ -11,7 +11,8 @@ enum {
     LM_OK = 0,
     LM_ERR_ARG = 1,      // unsupported shape / null pointer
     LM_ERR_HIP = 2,      // HIP runtime error (see lm_last_error)
-    LM_ERR_NO_DEVICE = 3
+    LM_ERR_NO_DEVICE = 3,
+    LM_ERR_CAPACITY = 4  // an output buffer is too small; the needed size has been reported
 };
 
 void lm_set_error(const char* fmt, ...);

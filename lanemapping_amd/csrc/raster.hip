@@ -30,22 +30,12 @@
 // = 110 MB = 1.32x the algorithmic bytes (16 N + 3 H W 4): at the 6.3 TB/s of a pure copy that alone is 17.5 us = 0.59 of 8 TB/s,
 // the ceiling of any two-pass scheme; measured 23-25 us = 0.42-0.45 (DESIGN.md §3.2 has the counter-backed breakdown).
 #include "common.h"
+#include "raster_xf.h"   // LmRasterParams, TileXf, lm_raster_derive, lm_point_window (shared with strip.hip)
 
 #include <cmath>
 #include <cstdlib>
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-struct LmRasterParams {      // mirrors the reference's per-tile parameter file (utils/io_utils.py:125-150)
-    float quat[4];           // las_rotation_trans_quan[3:7] = [w,x,y,z]
-    float trans[3];          // las_rotation_trans_quan[0:3]
-    float bev_img_offset[2];
-    float img_reso[2];
-    float local_min_ele;
-    float ele_reso;
-    float inten_lo, inten_hi;   // 800, 33000
-};
 
 namespace {
 
@@ -63,22 +53,14 @@ constexpr int MAX_BANDS = 96;             // (12-row bands of a 1152-row tile)
 constexpr int MAX_TILES = 16;          // tiles per launch (kernel-argument block)
 constexpr int REP = 8;                 // replication of the LDS rank counters (fewer same-address collisions)
 
-struct TileXf {                        // derived per-tile constants (host, double -> float)
-    float m[9], t[3], off[2], irow, icol, min_ele, iele, lo, hi, iscale;
-    long start, count;                 // point range of the tile in the concatenated buffer
-};
 struct BatchArgs {
     TileXf tile[MAX_TILES];
 };
 
 __device__ __forceinline__ bool point_record(const f32x4 p, const TileXf& X, int H, int W, int band_rows, int& band, unsigned& rec) {
-    const float dx = p[0] - X.t[0], dy = p[1] - X.t[1], dz = p[2] - X.t[2];
-    const float vx = (X.m[0] * dx + X.m[1] * dy) + X.m[2] * dz;
-    const float vy = (X.m[3] * dx + X.m[4] * dy) + X.m[5] * dz;
-    const float vz = (X.m[6] * dx + X.m[7] * dy) + X.m[8] * dz;
-    const int row = (int)floorf((vx - X.off[0]) * X.irow + 0.5f);
-    const int col = (int)floorf((vy - X.off[1]) * X.icol + 0.5f);
-    if ((unsigned)row >= (unsigned)H || (unsigned)col >= (unsigned)W) return false;
+    int row, col;
+    float vz;
+    if (!lm_point_window(p, X, H, W, row, col, vz)) return false;
     const float it = fminf(fmaxf(p[3], X.lo), X.hi) - X.lo;
     int I = (int)floorf(it * X.iscale + 0.5f);
     I = I < 1 ? 1 : (I > 255 ? 255 : I);
@@ -284,30 +266,6 @@ __global__ __launch_bounds__(256) void ingest_kernel(const unsigned char* __rest
     d[2 * HW] = (float)s[2] / 255.0f;
 }
 
-void derive(const LmRasterParams& P, long start, long count, TileXf& X) {
-    // inverse of the reference's rotation r(v) = q v q* / |q| = |q| R(q^) v   =>   M = R(q^)^T / |q|
-    const double n = std::sqrt((double)P.quat[0] * P.quat[0] + (double)P.quat[1] * P.quat[1] + (double)P.quat[2] * P.quat[2] +
-                               (double)P.quat[3] * P.quat[3]);
-    const double w = P.quat[0] / n, x = P.quat[1] / n, y = P.quat[2] / n, z = P.quat[3] / n;
-    const double R[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
-                         2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
-                         2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)};
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) X.m[i * 3 + j] = (float)(R[j * 3 + i] / n);
-    for (int i = 0; i < 3; ++i) X.t[i] = P.trans[i];
-    X.off[0] = P.bev_img_offset[0];
-    X.off[1] = P.bev_img_offset[1];
-    X.irow = 1.0f / P.img_reso[0];
-    X.icol = 1.0f / P.img_reso[1];
-    X.min_ele = P.local_min_ele;
-    X.iele = 1.0f / P.ele_reso;
-    X.lo = P.inten_lo;
-    X.hi = P.inten_hi;
-    X.iscale = 255.0f / P.inten_hi;
-    X.start = start;
-    X.count = count;
-}
-
 }  // namespace
 
 static long nblk_of(long n) { return (n + CHUNK - 1) / CHUNK; }
@@ -379,7 +337,7 @@ LM_API int lm_bev_raster_batch(void* stream, const float* points_xyzi, const lon
         long maxn = 0;
         for (int b = 0; b < nb; ++b) {
             const long n = tile_offsets[b0 + b + 1] - tile_offsets[b0 + b];
-            derive(params[b0 + b], tile_offsets[b0 + b], n, A.tile[b]);
+            lm_raster_derive(params[b0 + b], tile_offsets[b0 + b], n, A.tile[b]);
             BA.nblk[b] = (int)nblk_of(n);
             maxn = n > maxn ? n : maxn;
         }

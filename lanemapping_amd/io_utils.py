@@ -4,6 +4,7 @@
   save_seqs_json/txt/list        <- baseline/utils/io_utils.py:11-56 (3-D polylines after the back-projection / merge)
   load_lane_seq                  <- baseline/utils/io_utils.py:100-123
   load_pc_2_img_transform_paras  <- baseline/utils/io_utils.py:125-150 (values on lines 1,3,5,...,13 of the file)
+  save_pc_2_img_transform_paras  <- its inverse (the reference has no writer: the files come from the external cutting tool)
   pack_lane_vertices             <- heads/polyline_fpn_vit_vertex_2.py:997-1000 (row = 3 + 8 i, col, semantic)
 The JSON text equals the reference's byte for byte (json.dump(indent=4) of python floats / ints).
 """
@@ -156,14 +157,28 @@ def load_pc_2_img_transform_paras(param_path):
             'ele_reso': float(lines[13])}
 
 
-def raster_params_from_file(param_path):
-    """Reference parameter file -> LmRasterParams for lm_bev_raster_batch (points must already have
-    `las_read_offset` subtracted, as the reference's LAS reader hands them over)."""
+def save_pc_2_img_transform_paras(param_path, params):
+    """Writes a tile parameter file in the format load_pc_2_img_transform_paras reads (a key line, then a value line; floats as repr,
+    so a round trip returns the same numbers)."""
+    sp = lambda v: ' '.join(repr(float(x)) for x in v)
+    with open(param_path, 'w') as f:
+        f.write('\n'.join(['coor_las_path', str(params.get('coor_las_path', '')), 'las_read_offset', sp(params['las_read_offset']),
+                           'las_rotation_trans_quan', sp(params['las_rotation_trans_quan']), 'bev_img_offset', sp(params['bev_img_offset']),
+                           'img_reso', sp(params['img_reso']), 'local_min_ele', repr(float(params['local_min_ele'])),
+                           'ele_reso', repr(float(params['ele_reso'])), '']))
+
+
+def raster_params_from_dict(p):
     from .ops import make_raster_params
-    p = load_pc_2_img_transform_paras(param_path)
     q = p['las_rotation_trans_quan']
     return make_raster_params(quat=q[3:7], trans=q[0:3], bev_img_offset=p['bev_img_offset'], img_reso=p['img_reso'],
                               local_min_ele=p['local_min_ele'], ele_reso=p['ele_reso'])
+
+
+def raster_params_from_file(param_path):
+    """Reference parameter file -> LmRasterParams for lm_bev_raster_batch (points must already have
+    `las_read_offset` subtracted, as the reference's LAS reader hands them over)."""
+    return raster_params_from_dict(load_pc_2_img_transform_paras(param_path))
 
 
 # ------------------------------------------------------------------------------------------------ label JSON (training-set annotations)

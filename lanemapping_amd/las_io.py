@@ -66,3 +66,24 @@ def read_las(filepath, device='cuda:0', shift=None):
 def read_las_raw(filepath, device='cuda:0', shift=None):
     """-> ([N,4] float32 with RAW intensity, header dict): the record layout lm_bev_raster_batch consumes."""
     return _read(filepath, torch.device(device), shift, False)
+
+
+def grid_layout(header, img_reso=(0.05, 0.05), overlap_px=128, H=1152, W=1152, ele_reso=0.05, las_read_offset=None):
+    """A tile layout for a strip that comes without one: axis-aligned H x W windows (identity quaternion) over the bounding box of the
+    LAS header, neighbours sharing `overlap_px` pixels, rows along x and columns along y like the rasteriser.  -> list of parameter
+    dicts (the keys of io_utils.load_pc_2_img_transform_paras), x-major.  las_read_offset defaults to the header's minimum corner,
+    floored to whole metres; local_min_ele is the header's z minimum in that frame."""
+    lo, hi = header['min'], header['max']
+    off = [float(np.floor(v)) for v in lo] if las_read_offset is None else [float(v) for v in las_read_offset]
+    assert 0 <= overlap_px < min(H, W)
+    span = [(H - overlap_px) * float(img_reso[0]), (W - overlap_px) * float(img_reso[1])]
+    size = [H * float(img_reso[0]), W * float(img_reso[1])]
+    n = [max(1, int(np.ceil(((hi[a] - lo[a]) - size[a]) / span[a] - 1e-9)) + 1) for a in range(2)]
+    out = []
+    for i in range(n[0]):
+        for j in range(n[1]):
+            out.append({'coor_las_path': '', 'las_read_offset': list(off),
+                        'las_rotation_trans_quan': [lo[0] - off[0] + i * span[0], lo[1] - off[1] + j * span[1], 0.0, 1.0, 0.0, 0.0, 0.0],
+                        'bev_img_offset': [0.0, 0.0], 'img_reso': [float(img_reso[0]), float(img_reso[1])],
+                        'local_min_ele': float(lo[2] - off[2]), 'ele_reso': float(ele_reso)})
+    return out

@@ -11,7 +11,7 @@ import math
 
 import torch
 
-from ._lib import lib, check, LmRasterParams, LanemapHipError
+from ._lib import lib, check, LmRasterParams, LmStripGrid, LanemapHipError
 
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
 
@@ -643,6 +643,69 @@ def bev_raster(points, params, H=1152, W=1152, want_u8=False):
     """Single tile convenience wrapper: points [N,4] -> proj [3,H,W] (and u8 [H,W,3])."""
     r = bev_raster_batch(points, [0, points.shape[0]], [params], H, W, want_u8=want_u8)
     return (r[0][0], r[1][0]) if want_u8 else r[0]
+
+
+def strip_grid(params, H=1152, W=1152, z_range=None):
+    """The host-built point-to-tile grid behind strip_bin_points (no GPU): -> (dict x0, y0, cell, nx, ny; cells [ny, nx, 8] uint16
+    numpy array of tile indices, 0xFFFF = none).  Raises LanemapHipError when more than 8 tiles touch one cell: the limit counts the tiles
+    whose window reaches into a cell (cells are halved up to three times first), not the tiles a single point can lie in."""
+    import numpy as np
+    T = len(params)
+    par = (LmRasterParams * T)(*params)
+    z_lo, z_hi = (float(z_range[0]), float(z_range[1])) if z_range is not None else (-math.inf, math.inf)
+    g = LmStripGrid()
+    check(lib().lm_strip_build_grid(par, T, H, W, z_lo, z_hi, C.byref(g), None, 0))
+    cells = np.empty((g.ny, g.nx, 8), dtype=np.uint16)
+    check(lib().lm_strip_build_grid(par, T, H, W, z_lo, z_hi, C.byref(g), C.c_void_p(cells.ctypes.data), g.nx * g.ny))
+    return {'x0': g.x0, 'y0': g.y0, 'cell': g.cell, 'nx': g.nx, 'ny': g.ny}, cells
+
+
+def _tilted(p):
+    return p.quat[1] != 0.0 or p.quat[2] != 0.0
+
+
+def strip_bin_points(points, params, H=1152, W=1152, z_range=None, capacity=None):
+    """points [N,4] f32 on device (one whole strip), params: list of T LmRasterParams -> (binned [sum counts, 4], offsets: T+1 host
+    ints): the points of tile 0, then tile 1, ... in cloud order, exactly those the rasteriser keeps for each tile - the
+    (points, tile_offsets) pair bev_raster_batch takes.  z_range = (lo, hi) of the cloud (the LAS header's) bounds the lookup grid of
+    tilted tiles; None: taken from the points when a tile is tilted (one more pass and sync).  One device-to-host read of the offsets;
+    if the first guess of the output size was short, one second call."""
+    if not points.is_cuda:
+        _ptr(points)
+    assert points.dim() == 2 and points.shape[1] == 4 and points.is_contiguous() and points.dtype == torch.float32
+    T, N = len(params), points.shape[0]
+    par = (LmRasterParams * T)(*params)
+    if z_range is None and N and any(_tilted(p) for p in params):
+        z = points[:, 2]
+        z = z[torch.isfinite(z)]
+        z_range = (float(z.min()), float(z.max())) if z.numel() else (0.0, 0.0)
+    z_lo, z_hi = (float(z_range[0]), float(z_range[1])) if z_range is not None else (-math.inf, math.inf)
+    if not (math.isfinite(z_lo) and math.isfinite(z_hi)) and any(_tilted(p) for p in params):
+        if N:
+            raise ValueError('strip_bin_points: tilted tiles need a finite z_range (or None: it is then taken from the points)')
+        z_lo, z_hi = 0.0, 0.0                                                   # no points: any range will do
+    need = lib().lm_strip_bin_workspace_bytes(N, T)
+    if need <= 0:
+        raise LanemapHipError(f'strip_bin_points: {T} tiles / {N} points are not supported (1 to 4096 tiles)')
+    key = (points.device, _stream().value)
+    ws = _raster_ws.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _raster_ws[key] = torch.empty(need, device=points.device, dtype=torch.uint8)
+    meta = torch.empty(2 * T + 1, device=points.device, dtype=torch.int64)        # counts [T] | offsets [T+1]
+    offs = (C.c_long * (T + 1))()
+    cap = int(capacity) if capacity is not None else N + N // 4
+    binned = None
+    for attempt in range(2):
+        del binned                                                              # a retry must not hold both buffers
+        binned = torch.empty((cap, 4), device=points.device, dtype=torch.float32)
+        rc = lib().lm_strip_bin_points(_stream(), _ptr(points) if N else None, N, par, T, H, W, z_lo, z_hi, _ptr(ws), ws.numel(),
+                                       C.c_void_p(meta.data_ptr()), C.c_void_p(meta.data_ptr() + 8 * T), offs, _ptr(binned) if cap else None, cap)
+        if rc == 4 and attempt == 0 and capacity is None:                       # LM_ERR_CAPACITY: offs[T] is the size needed
+            cap = int(offs[T])
+            continue
+        check(rc)
+        break
+    return binned[:offs[T]], [int(o) for o in offs]
 
 
 def tile_ingest(u8_hwc):

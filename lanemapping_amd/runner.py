@@ -11,6 +11,7 @@
   Runner.infer_lane_geometry_segmentation_segmentor()<- :945-1036 (Segmentor config)
   Runner.infer_las_to_map()                          <- the offline chain LAS -> BEV -> polylines -> LAS frame -> merged map
                                                         (read_las, Las2BEV, Runner, coor_img2pc.py, merge_lines.py) in one call
+  Runner.infer_las_strip_to_map()                    <- the same chain from one LAS strip + a tile layout (points binned on the GPU)
 Deviations, all deliberate: (1) tiles are walked SORTED by stem, not in the seeded shuffle of the reference's test list (SURVEY C13;
 per-tile results and the summed counters do not depend on the order; datasets.load_datadir(shuffle_seed=cfg.seed) gives the reference's
 order); (2) `mode_view=True` is accepted and ignored with one notice: the cv2 overlays (:793-822) are not results (SURVEY 2: OUT);
@@ -293,13 +294,33 @@ class Runner:
 
         las_and_params: list of (las_path, param_path) in tile order.  Returns (per-tile dict name -> 3-D lines, merged list).
         Single rank (the merge is sequential over the sorted tiles)."""
-        from . import coor_img2pc, las_io, merge_lines as ml
+        from . import las_io
         if path_ckpt:
             self.load_ckpt(path_ckpt)
+        B = int(batch_size or self.cfg.get('batch_size', 8))
+        raster_batch, close = self._las_chain(work_dirs, merge)
+        for i in range(0, len(las_and_params), B):
+            chunk = las_and_params[i:i + B]
+            pts, offs, rpar, names, plist = [], [0], [], [], []
+            for las_path, param_path in chunk:
+                params = io_utils.load_pc_2_img_transform_paras(param_path)
+                p, _ = las_io.read_las_raw(las_path, self.device, shift=params['las_read_offset'])
+                pts.append(p)
+                offs.append(offs[-1] + p.shape[0])
+                rpar.append(io_utils.raster_params_from_file(param_path))
+                names.append(os.path.splitext(os.path.basename(las_path))[0][0:11])
+                plist.append(params)
+            raster_batch(names, plist, torch.cat(pts), offs, rpar)
+        return close()
+
+    def _las_chain(self, work_dirs, merge):
+        """The chain behind infer_las_to_map / infer_las_strip_to_map from the rasteriser on: -> (raster_batch, close).
+        raster_batch(names, params, points, offsets, raster_params) rasterises one batch of tiles out of `points` and runs it through
+        the pipeline, the per-tile JSON and the back-projection; close() drains the pipeline, merges and returns (lines3d, merged)."""
+        from . import coor_img2pc, merge_lines as ml
         out_dir = work_dirs or self.cfg.get('work_dirs', './work_dirs')
         pc_dir = os.path.join(out_dir, 'out_pc_seq_json_dir')
         os.makedirs(pc_dir, exist_ok=True)
-        B = int(batch_size or self.cfg.get('batch_size', 8))
         pipe = TilePipeline(self.net)
         H, W = self.cfg.list_img_size_xy[1], self.cfg.list_img_size_xy[0]
         queue, lines3d, pc_files = [], {}, []
@@ -325,28 +346,70 @@ class Runner:
                 pc_files.append(os.path.join(pc_dir, name + '.json'))
                 lines3d[name] = [l['seq'] for l in lines]
 
-        for i in range(0, len(las_and_params), B):
-            chunk = las_and_params[i:i + B]
-            pts, offs, rpar = [], [0], []
-            for las_path, param_path in chunk:
-                params = io_utils.load_pc_2_img_transform_paras(param_path)
-                p, _ = las_io.read_las_raw(las_path, self.device, shift=params['las_read_offset'])
-                pts.append(p)
-                offs.append(offs[-1] + p.shape[0])
-                rpar.append(io_utils.raster_params_from_file(param_path))
-                queue.append([os.path.splitext(os.path.basename(las_path))[0][0:11], params, None])
-            tiles, u8 = ops.bev_raster_batch(torch.cat(pts), offs, rpar, H, W, want_u8=True)
+        def raster_batch(names, params, points, offs, rpar):
+            for name, prm in zip(names, params):
+                queue.append([name, prm, None])
+            tiles, u8 = ops.bev_raster_batch(points, offs, rpar, H, W, want_u8=True)
             u8_host = u8.cpu().numpy()
-            for j in range(len(chunk)):
-                queue[len(queue) - len(chunk) + j][2] = u8_host[j]
+            for j in range(len(names)):
+                queue[len(queue) - len(names) + j][2] = u8_host[j]
             finish(pipe.submit(tiles))
-        finish(pipe.flush())
-        merged = []
-        if merge and pc_files:
-            merged = ml.merge_lines(pc_files)
-            io_utils.save_seqs_list(merged, os.path.join(pc_dir, 'merged.txt'))
-            io_utils.save_seqs_list([ml.downsample_seqs(m) for m in merged], os.path.join(pc_dir, 'merged_downsample.txt'))
-        return lines3d, merged
+
+        def close():
+            finish(pipe.flush())
+            merged = []
+            if merge and pc_files:
+                merged = ml.merge_lines(pc_files)
+                io_utils.save_seqs_list(merged, os.path.join(pc_dir, 'merged.txt'))
+                io_utils.save_seqs_list([ml.downsample_seqs(m) for m in merged], os.path.join(pc_dir, 'merged_downsample.txt'))
+            return lines3d, merged
+
+        return raster_batch, close
+
+    @staticmethod
+    def _strip_layout(param_paths):
+        """Parameter files of one strip -> (names, parameter dicts); all must carry the same las_read_offset."""
+        names, plist = [], []
+        for path in param_paths:
+            params = io_utils.load_pc_2_img_transform_paras(path)
+            if plist and list(params['las_read_offset']) != list(plist[0]['las_read_offset']):
+                raise ValueError(f"{param_paths[0]} and {path} carry different las_read_offset ({plist[0]['las_read_offset']} and "
+                                 f"{params['las_read_offset']}): the tiles of one strip share one read offset")
+            names.append(os.path.splitext(os.path.basename(path))[0][0:11])
+            plist.append(params)
+        return names, plist
+
+    def infer_las_strip_to_map(self, las_paths, param_paths, work_dirs=None, path_ckpt=None, batch_size=None, merge=True):
+        """A whole strip -> map-level lane lines: the LAS file(s) of the strip are read once, their points are binned into the tiles of
+        the layout on the GPU (ops.strip_bin_points: the windows of `param_paths` may overlap and be rotated), and every batch of tiles
+        then runs the chain of infer_las_to_map from the rasteriser on.  Same outputs under the same names; a tile is named by the
+        first 11 characters of its parameter file's stem.  las_paths: one path or a list; param_paths in tile order."""
+        from . import las_io
+        if isinstance(las_paths, (str, os.PathLike)):
+            las_paths = [las_paths]
+        names, plist = self._strip_layout(list(param_paths))
+        if path_ckpt:
+            self.load_ckpt(path_ckpt)
+        B = int(batch_size or self.cfg.get('batch_size', 8))
+        H, W = self.cfg.list_img_size_xy[1], self.cfg.list_img_size_xy[0]
+        raster_batch, close = self._las_chain(work_dirs, merge)
+        if plist:
+            shift = plist[0]['las_read_offset']
+            clouds, z_lo, z_hi = [], np.inf, -np.inf
+            for path in las_paths:
+                p, h = las_io.read_las_raw(path, self.device, shift=shift)
+                clouds.append(p)
+                z_lo, z_hi = min(z_lo, h['min'][2] - shift[2]), max(z_hi, h['max'][2] - shift[2])
+            cloud = clouds[0] if len(clouds) == 1 else torch.cat(clouds)
+            rpar = [io_utils.raster_params_from_dict(p) for p in plist]
+            # (the header's z range, widened by a float ulp's worth: it only bounds the lookup grid, never the result)
+            pad = 1e-3 * max(1.0, abs(z_lo), abs(z_hi))
+            binned, offs = ops.strip_bin_points(cloud, rpar, H, W, z_range=(z_lo - pad, z_hi + pad) if z_lo <= z_hi else None)
+            del cloud, clouds
+            for i in range(0, len(plist), B):
+                j = min(i + B, len(plist))
+                raster_batch(names[i:j], plist[i:j], binned, offs[i:j + 1], rpar[i:j])
+        return close()
 
     def infer_lane_geometry_segmentation_segmentor(self, path_ckpt=None, mode_view=False, write_lane_vertex=False,
                                                    *, tiles=None, batch_size=None, gt_avail=None):

@@ -188,6 +188,10 @@ class MultiGpuRunner:
         raise NotImplementedError('infer_las_to_map is a single-GPU chain (the cross-tile merge is sequential over the sorted tiles): '
                                   'use load_config_and_runner(path, "<one id>")')
 
+    def infer_las_strip_to_map(self, *a, **k):
+        raise NotImplementedError('infer_las_strip_to_map is a single-GPU chain (the cross-tile merge is sequential over the sorted tiles): '
+                                  'use load_config_and_runner(path, "<one id>")')
+
 
 def _rank_main(job_path):
     """One rank of a MultiGpuRunner call (a fresh process: the GPU is first touched here)."""
