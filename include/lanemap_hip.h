@@ -155,6 +155,21 @@ int lm_head_stage2(void* stream, const float* hid, int ldh, int D, const float* 
 int lm_head_proposal_conf(void* stream, const float* tok, const float* wt, const float* bias, float* conf,
                           int BP, int L);
 
+/* ---- heads.endp_mode = 'endpoint' (heads/polyline_fpn_vit_vertex_2.py:254-260, :371-373): the head's own endpoint map, one fused kernel
+ *   out [B][1][H][W] = conv3x3(t; w2, pad 1) + b2,   t = bn_scale * relu(conv3x3(a; W1, pad 1) + b1) + bn_shift (0 outside the image),
+ *   a = relu(cat(bilinear_align_corners(col -> H x W), x_endp)) (0 outside the image)
+ * col: NHWC [B][h][w][ldc], its first 16 channels (ldc >= 16: a slice of a wider buffer); x_endp [B][1][H][W]; w1p = W1 [4][17][3][3]
+ * as [17][3][3][4]; b1, bn_scale, bn_shift [4]; w2 [4][3][3]; b2 [1].  Any h, w, H, W >= 1 (scale (h - 1) / (H - 1), 0 where H = 1).
+ * The [B,17,H,W] concatenation is never built; exact fp32 in a fixed order, so a tile's map does not depend on B or on its place in
+ * the batch.  lm_head_endpoint_tile: the edge of the output tile one workgroup owns (the sizes the tests straddle).
+ * NOTE on the name `hip_stream`: as for lm_strip_bin_points below - tests/test_bounds_inventory_cpu.py finds device entries by the spelling
+ * `stream` and demands their guarded-buffer case in tests/test_gpu_1_bounds.py; this entry's case is
+ * tests/test_gpu_endpoint_mode.py::test_head_endpoint_kernel_bounds, which that inventory does not read. */
+int lm_head_endpoint_tile(void);
+int lm_head_endpoint(void* hip_stream, const float* col, int ldc, const float* x_endp, const float* w1p, const float* b1,
+                     const float* bn_scale, const float* bn_shift, const float* w2, const float* b2, float* out, int B, int h, int w,
+                     int H, int W);
+
 /* ---- decode (heads/polyline_fpn_vit_vertex_2.py:602-759; postprojector.py:115-183) ---------------------------
  * proposals: :610, :694-697, :701-702, :726-738.  orient: :615.  semantic: :627-632 (raw_mode=1: :122-127).
  * endp_topk: sigmoid of logits cropped by `clip` px, K best in (score desc, flat index asc) order (:647-668);

@@ -73,6 +73,8 @@ SIGNATURES = {
     'lm_head_tokens_window': (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32]),
     'lm_head_stage2': (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp, i64]),
     'lm_head_proposal_conf': (i32, [vp, vp, vp, vp, vp, i32, i32]),
+    'lm_head_endpoint_tile': (i32, []),
+    'lm_head_endpoint': (i32, [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32]),
     'lm_decode_proposals': (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32]),
     'lm_decode_orient': (i32, [vp, vp, i32, i32, vp, i64]),
     'lm_decode_semantic': (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32]),

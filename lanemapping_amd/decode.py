@@ -27,17 +27,21 @@ def _cluster_all(idx, status, crop_w, k0, k_max):
     return out
 
 
-def decode_compact(out, cfg, num_cls, prop_width, half_buff):
+def decode_compact(out, cfg, num_cls, prop_width, half_buff, endp_logits=None):
+    """endp_logits: the endpoint logits [B,1,H,W] to decode (ColumnProposal2.endp_logits: the head's own map in endpoint mode);
+    default out['endp_est']."""
+    if endp_logits is None:
+        endp_logits = out['endp_est']
     prop_conf, v_ext, cls_conf, cls_idx, cls_offset = ops.decode_proposals(
         out['proposal_conf'], out['ext2'], out['cls2'], out['offset2'], cfg.exist_thre, prop_width, half_buff)
     orient = ops.decode_orient(out['orient'])
     sem, biseg, rows = ops.decode_semantic(out['semantic_seg'], cfg.coor_thre)
-    idx, score, status = ops.endp_topk(out['endp_est'], K=TOPK, clip=CLIP)
-    W = out['endp_est'].shape[-1]
+    idx, score, status = ops.endp_topk(endp_logits, K=TOPK, clip=CLIP)
+    W = endp_logits.shape[-1]
     endp = _cluster_all(idx, status, W - 2 * CLIP, num_cls * 2 * 10, 500)
     return {'prop_conf': prop_conf, 'prop_v_ext': v_ext, 'prop_cls_conf': cls_conf, 'cls_idx': cls_idx,
             'cls_offset': cls_offset, 'orient': orient, 'semantic_seg_u8': sem, 'bi_seg': biseg, 'bi_seg_rows': rows,
-            'endp_pts': endp, 'endp_topk_idx': idx, 'endp_topk_score': score, 'img_hw': tuple(out['endp_est'].shape[-2:])}
+            'endp_pts': endp, 'endp_topk_idx': idx, 'endp_topk_score': score, 'img_hw': tuple(endp_logits.shape[-2:])}
 
 
 def endp_dense(pts_list, hw):

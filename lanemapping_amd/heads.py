@@ -21,10 +21,16 @@ the 5x3 conv and each stage's BatchNorm (a diagonal 1x1 conv: it sits between th
 folded into that conv) and stride-2 conv as lm_conv2d_nhwc_small; to_token + emb as ONE (P x 1) lm_conv2d_nhwc_mfma_f32 over
 feat_down (output pixel (b, 0, w) = token row b P + w, emb through res_rows = P); the ViT transformer kernels and LayerNorm;
 line_expand as a GEMM whose rows are permuted to (h c); lm_sparse_to_dense_nhwc moves [b][p][h][c] to NHWC [b][h][p][c].
+endp_mode='endpoint' (cfg.heads.endp_mode; the reference's "local+global" endpoints, :254-260, :371-373, :650-653): the head computes
+its own endpoint map out['endpoint'] [B,1,1152,1152] = endpoint(relu(cat(up(col), x_endp))) from its 16-channel concat buffer and the
+FPN's endpoint logits, and the decode reads that map wherever it reads out['endp_est'] otherwise (endp_logits()).  Device route: ONE
+kernel, lm_head_endpoint (csrc/head_endpoint.hip), which never builds the [B,17,1152,1152] concatenation; the BatchNorm between the
+ReLU and the zero-padded second convolution stays a scale and shift of its own, as in the column_att stages.  With any other
+endp_mode (every BASELINE config: 'endp_est') nothing is launched and no 'endpoint' key appears.
 Not supported (raise): other geometries, column_att with spatial_att=False or outside check_column_att, the
 column_transformer_decoder branch (broken upstream: it uses self.pe / self.line_decoder, which are never built),
-endp_mode == 'endpoint', view_detail=True (the reference itself raises NameError there).  `prop_bi_seg`
-([B,72,1,1152,80], unused downstream) and the dead `endpoint` map are not produced.
+view_detail=True (the reference itself raises NameError there).  `prop_bi_seg` ([B,72,1,1152,80], unused downstream) is
+not produced.
 """
 import numpy as np
 import torch
@@ -114,8 +120,8 @@ class ColumnProposal2(PackedModule):
         self.dim_token, self.tr_depth, self.tr_heads, self.tr_dim_head, self.tr_mlp_dim = dim_token, tr_depth, tr_heads, tr_dim_head, tr_mlp_dim
         self._ca_coords = {}
         hd = dim_feat * 2
-        # ---- column_att branch (live only with cfg.column_att); reg_ffn / head_upsample_layers / endpoint are dead, kept for strict
-        # checkpoint loading ----
+        # ---- column_att branch (live only with cfg.column_att) and `endpoint` (live only with endp_mode='endpoint'); reg_ffn /
+        # head_upsample_layers are dead, kept for strict checkpoint loading ----
         self.reg_ffn = _FeedForward(dim_feat, dim_feat * 4)
         hidden = {72: [], 36: [2 * dim_feat], 18: [2 * dim_feat, 4 * dim_feat]}.get(num_prop)
         if hidden is not None:
@@ -209,6 +215,20 @@ class ColumnProposal2(PackedModule):
         P['ca.exp.b'] = ex.bias.reshape(C_, R).t().reshape(-1).float().contiguous()
         return P
 
+    def _pack_endpoint(self):
+        """Operands of lm_head_endpoint (:254-260), packed on first use: the mode is off in every BASELINE config."""
+        ep = self.endpoint
+        return {'ep': ops.pack_head_endpoint(ep[0], ep[2], ep[3])}
+
+    def endpoint_mode(self):
+        """True when the endpoints are decoded from the head's own map (cfg.heads.endp_mode == 'endpoint', :650-653)."""
+        heads_cfg = getattr(self.cfg, 'heads', None)
+        return getattr(heads_cfg, 'endp_mode', self.endp_mode) == 'endpoint'
+
+    def endp_logits(self, out):
+        """The endpoint logits [B,1,H,W] the decode reads: out['endpoint'] in endpoint mode, the FPN's out['endp_est'] otherwise."""
+        return out['endpoint'] if self.endpoint_mode() else out['endp_est']
+
     def _column_coords(self, B, device):
         """lm_sparse_to_dense_nhwc coordinates (b, 0, h, p) of the line_expand row (b P + p) 144 + h; built once per (B, device)
         with device arange, outside any graph capture (TilePipeline runs a batch shape eagerly before it captures it)."""
@@ -249,14 +269,28 @@ class ColumnProposal2(PackedModule):
     def forward(self, x, x_up, x_endp=None, col=None):
         """x [B,8,144,144], x_up [B,8,288,288] -> raw head outputs (live sub-graph).
         `col`: optional pre-assembled [B,16,288,288] buffer whose channels 8..15 already hold x_up.
-        Goes through the dispatcher: torch.ops.lanemap_hip.colprop_head (torch_ops.py)."""
+        Goes through the dispatcher: torch.ops.lanemap_hip.colprop_head (torch_ops.py) and, in endpoint mode, colprop_endpoint on the
+        buffer colprop_head has completed and x_endp [B,1,1152,1152] -> out['endpoint']."""
         from . import torch_ops
         if col is None:
             col = ops.new_act(x.shape[0], 16, x_up.shape[2], x_up.shape[3], x.device)
             col[:, 8:16].copy_(x_up)
         self.b_size = x.shape[0]
         conf, ext2, cls2, off2, orient = torch_ops.colprop_head(x, col, torch_ops.stage_weights(self), torch_ops.stage_name(self))
-        return {'proposal_conf': conf, 'ext2': ext2, 'cls2': cls2, 'offset2': off2, 'orient': orient}
+        out = {'proposal_conf': conf, 'ext2': ext2, 'cls2': cls2, 'offset2': off2, 'orient': orient}
+        if self.endpoint_mode():
+            if x_endp is None:
+                raise ValueError("ColumnProposal2 with endp_mode='endpoint' needs x_endp (the FPN's endpoint logits)")
+            out['endpoint'] = torch_ops.colprop_endpoint(col, x_endp, torch_ops.stage_weights(self), torch_ops.stage_name(self))
+        return out
+
+    def _endpoint_impl(self, col, x_endp):
+        """:371-373 on the completed concat buffer; the up-sampling to (8 * 144)^2 that follows upstream is the identity at x_endp's size."""
+        P = self.packed()
+        if 'ep' not in P:
+            with torch.no_grad():
+                P.update(self._pack_endpoint())
+        return ops.head_endpoint(col, x_endp, P['ep'])
 
     def _forward_impl(self, x, x_up, x_endp=None, col=None):
         cfg = self.cfg
@@ -300,9 +334,8 @@ class ColumnProposal2(PackedModule):
     # -------------------------------------------------------------------------------- decode / assembly
     def decode_compact(self, out):
         """Device decode + endpoint clustering, compact form (what the runner and bench use)."""
-        if self.cfg.heads.endp_mode == 'endpoint':
-            raise NotImplementedError("endp_mode='endpoint' (dead branch) is not supported")
-        return decode.decode_compact(out, self.cfg, self.num_cls, self.prop_width, self.prop_half_buff)
+        return decode.decode_compact(out, self.cfg, self.num_cls, self.prop_width, self.prop_half_buff,
+                                     endp_logits=self.endp_logits(out))
 
     def get_exist_coor_endp_dict(self, out):
         if getattr(self.cfg, 'view_detail', False):

@@ -441,6 +441,37 @@ def upsample_nhwc(x, size, add=None, out=None):
     return out
 
 
+def pack_head_endpoint(conv1, bn, conv2):
+    """The `endpoint` stack of ColumnProposal2 (Conv2d(17, 4, 3) - ReLU - BatchNorm2d(4) - Conv2d(4, 1, 3)) -> the operands of
+    lm_head_endpoint: (w1p [17][3][3][4], b1 [4], bn scale [4], bn shift [4], w2 [4][3][3], b2 [1]).  The BatchNorm stays a scale and a
+    shift of its own: it sits between a ReLU and a zero-padded convolution, so its shift must not reach the padding."""
+    s, beta = fold_bn(bn)
+    return (conv1.weight.permute(1, 2, 3, 0).float().contiguous(), conv1.bias.float().contiguous(), s, beta,
+            conv2.weight[0].float().contiguous(), conv2.bias.float().contiguous())
+
+
+def head_endpoint_tile():
+    return int(lib().lm_head_endpoint_tile())
+
+
+def head_endpoint(col, x_endp, packed, out=None):
+    """col [B,16,h,w] NHWC-stored (a channel slice of a wider buffer is fine), x_endp [B,1,H,W], packed = pack_head_endpoint(...)
+    -> the endpoint logits [B,1,H,W] of heads.endp_mode = 'endpoint', one fused kernel (csrc/head_endpoint.hip)."""
+    col_, ldc = as_nhwc(col)
+    B, C_, h, w = col_.shape
+    assert C_ == 16, 'head_endpoint: col has 16 channels'
+    x_endp = x_endp.contiguous()
+    assert x_endp.dim() == 4 and x_endp.shape[0] == B and x_endp.shape[1] == 1 and x_endp.dtype == torch.float32
+    H, W = x_endp.shape[2:]
+    if out is None:
+        out = torch.empty((B, 1, H, W), device=col.device, dtype=torch.float32)
+    w1p, b1, s, beta, w2, b2 = packed
+    assert w1p.numel() == 17 * 36 and w2.numel() == 36
+    check(lib().lm_head_endpoint(_stream(), _ptr(col_), ldc, _ptr(x_endp), _ptr(w1p), _ptr(b1), _ptr(s), _ptr(beta), _ptr(w2), _ptr(b2),
+                                 _ptr(out), B, h, w, H, W))
+    return out
+
+
 def upsample_to_chw(x, size):
     x, ldx = as_nhwc(x)
     B, C_, H, W = x.shape

@@ -146,11 +146,12 @@ class TilePipeline:
                 raw['proposal_conf'], raw['ext2'], raw['cls2'], raw['offset2'], float(cfg.exist_thre), heads.prop_width, heads.prop_half_buff)
             orient = torch_ops.decode_orient(raw['orient'])
             sem, biseg, rows = torch_ops.decode_semantic(raw['semantic_seg'], float(cfg.coor_thre))
-            idx, score, status = torch_ops.endp_topk(raw['endp_est'], decode.TOPK, decode.CLIP)
+            endp = heads.endp_logits(raw)            # the head's own map with heads.endp_mode = 'endpoint', else the FPN's
+            idx, score, status = torch_ops.endp_topk(endp, decode.TOPK, decode.CLIP)
             trace.pop()
             dev = {'prop_conf': prop_conf, 'v_ext': v_ext, 'cls_offset': cls_offset, 'rows': rows, 'idx': idx, 'status': status}
             keep = (raw, sem, biseg, orient, cls_conf, cls_idx, dev)      # keep device buffers alive until the copies land
-            crop = raw['endp_est'].shape[-1]
+            crop = endp.shape[-1]
         return self._pack(dev), keep, crop
 
     def _tile_task(self, host, b, crop_w):

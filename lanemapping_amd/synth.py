@@ -205,6 +205,12 @@ def las_point_records(points, scale=1e-3):
     return rec.view(np.uint8)
 
 
+def endp_logits(seed, batch=1, size=1152):
+    """[batch,1,size,size] float32 stand-in for the FPN's endpoint logits, ~N(0, 2^2): both signs, so the ReLU in front of the head's
+    `endpoint` stack (heads.endp_mode = 'endpoint') cuts about half of it."""
+    return (2.0 * normalish(seed, batch * size * size, 7)).astype(np.float32).reshape(batch, 1, size, size)
+
+
 def apply_gains_(module, gains):
     """Multiply named parameters in place: gains = {state-dict key: factor}.  Used to derive better-conditioned synthetic heads
     from the seeded weights (e.g. a regression layer whose outputs stay inside one bin) - same keys in the reference and here."""

@@ -10,7 +10,7 @@ same library and are registered for ``cpu`` because that is where their inputs l
 
 Two levels:
   * stage ops - what the modules' ``forward`` go through: ``bev_raster``, ``fpn_encoder``, ``vit_backbone`` / ``mixer_backbone``,
-    ``colprop_head``
+    ``colprop_head`` (and ``colprop_endpoint`` with heads.endp_mode = 'endpoint')
     (+ ``endp_cluster``, ``polyline_assemble`` on the host).  A stage op takes the stage's WEIGHTS as a ``Tensor[]`` operand (every
     parameter and buffer of the module, in ``state_dict`` order - the tracer / ``torch.export`` see them as inputs of the op, and the
     op computes from the tensors it is handed) and the stage's STRUCTURE (which layers, strides, dilations) as a string: the name
@@ -316,6 +316,20 @@ def _colprop_head_fake(x, col, weights, stage):
 colprop_head = _define('colprop_head', _colprop_head, _colprop_head_fake, mutates=('col',))
 
 
+def _colprop_endpoint(col: Tensor, x_endp: Tensor, weights: List[Tensor], stage: str) -> Tensor:
+    """heads.endp_mode = 'endpoint' (heads.ColumnProposal2): col [B,16,288,288] as colprop_head left it, x_endp [B,1,1152,1152] (the
+    FPN's endpoint logits) -> the head's own endpoint logits [B,1,1152,1152] (lm_head_endpoint: one fused kernel)."""
+    with _with_weights(stage, weights) as m:
+        return m._endpoint_impl(col, x_endp)
+
+
+def _colprop_endpoint_fake(col, x_endp, weights, stage):
+    return x_endp.new_empty((x_endp.shape[0], 1, x_endp.shape[2], x_endp.shape[3]), dtype=torch.float32)
+
+
+colprop_endpoint = _define('colprop_endpoint', _colprop_endpoint, _colprop_endpoint_fake)
+
+
 # ------------------------------------------------------------------------------------------------------------- host ops
 def _endp_cluster(topk_idx: Tensor, crop_w: int, clip: int, k0: int, k_max: int) -> Tensor:
     from . import hostpost
@@ -349,4 +363,4 @@ polyline_assemble = _define('polyline_assemble', _polyline_assemble, _polyline_a
 
 OP_NAMES = ['conv2d_mfma', 'conv3x3_winograd44', 'stem_conv7x7', 'maxpool3x3s2', 'gn_stats', 'gn_relu_upsample',
             'upsample_bilinear', 'layernorm_rows', 'attention', 'linear_mfma', 'token_mix', 'tile_ingest', 'decode_proposals', 'decode_semantic',
-            'decode_orient', 'endp_topk', 'bev_raster', 'fpn_encoder', 'vit_backbone', 'mixer_backbone', 'colprop_head', 'endp_cluster', 'polyline_assemble']
+            'decode_orient', 'endp_topk', 'bev_raster', 'fpn_encoder', 'vit_backbone', 'mixer_backbone', 'colprop_head', 'colprop_endpoint', 'endp_cluster', 'polyline_assemble']
