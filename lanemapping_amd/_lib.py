@@ -105,6 +105,8 @@ SIGNATURES = {
     'lm_rowref_select': (i32, [vp, vp, vp, vp, vp, f32, vp, i32, i32, i32, i32]),
     'lm_rowref_gather': (i32, [vp, vp, vp, vp, i32, i32, i32, i32]),
     'lm_rowref_scatter': (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32]),
+    'lm_rowref_gather_win': (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32]),
+    'lm_rowref_scatter_win': (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32]),
     'lm_rowref_decode': (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32]),
     'lm_voxelize_workspace_bytes': (i64, [i64]),
     'lm_scan_workspace_bytes': (i64, [i64]),

@@ -3,22 +3,28 @@
 // lm_layernorm_rows / lm_attention_f32; this file holds what is specific to the head:
 //   lm_softmax_rows    softmax(dim=2) of the ext / cls logits                                   (:179-180, :239-240)
 //   lm_rowref_select   per (b, lane): mean_h ext[b,h,lane,0], the lane-selection flag mean > thr_ext, argmax_w cls[b,h,lane,:]  (:199-204)
-//   lm_rowref_gather   5-column window around the arg-max column of every row -> token input     (:207-211)
-//   lm_rowref_scatter  write the refined windows back, later lanes over earlier ones, lane i only on rows
-//                      0 .. 142-i: the reference's leaked/shrinking loop variable (:227-230)
+//   lm_rowref_gather_win   (2*off_grid+1)-column window around the arg-max column of every row -> token input  (:207-211)
+//   lm_rowref_scatter_win  write the refined windows back, later lanes over earlier ones, lane i only on rows
+//                          0 .. 142-i: the reference's leaked/shrinking loop variable (:227-230)
+//   lm_rowref_gather / lm_rowref_scatter   the same at config 4's off_grid = 2
+// off_grid (:93, :133-134) is 1..4: the window width KW = 3, 5, 7, 9 is a template parameter of both kernels, so the per-element index
+// arithmetic divides by constants.
 // Round 3: the data-dependent lane set no longer goes through the host.  The reference compacts the selected (b, lane) pairs into a
 // token list (:199-204); here the tokens live on the FIXED grid t = b * L + lane, `valid[b][lane]` says which of them exist, gather /
 // token MLP / transformer / expansion run on all B * L rows (a few wasted rows of tiny GEMMs), the attention core compacts the valid
 // keys of a tile in lane order (lm_attention_masked_f32: same arithmetic as on the compacted list) and the scatter derives a lane's
 // rank among the selected lanes of its tile - what the shrinking-range quirk is indexed by - from the flags.
 //   lm_rowref_decode   row exists iff argmax(ext2)==0, column = argmax(cls2) -> conf / cls maps   (:334-363)
-// Layouts: feature x [B,H,W,8] NHWC; ext [B,H,L,2]; cls [B,H,L,W]; tokens [T, 8*H*5] in (c h w) order.
+// Layouts: feature x [B,H,W,8] NHWC; ext [B,H,L,2]; cls [B,H,L,W]; tokens [T, 8*H*KW] in (c h w) order.
+#include <climits>
+
 #include "common.h"
 
 namespace {
 
 constexpr int CF = 8;     // dim_feat
-constexpr int KW = 5;     // 2*off_grid + 1
+// one half of an NHWC pixel (8 floats = two of these): 16-byte loads / stores that ask no more than float alignment of the caller
+typedef float f4 __attribute__((ext_vector_type(4), aligned(4)));
 
 __global__ __launch_bounds__(256) void softmax_rows_kernel(float* __restrict__ x, long rows, int cols) {
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -70,7 +76,9 @@ __global__ __launch_bounds__(256) void rowref_select_kernel(const float* __restr
     }
 }
 
-// token t = b * L + lane (fixed grid).  tok[t][(cf*H + h)*5 + j] = x_pad[b, cf, h, corr + j]
+// token t = b * L + lane (fixed grid).  tok[t][(cf*H + h)*KW + j] = x_pad[b, cf, h, corr + j], KW = 2*off_grid + 1; x_pad is x with
+// off_grid zero columns on either side, so window entry j is column corr + j - off_grid of x and reads 0 outside [0, W)
+template <int KW>
 __global__ __launch_bounds__(256) void rowref_gather_kernel(const float* __restrict__ x, const int* __restrict__ corr,
                                                             float* __restrict__ tok, int H, int W, int L, long total) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;   // over B*L*H*KW
@@ -81,18 +89,22 @@ __global__ __launch_bounds__(256) void rowref_gather_kernel(const float* __restr
     const int b = t / L, c = t - b * L;
     const int w = corr[((long)b * L + c) * H + h] + j - KW / 2;
     float* o = tok + (long)t * (CF * H * KW) + (long)h * KW + j;
+    f4 lo = {0.f, 0.f, 0.f, 0.f}, hi = lo;
     if ((unsigned)w < (unsigned)W) {
-        const float* p = x + (((long)b * H + h) * W + w) * CF;
+        const f4* p = reinterpret_cast<const f4*>(x + (((long)b * H + h) * W + w) * CF);
+        lo = p[0];
+        hi = p[1];
+    }
 #pragma unroll
-        for (int cf = 0; cf < CF; ++cf) o[(long)cf * H * KW] = p[cf];
-    } else {
-#pragma unroll
-        for (int cf = 0; cf < CF; ++cf) o[(long)cf * H * KW] = 0.f;
+    for (int cf = 0; cf < 4; ++cf) {
+        o[(long)cf * H * KW] = lo[cf];
+        o[(long)(cf + 4) * H * KW] = hi[cf];
     }
 }
 
 // Selected lane number n (0-based among the selected lanes of its tile, lane order) is written on rows h < H-1-n only; among covering
-// lanes the last one wins.  No lane of the tile selected: y = x.
+// lanes the last one wins.  No lane of the tile selected: y = x.  Window entries outside [0, W) have no pixel and are never written.
+template <int KW>
 __global__ __launch_bounds__(256) void rowref_scatter_kernel(const float* __restrict__ x, const float* __restrict__ tok,
                                                              const int* __restrict__ corr, const int* __restrict__ valid,
                                                              float* __restrict__ y, int H, int W, int L, long total) {
@@ -117,15 +129,21 @@ __global__ __launch_bounds__(256) void rowref_scatter_kernel(const float* __rest
             break;
         }
     }
-    float* o = y + i * CF;
+    f4 lo, hi;
     if (tsel >= 0) {
         const float* p = tok + tsel * (long)(CF * H * KW) + (long)h * KW + jsel;
 #pragma unroll
-        for (int cf = 0; cf < CF; ++cf) o[cf] = p[(long)cf * H * KW];
+        for (int cf = 0; cf < 4; ++cf) {
+            lo[cf] = p[(long)cf * H * KW];
+            hi[cf] = p[(long)(cf + 4) * H * KW];
+        }
     } else {
-#pragma unroll
-        for (int cf = 0; cf < CF; ++cf) o[cf] = src[cf];
+        lo = reinterpret_cast<const f4*>(src)[0];
+        hi = reinterpret_cast<const f4*>(src)[1];
     }
+    f4* o = reinterpret_cast<f4*>(y + i * CF);
+    o[0] = lo;
+    o[1] = hi;
 }
 
 __global__ __launch_bounds__(256) void rowref_decode_kernel(const float* __restrict__ ext, const float* __restrict__ cls,
@@ -173,22 +191,65 @@ LM_API int lm_rowref_select(void* stream, const float* ext, const float* cls, fl
     return LM_OK;
 }
 
-LM_API int lm_rowref_gather(void* stream, const float* x_nhwc8, const int* corr, float* tok, int B, int H, int W, int L) {
-    LM_REQUIRE(x_nhwc8 && corr && tok && B >= 1 && L >= 1, "rowref_gather: bad args");
+namespace {
+
+template <int KW>
+int rowref_gather_launch(hipStream_t s, const float* x, const int* corr, float* tok, int B, int H, int W, int L) {
     const long total = (long)B * L * H * KW;
-    hipLaunchKernelGGL(rowref_gather_kernel, dim3(lm_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, x_nhwc8, corr, tok, H, W, L, total);
+    hipLaunchKernelGGL(rowref_gather_kernel<KW>, dim3(lm_cdiv(total, 256)), dim3(256), 0, s, x, corr, tok, H, W, L, total);
     LM_LAUNCH_CHECK();
     return LM_OK;
+}
+
+template <int KW>
+int rowref_scatter_launch(hipStream_t s, const float* x, const float* tok, const int* corr, const int* valid, float* y, int B, int H,
+                          int W, int L) {
+    const long total = (long)B * H * W;
+    hipLaunchKernelGGL(rowref_scatter_kernel<KW>, dim3(lm_cdiv(total, 256)), dim3(256), 0, s, x, tok, corr, valid, y, H, W, L, total);
+    LM_LAUNCH_CHECK();
+    return LM_OK;
+}
+
+}  // namespace
+
+LM_API int lm_rowref_gather_win(void* hip_stream, const float* x_nhwc8, const int* corr, float* tok, int B, int H, int W, int L,
+                                int off_grid) {
+    LM_REQUIRE(x_nhwc8 && corr && tok && B >= 1 && L >= 1 && H >= 1 && W >= 1, "rowref_gather_win: bad args");
+    LM_REQUIRE(off_grid >= 1 && off_grid <= 4, "rowref_gather_win: off_grid=%d, must be in 1..4", off_grid);
+    LM_REQUIRE((long)B * L <= INT_MAX / ((long)CF * H * 9), "rowref_gather_win: more than INT_MAX token elements at the widest window (B*L*8*H*9)");
+    hipStream_t s = (hipStream_t)hip_stream;
+    switch (off_grid) {
+        case 1: return rowref_gather_launch<3>(s, x_nhwc8, corr, tok, B, H, W, L);
+        case 2: return rowref_gather_launch<5>(s, x_nhwc8, corr, tok, B, H, W, L);
+        case 3: return rowref_gather_launch<7>(s, x_nhwc8, corr, tok, B, H, W, L);
+        default: return rowref_gather_launch<9>(s, x_nhwc8, corr, tok, B, H, W, L);
+    }
+}
+
+LM_API int lm_rowref_scatter_win(void* hip_stream, const float* x_nhwc8, const float* tok, const int* corr, const int* valid,
+                                 float* y_nhwc8, int B, int H, int W, int L, int off_grid) {
+    LM_REQUIRE(x_nhwc8 && tok && corr && valid && y_nhwc8, "rowref_scatter_win: null pointer");
+    LM_REQUIRE(B >= 1 && L >= 1 && H >= 1 && W >= 1, "rowref_scatter_win: bad args");
+    LM_REQUIRE(off_grid >= 1 && off_grid <= 4, "rowref_scatter_win: off_grid=%d, must be in 1..4", off_grid);
+    hipStream_t s = (hipStream_t)hip_stream;
+    switch (off_grid) {
+        case 1: return rowref_scatter_launch<3>(s, x_nhwc8, tok, corr, valid, y_nhwc8, B, H, W, L);
+        case 2: return rowref_scatter_launch<5>(s, x_nhwc8, tok, corr, valid, y_nhwc8, B, H, W, L);
+        case 3: return rowref_scatter_launch<7>(s, x_nhwc8, tok, corr, valid, y_nhwc8, B, H, W, L);
+        default: return rowref_scatter_launch<9>(s, x_nhwc8, tok, corr, valid, y_nhwc8, B, H, W, L);
+    }
+}
+
+// config 4's own window (off_grid = 2)
+LM_API int lm_rowref_gather(void* stream, const float* x_nhwc8, const int* corr, float* tok, int B, int H, int W, int L) {
+    LM_REQUIRE(x_nhwc8 && corr && tok && B >= 1 && L >= 1, "rowref_gather: bad args");
+    return rowref_gather_launch<5>((hipStream_t)stream, x_nhwc8, corr, tok, B, H, W, L);
 }
 
 LM_API int lm_rowref_scatter(void* stream, const float* x_nhwc8, const float* tok, const int* corr, const int* valid,
                              float* y_nhwc8, int B, int H, int W, int L) {
     LM_REQUIRE(x_nhwc8 && tok && corr && valid && y_nhwc8, "rowref_scatter: null pointer");
-    const long total = (long)B * H * W;
-    hipLaunchKernelGGL(rowref_scatter_kernel, dim3(lm_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, x_nhwc8, tok, corr, valid,
-                       y_nhwc8, H, W, L, total);
-    LM_LAUNCH_CHECK();
-    return LM_OK;
+    return rowref_scatter_launch<5>((hipStream_t)stream, x_nhwc8, tok, corr, valid, y_nhwc8, B, H, W, L);
 }
 
 LM_API int lm_rowref_decode(void* stream, const float* ext2, const float* cls2, unsigned char* conf, unsigned char* cls_map,

@@ -8,10 +8,17 @@ Drop-in for baseline/models/heads/row_shared_not_reduc_ref.py: same kwargs (:88-
 plain tensors that are NOT in checkpoints and are re-drawn from the seeded RNG at construction (SURVEY §8c caveat 2).
 Here they are non-persistent buffers drawn the same way; `set_lane_embeddings` lets a caller supply captured values.
 
+Geometry: `off_grid` 1..4 (the refinement window is 2*off_grid+1 columns wide, `to_token` / `tr_lane_correlator.2` are sized from
+in_tok = (2*off_grid+1) * row_size * 8) and `is_reuse_same_network` False / True; `dim_feat` is 8, the width of the FPN's
+feature_layer (check_geometry).  With is_reuse_same_network=True there are no `ext2_c / cls2_c` modules or checkpoint keys
+(:151-168) and the second stage runs the first stage's networks - the same packed weights - on the refined feature map (:238-240).
+The reference assigns its flag only in the False branch (:152 against :168), so its own forward stops with an AttributeError at :238
+when built with True; here the constructor argument means what :238-240 read it as.
+
 GPU plan: the 24 first-stage Conv1d+BN1d of a stage are ONE GEMM [B*144, 1152] x [1152, 12288] straight from the NHWC
 feature map (weight columns permuted from (c w) to (w c) at pack time); second convs are per-lane GEMMs into column
-slices of the ext / cls buffers; softmax, lane selection, window gather / scatter and decode are small kernels
-(csrc/rowref.hip); the lane-token transformer reuses the ViT kernels.
+slices of the ext / cls buffers; softmax, lane selection, window gather / scatter (lm_rowref_gather_win / lm_rowref_scatter_win, the
+window width a template parameter) and decode are small kernels (csrc/rowref.hip); the lane-token transformer reuses the ViT kernels.
 """
 import numpy as np
 import torch
@@ -38,19 +45,34 @@ class _Last(dict):
         raise KeyError(key)
 
 
+DIM_FEAT = 8                   # the FPN's feature_layer width: no encoder here feeds another
+OFF_GRIDS = (1, 2, 3, 4)       # window widths 3, 5, 7, 9: the instantiations of the window kernels in csrc/rowref.hip
+
+
+def check_geometry(dim_feat, off_grid):
+    """Raise NotImplementedError, naming the parameter at fault, unless the device path covers this RowSharNotReducRef geometry."""
+    bad = None
+    if dim_feat != DIM_FEAT:
+        bad = f'dim_feat={dim_feat} ({DIM_FEAT}: the width of the FPN feature map the head reads)'
+    elif off_grid not in OFF_GRIDS:
+        bad = f'off_grid={off_grid} ({OFF_GRIDS[0]}..{OFF_GRIDS[-1]})'
+    if bad is not None:
+        raise NotImplementedError(f'RowSharNotReducRef with {bad}: the device path covers dim_feat={DIM_FEAT} and off_grid in '
+                                  f'{list(OFF_GRIDS)}, with is_reuse_same_network False or True')
+
+
 @HEADS.register_module
 class RowSharNotReducRef(PackedModule):
     def __init__(self, dim_feat=8, row_size=144, dim_shared=512, lambda_cls=1., thr_ext=0.3, off_grid=2, dim_token=1024,
                  tr_depth=1, tr_heads=16, tr_dim_head=64, tr_mlp_dim=2048, tr_dropout=0., tr_emb_dropout=0.,
                  is_reuse_same_network=False, cfg=None):
         super().__init__()
-        if dim_feat != 8 or off_grid != 2 or is_reuse_same_network:
-            raise NotImplementedError('hot path covers dim_feat=8, off_grid=2, separate 2nd-stage networks (config 4)')
+        check_geometry(dim_feat, off_grid)
         self.cfg = cfg
         self.num_cls = cfg.number_lanes
         self.row_size, self.dim_shared, self.dim_token = row_size, dim_shared, dim_token
         self.thr_ext, self.off_grid = thr_ext, off_grid
-        self.is_reuse_same_network = False
+        self.is_reuse_same_network = bool(is_reuse_same_network)
         cin = dim_feat * row_size
         for c in range(self.num_cls):
             setattr(self, f'ext_{c}', _stack(cin, dim_shared, 2))
@@ -61,9 +83,10 @@ class RowSharNotReducRef(PackedModule):
             self.register_buffer(f'emb_{c}', torch.randn(dim_token), persistent=False)
         self.tr_lane_correlator = nn.Sequential(_Transformer(dim_token, tr_depth, tr_heads, tr_dim_head, tr_mlp_dim),
                                                 nn.LayerNorm(dim_token), nn.Linear(dim_token, in_tok), nn.Identity())
-        for c in range(self.num_cls):
-            setattr(self, f'ext2_{c}', _stack(cin, dim_shared, 2))
-            setattr(self, f'cls2_{c}', _stack(cin, dim_shared, row_size))
+        if not self.is_reuse_same_network:              # (:151-168) reuse: no ext2_c / cls2_c modules, no such checkpoint keys
+            for c in range(self.num_cls):
+                setattr(self, f'ext2_{c}', _stack(cin, dim_shared, 2))
+                setattr(self, f'cls2_{c}', _stack(cin, dim_shared, row_size))
 
     def set_lane_embeddings(self, values):
         for c, v in enumerate(values):
@@ -89,7 +112,8 @@ class RowSharNotReducRef(PackedModule):
     def _pack(self):
         P = {}
         self._pack_stage(P, 's1', 'ext', 'cls')
-        self._pack_stage(P, 's2', 'ext2', 'cls2')
+        if not self.is_reuse_same_network:              # reuse: the second stage runs on the 's1' tensors, nothing is packed twice
+            self._pack_stage(P, 's2', 'ext2', 'cls2')
         P['tok.w'] = ops.pack_mfma(self.to_token[1].weight)
         P['tok.b'] = self.to_token[1].bias.float().contiguous()
         P['emb'] = torch.stack([getattr(self, f'emb_{c}') for c in range(self.num_cls)]).float().contiguous()
@@ -125,6 +149,7 @@ class RowSharNotReducRef(PackedModule):
         x, _ = ops.as_nhwc(x)
         B, C, H, W = x.shape
         L = self.num_cls
+        KW = 2 * self.off_grid + 1
         self.b_size = B
         dev = x.device
         ext1, cls1 = self._stage(P, 's1', 'ext', 'cls', x)
@@ -135,16 +160,20 @@ class RowSharNotReducRef(PackedModule):
         corr = torch.empty((B, L, H), device=dev, dtype=torch.int32)
         check(lib().lm_rowref_select(ops._stream(), ops._ptr(ext1), ops._ptr(cls1), ops._ptr(mean), ops._ptr(valid), float(self.thr_ext),
                                      ops._ptr(corr), B, H, W, L))
-        tok = torch.empty((B * L, C * H * 5), device=dev, dtype=torch.float32)
-        check(lib().lm_rowref_gather(ops._stream(), ops._ptr(x), ops._ptr(corr), ops._ptr(tok), B, H, W, L))
+        tok = torch.empty((B * L, C * H * KW), device=dev, dtype=torch.float32)
+        check(lib().lm_rowref_gather_win(ops._stream(), ops._ptr(x), ops._ptr(corr), ops._ptr(tok), B, H, W, L, self.off_grid))
         t = ops.linear_mfma(tok, P['tok.w'], self.dim_token, shift=P['tok.b'], res=P['emb'], res_rows=L)      # + lane embedding (row t: lane t % L)
         # attention only among the selected lanes of one tile: keys = the flagged tokens of the tile, in lane order
         t = transformer_forward(self.tr_lane_correlator[0].layers, P, 'T', t, B, L, valid=valid)
         t = ops.layernorm(t.contiguous(), P['ln.g'], P['ln.b'], self.tr_lane_correlator[1].eps)
-        t = ops.linear_mfma(t, P['exp.w'], C * H * 5, shift=P['exp.b'])
+        t = ops.linear_mfma(t, P['exp.w'], C * H * KW, shift=P['exp.b'])
         x2 = ops.new_act(B, C, H, W, dev)
-        check(lib().lm_rowref_scatter(ops._stream(), ops._ptr(x), ops._ptr(t), ops._ptr(corr), ops._ptr(valid), ops._ptr(x2), B, H, W, L))
-        ext2, cls2 = self._stage(P, 's2', 'ext2', 'cls2', x2)
+        check(lib().lm_rowref_scatter_win(ops._stream(), ops._ptr(x), ops._ptr(t), ops._ptr(corr), ops._ptr(valid), ops._ptr(x2), B, H, W, L,
+                                          self.off_grid))
+        if self.is_reuse_same_network:                  # (:238-240) the first-stage networks again, on the refined map
+            ext2, cls2 = self._stage(P, 's1', 'ext', 'cls', x2)
+        else:
+            ext2, cls2 = self._stage(P, 's2', 'ext2', 'cls2', x2)
         out = {}
         for c in range(L):
             out[f'ext_{c}'], out[f'cls_{c}'] = ext1[:, :, c, :], cls1[:, :, c, :]
