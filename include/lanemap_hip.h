@@ -308,6 +308,8 @@ int lm_rowref_decode(void* stream, const float* ext2, const float* cls2, unsigne
  * VoxelizationByGridShape (:29) and SparseEncoder (:33, called :93,:102); their published behaviour is restated.
  * voxelize_hard replaces :104-129 for one sample (hard voxelisation + mean of the kept points + batch index);
  * row_base / row_end are DEVICE ints (row range of this sample in the batch's feats / coords).
+ * voxelize_hard / sparse_grid_build / sparse_conv_outputs / sparse_rulebook are tested for exact equality with brute-force
+ * references (cell edges, caps, sort-key widths, cap_rows / ldf / chaining, volume seams) in tests/test_gpu_sparse_index.py.
  * sparse_grid_build / sparse_conv_outputs / sparse_rulebook / conv_gather_mfma_f32 replace the SparseEncoder call :93
  * (SubMConv3d and SparseConv3d, BatchNorm1d folded, ReLU, residual); ksp_zyx9 = {kz,ky,kx, sz,sy,sx, pz,py,px}.
  * sparse_to_dense_nhwc = SparseConvTensor.dense().view(N, C*D, H, W) + torch.flip(dims=[2]) (:70);
@@ -320,6 +322,7 @@ long lm_scan_workspace_bytes(long n);
 int lm_exclusive_scan_u32(void* stream, const unsigned* in, unsigned* out, long n, void* workspace, long workspace_bytes);
 long lm_sort_pairs_workspace_bytes(long n);
 int lm_sort_pairs_u32(void* stream, unsigned* keys_io, unsigned* vals_io, long n, int end_bit, void* workspace, long workspace_bytes);
+/* Points outside the grid are dropped; non-finite coordinates are dropped (NaN or +-Inf in x, y or z: no voxel, no share in any mean). */
 int lm_voxelize_hard(void* stream, const float* points, long n, const float* range_lo_xyz, const float* voxel_size_xyz,
                      const int* grid_xyz, int max_points, int max_voxels, int batch_idx, const int* row_base, int cap_rows,
                      float* feats, int ldf, int* coords, int* row_end, int raster_order, void* workspace,

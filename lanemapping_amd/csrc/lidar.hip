@@ -6,13 +6,16 @@
 // :93,:102 call them); the arithmetic lives in mmdet3d dev-1.x / mmcv.ops (unpinned commit, absent here).  What is
 // restated is their published behaviour:
 //   * hard voxelisation, deterministic flavour: c = floor((p - range_min) / voxel_size) per axis, points outside the grid
-//     are dropped, voxels are numbered by the index of their first point, a voxel keeps its first `max_points` points
-//     (index order), voxels beyond `max_voxels` are dropped; coords are (z, y, x);
+//     are dropped, non-finite coordinates are dropped (a point with a NaN or +-Inf x, y or z is outside every grid; a
+//     non-finite intensity is an ordinary value), voxels are numbered by the index of their first point, a voxel keeps
+//     its first `max_points` points (index order), voxels beyond `max_voxels` are dropped; coords are (z, y, x);
 //   * LidarEncoder.voxelize (:104-129): batch index prepended, feature = sum of kept points / count;
 //   * spconv: SubMConv3d keeps the active set, SparseConv3d activates every output site whose window holds an active
 //     input; out[o] = sum_k W[k] in[o*stride - pad + k] (cross-correlation, taps ordered (kz, ky, kx));
 //   * SparseConvTensor.dense() + view(N, C*D, H, W), then torch.flip(dims=[2]) (:70) and bicubic align_corners=False (:72).
 // The in-repo tail (bicubic .. 1x1 heads) IS pinned against the imported reference (tests/golden G11).
+// The index kernels (voxelize, grid build, output sites, rulebook) are held to exact equality with brute-force references at cell
+// edges, caps, key widths and volume seams by tests/test_gpu_sparse_index.py.
 //
 // Design: the grids are small enough (21 x 600 x 600 int32 = 30 MB per sample) to keep a DENSE row-index volume in HBM, so
 // "hashing" is a plain load and output-site compaction is one exclusive scan in raster order (deterministic row order).
@@ -29,16 +32,22 @@ struct VoxGeom {
     int g[3];             // grid size x, y, z
 };
 
+// floor((p - lo) / vs) as an int, -1 where it is no cell index of any grid.  The range is decided on the FLOAT: a NaN fails every
+// comparison, +-Inf and anything from 2^31 up fail one, so none of them reaches the conversion ((int)NaN is 0 on this hardware and
+// would pass for cell 0).  Every value that does convert is an integer below 2^31 and converts exactly.
+__device__ __forceinline__ int cell_index(float p, float lo, float vs) {
+    const float f = floorf((p - lo) / vs);
+    return (f >= 0.f && f < 2147483648.f) ? (int)f : -1;
+}
+
 __global__ __launch_bounds__(256) void vox_keys_kernel(const float4* __restrict__ pts, long n, VoxGeom G, unsigned* __restrict__ keys,
                                                        unsigned* __restrict__ vals, unsigned* __restrict__ flags) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float4 p = pts[i];
-    const int cx = (int)floorf((p.x - G.lo[0]) / G.vs[0]);
-    const int cy = (int)floorf((p.y - G.lo[1]) / G.vs[1]);
-    const int cz = (int)floorf((p.z - G.lo[2]) / G.vs[2]);
+    const int cx = cell_index(p.x, G.lo[0], G.vs[0]), cy = cell_index(p.y, G.lo[1], G.vs[1]), cz = cell_index(p.z, G.lo[2], G.vs[2]);
     const bool ok = cx >= 0 && cx < G.g[0] && cy >= 0 && cy < G.g[1] && cz >= 0 && cz < G.g[2];
-    keys[i] = ok ? (unsigned)((cz * G.g[1] + cy) * G.g[0] + cx) : INVALID_KEY;
+    keys[i] = ok ? ((unsigned)cz * (unsigned)G.g[1] + (unsigned)cy) * (unsigned)G.g[0] + (unsigned)cx : INVALID_KEY;
     vals[i] = (unsigned)i;
     flags[i] = 0u;
 }

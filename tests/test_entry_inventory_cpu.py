@@ -12,10 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NOT_DIRECTLY_TESTED = {
     'lm_winograd44_tiles': 'query: Winograd tile count (profiling FLOP count in conv_wino44)',
     'lm_endp_topk_workspace_bytes': 'query: workspace size of lm_endp_topk',
-    'lm_voxelize_workspace_bytes': 'query: workspace size of the voxeliser',
     'lm_scan_workspace_bytes': 'query: workspace size of the exclusive scan',
     'lm_sort_pairs_workspace_bytes': 'query: workspace size of the pair sort',
-    'lm_sparse_conv_outputs_workspace_bytes': 'query: workspace size of the sparse output-site pass',
 }
 
 

@@ -43,10 +43,10 @@ BOUNDS_EXEMPT = {
     'lm_rowref_decode': 'RowRef decision kernel; covered by test_rowref_decode_ties_and_null_maps',
     'lm_exclusive_scan_u32': 'device-wide primitive on a dense vector; sizes up to 2^25 + 1 covered by test_exclusive_scan_u32',
     'lm_sort_pairs_u32': 'device-wide primitive on dense vectors; covered by test_sort_pairs_u32_stable',
-    'lm_voxelize_hard': 'variable-length output (row_end on the device); covered against the oracle by test_voxelize_vs_oracle',
-    'lm_sparse_grid_build': 'hash-grid build whose output extent depends on the coordinates; covered by test_sparse_backbone_vs_oracle',
-    'lm_sparse_conv_outputs': 'variable-length output site list; covered by test_sparse_backbone_vs_oracle',
-    'lm_sparse_rulebook': 'writes the rulebook conv_gather reads; covered by test_sparse_backbone_vs_oracle',
+    'lm_voxelize_hard': 'variable-length output (row_end on the device); canary slabs under cap_rows, ldf and chaining in test_gpu_sparse_index.py::test_voxelize_raw_*',
+    'lm_sparse_grid_build': 'hash-grid build whose output extent depends on the coordinates; guarded slab in test_gpu_sparse_index.py::test_sparse_grid_build',
+    'lm_sparse_conv_outputs': 'variable-length output site list; canary slabs under cap_rows in test_gpu_sparse_index.py::test_conv_outputs_raw_cap_rows',
+    'lm_sparse_rulebook': 'writes the rulebook conv_gather reads; every word in a canary slab in test_gpu_sparse_index.py::test_conv_outputs_and_rulebook',
     'lm_las_decode_points': 'byte-record parser; every point format covered against the oracle by test_las_read_vs_oracle',
 }
 

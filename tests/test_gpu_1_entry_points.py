@@ -756,6 +756,7 @@ def test_upsample_bicubic_refusal(dev):
     (64, 64, 27, 1299, False),    # Cout <= 64 -> launch<128,64,32,64,true>
     (64, 128, 27, 2053, True),    # Cout > 64 -> launch<128,128,64,64,true>
     (32, 200, 9, 900, True),      # Cout > 64, ragged: launch<128,128,64,64,true>, 200 of 256 columns
+    (128, 128, 3, 900, True),     # conv_out of the network: the 3 taps of a (3,1,1) kernel, Cin = Cout = 128
 ])
 def test_conv_gather_vs_fp64(dev, cin, cout, taps, M, res):
     """lm_conv_gather_mfma_f32 (the sparse convolutions of config 5) against the fp64 sum over taps of W[t]^T x[nbr[m][t]] with -1
@@ -769,7 +770,7 @@ def test_conv_gather_vs_fp64(dev, cin, cout, taps, M, res):
     nbr = torch.randint(0, V, (M, taps), generator=g, dtype=torch.int32)
     nbr[torch.rand(M, taps, generator=g) < 0.35] = -1
     nbr[:5] = -1                                                   # rows with no active input at all
-    kdims = (3, 3, 3) if taps == 27 else (1, 3, 3)
+    kdims = {27: (3, 3, 3), 9: (1, 3, 3), 3: (3, 1, 1)}[taps]
     w = torch.randn(*kdims, cin, cout, generator=g) / (taps * cin) ** 0.5
     sc, sh = torch.rand(cout, generator=g) + 0.5, torch.randn(cout, generator=g)
     ldy = ops.sparse_ld(cout)
