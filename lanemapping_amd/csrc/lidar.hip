@@ -544,3 +544,215 @@ LM_API int lm_las_decode_points(void* stream, const unsigned char* records, int 
     LM_LAUNCH_CHECK();
     return LM_OK;
 }
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Decode + select + stable compaction: the records that pass a predicate on classification, flag bits, return numbers and
+// decoded height, written densely in file order.  Formats 0-5 and 6-10 keep these fields in different bits of bytes 14-16:
+//                      return number   number of returns   classification   synthetic / key-point / withheld / overlap
+//   formats 0-5        byte 14 [0:2]   byte 14 [3:5]       byte 15 [0:4]    byte 15 bits 5 / 6 / 7 / (does not exist)
+//   formats 6-10       byte 14 [0:3]   byte 14 [4:7]       byte 16          byte 15 bits 0 / 1 / 2 / 3
+// Three launches, nothing read back: a count pass (kept records of every 256-record block, and LDS class counters of all records),
+// prim.hip's exclusive scan over the block counts, and an emit pass that re-evaluates the predicate and stores to block offset + rank,
+// the rank from a ballot (lanes are in file order) plus the counts of the waves before.  Every slot is reserved by a prefix: no
+// atomics on HBM, the same bits each run.  HBM traffic = 2 n record_len read + 16 kept written + 4 bytes per block.
+namespace {
+
+constexpr int SEL_HIST_GROUPS = 2048;   // most workgroups of the count pass (8 resident per CU) = columns of the partial class histogram
+
+struct LasXf {
+    double sx, sy, sz, ox, oy, oz;
+    float lo, hi;
+    int normalise;
+};
+
+struct LasSel {
+    unsigned cls[8];
+    unsigned drop;       // LmLasSelect::drop_flags
+    int returns;
+    float z_lo, z_hi;
+    int fmt6;            // point formats 6-10
+};
+
+// The arithmetic of las_decode_kernel on one staged record: the same operations on the same values (this file is built with
+// -ffp-contract=off), hence the same bits.
+__device__ __forceinline__ float4 las_record_xyzi(const unsigned char* r, const LasXf& X) {
+    auto i32 = [&](int o) { return (int)((unsigned)r[o] | ((unsigned)r[o + 1] << 8) | ((unsigned)r[o + 2] << 16) | ((unsigned)r[o + 3] << 24)); };
+    const double x = (double)i32(0) * X.sx + X.ox, y = (double)i32(4) * X.sy + X.oy, z = (double)i32(8) * X.sz + X.oz;
+    const double raw = (double)((unsigned)r[12] | ((unsigned)r[13] << 8));
+    const double it = X.normalise ? (fmin(fmax(raw, (double)X.lo), (double)X.hi) - (double)X.lo) / (double)X.hi : raw;
+    return float4{(float)x, (float)y, (float)z, (float)it};
+}
+
+// the predicate of one record; cls = its classification, p = what the plain decode writes for it
+__device__ __forceinline__ bool las_record_keep(const unsigned char* r, const LasXf& X, const LasSel& S, unsigned& cls, float4& p) {
+    const unsigned b14 = r[14], b15 = r[15];
+    unsigned rn, nr, flags;
+    if (S.fmt6) {
+        rn = b14 & 15u, nr = b14 >> 4, flags = b15 & 15u, cls = r[16];
+    } else {
+        rn = b14 & 7u, nr = (b14 >> 3) & 7u, flags = b15 >> 5, cls = b15 & 31u;      // no overlap bit: bit 3 of flags stays 0
+    }
+    unsigned word = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+        if ((cls >> 5) == (unsigned)k) word = S.cls[k];
+    bool keep = (word >> (cls & 31u)) & 1u;
+    keep = keep && (flags & S.drop) == 0u;
+    if (S.returns == 1) keep = keep && rn == 1u;
+    else if (S.returns == 2) keep = keep && rn == nr;
+    else if (S.returns == 3) keep = keep && nr == 1u;
+    p = las_record_xyzi(r, X);
+    return keep && S.z_lo <= p.z && p.z <= S.z_hi;
+}
+
+// records [256 blk, 256 blk + cnt) -> LDS with coalesced dword loads; returns cnt.  Ends with a workgroup barrier.
+__device__ __forceinline__ int las_stage_block(const unsigned* __restrict__ rec, int record_len, long n, long blk, unsigned* stage) {
+    const long first = blk * 256;
+    const int cnt = (int)(n - first < 256 ? n - first : 256);
+    const int words = (cnt * record_len + 3) / 4;
+    const unsigned* src = rec + first * record_len / 4;            // first is a multiple of 256: 4-byte aligned
+    for (int w = threadIdx.x; w < words; w += 256) stage[w] = src[w];
+    __syncthreads();
+    return cnt;
+}
+
+// counts[b] = kept records of block b, counts[nblk] = 0 (the scan turns it into the total); hist_part (may be NULL) [256][gridDim.x]:
+// the classes of ALL records this workgroup walked, counted in LDS and written once
+__global__ __launch_bounds__(256) void las_select_count_kernel(const unsigned* __restrict__ rec, int record_len, long n, long nblk, LasXf X,
+                                                               LasSel S, unsigned* __restrict__ counts, unsigned* __restrict__ hist_part) {
+    extern __shared__ unsigned sel_stage[];
+    __shared__ unsigned hist[256];
+    __shared__ unsigned wcnt[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (hist_part) hist[threadIdx.x] = 0u;                         // (the barrier of the first staging orders this before the adds)
+    for (long b = blockIdx.x; b < nblk; b += gridDim.x) {
+        const int cnt = las_stage_block(rec, record_len, n, b, sel_stage);
+        bool keep = false;
+        if ((int)threadIdx.x < cnt) {
+            unsigned cls;
+            float4 p;
+            keep = las_record_keep(reinterpret_cast<const unsigned char*>(sel_stage) + (int)threadIdx.x * record_len, X, S, cls, p);
+            if (hist_part) atomicAdd(&hist[cls], 1u);
+        }
+        const unsigned long long bal = __ballot(keep);
+        if (lane == 0) wcnt[wv] = (unsigned)__popcll(bal);
+        __syncthreads();                                           // also: the stage is free for the next block
+        if (threadIdx.x == 0) counts[b] = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) counts[nblk] = 0u;
+    if (hist_part) {
+        __syncthreads();
+        hist_part[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = hist[threadIdx.x];
+    }
+}
+
+// one wave per class: the sum of its row of partial counts (integers: exact whatever the order), 64 workgroups
+__global__ __launch_bounds__(256) void las_select_hist_kernel(const unsigned* __restrict__ hist_part, int groups, unsigned long* __restrict__ hist) {
+    const int bin = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    unsigned long long s = 0;
+    for (int g = lane; g < groups; g += 64) s += hist_part[(size_t)bin * groups + g];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
+    if (lane == 0) hist[bin] = (unsigned long)s;
+}
+
+// offs = the scanned counts; one workgroup per block of 256 records
+__global__ __launch_bounds__(256) void las_select_emit_kernel(const unsigned* __restrict__ rec, int record_len, long n, long nblk, LasXf X,
+                                                              LasSel S, const unsigned* __restrict__ offs, float4* __restrict__ out,
+                                                              long* __restrict__ kept) {
+    extern __shared__ unsigned sel_stage[];
+    __shared__ unsigned wcnt[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long b = blockIdx.x;
+    const int cnt = las_stage_block(rec, record_len, n, b, sel_stage);
+    bool keep = false;
+    float4 p = {0.f, 0.f, 0.f, 0.f};
+    if ((int)threadIdx.x < cnt) {
+        unsigned cls;
+        keep = las_record_keep(reinterpret_cast<const unsigned char*>(sel_stage) + (int)threadIdx.x * record_len, X, S, cls, p);
+    }
+    const unsigned long long bal = __ballot(keep);
+    if (lane == 0) wcnt[wv] = (unsigned)__popcll(bal);
+    __syncthreads();
+    unsigned before = 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        if (k < wv) before += wcnt[k];
+    // offs[b] + rank < offs[nblk] <= n: the count pass evaluated the same predicate on the same bytes
+    if (keep) out[(long)offs[b] + before + (unsigned)__popcll(bal & ((1ull << lane) - 1ull))] = p;
+    if (b == 0 && threadIdx.x == 0) *kept = (long)offs[nblk];
+}
+
+long sel_blocks(long n) { return (n + 255) / 256; }
+long sel_groups(long n) { return sel_blocks(n) < SEL_HIST_GROUPS ? sel_blocks(n) : SEL_HIST_GROUPS; }
+
+}  // namespace
+
+struct LmLasSelect {          // include/lanemap_hip.h
+    unsigned class_mask[8];
+    unsigned drop_flags;
+    int returns;
+    float z_lo, z_hi;
+};
+
+LM_API long lm_las_select_workspace_bytes(long n) {
+    if (n < 0 || n > 2147483647L) return 0;
+    const long L = sel_blocks(n) + 1;
+    return (long)(align256((size_t)L * 4) + align256(scan_temp_bytes(L)) + align256((size_t)256 * (n ? sel_groups(n) : 1) * 4));
+}
+
+// lm_las_decode_points restricted to the records that pass `select`: out_xyzi[0 .. *kept) = the rows the plain decode writes for them,
+// in file order; rows from *kept on are not written.  kept: DEVICE long.  class_hist: DEVICE [256] u64 or NULL, the classification of
+// all n records.  Asynchronous like the plain decode: the caller reads *kept back when it needs the number.
+LM_API int lm_las_decode_select(void* hip_stream, const unsigned char* records, int record_len, int point_format, long n,
+                                const double* scale, const double* offset, const double* shift, float inten_lo, float inten_hi,
+                                int normalise, const LmLasSelect* select, void* workspace, long workspace_bytes, float* out_xyzi,
+                                long* kept, unsigned long* class_hist) {
+    LM_REQUIRE(record_len >= 20 && record_len <= 160, "las_decode_select: bad record length %d", record_len);
+    LM_REQUIRE(n >= 0 && n <= 2147483647L, "las_decode_select: n=%ld records, at most 2^31 - 1 are supported", n);
+    LM_REQUIRE(point_format >= 0 && point_format <= 10, "las_decode_select: unknown point data record format %d", point_format);
+    LM_REQUIRE(scale && offset && select && kept && (n == 0 || (records && out_xyzi && workspace)), "las_decode_select: null pointer");
+    LM_REQUIRE(select->returns >= 0 && select->returns <= 3, "las_decode_select: returns=%d is none of all (0), first (1), last (2), single (3)",
+               select->returns);
+    LM_REQUIRE(select->drop_flags < 16u, "las_decode_select: drop_flags=%u has bits beyond synthetic | key-point | withheld | overlap",
+               select->drop_flags);
+    LM_REQUIRE(select->z_lo == select->z_lo && select->z_hi == select->z_hi, "las_decode_select: z_lo / z_hi must not be NaN");
+    LM_REQUIRE(((uintptr_t)records & 3) == 0 && ((uintptr_t)out_xyzi & 15) == 0 && ((uintptr_t)workspace & 3) == 0 &&
+                   ((uintptr_t)kept & 7) == 0 && ((uintptr_t)class_hist & 7) == 0,
+               "las_decode_select: buffers must be 4 / 16 / 4 / 8 / 8-byte aligned");
+    LM_REQUIRE(lm_las_select_workspace_bytes(n) <= workspace_bytes, "las_decode_select: workspace too small (%ld B needed)",
+               lm_las_select_workspace_bytes(n));
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (n == 0) {
+        LM_HIP(hipMemsetAsync(kept, 0, sizeof(long), s));
+        if (class_hist) LM_HIP(hipMemsetAsync(class_hist, 0, 256 * sizeof(unsigned long), s));
+        return LM_OK;
+    }
+    const double sh[3] = {shift ? shift[0] : 0.0, shift ? shift[1] : 0.0, shift ? shift[2] : 0.0};
+    const LasXf X{scale[0], scale[1], scale[2], offset[0] - sh[0], offset[1] - sh[1], offset[2] - sh[2], inten_lo, inten_hi, normalise};
+    LasSel S;
+    for (int k = 0; k < 8; ++k) S.cls[k] = select->class_mask[k];
+    S.drop = select->drop_flags, S.returns = select->returns, S.z_lo = select->z_lo, S.z_hi = select->z_hi, S.fmt6 = point_format >= 6;
+    const long nblk = sel_blocks(n), L = nblk + 1;
+    const int groups = (int)sel_groups(n);
+    char* w = (char*)workspace;
+    unsigned* counts = (unsigned*)w;
+    w += align256((size_t)L * 4);
+    void* scan_tmp = w;
+    const size_t scan_bytes = align256(scan_temp_bytes(L));
+    w += scan_bytes;
+    unsigned* hist_part = class_hist ? (unsigned*)w : nullptr;
+    const size_t lds = ((size_t)256 * record_len + 3) / 4 * 4;
+    const unsigned* rec = reinterpret_cast<const unsigned*>(records);
+    hipLaunchKernelGGL(las_select_count_kernel, dim3((unsigned)groups), dim3(256), lds, s, rec, record_len, n, nblk, X, S, counts, hist_part);
+    LM_LAUNCH_CHECK();
+    if (class_hist) {
+        hipLaunchKernelGGL(las_select_hist_kernel, dim3(64), dim3(256), 0, s, hist_part, groups, class_hist);
+        LM_LAUNCH_CHECK();
+    }
+    if (int e = lm_prim_exclusive_scan_u32(s, counts, counts, L, scan_tmp, scan_bytes)) return e;
+    hipLaunchKernelGGL(las_select_emit_kernel, dim3((unsigned)nblk), dim3(256), lds, s, rec, record_len, n, nblk, X, S, counts,
+                       reinterpret_cast<float4*>(out_xyzi), kept);
+    LM_LAUNCH_CHECK();
+    return LM_OK;
+}

@@ -7,15 +7,93 @@ go to the GPU as raw bytes and are decoded there (`lm_las_decode_points`), strai
 hot path.  Differences from the reference, both deliberate: float32 instead of float64 (the hot path is fp32; pass
 `shift=las_read_offset` of the tile's parameter file so that metre-scale coordinates keep millimetre precision), and no
 `exit()` on clouds with fewer than 5 points (a ValueError instead).
+
+`select=PointFilter(...)` on any reader keeps only the records that pass a predicate on their classification, flag bits, return numbers
+and decoded height (`lm_las_decode_select`: decode, select and stable compaction on the GPU, file order kept), e.g. to keep noise,
+withheld points and gantry signs out of the rasteriser, which takes the brightest return of a pixel.
 """
 import ctypes as C
+import math
 
 import numpy as np
 import torch
 
-from ._lib import lib, check, LmLasHeader, LanemapHipError
+from ._lib import lib, check, LmLasHeader, LmLasSelect, LanemapHipError
 
 INTEN_MIN, INTEN_MAX = 800.0, 33000.0
+DROP_SYNTHETIC, DROP_KEYPOINT, DROP_WITHHELD, DROP_OVERLAP = 1, 2, 4, 8          # LM_LAS_DROP_* (include/lanemap_hip.h)
+RETURNS = {'all': 0, 'first': 1, 'last': 2, 'single': 3}                         # LM_LAS_RETURNS_*
+
+
+class PointFilter:
+    """Which point records a reader keeps (immutable).  A record is kept when all of these hold:
+
+      classes        its classification is one of `classes` (values 0..255; None: every class)
+      drop_withheld, drop_synthetic, drop_keypoint, drop_overlap
+                     it carries none of the flags asked to be dropped.  Point formats 0-5 have no overlap bit (overlap is class 12
+                     there): drop_overlap drops nothing in such a file
+      returns        'all'; 'first': return number == 1; 'last': return number == number of returns; 'single': number of returns == 1
+      z_range        (lo, hi): lo <= z <= hi on the float32 z the reader returns, i.e. AFTER `shift`; None or infinite bounds: no limit
+    """
+    __slots__ = ('classes', 'drop_withheld', 'drop_synthetic', 'drop_keypoint', 'drop_overlap', 'returns', 'z_range')
+
+    def __init__(self, classes=None, drop_withheld=True, drop_synthetic=False, drop_keypoint=False, drop_overlap=False, returns='all',
+                 z_range=None):
+        if classes is not None:
+            classes = tuple(sorted({int(c) for c in classes}))
+            bad = [c for c in classes if not 0 <= c <= 255]
+            if bad:
+                raise ValueError(f'PointFilter: classes must lie in 0..255, got {bad}')
+        if returns not in RETURNS:
+            raise ValueError(f'PointFilter: returns={returns!r} is none of {sorted(RETURNS)}')
+        if z_range is not None:
+            lo, hi = (float(v) for v in z_range)
+            if math.isnan(lo) or math.isnan(hi):
+                raise ValueError(f'PointFilter: z_range={z_range!r} has a NaN bound')
+            if lo > hi:
+                raise ValueError(f'PointFilter: z_range={z_range!r} is empty (lo > hi)')
+            z_range = (lo, hi)
+        for k, v in (('classes', classes), ('drop_withheld', bool(drop_withheld)), ('drop_synthetic', bool(drop_synthetic)),
+                     ('drop_keypoint', bool(drop_keypoint)), ('drop_overlap', bool(drop_overlap)), ('returns', returns),
+                     ('z_range', z_range)):
+            object.__setattr__(self, k, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError('PointFilter is immutable')
+
+    def __delattr__(self, name):
+        raise AttributeError('PointFilter is immutable')
+
+    def __repr__(self):
+        return 'PointFilter(' + ', '.join(f'{k}={getattr(self, k)!r}' for k in self.__slots__) + ')'
+
+    def __eq__(self, other):
+        return isinstance(other, PointFilter) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
+
+    def __hash__(self):
+        return hash(tuple(getattr(self, k) for k in self.__slots__))
+
+    def for_format(self, point_format):
+        """-> self, after checking the filter against a file's point data record format: formats 0-5 store the classification in five
+        bits, so a class above 31 cannot occur there and asking for one is refused."""
+        if not 0 <= int(point_format) <= 10:
+            raise ValueError(f'PointFilter: unknown point data record format {point_format}')
+        if self.classes is not None and int(point_format) <= 5:
+            bad = [c for c in self.classes if c > 31]
+            if bad:
+                raise ValueError(f'PointFilter: classes {bad} do not exist in point format {point_format} (formats 0-5 hold 0..31)')
+        return self
+
+    def as_struct(self):
+        """-> the LmLasSelect of include/lanemap_hip.h."""
+        s = LmLasSelect()
+        for w in range(8):
+            s.class_mask[w] = 0xFFFFFFFF if self.classes is None else sum(1 << (c & 31) for c in self.classes if c >> 5 == w)
+        s.drop_flags = (DROP_SYNTHETIC * self.drop_synthetic | DROP_KEYPOINT * self.drop_keypoint | DROP_WITHHELD * self.drop_withheld |
+                        DROP_OVERLAP * self.drop_overlap)
+        s.returns = RETURNS[self.returns]
+        s.z_lo, s.z_hi = (-math.inf, math.inf) if self.z_range is None else self.z_range
+        return s
 
 
 def parse_header(data):
@@ -28,11 +106,22 @@ def parse_header(data):
             'min': list(h.min_xyz), 'max': list(h.max_xyz)}
 
 
-def decode_points(records_u8, record_len, n, scale, offset, shift=None, normalise=True, out=None):
+def decode_points(records_u8, record_len, n, scale, offset, shift=None, normalise=True, out=None, point_format=None, select=None,
+                  return_hist=False):
     """records_u8: DEVICE uint8 tensor holding n records (padded to a multiple of 4 bytes) -> [n,4] float32 on that device
-    (`out`: a contiguous [n,4] float32 tensor to decode into, e.g. a slice of a batch's point buffer)."""
+    (`out`: a contiguous [n,4] float32 tensor to decode into, e.g. a slice of a batch's point buffer).
+
+    select: a PointFilter (needs `point_format`, the file's point data record format) -> the [kept,4] rows of the records that pass it,
+    in file order, the same bits the plain decode gives them: the contiguous view out[:kept] (rows from `kept` on are not written).
+    UNLIKE the plain decode this synchronises once, as ops.strip_bin_points does: `kept` is read back to size the view.  z_range is
+    compared with the z that is returned, i.e. after `shift`.  return_hist=True: -> (points, hist), hist = int64 numpy [256], the
+    classification counts of ALL n records (it travels in the same read-back)."""
     if not records_u8.is_cuda:
         raise LanemapHipError('las_io.decode_points needs the records on an MI355X (HIP) device; no CPU fallback exists')
+    if select is not None:
+        return _decode_select(records_u8, record_len, n, scale, offset, shift, normalise, out, point_format, select, return_hist)
+    if return_hist:
+        raise ValueError('las_io.decode_points: return_hist needs select= (PointFilter(drop_withheld=False) keeps every record)')
     if out is None:
         out = torch.empty((n, 4), device=records_u8.device, dtype=torch.float32)
     elif tuple(out.shape) != (n, 4) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != records_u8.device:
@@ -44,28 +133,70 @@ def decode_points(records_u8, record_len, n, scale, offset, shift=None, normalis
     return out
 
 
-def _read(path, device, shift, normalise):
+def _decode_select(records_u8, record_len, n, scale, offset, shift, normalise, out, point_format, select, return_hist):
+    if not isinstance(select, PointFilter):
+        raise TypeError(f'las_io.decode_points: select must be a PointFilter, not {type(select).__name__}')
+    if point_format is None:
+        raise ValueError('las_io.decode_points: select= needs point_format (classification and flags sit in other bits from format 6 on)')
+    sel = select.for_format(point_format).as_struct()
+    dev = records_u8.device
+    if out is None:
+        out = torch.empty((n, 4), device=dev, dtype=torch.float32)
+    elif tuple(out.shape) != (n, 4) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f'las_io.decode_points: out must be a contiguous [{n},4] float32 tensor on {dev}')
+    L = lib()
+    need = int(L.lm_las_select_workspace_bytes(int(n)))
+    ws = torch.empty((max(need, 4),), device=dev, dtype=torch.uint8)
+    meta = torch.empty((257,), device=dev, dtype=torch.int64)          # kept, then the class histogram
+    d3 = lambda v: (C.c_double * 3)(*[float(x) for x in v])
+    check(L.lm_las_decode_select(C.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index)), C.c_void_p(records_u8.data_ptr()),
+                                 int(record_len), int(point_format), int(n), d3(scale), d3(offset), d3(shift) if shift is not None else None,
+                                 INTEN_MIN, INTEN_MAX, int(normalise), C.byref(sel), C.c_void_p(ws.data_ptr()), need,
+                                 C.c_void_p(out.data_ptr()), C.c_void_p(meta.data_ptr()),
+                                 C.c_void_p(meta.data_ptr() + 8) if return_hist else None))
+    host = (meta if return_hist else meta[:1]).cpu().numpy()          # the one synchronisation
+    kept = int(host[0])
+    pts = out[:kept]
+    return (pts, host[1:].copy()) if return_hist else pts
+
+
+def _read(path, device, shift, normalise, select=None, class_hist=False):
     data = np.fromfile(path, dtype=np.uint8)
     h = parse_header(data)
     n, rl, off = h['n_points'], h['record_len'], h['offset_to_points']
+    if select is not None:
+        select.for_format(h['point_format'])                          # refused before anything is uploaded
+    elif class_hist:
+        raise ValueError('las_io: class_hist needs select= (PointFilter(drop_withheld=False) keeps every record)')
     nbytes = n * rl
     padded = np.zeros(((nbytes + 3) // 4 * 4,), dtype=np.uint8)
     padded[:nbytes] = data[off:off + nbytes]
     rec = torch.from_numpy(padded).to(device, non_blocking=True)
-    return decode_points(rec, rl, n, h['scale'], h['offset'], shift, normalise), h
+    if select is None:
+        return decode_points(rec, rl, n, h['scale'], h['offset'], shift, normalise), h
+    res = decode_points(rec, rl, n, h['scale'], h['offset'], shift, normalise, point_format=h['point_format'], select=select,
+                        return_hist=class_hist)
+    pts = res[0] if class_hist else res
+    h['n_kept'] = int(pts.shape[0])
+    if class_hist:
+        h['class_hist'] = res[1]
+    return pts, h
 
 
-def read_las(filepath, device='cuda:0', shift=None):
-    """-> [N,4] float32 (x, y, z, normalised intensity) on `device`, like the reference's read_las."""
-    pts, _ = _read(filepath, torch.device(device), shift, True)
+def read_las(filepath, device='cuda:0', shift=None, select=None):
+    """-> [N,4] float32 (x, y, z, normalised intensity) on `device`, like the reference's read_las.  select: a PointFilter, see
+    decode_points (one synchronisation; the "fewer than 5 points" refusal then counts the kept points)."""
+    pts, _ = _read(filepath, torch.device(device), shift, True, select)
     if pts.shape[0] < 5:
-        raise ValueError(f'{filepath}: only {pts.shape[0]} lidar points')
+        raise ValueError(f'{filepath}: only {pts.shape[0]} lidar points' + (' pass the filter' if select is not None else ''))
     return pts
 
 
-def read_las_raw(filepath, device='cuda:0', shift=None):
-    """-> ([N,4] float32 with RAW intensity, header dict): the record layout lm_bev_raster_batch consumes."""
-    return _read(filepath, torch.device(device), shift, False)
+def read_las_raw(filepath, device='cuda:0', shift=None, select=None, class_hist=False):
+    """-> ([N,4] float32 with RAW intensity, header dict): the record layout lm_bev_raster_batch consumes.  select: a PointFilter, see
+    decode_points: the kept points only, header['n_kept'] their number (header['n_points'] stays the file's); class_hist=True adds
+    header['class_hist'], int64 [256], the classification counts of all records of the file."""
+    return _read(filepath, torch.device(device), shift, False, select, class_hist)
 
 
 def grid_layout(header, img_reso=(0.05, 0.05), overlap_px=128, H=1152, W=1152, ele_reso=0.05, las_read_offset=None):

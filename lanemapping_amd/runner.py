@@ -282,7 +282,16 @@ class Runner:
                 print(f'{k}={v}')
         return results
 
-    def infer_las_to_map(self, las_and_params, work_dirs=None, path_ckpt=None, batch_size=None, merge=True):
+    def _las_select(self, select):
+        """The point filter of the LAS readers: the argument, else cfg['las_select'] (a dict of las_io.PointFilter arguments), else none."""
+        from . import las_io
+        if select is None and self.cfg.get('las_select') is not None:
+            select = las_io.PointFilter(**dict(self.cfg.get('las_select')))
+        if select is not None and not isinstance(select, las_io.PointFilter):
+            raise TypeError(f'select must be a las_io.PointFilter, not {type(select).__name__}')
+        return select
+
+    def infer_las_to_map(self, las_and_params, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None):
         """LAS tiles -> map-level 3-D lane lines, every stage of the reference's offline chain on this stack:
 
           LAS file + tile parameter file (utils/io_utils.py:125-150)
@@ -293,8 +302,11 @@ class Runner:
             -> merged + 0.6 m down-sampled lines -> merged.txt / merged_downsample.txt  [merge_lines.py __main__]
 
         las_and_params: list of (las_path, param_path) in tile order.  Returns (per-tile dict name -> 3-D lines, merged list).
+        select: a las_io.PointFilter applied to every file (default: cfg['las_select'], a dict of its arguments): only the records
+        that pass it reach the rasteriser; its z_range is in the frame shifted by las_read_offset.
         Single rank (the merge is sequential over the sorted tiles)."""
         from . import las_io
+        select = self._las_select(select)
         if path_ckpt:
             self.load_ckpt(path_ckpt)
         B = int(batch_size or self.cfg.get('batch_size', 8))
@@ -304,7 +316,7 @@ class Runner:
             pts, offs, rpar, names, plist = [], [0], [], [], []
             for las_path, param_path in chunk:
                 params = io_utils.load_pc_2_img_transform_paras(param_path)
-                p, _ = las_io.read_las_raw(las_path, self.device, shift=params['las_read_offset'])
+                p, _ = las_io.read_las_raw(las_path, self.device, shift=params['las_read_offset'], select=select)
                 pts.append(p)
                 offs.append(offs[-1] + p.shape[0])
                 rpar.append(io_utils.raster_params_from_file(param_path))
@@ -379,15 +391,18 @@ class Runner:
             plist.append(params)
         return names, plist
 
-    def infer_las_strip_to_map(self, las_paths, param_paths, work_dirs=None, path_ckpt=None, batch_size=None, merge=True):
+    def infer_las_strip_to_map(self, las_paths, param_paths, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None):
         """A whole strip -> map-level lane lines: the LAS file(s) of the strip are read once, their points are binned into the tiles of
         the layout on the GPU (ops.strip_bin_points: the windows of `param_paths` may overlap and be rotated), and every batch of tiles
         then runs the chain of infer_las_to_map from the rasteriser on.  Same outputs under the same names; a tile is named by the
-        first 11 characters of its parameter file's stem.  las_paths: one path or a list; param_paths in tile order."""
+        first 11 characters of its parameter file's stem.  las_paths: one path or a list; param_paths in tile order.
+        select: as for infer_las_to_map, applied to every file of the strip before the binning (the lookup grid of the binning keeps
+        the z range of the file headers: a narrower z_range only makes it conservative)."""
         from . import las_io
         if isinstance(las_paths, (str, os.PathLike)):
             las_paths = [las_paths]
         names, plist = self._strip_layout(list(param_paths))
+        select = self._las_select(select)
         if path_ckpt:
             self.load_ckpt(path_ckpt)
         B = int(batch_size or self.cfg.get('batch_size', 8))
@@ -397,7 +412,7 @@ class Runner:
             shift = plist[0]['las_read_offset']
             clouds, z_lo, z_hi = [], np.inf, -np.inf
             for path in las_paths:
-                p, h = las_io.read_las_raw(path, self.device, shift=shift)
+                p, h = las_io.read_las_raw(path, self.device, shift=shift, select=select)
                 clouds.append(p)
                 z_lo, z_hi = min(z_lo, h['min'][2] - shift[2]), max(z_hi, h['max'][2] - shift[2])
             cloud = clouds[0] if len(clouds) == 1 else torch.cat(clouds)
