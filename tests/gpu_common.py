@@ -1,5 +1,8 @@
-"""Helpers shared by the GPU parity test files (tests/test_gpu_*.py)."""
+"""Helpers shared by the GPU test files (tests/test_gpu_*.py): library access, layouts, golden comparisons, the fp64 GroupNorm statistic,
+the per-tag net cache and the child processes of the A/B tests.  Raw calls of the library's entry points stay in the test files."""
 import os
+import subprocess
+import sys
 
 import numpy as np
 import torch
@@ -7,6 +10,42 @@ import torch
 from lanemapping_amd import synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _lib():
+    from lanemapping_amd._lib import lib
+    return lib()
+
+
+def _chk(code):
+    from lanemapping_amd._lib import check
+    check(code)
+
+
+def _s():
+    from lanemapping_amd import ops
+    return ops._stream()
+
+
+def _g(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def _nhwc_dev(x, dev):
+    return x.to(dev).permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+
+
+def _nhwc_rows(x):
+    """logical [B,C,H,W] (CPU) -> [B*H*W, C] pixel rows."""
+    return x.permute(0, 2, 3, 1).reshape(-1, x.shape[1])
+
+
+def _rows_nchw(rows, B, H, W):
+    return rows.reshape(B, H, W, -1).permute(0, 3, 1, 2)
+
+
+def _quarter_grid(t):
+    return torch.round(t * 4) / 4
 
 
 def _close(a, ref, tol=1e-4, name=''):
@@ -17,6 +56,82 @@ def _close(a, ref, tol=1e-4, name=''):
     err = float(np.abs(a - ref).max())
     assert err <= tol * scale, f'{name}: max err {err:.3e} > {tol:.0e} * scale {scale:.3f}'
     return err
+
+
+def _close_sampled(a, g, name, tol=1e-4):
+    """_close against a golden float tensor kept as samples + chunk means (make_golden_mixseg.sampled): the shape, every sampled element
+    and the mean of every chunk of the flat tensor (together covering every element) within tol of the reference's largest magnitude."""
+    a = a.detach().float().cpu().numpy() if torch.is_tensor(a) else np.asarray(a, dtype=np.float32)
+    assert a.shape == tuple(g[f'{name}_shape']), (name, a.shape, tuple(g[f'{name}_shape']))
+    scale = max(1.0, float(g[f'{name}_absmax']))
+    flat = a.reshape(-1)
+    err = float(np.abs(flat[::int(g[f'{name}_stride'])] - g[f'{name}_samples']).max())
+    assert err <= tol * scale, f'{name}: max sampled err {err:.3e} > {tol:.0e} * scale {scale:.3f}'
+    means = np.array([c.astype(np.float64).mean() for c in np.array_split(flat, len(g[f'{name}_chunk_mean']))])
+    err = float(np.abs(means - g[f'{name}_chunk_mean']).max())
+    assert err <= tol * scale, f'{name}: max chunk-mean err {err:.3e} > {tol:.0e} * scale {scale:.3f}'
+    assert abs(float(np.abs(flat).max()) - float(g[f'{name}_absmax'])) <= tol * scale, f'{name}: largest magnitude differs'
+
+
+def _flips_inside_noise(mine, ref, low_idx, name, budget):
+    """Integer decisions against the reference's: every mismatch lies where the reference's own margin is below 1e-4 (low_idx), and there
+    are at most `budget` of them."""
+    bad = np.flatnonzero(np.asarray(mine).reshape(-1) != np.asarray(ref).reshape(-1))
+    outside = np.setdiff1d(bad, low_idx)
+    assert outside.size == 0, f'{name}: {outside.size} mismatches where the reference margin is >= 1e-4'
+    assert bad.size <= budget, f'{name}: {bad.size} noise-margin flips (budget {budget})'
+
+
+def _same_polylines(V, g, name, prefix='e2e_'):
+    """The reference's polylines vertex for vertex: the same lanes, rows and per-vertex labels exactly; the column coordinate carries
+    one fp32 regression output (offset2) whose summation order differs from the reference's, so it is held to offset2's bound.
+    `prefix` is what the golden file puts in front of its end-to-end keys ('' in G23, 'e2e_' in the later ones)."""
+    R = g[f'{prefix}cls_offset_smooth']
+    assert V.shape == R.shape, (name, V.shape, R.shape)
+    assert np.array_equal(V[..., 0] > 0, R[..., 0] > 0), f'{name}: vertex sets differ'
+    assert np.array_equal(V[..., 1], R[..., 1]), f'{name}: vertex labels differ'
+    off_scale = max(1.0, float(g[f'{prefix}offset2_absmax']))
+    np.testing.assert_allclose(V[..., 0], R[..., 0], rtol=0, atol=1e-4 * off_scale, err_msg=name)
+
+
+def _gn_ref(y):
+    """fp64 per-(b, c) mean and 1/sqrt(var + eps) (two-pass, biased variance) of a logical [B,C,H,W] tensor."""
+    y = y.detach().double().cpu().flatten(2)
+    mean = y.mean(2)
+    var = ((y - mean[:, :, None]) ** 2).mean(2)
+    return mean, 1.0 / torch.sqrt(var + 1e-5)
+
+
+_NETS = {}
+
+
+def _cached_net(dev, key, build):
+    """The net build() makes, with the synthetic weights of seed 2021, on the GPU; built once per key.  A test file passes
+    (__name__, tag) so that its keys cannot meet another file's."""
+    if key not in _NETS:
+        _NETS[key] = synth.fill_module_(build(), 2021).to(dev)
+    return _NETS[key]
+
+
+def _run_child(script, *argv, env=None, timeout=900):
+    """Run `script` in a fresh Python child (the library reads its environment switches once per process) from the repository root, with
+    `env` on top of this process's environment, under a time limit.  A non-zero exit status is an AssertionError with the end of stderr."""
+    e = {**os.environ, **(env or {})}
+    e['PYTHONPATH'] = os.pathsep.join(p for p in (ROOT, e.get('PYTHONPATH')) if p)
+    r = subprocess.run([sys.executable, '-c', script, *argv], capture_output=True, text=True, timeout=timeout, cwd=ROOT, env=e)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return r
+
+
+def _ab_npz(script, variants, tmp_path, **kw):
+    """One child per (tag, env) of `variants`, each writing the .npz named by its argv[1]: {tag: arrays}.  The first failing child ends
+    the loop, so nothing more is started on a card that has just faulted."""
+    res = {}
+    for tag, env in variants:
+        path = str(tmp_path / f'{tag}.npz')
+        _run_child(script, path, env=env, **kw)
+        res[tag] = np.load(path)
+    return res
 
 
 def _rowref_head(dev):

@@ -12,21 +12,16 @@ outputs are held to an fp64 restatement at the tolerances of the existing tests 
 Guard sizes are given per case: at least one workgroup tile of the kernel that reads or writes the slab.  Shapes are chosen so that a
 workgroup tile straddles a batch boundary (H*W not a multiple of the tile, ragged Winograd blocks, 324 / 330 attention tokens)."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
-from gpu_common import _close
+from gpu_common import ROOT, _chk, _close, _g, _gn_ref, _lib, _nhwc_dev, _nhwc_rows, _rows_nchw, _run_child, _s
 from guards import INF, NAN, Slab, batched, guarded_runs
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # Entries taking a stream that this file does not run through guarded slabs, each with the reason.
 BOUNDS_EXEMPT = {
@@ -49,34 +44,6 @@ BOUNDS_EXEMPT = {
     'lm_sparse_rulebook': 'writes the rulebook conv_gather reads; every word in a canary slab in test_gpu_sparse_index.py::test_conv_outputs_and_rulebook',
     'lm_las_decode_points': 'byte-record parser; every point format covered against the oracle by test_las_read_vs_oracle',
 }
-
-
-def _lib():
-    from lanemapping_amd._lib import lib
-    return lib()
-
-
-def _s():
-    from lanemapping_amd import ops
-    return ops._stream()
-
-
-def _chk(code):
-    from lanemapping_amd._lib import check
-    check(code)
-
-
-def _g(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def _nhwc_rows(x):
-    """logical [B,C,H,W] (CPU) -> [B*H*W, C] pixel rows."""
-    return x.permute(0, 2, 3, 1).reshape(-1, x.shape[1])
-
-
-def _rows_nchw(rows, B, H, W):
-    return rows.reshape(B, H, W, -1).permute(0, 3, 1, 2)
 
 
 def _up(x, Ho, Wo):
@@ -209,15 +176,9 @@ def test_conv_mfma_lateral_plain_residual_bounds(dev):
     _close(_rows_nchw(y, 1, H, W), ref, 1e-5, 'lateral plain residual')
 
 
-def _gn64(y):
-    y = y.double().flatten(2)
-    mean = y.mean(2)
-    return mean, 1.0 / torch.sqrt(((y - mean[..., None]) ** 2).mean(2) + 1e-5)
-
-
 def _stats_close(st, y_ref, name):
     """st [C, 2] (mean, rstd) of one image against fp64: mean within 1e-5 of max(1, |mean|), rstd within 1e-5 relative."""
-    mean, rstd = _gn64(y_ref)
+    mean, rstd = _gn_ref(y_ref)
     mean, rstd = mean[0], rstd[0]
     st = st.double()
     assert float(((st[:, 0] - mean).abs() / mean.abs().clamp_min(1.0)).max()) <= 1e-5, name + ' mean'
@@ -415,9 +376,8 @@ print('ok')
 
 def test_conv_small_forced_valu_bounds(dev):
     """The Cin = 16 3x3 shapes on the VALU kernel (LM_SMALL_CONV_VALU=1, read once per process: a child process)."""
-    env = {**os.environ, 'LM_SMALL_CONV_VALU': '1', 'PYTHONPATH': ROOT}
-    p = subprocess.run([sys.executable, '-c', _SMALL_VALU_CHILD, ROOT], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0 and p.stdout.strip().endswith('ok'), p.stdout[-2000:] + p.stderr[-4000:]
+    p = _run_child(_SMALL_VALU_CHILD, ROOT, env={'LM_SMALL_CONV_VALU': '1'}, timeout=600)
+    assert p.stdout.strip().endswith('ok'), p.stdout[-2000:] + p.stderr[-4000:]
 
 
 @pytest.mark.parametrize('u8', [False, True])
@@ -496,7 +456,7 @@ def _gn_relu64(x, st, gamma, beta):
 def _gn_input(seed, Cc, H, W):
     g = _g(seed)
     x = torch.randn(1, Cc, H, W, generator=g) * 2 + 1
-    m, r = _gn64(x)
+    m, r = _gn_ref(x)
     st = torch.stack([m[0], r[0]], 1).float()
     return x, st
 
@@ -799,10 +759,6 @@ def test_head_tokens_bounds(dev, spatial):
         assert torch.equal(tok, ref)
     else:
         _close(tok, ref, 1e-5, 'head_tokens_window')
-
-
-def _nhwc_dev(x, dev):
-    return x.to(dev).permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
 
 
 # ==================================================================================================== sparse (config 5)

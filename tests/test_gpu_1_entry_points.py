@@ -14,14 +14,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from gpu_common import _close
+from gpu_common import _close, _gn_ref, _lib, _quarter_grid
 
 pytestmark = pytest.mark.gpu
-
-
-def _lib():
-    from lanemapping_amd._lib import lib
-    return lib()
 
 
 def _rel_close(a, ref, tol, name, floor=1e-30):
@@ -211,14 +206,6 @@ def test_conv_mfma_refusals(dev):
 
 
 # ================================================================================ 2. GroupNorm statistics
-def _gn_ref(y):
-    """fp64 per-(b, c) mean and 1/sqrt(var + eps) (two-pass, biased variance) of a logical [B,C,H,W] tensor."""
-    y = y.detach().double().cpu().flatten(2)
-    mean = y.mean(2)
-    var = ((y - mean[:, :, None]) ** 2).mean(2)
-    return mean, 1.0 / torch.sqrt(var + 1e-5)
-
-
 def _check_stats(st, y_ref, name):
     mean, rstd = _gn_ref(y_ref)
     _rel_close(st[..., 0], mean, 1e-5, name + ' mean', floor=1.0)
@@ -380,10 +367,6 @@ def test_head_proposal_conf_vs_fp64(dev, B, P, L):
 
 
 # ================================================================================ 4. decode (csrc/decode.hip)
-def _quarter_grid(t):
-    return torch.round(t * 4) / 4
-
-
 def test_decode_orient_ties_inf_and_slices(dev):
     """lm_decode_orient = argmax over the orientation channels (:615) with ties to the LOWEST index: 11 channels on a
     quarter grid of few values (many exact ties), -inf entries and all--inf pixels (-> 0); once as a whole NHWC tensor, once as an

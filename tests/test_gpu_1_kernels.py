@@ -10,7 +10,7 @@ import torch
 import torch.nn.functional as F
 
 import cases
-from gpu_common import ROOT, _close, _lidar_module, _rowref_head
+from gpu_common import _ab_npz, _close, _lidar_module, _rowref_head
 from lanemapping_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -233,15 +233,7 @@ def test_lateral_kernel_bit_identical(dev, tmp_path):
     LDS / barrier, residual and stores straight from the accumulator quads, persistent workgroups) against the tiled conv_mfma_kernel
     (LM_CONV_LATERAL=0, read once per process) on the same inputs, bit for bit: bilinear coarse residual, plain residual, residual rows;
     ragged sizes (which fall back to the tiled kernel), fewer tiles than XCDs, more tiles than workgroups, strided channel-slice views."""
-    import subprocess
-    import sys
-    outs = {}
-    for flag in ('1', '0'):
-        path = tmp_path / f'lateral_{flag}.npz'
-        r = subprocess.run([sys.executable, '-c', _LATERAL_AB, str(path)], capture_output=True, text=True, timeout=900, cwd=ROOT,
-                           env=dict(os.environ, LM_CONV_LATERAL=flag))
-        assert r.returncode == 0, r.stderr[-2000:]
-        outs[flag] = np.load(path)
+    outs = _ab_npz(_LATERAL_AB, [(flag, {'LM_CONV_LATERAL': flag}) for flag in ('1', '0')], tmp_path)
     assert len(outs['1'].files) == 14
     for k in outs['1'].files:
         assert np.array_equal(outs['1'][k], outs['0'][k]), f'{k}: lateral_mfma_kernel differs from conv_mfma_kernel'
@@ -269,13 +261,7 @@ def test_stem_mfma_bit_identical_to_valu(dev, tmp_path):
     """stem_mfma_kernel (7x7 s2 stem on v_mfma_f32_32x32x2_f32: weights resident in VGPRs, zero-weight pads so that the two k of an MFMA
     are neighbours in LDS, persistent workgroups) against the VALU stem_kernel (LM_STEM_VALU=1, read once per process) on the same inputs,
     bit for bit: u8 HWC and f32 planar tiles, ragged sizes, more tiles than resident workgroups."""
-    import subprocess
-    import sys
-    res = {}
-    for tag, env in (('mfma', {}), ('valu', {'LM_STEM_VALU': '1'})):
-        path = str(tmp_path / f'{tag}.npz')
-        subprocess.run([sys.executable, '-c', _STEM_AB, path], check=True, env={**os.environ, **env, 'PYTHONPATH': ROOT}, cwd=ROOT)
-        res[tag] = np.load(path)
+    res = _ab_npz(_STEM_AB, (('mfma', {}), ('valu', {'LM_STEM_VALU': '1'})), tmp_path)
     for k in res['mfma'].files:
         a, b = res['mfma'][k], res['valu'][k]
         assert np.isfinite(a).all() and a.shape == b.shape
@@ -306,13 +292,7 @@ def test_small_conv_mfma_bit_identical_to_valu(dev, tmp_path):
     """small_conv3x3_mfma_kernel (16-input-channel 3x3 convolutions of the head on v_mfma_f32_16x16x4_f32) against the VALU
     small_conv_kernel (LM_SMALL_CONV_VALU=1, read once per process), bit for bit: strides 1 / 2, ragged sizes, Cout < 16, scale / shift,
     pre-ReLU, ReLU, a channel slice of a wider tensor, more tiles than resident workgroups; and against torch."""
-    import subprocess
-    import sys
-    res = {}
-    for tag, env in (('mfma', {}), ('valu', {'LM_SMALL_CONV_VALU': '1'})):
-        path = str(tmp_path / f'{tag}.npz')
-        subprocess.run([sys.executable, '-c', _SMALL_AB, path], check=True, env={**os.environ, **env, 'PYTHONPATH': ROOT}, cwd=ROOT)
-        res[tag] = np.load(path)
+    res = _ab_npz(_SMALL_AB, (('mfma', {}), ('valu', {'LM_SMALL_CONV_VALU': '1'})), tmp_path)
     for k in res['mfma'].files:
         a, b = res['mfma'][k], res['valu'][k]
         assert np.isfinite(a).all() and a.shape == b.shape
@@ -352,13 +332,7 @@ def test_head_tokens_lds_bit_identical_to_gather(dev, tmp_path):
     the one-thread-per-token gather kernel (LM_HEAD_TOKENS_GATHER=1, read once per process): the same expression in the same order, bit for
     bit - the BASELINE shape, a small one and one with a ragged last block; proposals whose window leaves the map (conv-bias columns).
     Also head_stage2_lds_kernel (rows staged through LDS with coalesced loads) against the one-row-per-lane kernel (LM_HEAD_STAGE2_DIRECT=1)."""
-    import subprocess
-    import sys
-    res = {}
-    for tag, env in (('lds', {}), ('gather', {'LM_HEAD_TOKENS_GATHER': '1', 'LM_HEAD_STAGE2_DIRECT': '1'})):
-        path = str(tmp_path / f'{tag}.npz')
-        subprocess.run([sys.executable, '-c', _TOKENS_AB, path], check=True, env={**os.environ, **env, 'PYTHONPATH': ROOT}, cwd=ROOT)
-        res[tag] = np.load(path)
+    res = _ab_npz(_TOKENS_AB, (('lds', {}), ('gather', {'LM_HEAD_TOKENS_GATHER': '1', 'LM_HEAD_STAGE2_DIRECT': '1'})), tmp_path)
     for k in res['lds'].files:
         a, b = res['lds'][k], res['gather'][k]
         assert np.isfinite(a).all() and a.shape == b.shape
@@ -398,13 +372,7 @@ def test_gn_sum_three_terms_lds_bit_identical(dev, tmp_path):
     projection weights once per thread) against gn_relu_upsample_sum_kernel<3, 5> (LM_GN_SUM_LDS=0, read once per process): the same
     arithmetic in the same order, bit for bit - the sum, the projection with and without bias, with and without writing the sum; the
     BASELINE shape with channel-slice operands, ragged tiles, 32 / 64 / 128 / 256 channels."""
-    import subprocess
-    import sys
-    res = {}
-    for tag, env in (('lds', {}), ('per_output', {'LM_GN_SUM_LDS': '0'})):
-        path = str(tmp_path / f'{tag}.npz')
-        subprocess.run([sys.executable, '-c', _GNSUM_AB, path], check=True, env={**os.environ, **env, 'PYTHONPATH': ROOT}, cwd=ROOT)
-        res[tag] = np.load(path)
+    res = _ab_npz(_GNSUM_AB, (('lds', {}), ('per_output', {'LM_GN_SUM_LDS': '0'})), tmp_path)
     for k in res['lds'].files:
         a, b = res['lds'][k], res['per_output'][k]
         assert np.isfinite(a).all() and a.shape == b.shape
@@ -635,7 +603,7 @@ def test_c_abi_from_plain_c(dev, tmp_path):
     cmd = ['gcc', os.path.join(root, 'tests', 'c_abi', 'smoke.c'), os.path.join(root, 'oracle', 'raster_ref.c'), '-O2', '-ffp-contract=off',
            '-std=gnu11', '-I', os.path.join(root, 'include'), '-I', '/opt/rocm/include', '-D__HIP_PLATFORM_AMD__', '-L', lib_dir,
            '-llanemap_hip', '-L/opt/rocm/lib', '-lamdhip64', f'-Wl,-rpath,{lib_dir}', '-Wl,-rpath,/opt/rocm/lib', '-lm', '-o', exe]
-    subprocess.run(cmd, check=True, capture_output=True, text=True)
+    subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=120)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     print(r.stdout)
     assert r.returncode == 0 and 'C-ABI smoke OK' in r.stdout, r.stdout + r.stderr

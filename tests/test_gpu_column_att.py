@@ -11,41 +11,15 @@ import torch
 import torch.nn.functional as F
 
 import cases
-from gpu_common import _close
+from gpu_common import (_cached_net, _chk, _close, _close_sampled, _flips_inside_noise, _g, _lib, _nhwc_dev, _nhwc_rows, _rows_nchw,
+                        _same_polylines)
 from guards import INF, NAN, Slab, batched, guarded_runs
 from lanemapping_amd import ops, synth
 from test_column_att_cpu import _layouts, build_colatt
-from test_gpu_head_geometry import _close_sampled, _flips_inside_noise, _same_polylines
 
 pytestmark = pytest.mark.gpu
 
 TAGS = ('att_p72', 'att_p36', 'att_p18', 'att_t2')
-
-
-def _lib():
-    from lanemapping_amd._lib import lib
-    return lib()
-
-
-def _chk(rc):
-    from lanemapping_amd._lib import check
-    check(rc)
-
-
-def _g(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def _nhwc_dev(x, dev):
-    return x.to(dev).permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-
-
-def _nhwc_rows(x):
-    return x[0].permute(1, 2, 0).reshape(-1, x.shape[1])
-
-
-def _rows_nchw(rows, B, H, W):
-    return rows.reshape(B, H, W, -1).permute(0, 3, 1, 2)
 
 
 # ----------------------------------------------------------------------------------------------- widened small conv
@@ -81,7 +55,7 @@ def test_small_conv_wide_bounds(dev, name, H, W, cin, cout, k, stride, pre_relu)
 
     def run(B, poisoned):
         pad = poison if poisoned else 0.0
-        xs = Slab(dev, B * P, cin, ldx, 4, 256 + 2 * W, 256 + 2 * W).fill_input(batched(_nhwc_rows(x), B, poison), pad)
+        xs = Slab(dev, B * P, cin, ldx, 4, 256 + 2 * W, 256 + 2 * W).fill_input(batched(_nhwc_rows(x[:1]), B, poison), pad)
         ys = Slab(dev, B * Po, cout, ldy, 4, 256, 256).fill_canary()
         _chk(_lib().lm_conv2d_nhwc_small(ops._stream(), xs.ptr(), ldx, w16.data_ptr(), scd.data_ptr(), shd.data_ptr(), ys.ptr(), ldy, B,
                                          H, W, cin, cout, kh, kw, stride, kh // 2, kw // 2, int(pre_relu), ops.ACT_NONE))
@@ -115,16 +89,9 @@ def test_small_conv_wide_refusals(dev, cout):
 
 
 # ----------------------------------------------------------------------------------------------- goldens
-_NETS = {}
-
-
 def _net(dev, tag):
     """The tag's column_att net with the synthetic weights of seed 2021 on the GPU (tests restore whatever they change)."""
-    if tag not in _NETS:
-        n = build_colatt(_layouts()[tag]['heads'])
-        synth.fill_module_(n, 2021)
-        _NETS[tag] = n.to(dev)
-    return _NETS[tag]
+    return _cached_net(dev, (__name__, tag), lambda: build_colatt(_layouts()[tag]['heads']))
 
 
 @pytest.mark.parametrize('tag', TAGS)

@@ -10,34 +10,15 @@ import pytest
 import torch
 
 import cases
-from gpu_common import _close
+from gpu_common import _cached_net, _chk, _close, _close_sampled, _flips_inside_noise, _g, _lib, _nhwc_dev, _same_polylines
 from guards import INF, Slab, batched, guarded_runs
 from lanemapping_amd import ops, synth
 from test_endpoint_mode_cpu import _layouts, build_endpoint, build_tag, endpoint_ref64
-from test_gpu_head_geometry import _close_sampled, _flips_inside_noise, _same_polylines
 
 pytestmark = pytest.mark.gpu
 
 TAGS = ('ep_c2', 'ep_att', 'ep_mixseg')
 FRAME = (0, 1, 1150, 1151)
-
-
-def _lib():
-    from lanemapping_amd._lib import lib
-    return lib()
-
-
-def _chk(rc):
-    from lanemapping_amd._lib import check
-    check(rc)
-
-
-def _g(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def _nhwc_dev(x, dev):
-    return x.to(dev).permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
 
 
 # ----------------------------------------------------------------------------------------------- the kernel
@@ -146,16 +127,9 @@ def test_head_endpoint_refusals(dev):
 
 
 # ----------------------------------------------------------------------------------------------- goldens
-_NETS = {}
-
-
 def _net(dev, tag):
     """The tag's endpoint-mode net with the synthetic weights of seed 2021 on the GPU (tests restore whatever they change)."""
-    if tag not in _NETS:
-        n = build_tag(tag)
-        synth.fill_module_(n, 2021)
-        _NETS[tag] = n.to(dev)
-    return _NETS[tag]
+    return _cached_net(dev, (__name__, tag), lambda: build_tag(tag))
 
 
 class _endp_est_mode:

@@ -5,8 +5,6 @@ goldens G25 (tests/golden/make_golden_propgeom.py), batch invariance, graph repl
 import ctypes as C
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -14,7 +12,8 @@ import torch
 import torch.nn.functional as F
 
 import cases
-from gpu_common import ROOT, _close
+from gpu_common import (_ab_npz, _cached_net, _chk, _close, _close_sampled, _flips_inside_noise, _g, _lib, _nhwc_dev, _nhwc_rows,
+                        _quarter_grid, _same_polylines)
 from guards import NAN, Slab, batched, guarded_runs
 from lanemapping_amd import ops, synth
 from test_head_geometry_cpu import build_geometry
@@ -23,28 +22,6 @@ pytestmark = pytest.mark.gpu
 
 TAGS = ('c2_p36', 'c2_p18', 'c2_d512', 'mixseg_p36')
 GEOM = {12: (36, 4), 16: (18, 8)}        # FW -> (num_prop, prop_width); prop_half_buff = 4
-
-
-def _lib():
-    from lanemapping_amd._lib import lib
-    return lib()
-
-
-def _chk(rc):
-    from lanemapping_amd._lib import check
-    check(rc)
-
-
-def _g(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def _nhwc_dev(x, dev):
-    return x.to(dev).permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-
-
-def _nhwc_rows(x):
-    return x[0].permute(1, 2, 0).reshape(-1, x.shape[1])
 
 
 # ----------------------------------------------------------------------------------------------- fp64 restatements
@@ -119,12 +96,7 @@ np.savez(sys.argv[1], **out)
 def test_head_tokens_lds_bit_identical_to_gather_fw12_fw16(dev, tmp_path):
     """head_tokens_lds_kernel<12 / 16> (its own tiling: 21 / 16 token rows per workgroup) against the one-thread-per-token gather kernel
     (LM_HEAD_TOKENS_GATHER=1, read once per process, so each runs in a fresh child process): bit for bit."""
-    res = {}
-    for tag, env in (('lds', {}), ('gather', {'LM_HEAD_TOKENS_GATHER': '1'})):
-        path = str(tmp_path / f'{tag}.npz')
-        subprocess.run([sys.executable, '-c', _TOKENS_AB, path], check=True, env={**os.environ, **env, 'PYTHONPATH': ROOT}, cwd=ROOT,
-                       timeout=600)
-        res[tag] = np.load(path)
+    res = _ab_npz(_TOKENS_AB, (('lds', {}), ('gather', {'LM_HEAD_TOKENS_GATHER': '1'})), tmp_path, timeout=600)
     assert len(res['lds'].files) == 6
     for k in res['lds'].files:
         a, b = res['lds'][k], res['gather'][k]
@@ -141,10 +113,6 @@ def test_head_tokens_refuses_other_widths(dev):
 
 
 # ----------------------------------------------------------------------------------------------- decode
-def _quarter_grid(t):
-    return torch.round(t * 4) / 4
-
-
 @pytest.mark.parametrize('fw', [12, 16])
 def test_decode_proposals_ties_saturation_clamp(dev, fw):
     """lm_decode_proposals at FW 12 / 16 against fp64: cls_idx, v_ext and cls_offset bit-exact for every proposal index, probabilities at
@@ -255,7 +223,7 @@ def test_head_tokens_bounds_fw(dev, fw, spatial):
 
     def run(B, poisoned):
         pad = NAN if poisoned else 0.0
-        rs = Slab(dev, B * Hr * Wr, 16, None, 0, 2 * Wr + 256, 2 * Wr + 256).fill_input(batched(_nhwc_rows(row), B, NAN), pad)
+        rs = Slab(dev, B * Hr * Wr, 16, None, 0, 2 * Wr + 256, 2 * Wr + 256).fill_input(batched(_nhwc_rows(row[:1]), B, NAN), pad)
         ts = Slab(dev, B * rows_el, 16 * fw, None, 0, 64, 64).fill_canary()
         if spatial:
             ss = Slab(dev, B * 2 * Hr, 2 * Wr, None, 0, 8, 8).fill_input(batched(seg[0], B, NAN), pad)
@@ -314,49 +282,13 @@ def test_head_proposal_conf_bounds_fw(dev, fw):
 
 
 # ----------------------------------------------------------------------------------------------- goldens
-_NETS = {}
-
-
 def _net(dev, tag):
     """The geometry's net with the synthetic weights of seed 2021 on the GPU (tests do not mutate it)."""
-    if tag not in _NETS:
+    def build():
         from test_head_geometry_cpu import _layouts
         ref = _layouts()[tag]
-        n = build_geometry(ref['config'], ref['heads'])
-        synth.fill_module_(n, 2021)
-        _NETS[tag] = n.to(dev)
-    return _NETS[tag]
-
-
-def _close_sampled(a, g, name, tol=1e-4):
-    """As test_gpu_mixseg._close_sampled: shape, samples, chunk means and largest magnitude within tol of the reference's scale."""
-    a = a.detach().float().cpu().numpy() if torch.is_tensor(a) else np.asarray(a, dtype=np.float32)
-    assert a.shape == tuple(g[f'{name}_shape']), (name, a.shape, tuple(g[f'{name}_shape']))
-    scale = max(1.0, float(g[f'{name}_absmax']))
-    flat = a.reshape(-1)
-    err = float(np.abs(flat[::int(g[f'{name}_stride'])] - g[f'{name}_samples']).max())
-    assert err <= tol * scale, f'{name}: max sampled err {err:.3e} > {tol:.0e} * scale {scale:.3f}'
-    means = np.array([c.astype(np.float64).mean() for c in np.array_split(flat, len(g[f'{name}_chunk_mean']))])
-    err = float(np.abs(means - g[f'{name}_chunk_mean']).max())
-    assert err <= tol * scale, f'{name}: max chunk-mean err {err:.3e} > {tol:.0e} * scale {scale:.3f}'
-    assert abs(float(np.abs(flat).max()) - float(g[f'{name}_absmax'])) <= tol * scale, f'{name}: largest magnitude differs'
-
-
-def _flips_inside_noise(mine, ref, low_idx, name, budget):
-    bad = np.flatnonzero(np.asarray(mine).reshape(-1) != np.asarray(ref).reshape(-1))
-    outside = np.setdiff1d(bad, low_idx)
-    assert outside.size == 0, f'{name}: {outside.size} mismatches where the reference margin is >= 1e-4'
-    assert bad.size <= budget, f'{name}: {bad.size} noise-margin flips (budget {budget})'
-
-
-def _same_polylines(V, g, name):
-    """As test_gpu_mixseg._same_polylines: vertex sets and labels exact, column coordinates within offset2's bound."""
-    R = g['e2e_cls_offset_smooth']
-    assert V.shape == R.shape, (name, V.shape, R.shape)
-    assert np.array_equal(V[..., 0] > 0, R[..., 0] > 0), f'{name}: vertex sets differ'
-    assert np.array_equal(V[..., 1], R[..., 1]), f'{name}: vertex labels differ'
-    off_scale = max(1.0, float(g['e2e_offset2_absmax']))
-    np.testing.assert_allclose(V[..., 0], R[..., 0], rtol=0, atol=1e-4 * off_scale, err_msg=name)
+        return build_geometry(ref['config'], ref['heads'])
+    return _cached_net(dev, (__name__, tag), build)
 
 
 @pytest.mark.parametrize('tag', TAGS)

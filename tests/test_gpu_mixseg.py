@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import cases
-from gpu_common import _close
+from gpu_common import _close, _close_sampled, _same_polylines
 from lanemapping_amd import ops, synth
 
 pytestmark = pytest.mark.gpu
@@ -85,21 +85,6 @@ def test_token_mix_batch_isolation(dev, K, M):
 
 
 # ----------------------------------------------------------------------------------------------- goldens
-def _close_sampled(a, g, name, tol=1e-4):
-    """_close against a golden float tensor kept as samples + chunk means (make_golden_mixseg.sampled): the shape, every sampled element
-    and the mean of every chunk of the flat tensor (together covering every element) within tol of the reference's largest magnitude."""
-    a = a.detach().float().cpu().numpy() if torch.is_tensor(a) else np.asarray(a, dtype=np.float32)
-    assert a.shape == tuple(g[f'{name}_shape']), (name, a.shape, tuple(g[f'{name}_shape']))
-    scale = max(1.0, float(g[f'{name}_absmax']))
-    flat = a.reshape(-1)
-    err = float(np.abs(flat[::int(g[f'{name}_stride'])] - g[f'{name}_samples']).max())
-    assert err <= tol * scale, f'{name}: max sampled err {err:.3e} > {tol:.0e} * scale {scale:.3f}'
-    means = np.array([c.astype(np.float64).mean() for c in np.array_split(flat, len(g[f'{name}_chunk_mean']))])
-    err = float(np.abs(means - g[f'{name}_chunk_mean']).max())
-    assert err <= tol * scale, f'{name}: max chunk-mean err {err:.3e} > {tol:.0e} * scale {scale:.3f}'
-    assert abs(float(np.abs(flat).max()) - float(g[f'{name}_absmax'])) <= tol * scale, f'{name}: largest magnitude differs'
-
-
 def test_mixseg_backbone_golden_g21(dev, mnet, golden):
     g = golden('g21_mixseg_backbone.npz')
     with torch.no_grad():
@@ -124,17 +109,6 @@ def test_mixseg_head_golden_g22(dev, mnet, golden):
         bad = np.flatnonzero(out[k].argmax(dim).cpu().numpy().reshape(-1) != g[f'{k}_argmax'].reshape(-1))
         outside = np.setdiff1d(bad, g[f'{k}_lowmargin'])
         assert outside.size == 0, f'{k}: {outside.size} argmax flips where the reference margin is >= 1e-4'
-
-
-def _same_polylines(V, g, name):
-    """The reference's polylines vertex for vertex: the same lanes, rows and per-vertex labels exactly; the column coordinate carries
-    one fp32 regression output (offset2) whose summation order differs from the reference's, so it is held to offset2's bound."""
-    R = g['cls_offset_smooth']
-    assert V.shape == R.shape, name
-    assert np.array_equal(V[..., 0] > 0, R[..., 0] > 0), f'{name}: vertex sets differ'
-    assert np.array_equal(V[..., 1], R[..., 1]), f'{name}: vertex labels differ'
-    off_scale = max(1.0, float(g['offset2_absmax']))
-    np.testing.assert_allclose(V[..., 0], R[..., 0], rtol=0, atol=1e-4 * off_scale, err_msg=name)
 
 
 def test_mixseg_end_to_end_golden_g23(dev, mnet, golden):
@@ -163,7 +137,7 @@ def test_mixseg_end_to_end_golden_g23(dev, mnet, golden):
     _close(o['prop_conf'], g['prop_conf'], 1e-4, 'prop_conf')
     assert np.array_equal(np.stack(np.nonzero(o['endp'][0].numpy()), axis=1), g['endp'])
     assert np.array_equal(np.stack(np.nonzero(o['lane_maps']['endp_by_cls'][0]), axis=1), g['endp_final'])
-    _same_polylines(o['lane_maps']['cls_offset_smooth'][0], g, 'polylines')
+    _same_polylines(o['lane_maps']['cls_offset_smooth'][0], g, 'polylines', prefix='')
 
 
 def test_mixseg_tile_inside_batch8_bit_identical(dev, mnet):
@@ -209,7 +183,7 @@ def test_mixseg_runner_tiles_to_json(dev, mnet, golden, tmp_path, monkeypatch):
     res = runner.infer_lane_coordinate_endpoint_semantics(tiles=str(tiles), batch_size=1, work_dirs=str(out), write_lane_vertex=True)
     assert list(res) == ['19012021_00']
     lanes = res['19012021_00'][0]
-    _same_polylines(lanes, g, 'runner polylines')
+    _same_polylines(lanes, g, 'runner polylines', prefix='')
     recs = json.load(open(out / '19012021_00.json'))
     assert recs == io_utils.lane_records(io_utils.pack_lane_vertices(lanes))
     want = io_utils.lane_records(io_utils.pack_lane_vertices(g['cls_offset_smooth']))

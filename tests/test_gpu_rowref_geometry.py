@@ -12,7 +12,7 @@ import pytest
 import torch
 
 import cases
-from gpu_common import _close
+from gpu_common import _chk, _close, _lib, _s
 from guards import NAN, Slab
 from lanemapping_amd import synth
 
@@ -20,21 +20,6 @@ pytestmark = pytest.mark.gpu
 
 CONFIG4 = 'Proj28_GFC-T3_RowRef_82_73_laser'
 CF = 8
-
-
-def _lib():
-    from lanemapping_amd._lib import lib
-    return lib()
-
-
-def _chk(code):
-    from lanemapping_amd._lib import check
-    check(code)
-
-
-def _s():
-    from lanemapping_amd import ops
-    return ops._stream()
 
 
 # ================================================================================ 1 / 2. window kernels against plain loops

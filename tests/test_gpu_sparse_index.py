@@ -15,28 +15,13 @@ import pytest
 import torch
 
 import sparse_ref as R
-from gpu_common import _close
+from gpu_common import _chk, _close, _lib, _s
 from guards import CANARY, Slab, _signed
 
 pytestmark = pytest.mark.gpu
 
 I32_CANARY = _signed(CANARY[torch.int32], torch.int32)
 F32_CANARY = _signed(CANARY[torch.float32], torch.float32)          # the fp32 canary read as int32 bits
-
-
-def _lib():
-    from lanemapping_amd._lib import lib
-    return lib()
-
-
-def _chk(code):
-    from lanemapping_amd._lib import check
-    check(code)
-
-
-def _s():
-    from lanemapping_amd import ops
-    return ops._stream()
 
 
 def _bits(a):

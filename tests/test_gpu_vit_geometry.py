@@ -12,41 +12,23 @@ import torch
 import torch.nn.functional as F
 
 import cases
-from gpu_common import _close
+from gpu_common import _cached_net, _chk, _close, _close_sampled, _flips_inside_noise, _g, _lib, _same_polylines
 from guards import NAN, Slab, batched, guarded_runs
 from lanemapping_amd import ops, synth
-from test_gpu_head_geometry import _close_sampled, _flips_inside_noise, _same_polylines
 from test_vit_geometry_cpu import _layouts, build_geometry
 
 pytestmark = pytest.mark.gpu
 
 TAGS = ('p4', 'p6', 'p12', 'p16', 'p4_mlp')
 E2E_TAGS = ('p4', 'p6')
-_NETS = {}
-
-
-def _lib():
-    from lanemapping_amd._lib import lib
-    return lib()
-
-
-def _chk(rc):
-    from lanemapping_amd._lib import check
-    check(rc)
-
-
-def _g(seed):
-    return torch.Generator().manual_seed(seed)
 
 
 def _net(dev, tag):
     """The geometry's net with the synthetic weights of seed 2021 on the GPU (tests do not mutate it)."""
-    if tag not in _NETS:
+    def build():
         ref = _layouts()[tag]
-        n = build_geometry(ref['backbone'], ref['config'])
-        synth.fill_module_(n, 2021)
-        _NETS[tag] = n.to(dev)
-    return _NETS[tag]
+        return build_geometry(ref['backbone'], ref['config'])
+    return _cached_net(dev, (__name__, tag), build)
 
 
 # ----------------------------------------------------------------------------------------------- attention, N >= 382

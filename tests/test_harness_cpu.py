@@ -316,3 +316,19 @@ def test_bench_dump_outputs_files(tmp_path):
     tiles = np.load(tmp_path / 'b' / 'tiles.npy')
     assert total <= 64 << 20 and 0 < len(tiles) < 400 and np.array_equal(tiles, np.load(tmp_path / 'c' / 'tiles.npy'))
     assert np.load(tmp_path / 'b' / 'lanes.npy').shape == (len(tiles), 72, 144, 2)
+
+
+def test_run_child_reports_exit_status_and_enforces_its_time_limit(tmp_path):
+    """gpu_common._run_child (every A/B child of the GPU tests): a child that exits 0 returns; one that exits 3 is an AssertionError with
+    its stderr; one that outlives the limit raises, and is no longer running afterwards."""
+    import subprocess
+    from gpu_common import ROOT, _run_child
+    r = _run_child('import os, sys; print(sys.argv[1], os.environ["LM_X"], os.getcwd()); print(os.environ["PYTHONPATH"])', 'a', env={'LM_X': 'b'})
+    assert r.stdout.splitlines()[0] == f'a b {ROOT}' and r.stdout.splitlines()[1].split(os.pathsep)[0] == ROOT
+    with pytest.raises(AssertionError, match='the reason'):
+        _run_child('import sys; print("the reason", file=sys.stderr); sys.exit(3)')
+    pid_file = tmp_path / 'pid'
+    with pytest.raises(subprocess.TimeoutExpired):
+        _run_child('import os, sys, time; open(sys.argv[1], "w").write(str(os.getpid())); time.sleep(60)', str(pid_file), timeout=1)
+    with pytest.raises(ProcessLookupError):
+        os.kill(int(pid_file.read_text()), 0)
