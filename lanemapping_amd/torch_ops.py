@@ -245,6 +245,40 @@ bev_raster = _define('bev_raster', _bev_raster,
                      lambda points, tile_offsets, params, H, W: points.new_empty((len(tile_offsets) - 1, H, W, 3), dtype=torch.uint8))
 
 
+def _params_list(params):
+    p = params.detach().cpu().float().numpy()
+    return [_ops.make_raster_params(quat=r[0:4], trans=r[4:7], bev_img_offset=r[7:9], img_reso=r[9:11], local_min_ele=r[11],
+                                    ele_reso=r[12], inten_lo=r[13], inten_hi=r[14]) for r in p]
+
+
+def _tile_ground(points: Tensor, tile_offsets: List[int], params: Tensor, H: int, W: int, cell_px: int) -> Tuple[Tensor, Tensor]:
+    """points, tile_offsets, params as for bev_raster -> (ground [B,Gy,Gx] f32, ground_min [B] f32): ops.tile_ground."""
+    return _ops.tile_ground(points, tile_offsets, _params_list(params), H, W, cell_px)
+
+
+def _tile_ground_fake(points, tile_offsets, params, H, W, cell_px):
+    B = len(tile_offsets) - 1
+    return points.new_empty((B, -(-H // cell_px), -(-W // cell_px))), points.new_empty((B,))
+
+
+tile_ground = _define('tile_ground', _tile_ground, _tile_ground_fake)
+
+
+def _ground_select(points: Tensor, tile_offsets: List[int], params: Tensor, ground: Tensor, H: int, W: int, cell_px: int, h_lo: float,
+                   h_hi: float) -> Tuple[Tensor, Tensor]:
+    """-> (points_out [kept,4] f32, offsets [B+1] int64 on the device): ops.ground_select (one synchronisation: kept sizes the result)."""
+    out, offs = _ops.ground_select(points, tile_offsets, _params_list(params), ground, H, W, cell_px, (h_lo, h_hi))
+    return out, torch.tensor(offs, dtype=torch.int64, device=points.device)
+
+
+def _ground_select_fake(points, tile_offsets, params, ground, H, W, cell_px, h_lo, h_hi):
+    n = torch.library.get_ctx().new_dynamic_size()
+    return points.new_empty((n, 4)), points.new_empty((len(tile_offsets),), dtype=torch.int64)
+
+
+ground_select = _define('ground_select', _ground_select, _ground_select_fake)
+
+
 def raster_params_tensor(params):
     """list of LmRasterParams -> the [B,15] float tensor `bev_raster` takes."""
     rows = [[*p.quat, *p.trans, *p.bev_img_offset, *p.img_reso, p.local_min_ele, p.ele_reso, p.inten_lo, p.inten_hi] for p in params]
@@ -363,4 +397,4 @@ polyline_assemble = _define('polyline_assemble', _polyline_assemble, _polyline_a
 
 OP_NAMES = ['conv2d_mfma', 'conv3x3_winograd44', 'stem_conv7x7', 'maxpool3x3s2', 'gn_stats', 'gn_relu_upsample',
             'upsample_bilinear', 'layernorm_rows', 'attention', 'linear_mfma', 'token_mix', 'tile_ingest', 'decode_proposals', 'decode_semantic',
-            'decode_orient', 'endp_topk', 'bev_raster', 'fpn_encoder', 'vit_backbone', 'mixer_backbone', 'colprop_head', 'colprop_endpoint', 'endp_cluster', 'polyline_assemble']
+            'decode_orient', 'endp_topk', 'bev_raster', 'tile_ground', 'ground_select', 'fpn_encoder', 'vit_backbone', 'mixer_backbone', 'colprop_head', 'colprop_endpoint', 'endp_cluster', 'polyline_assemble']
