@@ -208,6 +208,15 @@ long lm_bev_raster_workspace_bytes(int B, long max_points_per_tile, int H, int W
 int lm_bev_raster_batch(void* stream, const float* points_xyzi, const long* tile_offsets, const LmRasterParams* params,
                         int B, void* workspace, long workspace_bytes, float* out_chw, unsigned char* out_hwc_u8,
                         int H, int W);
+/* bev_raster_batch_scaled: lm_bev_raster_batch with a per-tile intensity scale.  inten_scale: HOST [B] or NULL.  Where it is given and
+ * positive it replaces the tile's derived scale 255 / inten_hi: I = clamp(floor((clip(i, inten_lo, inten_hi) - inten_lo) * scale + .5),
+ * 1, 255), so that a window lo..hi can be stretched over the whole channel (scale = white / (hi - lo)); NULL or a non-positive entry: the
+ * derived scale, i.e. lm_bev_raster_batch, which is this call with NULL.  The scale is a per-tile kernel argument either way: host side
+ * only, the kernels are the same.  Bounds cases: tests/test_gpu_intensity.py::test_scaled_raster_guards (see the NOTE on `hip_stream`
+ * under the ground model below). */
+int lm_bev_raster_batch_scaled(void* hip_stream, const float* points_xyzi, const long* tile_offsets, const LmRasterParams* params,
+                               int B, void* workspace, long workspace_bytes, float* out_chw, unsigned char* out_hwc_u8,
+                               int H, int W, const float* inten_scale);
 int lm_tile_ingest_u8(void* stream, const unsigned char* src_hwc, float* dst_chw, int B, int H, int W, int C);
 
 /* ---- strip binning (csrc/strip.hip): one cloud + T tile windows -> the per-tile point ranges lm_bev_raster_batch takes ------------
@@ -274,6 +283,31 @@ long lm_ground_select_workspace_bytes(long N, int B);
 int lm_ground_select(void* hip_stream, const float* points_xyzi, const long* tile_offsets, const LmRasterParams* params, int B, int H,
                      int W, int cell_px, const float* ground, float h_lo, float h_hi, void* workspace, long workspace_bytes,
                      float* points_out, long* out_offsets, long* out_offsets_host);
+
+/* ---- intensity window per tile or group of tiles (csrc/intensity.hip): two percentiles of the intensities of the points a tile keeps,
+ * for a rasteriser window that fits the scanner and the strip instead of the reference's constants 800 / 33000.
+ * (points, tile_offsets, params, B, H, W) as for lm_tile_ground; fewer than 2^32 points between tile_offsets[0] and tile_offsets[B] (the
+ * counters are 32-bit).  group: HOST [B], values in 0..G-1: the tiles of a group are counted together; NULL: tile b is group b, G == B.
+ * 1 <= G <= B <= 4096.  q_lo_ppm, q_hi_ppm: the two quantiles in parts per million, 0 <= q_lo_ppm <= q_hi_ppm <= 1000000.
+ * A point counts for tile b exactly when the rasteriser keeps it for b (the shared window test of csrc/raster_xf.h) and its intensity
+ * p[3] is not NaN.  Its key is k = (int)floorf(fminf(fmaxf(i, 0), 65535)): LAS intensities are u16, so the key is the intensity;
+ * non-integer, negative, larger and infinite values clamp.  With n = the counted points of group g over all its tiles:
+ *   window [G][2] int32, DEVICE: window[g][0] = the key of 0-based rank (n - 1) * q_lo_ppm / 1000000 (64-bit integer floor division) among
+ *                 the group's keys in ascending order - the lower order statistic, a value that occurs in the data; window[g][1] the same
+ *                 with q_hi_ppm; (-1, -1) for n = 0
+ *   count [G] int64, DEVICE: n
+ *   coarse_hist [G][4096] u32, DEVICE, or NULL: the number of counted points with k >> 4 == bin
+ * Exact: a histogram of k >> 4 per group (LDS, then integer atomic adds), the two coarse bins that hold the ranks, a second pass that
+ * counts the 16 keys of each of the two bins.  Integer adds are order independent: the same bits on every run and stream.  Asynchronous,
+ * no host synchronisation.  workspace: device, 16-byte aligned, lm_tile_intensity_workspace_bytes(B, G) bytes (0 = unsupported arguments).
+ * Bad arguments are refused with LM_ERR_ARG and a message that names the argument (B, G, group, q_lo_ppm, q_hi_ppm, tile_offsets,
+ * workspace, null pointer).
+ * NOTE on the name `hip_stream`: as for lm_tile_ground above; the guarded-buffer case is tests/test_gpu_intensity.py::
+ * test_tile_intensity_window_guards. */
+long lm_tile_intensity_workspace_bytes(int B, int G);
+int lm_tile_intensity_window(void* hip_stream, const float* points_xyzi, const long* tile_offsets, const LmRasterParams* params, int B,
+                             int H, int W, const int* group, int G, int q_lo_ppm, int q_hi_ppm, void* workspace, long workspace_bytes,
+                             int* window, long* count, unsigned* coarse_hist);
 
 /* ---- host-side tail (HOST pointers; no GPU is touched) --------------------------------------------------------
  * endp_cluster: heads/polyline_fpn_vit_vertex_2.py:661-688 + :903-924.

@@ -88,6 +88,7 @@ SIGNATURES = {
     'lm_pack_segments': (i32, [vp, i32, vp, vp, vp, vp]),
     'lm_bev_raster_workspace_bytes': (i64, [i32, i64, i32, i32]),
     'lm_bev_raster_batch': (i32, [vp, vp, C.POINTER(i64), C.POINTER(LmRasterParams), i32, vp, i64, vp, vp, i32, i32]),
+    'lm_bev_raster_batch_scaled': (i32, [vp, vp, C.POINTER(i64), C.POINTER(LmRasterParams), i32, vp, i64, vp, vp, i32, i32, c_f32p]),
     'lm_tile_ingest_u8': (i32, [vp, vp, vp, i32, i32, i32, i32]),
     'lm_strip_build_grid': (i32, [C.POINTER(LmRasterParams), i32, i32, i32, C.c_double, C.c_double, C.POINTER(LmStripGrid), vp, i64]),
     'lm_strip_bin_workspace_bytes': (i64, [i64, i32]),
@@ -98,6 +99,9 @@ SIGNATURES = {
     'lm_ground_select_workspace_bytes': (i64, [i64, i32]),
     'lm_ground_select': (i32, [vp, vp, C.POINTER(i64), C.POINTER(LmRasterParams), i32, i32, i32, i32, vp, f32, f32, vp, i64, vp, vp,
                                C.POINTER(i64)]),
+    'lm_tile_intensity_workspace_bytes': (i64, [i32, i32]),
+    'lm_tile_intensity_window': (i32, [vp, vp, C.POINTER(i64), C.POINTER(LmRasterParams), i32, i32, i32, C.POINTER(i32), i32, i32, i32, vp, i64,
+                                       vp, vp, vp]),
     'lm_endp_cluster': (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp]),
     'lm_polyline_assemble': (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp]),
     'lm_raster_polylines': (i32, [vp, i32, i32, vp]),

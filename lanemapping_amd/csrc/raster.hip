@@ -300,10 +300,13 @@ LM_API long lm_bev_raster_workspace_bytes(int B, long max_points_per_tile, int H
     return head + (long)B * nbands * nblk * CHUNK * (long)sizeof(unsigned);
 }
 
-// points: device [sum N, 4] f32; tile_offsets: HOST [B+1] (point index of each tile's first record); params: HOST [B]
-LM_API int lm_bev_raster_batch(void* stream, const float* points_xyzi, const long* tile_offsets, const LmRasterParams* params,
-                               int B, void* workspace, long workspace_bytes, float* out_chw, unsigned char* out_hwc_u8,
-                               int H, int W) {
+// points: device [sum N, 4] f32; tile_offsets: HOST [B+1] (point index of each tile's first record); params: HOST [B];
+// inten_scale: HOST [B] or NULL: where given and positive it replaces the tile's derived intensity scale 255 / inten_hi, so that
+// I = clamp(floor((clip(i, lo, hi) - lo) * scale + .5), 1, 255) (a per-tile kernel argument either way: the kernels are the same)
+LM_API int lm_bev_raster_batch_scaled(void* hip_stream, const float* points_xyzi, const long* tile_offsets, const LmRasterParams* params,
+                                      int B, void* workspace, long workspace_bytes, float* out_chw, unsigned char* out_hwc_u8,
+                                      int H, int W, const float* inten_scale) {
+    void* const stream = hip_stream;
     LM_REQUIRE(tile_offsets && params && workspace && (out_chw || out_hwc_u8) && B >= 1, "bev_raster: null pointer");
     const int band_rows = band_rows_for(B, H, W);
     LM_REQUIRE(band_rows > 0 && W > 0, "bev_raster: H=%d must be a multiple of 16 or 12 (at most %d bands) and rows*W <= 65536", H, MAX_BANDS);
@@ -338,6 +341,7 @@ LM_API int lm_bev_raster_batch(void* stream, const float* points_xyzi, const lon
         for (int b = 0; b < nb; ++b) {
             const long n = tile_offsets[b0 + b + 1] - tile_offsets[b0 + b];
             lm_raster_derive(params[b0 + b], tile_offsets[b0 + b], n, A.tile[b]);
+            if (inten_scale && inten_scale[b0 + b] > 0.0f) A.tile[b].iscale = inten_scale[b0 + b];
             BA.nblk[b] = (int)nblk_of(n);
             maxn = n > maxn ? n : maxn;
         }
@@ -355,6 +359,13 @@ LM_API int lm_bev_raster_batch(void* stream, const float* points_xyzi, const lon
         LM_LAUNCH_CHECK();
     }
     return LM_OK;
+}
+
+LM_API int lm_bev_raster_batch(void* stream, const float* points_xyzi, const long* tile_offsets, const LmRasterParams* params,
+                               int B, void* workspace, long workspace_bytes, float* out_chw, unsigned char* out_hwc_u8,
+                               int H, int W) {
+    return lm_bev_raster_batch_scaled(stream, points_xyzi, tile_offsets, params, B, workspace, workspace_bytes, out_chw, out_hwc_u8, H, W,
+                                      nullptr);
 }
 
 LM_API int lm_tile_ingest_u8(void* stream, const unsigned char* src_hwc, float* dst_chw, int B, int H, int W, int C) {

@@ -14,6 +14,9 @@ withheld points and gantry signs out of the rasteriser, which takes the brightes
 
 `GroundFilter` / `ground_datum` describe how the map routes follow the terrain: a per-tile elevation datum and a height-above-ground
 selection, both from the ground model the GPU computes out of the binned points (`ops.tile_ground`, `ops.ground_select`).
+
+`IntensityStretch` / `intensity_window` describe how the map routes fit the rasteriser's intensity window to the data: two percentiles of
+the intensities a tile, or the whole strip, keeps (`ops.tile_intensity_window`), stretched over the intensity channel.
 """
 import ctypes as C
 import math
@@ -157,6 +160,80 @@ def ground_datum(ground_min, ele_reso, margin, fallback):
     if g == math.inf:
         return float(fallback)
     return math.floor((g - float(margin)) / float(ele_reso)) * float(ele_reso)
+
+
+class IntensityStretch:
+    """How the LAS -> map routes choose the rasteriser's intensity window (immutable; Runner.infer_las_strip_to_map / infer_las_to_map,
+    `intensity=`).  The window is read off the data: two percentiles of the intensities of the points a tile keeps
+    (ops.tile_intensity_window), stretched so that the upper one lands on `white` (intensity_window below).
+
+      percentiles   (lo, hi) in percent, 0 <= lo <= hi <= 100, resolved to parts per million
+      scope         'tile': every tile its own window, from the point ranges the rasteriser will see; 'strip': one window for all tiles of
+                    the call, from all binned ranges before the batch loop (infer_las_strip_to_map only)
+      white         the level (0 < white <= 255) the upper percentile maps to; the reference's own window puts 33000 at
+                    255 * 32200 / 33000 = 248.8
+      min_span      the window is at least this many intensity steps wide (> 0): a featureless tile is not amplified into noise
+      min_points    a tile or strip with fewer counted points keeps the `fallback` window and the reference's rule
+      fallback      (inten_lo, inten_hi) of that case: the constants of the reference's read_las
+    min_span and min_points are plain defaults, not tuned values."""
+    __slots__ = ('percentiles', 'scope', 'white', 'min_span', 'min_points', 'fallback')
+
+    def __init__(self, percentiles=(1.0, 99.9), scope='tile', white=249, min_span=16, min_points=1024, fallback=(800.0, 33000.0)):
+        try:
+            lo, hi = (float(v) for v in percentiles)
+        except (TypeError, ValueError):
+            raise ValueError(f'IntensityStretch: percentiles={percentiles!r} must be a pair of numbers') from None
+        if not (0.0 <= lo <= hi <= 100.0):
+            raise ValueError(f'IntensityStretch: percentiles={percentiles!r} must satisfy 0 <= lo <= hi <= 100')
+        if scope not in ('tile', 'strip'):
+            raise ValueError(f"IntensityStretch: scope={scope!r} must be 'tile' or 'strip'")
+        if isinstance(white, bool) or not (0.0 < float(white) <= 255.0):
+            raise ValueError(f'IntensityStretch: white={white!r} must be a level in (0, 255]')
+        if isinstance(min_span, bool) or not (0.0 < float(min_span) < math.inf):
+            raise ValueError(f'IntensityStretch: min_span={min_span!r} must be a finite number > 0')
+        if isinstance(min_points, bool) or int(min_points) != min_points or int(min_points) < 0:
+            raise ValueError(f'IntensityStretch: min_points={min_points!r} must be a whole number >= 0')
+        try:
+            f_lo, f_hi = (float(v) for v in fallback)
+        except (TypeError, ValueError):
+            raise ValueError(f'IntensityStretch: fallback={fallback!r} must be a pair of numbers') from None
+        if not (f_lo < f_hi < math.inf and f_hi > 0.0 and f_lo > -math.inf):
+            raise ValueError(f'IntensityStretch: fallback={fallback!r} must be a finite window lo < hi with hi > 0')
+        for k, v in (('percentiles', (lo, hi)), ('scope', scope), ('white', float(white)), ('min_span', float(min_span)),
+                     ('min_points', int(min_points)), ('fallback', (f_lo, f_hi))):
+            object.__setattr__(self, k, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError('IntensityStretch is immutable')
+
+    def __delattr__(self, name):
+        raise AttributeError('IntensityStretch is immutable')
+
+    def __repr__(self):
+        return 'IntensityStretch(' + ', '.join(f'{k}={getattr(self, k)!r}' for k in self.__slots__) + ')'
+
+    def __eq__(self, other):
+        return isinstance(other, IntensityStretch) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
+
+    def __hash__(self):
+        return hash(tuple(getattr(self, k) for k in self.__slots__))
+
+
+def intensity_window(lo_key, hi_key, count, stretch):
+    """The rasteriser's intensity window from the two percentile keys and the count of ops.tile_intensity_window: -> (inten_lo, inten_hi,
+    scale).  count < stretch.min_points (or no point at all): the fallback window with scale None, i.e. the reference's rule
+    I = round(255 (clip(i) - lo) / hi).  Otherwise lo = lo_key, hi = max(hi_key, lo + min_span), scale = white / (hi - lo):
+    I = clamp(floor((clip(i, lo, hi) - lo) * scale + .5), 1, 255) puts the upper percentile at `white`."""
+    if not isinstance(stretch, IntensityStretch):
+        raise TypeError(f'intensity_window: stretch must be a las_io.IntensityStretch, not {type(stretch).__name__}')
+    lo_key, hi_key, count = int(lo_key), int(hi_key), int(count)
+    if count < stretch.min_points or count <= 0:
+        return stretch.fallback[0], stretch.fallback[1], None
+    if not 0 <= lo_key <= hi_key <= 65535:
+        raise ValueError(f'intensity_window: keys ({lo_key}, {hi_key}) of {count} points are not 0 <= lo <= hi <= 65535')
+    lo = float(lo_key)
+    hi = max(float(hi_key), lo + stretch.min_span)
+    return lo, hi, stretch.white / (hi - lo)
 
 
 def parse_header(data):

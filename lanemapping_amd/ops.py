@@ -641,10 +641,12 @@ def make_raster_params(quat=(1, 0, 0, 0), trans=(0, 0, 0), bev_img_offset=(0, 0)
 _raster_ws = {}
 
 
-def bev_raster_batch(points, tile_offsets, params, H=1152, W=1152, out=None, want_u8=False, u8_only=False, out_u8=None):
+def bev_raster_batch(points, tile_offsets, params, H=1152, W=1152, out=None, want_u8=False, u8_only=False, out_u8=None, inten_scale=None):
     """points [sum N,4] f32 (x,y,z,raw intensity) on device, tile_offsets: B+1 ints, params: list of LmRasterParams
     -> proj [B,3,H,W] f32 (= u8/255), optional u8 [B,H,W,3].  u8_only: only the u8 HWC tile is written (the stem takes it
-    directly, ops.stem) - a quarter of the output bytes."""
+    directly, ops.stem) - a quarter of the output bytes.
+    inten_scale: a sequence of B floats (None or an entry <= 0: the derived 255 / inten_hi): the tile's intensity channel becomes
+    I = clamp(floor((clip(i, inten_lo, inten_hi) - inten_lo) * scale + .5), 1, 255) (lm_bev_raster_batch_scaled)."""
     assert points.dim() == 2 and points.shape[1] == 4 and points.is_contiguous() and points.dtype == torch.float32
     B = len(params)
     assert len(tile_offsets) == B + 1
@@ -663,8 +665,15 @@ def bev_raster_batch(points, tile_offsets, params, H=1152, W=1152, out=None, wan
     if want_u8:
         u8 = out_u8 if out_u8 is not None else torch.empty((B, H, W, 3), device=points.device, dtype=torch.uint8)
         assert u8.dtype == torch.uint8 and u8.is_contiguous() and tuple(u8.shape) == (B, H, W, 3)
-    check(lib().lm_bev_raster_batch(_stream(), _ptr(points) if points.numel() else None, offs, par, B, _ptr(ws), ws.numel(),
-                                    None if u8_only else _ptr(out), _ptr(u8), H, W))
+    if inten_scale is None:
+        check(lib().lm_bev_raster_batch(_stream(), _ptr(points) if points.numel() else None, offs, par, B, _ptr(ws), ws.numel(),
+                                        None if u8_only else _ptr(out), _ptr(u8), H, W))
+    else:
+        if len(inten_scale) != B:
+            raise ValueError(f'bev_raster_batch: {len(inten_scale)} inten_scale entries for {B} tiles')
+        scale = (C.c_float * B)(*[0.0 if v is None else float(v) for v in inten_scale])
+        check(lib().lm_bev_raster_batch_scaled(_stream(), _ptr(points) if points.numel() else None, offs, par, B, _ptr(ws), ws.numel(),
+                                               None if u8_only else _ptr(out), _ptr(u8), H, W, scale))
     if u8_only:
         return u8
     return (out, u8) if want_u8 else out
@@ -800,6 +809,38 @@ def ground_select(points, tile_offsets, params, ground, H=1152, W=1152, cell_px=
                                  float(h_range[0]), float(h_range[1]), _ptr(ws), ws.numel() if need else 0, _ptr(out) if N > 0 else None,
                                  C.c_void_p(doffs.data_ptr()), hoffs))
     return out[:hoffs[B]], [int(o) for o in hoffs]
+
+
+def tile_intensity_window(points, tile_offsets, params, H=1152, W=1152, percentiles=(1.0, 99.9), group=None, want_hist=False):
+    """Two percentiles of the intensities of the points every tile (or group of tiles) keeps (csrc/intensity.hip), from the (points,
+    tile_offsets, params) triple bev_raster_batch takes: -> (window [G,2] int32, count [G] int64) on the device, with want_hist also
+    hist [G,4096] int32 (the counted points per coarse bin key >> 4).  A point counts for a tile when the rasteriser keeps it for the
+    tile and its intensity is not NaN; its key is floor(clamp(intensity, 0, 65535)).  With n counted points in a group, window[g] holds the
+    keys of 0-based ranks (n - 1) * ppm // 10**6 in ascending order for ppm = round(p * 10**4) of the two percentiles; n = 0: (-1, -1).
+    group: B ints in 0..G-1 with G = max + 1 (None: every tile its own group).  Exact and reproducible.  No synchronisation."""
+    B, offs, par = _ground_args('tile_intensity_window', points, tile_offsets, params)
+    H, W = int(H), int(W)
+    if group is None:
+        G, grp = B, None
+    else:
+        if len(group) != B:
+            raise ValueError(f'tile_intensity_window: {len(group)} group entries for {B} tiles')
+        ids = [int(g) for g in group]
+        if any(not 0 <= g < B for g in ids):                    # before anything is sized by G (the library names G <= B the same way)
+            bad = next(b for b, g in enumerate(ids) if not 0 <= g < B)
+            raise ValueError(f'tile_intensity_window: group[{bad}]={ids[bad]} is outside 0..B-1={B - 1} (G = max(group) + 1 <= B)')
+        grp = (C.c_int * B)(*ids)
+        G = max(ids + [0]) + 1
+    q_lo, q_hi = (int(round(float(p) * 1e4)) for p in percentiles)
+    need = lib().lm_tile_intensity_workspace_bytes(B, G)
+    ws = _ground_ws(points, max(need, 16))
+    window = torch.empty((max(G, 0), 2), device=points.device, dtype=torch.int32)
+    count = torch.empty((max(G, 0),), device=points.device, dtype=torch.int64)
+    hist = torch.empty((max(G, 0), 4096), device=points.device, dtype=torch.int32) if want_hist else None
+    # (need == 0: unsupported arguments; the call below refuses them with the argument's name)
+    check(lib().lm_tile_intensity_window(_stream(), _ptr(points) if points.numel() else None, offs, par, B, H, W, grp, G, q_lo, q_hi,
+                                         _ptr(ws), ws.numel() if need else 0, _ptr(window), _ptr(count), _ptr(hist)))
+    return (window, count, hist) if want_hist else (window, count)
 
 
 def tile_ingest(u8_hwc):

@@ -22,6 +22,7 @@ converted u8 -> f32/255 on the GPU (lm_tile_ingest_u8).  With torch.distributed 
 over the ranks (lanemapping_amd/shard.py) and rank 0 writes every file after one all-gather per batch.
 """
 import glob
+import json
 import os
 import random
 
@@ -323,7 +324,61 @@ class Runner:
             io_utils.save_pc_2_img_transform_paras(os.path.join(par_dir, name + '.txt'), p)
         return plist, points, offs, rpar
 
-    def infer_las_to_map(self, las_and_params, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None, ground=None):
+    def _las_intensity(self, intensity):
+        """The intensity window of the LAS routes: the argument, else cfg['las_intensity'] (a dict of las_io.IntensityStretch arguments),
+        else none."""
+        from . import las_io
+        if intensity is None and self.cfg.get('las_intensity') is not None:
+            intensity = las_io.IntensityStretch(**dict(self.cfg.get('las_intensity')))
+        if intensity is not None and not isinstance(intensity, las_io.IntensityStretch):
+            raise TypeError(f'intensity must be a las_io.IntensityStretch, not {type(intensity).__name__}')
+        return intensity
+
+    @staticmethod
+    def _strip_intensity(st, points, offs, rpar, H, W):
+        """scope='strip': the one window of all tiles of the call, from all binned ranges (one group): -> (inten_lo, inten_hi, scale, count).
+        One device-to-host read."""
+        from . import las_io
+        window, count = ops.tile_intensity_window(points, offs, rpar, H, W, percentiles=st.percentiles, group=[0] * len(rpar))
+        lo, hi, n = (int(v) for v in torch.cat([window.to(torch.int64), count[:, None]], dim=1).cpu().numpy()[0])   # the one read-back
+        return (*las_io.intensity_window(lo, hi, n, st), n)
+
+    def _stretch_intensity(self, st, names, points, offs, rpar, H, W, out_dir, used, strip=None):
+        """One batch of tiles through a las_io.IntensityStretch: -> (rpar, inten_scale) to rasterise with.  scope='tile': the two
+        percentiles of every tile come from the point ranges the rasteriser will see (ops.tile_intensity_window; one device-to-host read
+        of window and count per batch); scope='strip': `strip` is the window found once for the whole call.  Every tile's inten_lo /
+        inten_hi are replaced in a copy of its LmRasterParams; the scale travels beside them (0: the derived 255 / inten_hi).  `used`
+        collects {tile name: [inten_lo, inten_hi, scale or None, count]} over the call and is written to <out_dir>/params/intensity.json."""
+        from . import las_io
+        from ._lib import LmRasterParams
+        if strip is None:
+            window, count = ops.tile_intensity_window(points, offs, rpar, H, W, percentiles=st.percentiles)
+            both = torch.cat([window.to(torch.int64), count[:, None]], dim=1).cpu().numpy()      # the one read-back
+            wins = [(*las_io.intensity_window(r[0], r[1], r[2], st), int(r[2])) for r in both]
+        else:
+            wins = [strip] * len(rpar)
+        rpar = [LmRasterParams.from_buffer_copy(r) for r in rpar]
+        scales = []
+        for name, r, (lo, hi, scale, n) in zip(names, rpar, wins):
+            r.inten_lo, r.inten_hi = lo, hi
+            scales.append(0.0 if scale is None else scale)
+            used[name] = [lo, hi, scale, n]
+        par_dir = os.path.join(out_dir, 'params')
+        os.makedirs(par_dir, exist_ok=True)
+        with open(os.path.join(par_dir, 'intensity.json'), 'w') as f:
+            json.dump(used, f, indent=1)
+        return rpar, scales
+
+    def _raster_stretched(self, raster_batch, st, names, plist, points, offs, rpar, H, W, out_dir, used, strip=None):
+        """One batch into the chain of _las_chain: as it is without an IntensityStretch (no new code runs), else with every tile's fitted
+        window in its LmRasterParams and its scale beside them (the one call site of both LAS routes)."""
+        if st is None:
+            return raster_batch(names, plist, points, offs, rpar)
+        rpar, scales = self._stretch_intensity(st, names, points, offs, rpar, H, W, out_dir, used, strip)
+        return raster_batch(names, plist, points, offs, rpar, scales)
+
+    def infer_las_to_map(self, las_and_params, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None, ground=None,
+                         intensity=None):
         """LAS tiles -> map-level 3-D lane lines, every stage of the reference's offline chain on this stack:
 
           LAS file + tile parameter file (utils/io_utils.py:125-150)
@@ -340,9 +395,18 @@ class Runner:
         ground model of every tile is computed on the GPU from the points `select` left; every tile gets an elevation datum under its
         own ground and / or only the points in a range of heights above the ground are rasterised.  The parameters actually used are
         written to <work_dirs>/params/<name>.txt.
+        intensity: a las_io.IntensityStretch (default: cfg['las_intensity'], a dict of its arguments; absent: nothing changes): per batch,
+        after `select` and `ground`, every tile's intensity window is fitted to two percentiles of the intensities it keeps
+        (ops.tile_intensity_window) and stretched (lm_bev_raster_batch_scaled); what was used is written to
+        <work_dirs>/params/intensity.json as {tile name: [inten_lo, inten_hi, scale or null, count]}.  scope='strip' is refused here: the
+        tiles arrive file by file.
         Single rank (the merge is sequential over the sorted tiles)."""
         from . import las_io
-        select, ground = self._las_select(select), self._las_ground(ground)
+        select, ground, intensity = self._las_select(select), self._las_ground(ground), self._las_intensity(intensity)
+        if intensity is not None and intensity.scope == 'strip':
+            raise ValueError("intensity: scope='strip' needs the whole strip in one cloud (infer_las_strip_to_map); infer_las_to_map reads "
+                             "its tiles file by file, use scope='tile'")
+        used = {}
         if path_ckpt:
             self.load_ckpt(path_ckpt)
         B = int(batch_size or self.cfg.get('batch_size', 8))
@@ -363,12 +427,12 @@ class Runner:
             pts = torch.cat(pts)
             if ground is not None:
                 plist, pts, offs, rpar = self._follow_ground(ground, names, plist, pts, offs, rpar, H, W, out_dir)
-            raster_batch(names, plist, pts, offs, rpar)
+            self._raster_stretched(raster_batch, intensity, names, plist, pts, offs, rpar, H, W, out_dir, used)
         return close()
 
     def _las_chain(self, work_dirs, merge):
         """The chain behind infer_las_to_map / infer_las_strip_to_map from the rasteriser on: -> (raster_batch, close).
-        raster_batch(names, params, points, offsets, raster_params) rasterises one batch of tiles out of `points` and runs it through
+        raster_batch(names, params, points, offsets, raster_params[, inten_scale]) rasterises one batch of tiles out of `points` and runs it through
         the pipeline, the per-tile JSON and the back-projection; close() drains the pipeline, merges and returns (lines3d, merged)."""
         from . import coor_img2pc, merge_lines as ml
         out_dir = work_dirs or self.cfg.get('work_dirs', './work_dirs')
@@ -399,10 +463,13 @@ class Runner:
                 pc_files.append(os.path.join(pc_dir, name + '.json'))
                 lines3d[name] = [l['seq'] for l in lines]
 
-        def raster_batch(names, params, points, offs, rpar):
+        def raster_batch(names, params, points, offs, rpar, inten_scale=None):
             for name, prm in zip(names, params):
                 queue.append([name, prm, None])
-            tiles, u8 = ops.bev_raster_batch(points, offs, rpar, H, W, want_u8=True)
+            if inten_scale is None:
+                tiles, u8 = ops.bev_raster_batch(points, offs, rpar, H, W, want_u8=True)
+            else:
+                tiles, u8 = ops.bev_raster_batch(points, offs, rpar, H, W, want_u8=True, inten_scale=inten_scale)
             u8_host = u8.cpu().numpy()
             for j in range(len(names)):
                 queue[len(queue) - len(names) + j][2] = u8_host[j]
@@ -433,19 +500,23 @@ class Runner:
         return names, plist
 
     def infer_las_strip_to_map(self, las_paths, param_paths, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None,
-                               ground=None):
+                               ground=None, intensity=None):
         """A whole strip -> map-level lane lines: the LAS file(s) of the strip are read once, their points are binned into the tiles of
         the layout on the GPU (ops.strip_bin_points: the windows of `param_paths` may overlap and be rotated), and every batch of tiles
         then runs the chain of infer_las_to_map from the rasteriser on.  Same outputs under the same names; a tile is named by the
         first 11 characters of its parameter file's stem.  las_paths: one path or a list; param_paths in tile order.
         select: as for infer_las_to_map, applied to every file of the strip before the binning (the lookup grid of the binning keeps
         the z range of the file headers: a narrower z_range only makes it conservative).
-        ground: as for infer_las_to_map, applied per batch of tiles to the binned ranges, i.e. after `select` and the binning."""
+        ground: as for infer_las_to_map, applied per batch of tiles to the binned ranges, i.e. after `select` and the binning.
+        intensity: as for infer_las_to_map, after `ground`.  scope='tile': per batch, on the ranges the rasteriser will see (after the
+        height selection of `ground`).  scope='strip': one window for every tile, found once over all binned ranges before the batch
+        loop - BEFORE `ground`'s height selection, which runs per batch: points it later drops still count for the strip's window."""
         from . import las_io
         if isinstance(las_paths, (str, os.PathLike)):
             las_paths = [las_paths]
         names, plist = self._strip_layout(list(param_paths))
-        select, ground = self._las_select(select), self._las_ground(ground)
+        select, ground, intensity = self._las_select(select), self._las_ground(ground), self._las_intensity(intensity)
+        used = {}
         if path_ckpt:
             self.load_ckpt(path_ckpt)
         B = int(batch_size or self.cfg.get('batch_size', 8))
@@ -465,12 +536,15 @@ class Runner:
             pad = 1e-3 * max(1.0, abs(z_lo), abs(z_hi))
             binned, offs = ops.strip_bin_points(cloud, rpar, H, W, z_range=(z_lo - pad, z_hi + pad) if z_lo <= z_hi else None)
             del cloud, clouds
+            strip = None
+            if intensity is not None and intensity.scope == 'strip':
+                strip = self._strip_intensity(intensity, binned, offs, rpar, H, W)
             for i in range(0, len(plist), B):
                 j = min(i + B, len(plist))
                 batch = (plist[i:j], binned, offs[i:j + 1], rpar[i:j])
                 if ground is not None:
                     batch = self._follow_ground(ground, names[i:j], *batch, H, W, out_dir)
-                raster_batch(names[i:j], *batch)
+                self._raster_stretched(raster_batch, intensity, names[i:j], *batch, H, W, out_dir, used, strip)
         return close()
 
     def infer_lane_geometry_segmentation_segmentor(self, path_ckpt=None, mode_view=False, write_lane_vertex=False,

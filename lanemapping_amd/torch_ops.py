@@ -279,6 +279,32 @@ def _ground_select_fake(points, tile_offsets, params, ground, H, W, cell_px, h_l
 ground_select = _define('ground_select', _ground_select, _ground_select_fake)
 
 
+def _tile_intensity_window(points: Tensor, tile_offsets: List[int], params: Tensor, H: int, W: int, p_lo: float, p_hi: float,
+                           group: Optional[List[int]]) -> Tuple[Tensor, Tensor]:
+    """points, tile_offsets, params as for bev_raster; the two percentiles; group: B ints or None (every tile its own group)
+    -> (window [G,2] int32, count [G] int64): ops.tile_intensity_window."""
+    return _ops.tile_intensity_window(points, tile_offsets, _params_list(params), H, W, (p_lo, p_hi), group)
+
+
+def _tile_intensity_window_fake(points, tile_offsets, params, H, W, p_lo, p_hi, group):
+    G = len(tile_offsets) - 1 if group is None else max(list(group) + [0]) + 1
+    return points.new_empty((G, 2), dtype=torch.int32), points.new_empty((G,), dtype=torch.int64)
+
+
+tile_intensity_window = _define('tile_intensity_window', _tile_intensity_window, _tile_intensity_window_fake)
+
+
+def _bev_raster_scaled(points: Tensor, tile_offsets: List[int], params: Tensor, H: int, W: int) -> Tensor:
+    """bev_raster with params [B,16]: the 15 columns of bev_raster, then the tile's intensity scale (0: the derived 255 / inten_hi)
+    -> u8 HWC tiles [B,H,W,3]."""
+    scale = [float(v) for v in params.detach().cpu().float()[:, 15]]
+    return _ops.bev_raster_batch(points, tile_offsets, _params_list(params), H, W, u8_only=True, inten_scale=scale)
+
+
+bev_raster_scaled = _define('bev_raster_scaled', _bev_raster_scaled,
+                            lambda points, tile_offsets, params, H, W: points.new_empty((len(tile_offsets) - 1, H, W, 3), dtype=torch.uint8))
+
+
 def raster_params_tensor(params):
     """list of LmRasterParams -> the [B,15] float tensor `bev_raster` takes."""
     rows = [[*p.quat, *p.trans, *p.bev_img_offset, *p.img_reso, p.local_min_ele, p.ele_reso, p.inten_lo, p.inten_hi] for p in params]
@@ -397,4 +423,4 @@ polyline_assemble = _define('polyline_assemble', _polyline_assemble, _polyline_a
 
 OP_NAMES = ['conv2d_mfma', 'conv3x3_winograd44', 'stem_conv7x7', 'maxpool3x3s2', 'gn_stats', 'gn_relu_upsample',
             'upsample_bilinear', 'layernorm_rows', 'attention', 'linear_mfma', 'token_mix', 'tile_ingest', 'decode_proposals', 'decode_semantic',
-            'decode_orient', 'endp_topk', 'bev_raster', 'tile_ground', 'ground_select', 'fpn_encoder', 'vit_backbone', 'mixer_backbone', 'colprop_head', 'colprop_endpoint', 'endp_cluster', 'polyline_assemble']
+            'decode_orient', 'endp_topk', 'bev_raster', 'bev_raster_scaled', 'tile_ground', 'ground_select', 'tile_intensity_window', 'fpn_encoder', 'vit_backbone', 'mixer_backbone', 'colprop_head', 'colprop_endpoint', 'endp_cluster', 'polyline_assemble']

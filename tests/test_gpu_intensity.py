@@ -1,0 +1,501 @@
+"""GPU: the intensity window (csrc/intensity.hip) and the scaled rasteriser entry - ops.tile_intensity_window and
+ops.bev_raster_batch(inten_scale=) against the numpy restatement of tests/intensity_ref.py, compared for equality; guarded buffers;
+refusals; the effect on a tile of a scanner with a pedestal; Runner.infer_las_strip_to_map with `intensity=` in both scopes.
+
+Sizes the kernels switch at (csrc/intensity.hip): a chunk is ICHUNK = 16,384 points, a workgroup covers a span of 4 chunks = 65,536
+points of one tile, a wave is 64 points."""
+import ctypes as C
+import json
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import ground_ref as gr
+import intensity_ref as ir
+from guards import NAN, Slab, guarded_runs
+from lanemapping_amd import io_utils, las_io, ops
+from lanemapping_amd._lib import LanemapHipError, LmRasterParams, lib
+from lanemapping_amd.las_io import IntensityStretch, intensity_window
+
+pytestmark = pytest.mark.gpu
+
+f32 = np.float32
+ICHUNK, ISPAN = 16384, 65536
+S = 96                                                             # H = W of the small tiles
+RESO = 0.0625
+PAIRS = [(0.0, 100.0), (1.0, 99.9), (50.0, 50.0)]
+
+
+def _axis_tile(**kw):
+    return ops.make_raster_params(trans=(8.0, 16.0, 0.5), bev_img_offset=(-1.0, 0.5), img_reso=(RESO, RESO), local_min_ele=-1.0, ele_reso=0.02,
+                                  **kw)
+
+
+def _shift_tile(**kw):
+    return ops.make_raster_params(trans=(-30.0, 5.0, 0.0), bev_img_offset=(0.25, -0.75), img_reso=(RESO, RESO), local_min_ele=-1.0,
+                                  ele_reso=0.02, **kw)
+
+
+def _rot_tile(**kw):
+    yaw = 0.4
+    q = np.array([math.cos(yaw / 2), 0.013, -0.017, math.sin(yaw / 2)]) * 1.03
+    return ops.make_raster_params(quat=q, trans=(40.0, 3.0, -0.25), bev_img_offset=(0.3, -0.6), img_reso=(0.05, 0.05), local_min_ele=-1.0,
+                                  ele_reso=0.02, **kw)
+
+
+FAR = ops.make_raster_params(trans=(4000.0, 4000.0, 0.0), img_reso=(RESO, RESO))
+
+
+def _cloud(seed, n, p, inten, T=S, spread=1.3):
+    """n points around the T x T window of tile p (about a third outside it) in the LAS frame of the tile; intensities inten(rng, n), and
+    the points OUTSIDE the window get extreme intensities (0, 65535, 1e9, -1e9 in turn), which must not count."""
+    rng = np.random.RandomState(seed)
+    reso = float(p.img_reso[0])
+    v = rng.uniform(-0.15 * T * reso, (spread - 0.15) * T * reso, (n, 2))
+    vz = 0.5 + 0.05 * v[:, 0] + 0.03 * v[:, 1] + rng.normal(0, 0.05, n)
+    q = np.array([float(c) for c in p.quat])
+    nq = np.linalg.norm(q)
+    w, x, y, z = q / nq
+    R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                  [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                  [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+    local = np.stack([v[:, 0] + p.bev_img_offset[0], v[:, 1] + p.bev_img_offset[1], vz], axis=1)
+    world = (nq * R @ local.T).T + np.array([float(c) for c in p.trans])
+    pts = np.ascontiguousarray(np.concatenate([world, np.zeros((n, 1))], axis=1), dtype=f32)
+    pts[:, 3] = np.asarray(inten(rng, n), dtype=f32)
+    out = np.flatnonzero(~gr.window(pts, p, T, T)[0])
+    pts[out, 3] = np.array([0.0, 65535.0, 1e9, -1e9], dtype=f32)[np.arange(len(out)) % 4]
+    return pts
+
+
+def _special(rng, n):
+    v = np.floor(rng.uniform(0, 65536, n)).astype(f32)
+    v[::7] = np.nan
+    v[1::7] = np.inf
+    v[2::7] = -np.inf
+    return v
+
+
+KINDS = {
+    'uniform_u16': lambda rng, n: np.floor(rng.uniform(0, 65536, n)),
+    'all_equal': lambda rng, n: np.full(n, 33000.0),
+    'two_values': lambda rng, n: np.where(rng.uniform(size=n) < 0.3, 1007.0, 1008.0),
+    'saturated': lambda rng, n: np.where(rng.uniform(size=n) < 0.6, 0.0, 65535.0),
+    'non_integers': lambda rng, n: rng.uniform(0, 300, n),
+    'negatives': lambda rng, n: rng.uniform(-500, 500, n),
+    'above_u16': lambda rng, n: rng.uniform(60000, 70000, n),
+    'nan_and_inf': _special,
+}
+# per-tile point counts: empty, one, below / at a wave and a chunk, across a chunk seam, several chunks per workgroup, across a span seam
+COUNTS = [(0, 1, 255), (256, ICHUNK, ICHUNK + 1), (40000, 0, ISPAN + 1), (2 * ISPAN + 300, 1, 256)]
+
+
+def _eq(got, want, name):
+    g = got.detach().cpu().numpy() if torch.is_tensor(got) else np.asarray(got)
+    w = np.asarray(want)
+    assert g.shape == w.shape and g.dtype == w.dtype, (name, g.shape, w.shape, g.dtype, w.dtype)
+    assert np.array_equal(g, w), f'{name}: {int((g != w).sum())} of {g.size} entries differ from the reference (first at {np.argwhere(g != w)[0].tolist()}: {g[tuple(np.argwhere(g != w)[0])]} for {w[tuple(np.argwhere(g != w)[0])]})'
+
+
+def _check(dev, pts, offs, params, H, W, pair, group=None, name=''):
+    cloud = torch.from_numpy(pts).to(dev)
+    win, cnt, hist = ops.tile_intensity_window(cloud, offs, params, H, W, percentiles=pair, group=group, want_hist=True)
+    rw, rc, rh = ir.window(pts, offs, params, H, W, pair, group)
+    _eq(cnt, rc, f'{name} {pair}: count')
+    _eq(hist, rh, f'{name} {pair}: coarse_hist')
+    _eq(win, rw, f'{name} {pair}: window')
+    w2, c2 = ops.tile_intensity_window(cloud, offs, params, H, W, percentiles=pair, group=group)
+    assert torch.equal(w2, win) and torch.equal(c2, cnt), 'without the histogram the same window'
+    return rw, rc
+
+
+# ------------------------------------------------------------------------------------------------ 1. windows
+@pytest.mark.parametrize('kind', sorted(KINDS))
+def test_windows_per_tile(dev, kind):
+    """B = 3 windows (axis-aligned, rotated and tilted, axis-aligned elsewhere), every count of COUNTS, three percentile pairs."""
+    tiles = [_axis_tile(), _rot_tile(), _shift_tile()]
+    seen = 0
+    for ci, counts in enumerate(COUNTS):
+        parts = [_cloud(1000 * ci + 10 * t + len(kind), n, tiles[t], KINDS[kind]) for t, n in enumerate(counts)]
+        pts = np.concatenate(parts)
+        offs = [0, counts[0], counts[0] + counts[1], len(pts)]
+        for pair in PAIRS:
+            rw, rc = _check(dev, pts, offs, tiles, S, S, pair, name=f'{kind} {counts}')
+        seen += int(rc.sum())
+        for t, n in enumerate(counts):
+            if n >= 255:
+                assert 0.3 * n < rc[t] < n, 'a good share of the points counts, and some lie outside the window'
+            if n == 0:
+                assert rw[t].tolist() == [-1, -1] and rc[t] == 0
+    assert seen > 100000
+    # leading empty tiles and a point range that does not start at row 0
+    pts = np.concatenate([_cloud(1, 700, FAR, KINDS[kind]), _cloud(2, 3001, tiles[1], KINDS[kind])])
+    _check(dev, pts, [700, 700, 700, 3701], [FAR, tiles[0], tiles[1]], S, S, (1.0, 99.9), name=f'{kind} leading empty tiles')
+
+
+def test_ranks_on_the_seam_of_two_coarse_bins(dev):
+    """50 x 500, 100 x 1007 (the last key of coarse bin 62), 100 x 1008 (the first key of bin 63), 50 x 2000, all inside the window, in a
+    shuffled order: rank 149 is the last 1007, rank 150 the first 1008."""
+    p = _axis_tile()
+    keys = np.repeat([500.0, 1007.0, 1008.0, 2000.0], [50, 100, 100, 50])
+    np.random.RandomState(5).shuffle(keys)
+    pts = _cloud(77, len(keys), p, lambda rng, n: np.zeros(n), spread=0.8)        # -0.15 .. 0.65 of the window: some rows are outside
+    pts = pts[gr.window(pts, p, S, S)[0]]
+    pts = np.concatenate([pts] * 2)[:len(keys)]
+    pts[:, 3] = keys
+    assert gr.window(pts, p, S, S)[0].all()
+    for pair, want in (((50.0, 50.2), [1007, 1008]), ((16.5, 83.4), [500, 1008]), ((16.8, 83.7), [1007, 2000]), ((0.0, 100.0), [500, 2000])):
+        rw, rc = _check(dev, pts, [0, len(pts)], [p], S, S, pair, name='seam')
+        assert rw[0].tolist() == want and rc[0] == 300, (pair, rw)
+
+
+# ------------------------------------------------------------------------------------------------ 2. groups
+def test_groups(dev):
+    """G = 1 over all tiles, G = 2 with interleaved membership, a group without a tile: against the reference on the concatenation."""
+    tiles = [_axis_tile(), _rot_tile(), _shift_tile(), _axis_tile()]
+    kinds = ['uniform_u16', 'two_values', 'non_integers', 'saturated']
+    counts = [40000, ICHUNK + 1, 255, ISPAN + 1]
+    parts = [_cloud(300 + t, n, tiles[t], KINDS[kinds[t]]) for t, n in enumerate(counts)]
+    pts = np.concatenate(parts)
+    offs = [0] + np.cumsum(counts).tolist()
+    per_tile = [ir.keys(parts[t], tiles[t], S, S) for t in range(4)]
+    for pair in PAIRS:
+        rw, rc = _check(dev, pts, offs, tiles, S, S, pair, group=[0, 0, 0, 0], name='G=1')
+        assert rc.tolist() == [sum(len(k) for k in per_tile)] and rw[0].tolist() == list(ir.order_stats(np.concatenate(per_tile), ir.ppm(pair[0]), ir.ppm(pair[1])))
+        rw, rc = _check(dev, pts, offs, tiles, S, S, pair, group=[0, 1, 0, 1], name='G=2')
+        assert rc.tolist() == [len(per_tile[0]) + len(per_tile[2]), len(per_tile[1]) + len(per_tile[3])]
+        rw, rc = _check(dev, pts, offs, tiles, S, S, pair, group=[3, 0, 3, 0], name='G=4, two without a tile')
+        assert rw[1].tolist() == [-1, -1] and rw[2].tolist() == [-1, -1] and rc[1] == 0 and rc[2] == 0 and rc[0] > 0 and rc[3] > 0
+    # the torch.ops entry gives the same tensors
+    from lanemapping_amd import torch_ops
+    cloud = torch.from_numpy(pts).to(dev)
+    par = torch_ops.raster_params_tensor(tiles)
+    w1, c1 = torch.ops.lanemap_hip.tile_intensity_window(cloud, offs, par, S, S, 1.0, 99.9, [0, 1, 0, 1])
+    w2, c2 = ops.tile_intensity_window(cloud, offs, tiles, S, S, (1.0, 99.9), [0, 1, 0, 1])
+    w3, _ = torch.ops.lanemap_hip.tile_intensity_window(cloud, offs, par, S, S, 1.0, 99.9, None)
+    assert torch.equal(w1, w2) and torch.equal(c1, c2) and tuple(w3.shape) == (4, 2)
+
+
+# ------------------------------------------------------------------------------------------------ 3. shipped shape, determinism
+def test_shipped_shape_and_determinism(dev):
+    """One 1152 x 1152 call at B = 16 with 200,000 points per tile (the bench's synthetic clouds, another gain per tile, so that some
+    tiles clamp at 65535); two runs and a run on a second stream give the same bits."""
+    from lanemapping_amd import synth
+    H = W = 1152
+    base = [synth.las_points(2021 + i, 200_000) for i in range(4)]
+    parts = []
+    for t in range(16):
+        c = base[t % 4].copy()
+        c[:, 3] = np.floor(c[:, 3] * f32(0.4 + 0.12 * t))
+        parts.append(c)
+    pts = np.concatenate(parts)
+    offs = [200_000 * i for i in range(17)]
+    params = [ops.make_raster_params(local_min_ele=-0.5, ele_reso=0.02) for _ in range(16)]
+    rw, rc = _check(dev, pts, offs, params, H, W, (1.0, 99.9), name='shipped')
+    assert (rc > 150_000).all() and (np.diff(rw[:, 1].astype(np.int64))[:8] > 0).all() and rw[-1, 1] == 65535
+    cloud = torch.from_numpy(pts).to(dev)
+    a = ops.tile_intensity_window(cloud, offs, params, H, W, want_hist=True)
+    b = ops.tile_intensity_window(cloud, offs, params, H, W, want_hist=True)
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        c = ops.tile_intensity_window(cloud, offs, params, H, W, want_hist=True)
+    side.synchronize()
+    for x, y, z in zip(a, b, c):
+        assert torch.equal(x, y) and torch.equal(x, z), 'two runs or two streams differ'
+    g = ops.tile_intensity_window(cloud, offs, params, H, W, group=[0] * 16)
+    _eq(g[0], ir.window(pts, offs, params, H, W, group=[0] * 16)[0], 'shipped, one group')
+
+
+# ------------------------------------------------------------------------------------------------ 4. guards and refusals
+def _guard_case():
+    tiles = [_axis_tile(), _rot_tile(), _shift_tile()]
+    counts = [ISPAN + 257, 1500, 0]
+    parts = [_cloud(41 + t, n, tiles[t], KINDS['nan_and_inf' if t == 0 else 'two_values']) for t, n in enumerate(counts)]
+    return np.concatenate(parts), [0] + np.cumsum(counts).tolist(), tiles
+
+
+@pytest.mark.parametrize('group', [None, [1, 0, 1]])
+def test_tile_intensity_window_guards(dev, group):
+    """lm_tile_intensity_window with the points, every output and the workspace between guard slabs; the points are not changed."""
+    L = lib()
+    pts, offs, params = _guard_case()
+    B = len(params)
+    G = B if group is None else 2
+    need = L.lm_tile_intensity_workspace_bytes(B, G)
+    assert need > 0 and need % 256 == 0
+    assert L.lm_tile_intensity_workspace_bytes(0, 0) == 0 and L.lm_tile_intensity_workspace_bytes(4097, 1) == 0 \
+        and L.lm_tile_intensity_workspace_bytes(3, 4) == 0 and L.lm_tile_intensity_workspace_bytes(3, 0) == 0
+    par, coffs = (LmRasterParams * B)(*params), (C.c_long * (B + 1))(*offs)
+    grp = None if group is None else (C.c_int * B)(*group)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+    def run(_, poisoned):
+        s_pts = Slab(dev, len(pts), 4, front=64, back=64).fill_input(torch.from_numpy(pts), NAN if poisoned else 0.0)
+        before = s_pts.bits().clone()
+        s_w = Slab(dev, G, 2, front=8, back=8, dtype=torch.int32).fill_canary()
+        s_c = Slab(dev, 1, 2 * G, front=8, back=8, dtype=torch.int32).fill_canary()
+        s_h = Slab(dev, G, 4096, front=1, back=1, dtype=torch.int32).fill_canary()
+        s_ws = Slab(dev, 1, need, front=1, back=1, dtype=torch.uint8).fill_canary()
+        rc = L.lm_tile_intensity_window(stream, C.c_void_p(s_pts.ptr()), coffs, par, B, S, S, grp, G, 10000, 999000, C.c_void_p(s_ws.ptr()),
+                                        need, C.c_void_p(s_w.ptr()), C.c_void_p(s_c.ptr()), C.c_void_p(s_h.ptr()))
+        assert rc == 0, L.lm_last_error()
+        torch.cuda.synchronize()
+        assert torch.equal(s_pts.bits(), before), 'the points buffer was written'
+        return {'window': (s_w, G), 'count': (s_c, 1), 'coarse_hist': (s_h, G), 'workspace': (s_ws, 1)}
+
+    got = guarded_runs(run, 'tile_intensity_window', batch=False)
+    rw, rc_, rh = ir.window(pts, offs, params, S, S, (1.0, 99.9), group)
+    _eq(got['window'].numpy(), rw, 'guards: window')
+    _eq(got['count'].numpy().view(np.int64).reshape(-1), rc_, 'guards: count')
+    _eq(got['coarse_hist'].numpy(), rh, 'guards: coarse_hist')
+
+
+def test_bad_arguments_are_refused_by_name(dev):
+    L = lib()
+    pts, offs, params = _guard_case()
+    cloud = torch.from_numpy(pts).to(dev)
+    with pytest.raises(LanemapHipError, match='q_lo_ppm=600000 > q_hi_ppm=400000'):
+        ops.tile_intensity_window(cloud, offs, params, S, S, percentiles=(60.0, 40.0))
+    with pytest.raises(LanemapHipError, match='q_lo_ppm=-10000 is outside'):
+        ops.tile_intensity_window(cloud, offs, params, S, S, percentiles=(-1.0, 40.0))
+    with pytest.raises(LanemapHipError, match='q_hi_ppm=1000001 is outside'):
+        ops.tile_intensity_window(cloud, offs, params, S, S, percentiles=(1.0, 100.0001))
+    with pytest.raises(ValueError, match=r'group\[1\]=-1 is outside'):
+        ops.tile_intensity_window(cloud, offs, params, S, S, group=[0, -1, 0])
+    with pytest.raises(ValueError, match=r'group\[0\]=1000000000 is outside'):
+        ops.tile_intensity_window(cloud, offs, params, S, S, group=[10 ** 9, 0, 0])
+    with pytest.raises(LanemapHipError, match='tile_offsets'):
+        ops.tile_intensity_window(cloud, [0, 500, 400, 600], params, S, S)
+    with pytest.raises(LanemapHipError, match='B=4097'):
+        ops.tile_intensity_window(cloud, [0] * 4098, [params[0]] * 4097, S, S)
+    with pytest.raises(ValueError, match='group entries'):
+        ops.tile_intensity_window(cloud, offs, params, S, S, group=[0, 0])
+    # the raw entry: what the wrapper cannot be made to pass
+    B = len(params)
+    par, coffs = (LmRasterParams * B)(*params), (C.c_long * (B + 1))(*offs)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    need = L.lm_tile_intensity_workspace_bytes(B, B)
+    ws = torch.empty(need, device=dev, dtype=torch.uint8)
+    win = torch.full((B, 2), 77, device=dev, dtype=torch.int32)
+    cnt = torch.full((B,), 77, device=dev, dtype=torch.int64)
+    vp = lambda t: C.c_void_p(t.data_ptr())
+
+    def raw(offsets=coffs, group=None, G=B, ws_bytes=need, window=vp(win), count=vp(cnt), wsp=vp(ws), points=vp(cloud)):
+        rc = L.lm_tile_intensity_window(stream, points, offsets, par, B, S, S, group, G, 10000, 999000, wsp, ws_bytes, window, count, None)
+        return rc, L.lm_last_error().decode()
+
+    for kw, msg in (({'group': (C.c_int * B)(0, 2, 1), 'G': 2}, 'group[1]=2 is outside 0..G-1=1'),
+                    ({'group': (C.c_int * B)(0, 1, -1), 'G': 2}, 'group[2]=-1 is outside 0..G-1=1'),
+                    ({'G': 2}, 'group is null'), ({'G': 4, 'group': (C.c_int * B)(0, 0, 0)}, 'G=4 groups'), ({'G': 0}, 'G=0 groups'),
+                    ({'ws_bytes': need - 1}, 'workspace too small'), ({'window': None}, 'null pointer (workspace / window / count)'),
+                    ({'count': None}, 'null pointer (workspace / window / count)'), ({'wsp': None}, 'null pointer (workspace / window / count)'),
+                    ({'points': None}, 'null points'), ({'offsets': None}, 'null pointer (tile_offsets / params)'),
+                    ({'offsets': (C.c_long * (B + 1))(0, 0, 0, 2 ** 32)}, 'span 4294967296 points')):
+        rc, err = raw(**kw)
+        assert rc == 1 and msg in err, (kw, rc, err)
+    torch.cuda.synchronize()
+    assert bool((win == 77).all()) and bool((cnt == 77).all()), 'a refused call writes nothing'
+    # B = 4096 is served: every tile but the last three empty, one group per tile
+    many = [params[0]] * 4093 + params
+    w, c = ops.tile_intensity_window(cloud, [0] * 4094 + offs[1:], many, S, S)
+    rw, rc_, _ = ir.window(pts, offs, params, S, S)
+    _eq(w[-3:], rw, 'B = 4096: window')
+    _eq(c[-3:], rc_, 'B = 4096: count')
+    assert bool((w[:-3] == -1).all()) and bool((c[:-3] == 0).all())
+
+
+# ------------------------------------------------------------------------------------------------ 5. the scaled rasteriser entry
+def _raster_case():
+    tiles = [_axis_tile(inten_lo=30000.0, inten_hi=40000.0), _rot_tile(inten_lo=100.0, inten_hi=116.0)]
+    a = _cloud(61, 3000, tiles[0], lambda rng, n: np.floor(rng.uniform(25000, 45000, n)))
+    b = _cloud(62, 2500, tiles[1], lambda rng, n: rng.uniform(90, 130, n))
+    a[::50, 3] = np.nan
+    return np.concatenate([a, b]), [0, len(a), len(a) + len(b)], tiles
+
+
+def test_scaled_raster_against_the_rule(dev):
+    pts, offs, tiles = _raster_case()
+    cloud = torch.from_numpy(pts).to(dev)
+    plain, plain_u8 = ops.bev_raster_batch(cloud, offs, tiles, S, S, want_u8=True)
+    _eq(plain_u8, ir.raster(pts, offs, tiles, S, S), 'derived scale')
+    for scales in ([249.0 / 10000.0, 249.0 / 16.0], [1.0, 0.001], [255.0 / 9000.0, 3.7], [None, 0.0], [-1.0, 249.0 / 16.0]):
+        chw, u8 = ops.bev_raster_batch(cloud, offs, tiles, S, S, want_u8=True, inten_scale=scales)
+        want = ir.raster(pts, offs, tiles, S, S, scales)
+        _eq(u8, want, f'inten_scale={scales}')
+        _eq(chw, (want.transpose(0, 3, 1, 2).astype(f32) / f32(255.0)), f'inten_scale={scales}: planar')
+    assert ir.raster(pts, offs, tiles, S, S, [249.0 / 10000.0, 249.0 / 16.0])[0, ..., 0].max() == 249
+    # absent, all-derived and the explicit derived scale: today's bytes
+    for scales in (None, [0.0, 0.0], [None, None], [f32(255.0) / f32(40000.0), f32(255.0) / f32(116.0)]):
+        chw, u8 = ops.bev_raster_batch(cloud, offs, tiles, S, S, want_u8=True, inten_scale=scales)
+        assert torch.equal(u8, plain_u8) and torch.equal(chw.view(torch.int32), plain.view(torch.int32)), scales
+    from lanemapping_amd import torch_ops
+    par15 = torch_ops.raster_params_tensor(tiles)
+    par16 = torch.cat([par15, torch.tensor([[249.0 / 10000.0], [0.0]])], dim=1)
+    t = torch.ops.lanemap_hip.bev_raster_scaled(cloud, offs, par16, S, S)
+    _eq(t, ir.raster(pts, offs, tiles, S, S, [249.0 / 10000.0, 0.0]), 'torch op')
+    with pytest.raises(ValueError, match='inten_scale'):
+        ops.bev_raster_batch(cloud, offs, tiles, S, S, inten_scale=[1.0])
+
+
+def test_scaled_raster_guards(dev):
+    """lm_bev_raster_batch_scaled with the points, both outputs and the workspace between guard slabs."""
+    L = lib()
+    pts, offs, tiles = _raster_case()
+    B = len(tiles)
+    par, coffs = (LmRasterParams * B)(*tiles), (C.c_long * (B + 1))(*offs)
+    scale = (C.c_float * B)(249.0 / 10000.0, 249.0 / 16.0)
+    need = L.lm_bev_raster_workspace_bytes(B, max(np.diff(offs)), S, S)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+    def run(_, poisoned):
+        s_pts = Slab(dev, len(pts), 4, front=64, back=64).fill_input(torch.from_numpy(pts), NAN if poisoned else 0.0)
+        ys = Slab(dev, B * 3 * S, S, front=4, back=4).fill_canary()
+        us = Slab(dev, B * S, S * 3, front=4, back=4, dtype=torch.uint8).fill_canary()
+        s_ws = Slab(dev, 1, need, front=1, back=1, dtype=torch.uint8).fill_canary()
+        rc = L.lm_bev_raster_batch_scaled(stream, C.c_void_p(s_pts.ptr()), coffs, par, B, C.c_void_p(s_ws.ptr()), need, C.c_void_p(ys.ptr()),
+                                          C.c_void_p(us.ptr()), S, S, scale)
+        assert rc == 0, L.lm_last_error()
+        torch.cuda.synchronize()
+        s_ws.check_canary('bev_raster_batch_scaled [workspace]')    # its guards only: the order of the records in it is not fixed
+        return {'chw': (ys, 3 * S), 'u8': (us, S)}
+
+    got = guarded_runs(run, 'bev_raster_batch_scaled', batch=False)
+    _eq(got['u8'].numpy().reshape(B, S, S, 3), ir.raster(pts, offs, tiles, S, S, list(scale)), 'guards: u8')
+
+
+# ------------------------------------------------------------------------------------------------ 6. the effect on a tile
+def test_a_pedestal_scanner_is_flat_under_the_default_window_and_stretched_with_it(dev):
+    """A scanner with a pedestal: asphalt 30000-33000, paint (columns 40-43) 38000-40000, one point at every pixel centre."""
+    p = _axis_tile()
+    r, c = np.meshgrid(np.arange(S), np.arange(S), indexing='ij')
+    rng = np.random.RandomState(9)
+    paint = (c >= 40) & (c < 44)
+    inten = np.where(paint, np.floor(rng.uniform(38000, 40001, (S, S))), np.floor(rng.uniform(30000, 33001, (S, S))))
+    x = r * RESO + p.bev_img_offset[0] + p.trans[0]
+    y = c * RESO + p.bev_img_offset[1] + p.trans[1]
+    pts = np.stack([x.ravel(), y.ravel(), np.full(S * S, 0.5 + p.trans[2]), inten.ravel()], axis=1).astype(f32)
+    assert gr.window(pts, p, S, S)[0].all()
+    cloud = torch.from_numpy(pts).to(dev)
+    offs = [0, len(pts)]
+    flat = ops.bev_raster_batch(cloud, offs, [p], S, S, u8_only=True).cpu().numpy()[0, ..., 0]
+    assert flat.min() >= 225 and flat.max() == 249 and (flat[paint] == 249).all() and (flat[~paint] == 249).any(), \
+        'the default window 800..33000: asphalt in the top tenth of the channel, paint clipped to the brightest asphalt'
+    st = IntensityStretch()
+    win, cnt = ops.tile_intensity_window(cloud, offs, [p], S, S, percentiles=st.percentiles)
+    rw, rc = ir.window(pts, offs, [p], S, S, st.percentiles)[:2]
+    _eq(win, rw, 'pedestal: window')
+    lo, hi, scale = intensity_window(int(win[0, 0]), int(win[0, 1]), int(cnt[0]), st)
+    assert 30000 <= lo <= 30100 and 39900 <= hi <= 40000 and scale == 249.0 / (hi - lo) and rc[0] == S * S
+    q = LmRasterParams.from_buffer_copy(p)
+    q.inten_lo, q.inten_hi = lo, hi
+    u8 = ops.bev_raster_batch(cloud, offs, [q], S, S, u8_only=True, inten_scale=[scale]).cpu().numpy()
+    _eq(u8, ir.raster(pts, offs, [q], S, S, [scale]), 'pedestal: the stretched tile')
+    I = u8[0, ..., 0]
+    assert I[paint].min() > I[~paint].max() + 100 and I[~paint].min() == 1 and I[paint].max() == 249 and I[~paint].max() < 80
+
+
+# ------------------------------------------------------------------------------------------------ 7. Runner
+def test_runner_strip_fits_the_intensity_window(dev, net, tmp_path, monkeypatch):
+    """Two overlapping axis-aligned 1152 x 1152 tiles over a strip of a pedestal scanner that gets brighter along the strip, one point per
+    2 x 2 pixels.  intensity=None equals a call without the argument, file by file; scope='tile' and scope='strip' write the reference's
+    windows to params/intensity.json and rasterise the reference's tiles; 'strip' gives every tile one window."""
+    from lanemapping_amd.runner import Runner
+    from oracle import las_ref
+    H = W = 1152
+    reso, ele = 0.05, 0.05
+    off = np.array([351200.0, 3433000.0, 12.0])
+    step = 1024
+    rows = step + H
+    r, c = np.meshgrid(np.arange(0, rows, 2), np.arange(0, W, 2), indexing='ij')
+    x, y = (r * reso).ravel(), (c * reso).ravel()
+    rng = np.random.RandomState(4)
+    lane_y = [(0.12 + 0.152 * l) * 57.6 + 0.01 * (l - 2.5) * x for l in range(6)]
+    paint = np.zeros(len(x), bool)
+    for ly in lane_y:
+        paint |= np.abs(y - ly) < 0.1
+    gain = 3000.0 * x / x.max()                                    # brighter along the strip: the two tiles get different windows
+    inten = np.floor(np.where(paint, rng.uniform(38000, 40000, len(x)), rng.uniform(30000, 33000, len(x))) + gain)
+    world = np.stack([x, y, 0.02 * x + 0.01 * y], axis=1)
+    order = rng.permutation(len(world))
+    las = str(tmp_path / 'strip.las')
+    las_ref.write_las(las, world[order] + off, inten[order], point_format=1, offset=tuple(off))
+    plist, prm_paths, names = [], [], []
+    for t in range(2):
+        plist.append({'coor_las_path': '', 'las_read_offset': list(off), 'las_rotation_trans_quan': [t * step * reso, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0],
+                      'bev_img_offset': [0.0, 0.0], 'img_reso': [reso, reso], 'local_min_ele': -0.5, 'ele_reso': ele})
+        names.append(f'18102{t}_0209')
+        prm_paths.append(str(tmp_path / (names[t] + '.txt')))
+        io_utils.save_pc_2_img_transform_paras(prm_paths[t], plist[t])
+    rn = Runner.__new__(Runner)
+    rn.cfg, rn.device, rn.net = net.cfg, dev, net
+    assert rn.cfg.get('las_intensity') is None
+    seen = []
+    real = ops.bev_raster_batch
+
+    def recording(points, offs, rpar, H_, W_, **kw):
+        out = real(points, offs, rpar, H_, W_, **kw)
+        seen.append((out[1].cpu().numpy(), kw.get('inten_scale')))
+        return out
+
+    monkeypatch.setattr(ops, 'bev_raster_batch', recording)
+    out = {k: str(tmp_path / k) for k in ('omitted', 'none', 'tile', 'strip')}
+    rn.infer_las_strip_to_map(las, prm_paths, work_dirs=out['omitted'], batch_size=2)
+    rn.infer_las_strip_to_map(las, prm_paths, work_dirs=out['none'], batch_size=2, intensity=None)
+    assert len(seen) == 2 and seen[0][1] is None and seen[1][1] is None and np.array_equal(seen[0][0], seen[1][0])
+    tree = lambda root: sorted(os.path.relpath(os.path.join(d, f), root) for d, _, fs in os.walk(root) for f in fs)
+    files = tree(out['omitted'])
+    assert files == tree(out['none']) and not any(f.startswith('params') for f in files)
+    for f in files:
+        assert open(os.path.join(out['omitted'], f), 'rb').read() == open(os.path.join(out['none'], f), 'rb').read(), f
+    default_tiles = seen[0][0]
+    assert default_tiles[..., 0][default_tiles.sum(axis=3) > 0].min() >= 225, 'the default window: every filled pixel in the top tenth'
+
+    # the reference: the points each tile holds, from the file as the reference reader decodes it
+    host = las_ref.read_las_ref(las, shift=off, normalise=False).astype(f32)
+    rps = [io_utils.raster_params_from_dict(p) for p in plist]
+    held = [host[gr.window(host, rp, H, W)[0]] for rp in rps]
+    keys = [ir.keys(h, rp, H, W) for h, rp in zip(held, rps)]
+    assert all(len(k) == (H // 2) * (W // 2) for k in keys)
+    for scope in ('tile', 'strip'):
+        seen.clear()
+        st = IntensityStretch(scope=scope)
+        rn.infer_las_strip_to_map(las, prm_paths, work_dirs=out[scope], batch_size=2, intensity=st)
+        used = json.load(open(os.path.join(out[scope], 'params', 'intensity.json')))
+        q = [ir.ppm(v) for v in st.percentiles]
+        if scope == 'tile':
+            want = {names[t]: [*intensity_window(*ir.order_stats(keys[t], *q), len(keys[t]), st), len(keys[t])] for t in range(2)}
+            assert want[names[0]][:2] != want[names[1]][:2]
+        else:
+            both = np.concatenate(keys)
+            one = [*intensity_window(*ir.order_stats(both, *q), len(both), st), len(both)]
+            want = {names[t]: one for t in range(2)}
+        assert used == want, (scope, used, want)
+        assert len(seen) == 1 and [f32(s) for s in seen[0][1]] == [f32(want[n][2]) for n in names]
+        for t in range(2):
+            rp = LmRasterParams.from_buffer_copy(rps[t])
+            rp.inten_lo, rp.inten_hi = want[names[t]][0], want[names[t]][1]
+            ref = ir.raster(held[t], [0, len(held[t])], [rp], H, W, [want[names[t]][2]])
+            _eq(seen[0][0][t], ref[0], f'scope={scope}: tile {t}')
+            I = ref[0, ..., 0]
+            # the points at and above the upper percentile land on `white`: in every tile of its own window, somewhere in the strip of one
+            assert I.max() == 249 if scope == 'tile' else I.max() <= 249, 'the upper percentile is white'
+            assert np.percentile(I[I > 0], 50) < 100, 'stretched: asphalt dark'
+        assert max(int(t[..., 0].max()) for t in seen[0][0]) == 249
+        assert sorted(f for f in tree(out[scope]) if f.startswith('params')) == ['params/intensity.json']
+        if scope == 'tile':
+            tile_want, tile_seen = want, seen[0][0].copy()
+
+    # the file-by-file route: every tile reads the whole strip under its own name; the same windows, the same tiles
+    import shutil
+    pairs = []
+    for t in range(2):
+        shutil.copy(las, str(tmp_path / (names[t] + '.las')))
+        pairs.append((str(tmp_path / (names[t] + '.las')), prm_paths[t]))
+    seen.clear()
+    rn.infer_las_to_map(pairs, work_dirs=str(tmp_path / 'files'), batch_size=2, intensity=IntensityStretch())
+    assert json.load(open(str(tmp_path / 'files' / 'params' / 'intensity.json'))) == tile_want
+    assert len(seen) == 1 and np.array_equal(seen[0][0], tile_seen) and [f32(v) for v in seen[0][1]] == [f32(tile_want[n][2]) for n in names]
