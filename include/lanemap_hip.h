@@ -309,6 +309,28 @@ int lm_tile_intensity_window(void* hip_stream, const float* points_xyzi, const l
                              int H, int W, const int* group, int G, int q_lo_ppm, int q_hi_ppm, void* workspace, long workspace_bytes,
                              int* window, long* count, unsigned* coarse_hist);
 
+/* ---- vertex heights from the points (csrc/drape.hip): a pixel-scale ground model around the polyline vertices of every tile.
+ * (points, tile_offsets, params, H, W) as for lm_tile_ground, 0 <= B <= 4096, H and W at most 32768.  vertices_rc: HOST [V][2] int32
+ * (row, col), the vertex pixels of tile 0, then tile 1, ...; vertex_offsets: HOST [B+1], vertex_offsets[0] = 0, non-decreasing,
+ * V = vertex_offsets[B]; at most 16384 vertices per tile; every vertex satisfies 0 <= row < H, 0 <= col < W.  0 <= radius_px = R <= 8.
+ * A point counts for tile b exactly when the rasteriser keeps it for b (the shared window test of csrc/raster_xf.h) and its tile-frame
+ * height vz - the quantity G * ele_reso + local_min_ele approximates - is finite.  Vertex v of tile b owns (2R+1)^2 slots; slot (i, j),
+ * i, j in -R..R, is the smallest vz (on lm_tile_ground's order-preserving integer key: -0.0 < +0.0) over the tile's points in pixel
+ * (row + i, col + j); a window pixel outside the tile stays empty.  One point serves every vertex whose window holds its pixel.
+ *   z [V] f32, DEVICE: the LOWER MEDIAN (element (k - 1) / 2 of the k non-empty slots in ascending order), NaN for k = 0
+ *   npix [V] int32, DEVICE: k
+ *   pixel_min [V][2R+1][2R+1] f32, DEVICE, or NULL: the slots, NaN = empty
+ * Integer atomic min on slots preset to all-ones: order independent, the same bits every run.  Asynchronous; no read-back.
+ * workspace: device, 16-byte aligned, lm_drape_workspace_bytes(V, B, R) bytes (0 = unsupported arguments).  B = 0 or V = 0: LM_OK, nothing
+ * is launched or written.  Bad arguments are refused with LM_ERR_ARG and a message that names the argument (radius_px, B, tile_offsets,
+ * vertex_offsets, vertex, workspace, null pointer) before anything is launched.
+ * NOTE on the name `hip_stream`: as for lm_tile_ground above; the guarded-buffer case is tests/test_gpu_drape.py::
+ * test_drape_vertices_guards. */
+long lm_drape_workspace_bytes(long n_vertices, int B, int radius_px);
+int lm_drape_vertices(void* hip_stream, const float* points_xyzi, const long* tile_offsets, const LmRasterParams* params, int B, int H,
+                      int W, const int* vertices_rc, const long* vertex_offsets, int radius_px, void* workspace, long workspace_bytes,
+                      float* z, int* npix, float* pixel_min);
+
 /* ---- host-side tail (HOST pointers; no GPU is touched) --------------------------------------------------------
  * endp_cluster: heads/polyline_fpn_vit_vertex_2.py:661-688 + :903-924.
  * polyline_assemble: :805-861 + baseline/utils/polyline_utils.py (whole file) + :1091-1115.
@@ -327,6 +349,15 @@ int lm_trace_lines(const double* cols, int n, int R, const float* seg_rows, doub
  * params13 = img_reso[2], bev_img_offset[2], ele_reso, local_min_ele, las_rotation_trans_quan[7]; out [L][Vmax][3]. */
 int lm_polyline_backproject(unsigned char* bev_hwc, int H, int W, int C, const double* img_seqs, const int* seq_lens, int L,
                             int Vmax, const double* params13, const double* las_read_offset, double* out);
+/* The same with vertex heights given from outside (lm_drape_vertices).  vertex_z: [L][Vmax] f32, a value that is not finite (NaN) =
+ * no height for this vertex; fit: 1 = the least-squares line over the vertex index (step 3 of the reference), 0 = none.
+ *   1) the elevation fill runs only for the vertices without a height (and mutates the tile only there)
+ *   2) z = (double)vertex_z where it is finite, G * ele_reso + local_min_ele elsewhere; padding slots beyond seq_lens[l] keep the G rule
+ *   3) only with fit = 1      4) unchanged
+ * With every vertex_z NaN and fit = 1 the output and the tile are bit-identical to lm_polyline_backproject's. */
+int lm_polyline_backproject_z(unsigned char* bev_hwc, int H, int W, int C, const double* img_seqs, const int* seq_lens, int L,
+                              int Vmax, const double* params13, const double* las_read_offset, double* out,
+                              const float* vertex_z, int fit);
 
 /* ---- evaluation: Lee-Kashyap-Chu thinning of a 2-D binary image, the skeletonisation inside the reference's semantic-line F1
  * (baseline/utils/metric_utils.py:415-481 -> skimage.morphology.skeletonize(method='lee')).  PARITY UNPINNED (skimage absent: the

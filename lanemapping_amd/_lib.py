@@ -102,12 +102,15 @@ SIGNATURES = {
     'lm_tile_intensity_workspace_bytes': (i64, [i32, i32]),
     'lm_tile_intensity_window': (i32, [vp, vp, C.POINTER(i64), C.POINTER(LmRasterParams), i32, i32, i32, C.POINTER(i32), i32, i32, i32, vp, i64,
                                        vp, vp, vp]),
+    'lm_drape_workspace_bytes': (i64, [i64, i32, i32]),
+    'lm_drape_vertices': (i32, [vp, vp, C.POINTER(i64), C.POINTER(LmRasterParams), i32, i32, i32, vp, C.POINTER(i64), i32, vp, i64, vp, vp, vp]),
     'lm_endp_cluster': (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp]),
     'lm_polyline_assemble': (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp]),
     'lm_raster_polylines': (i32, [vp, i32, i32, vp]),
     'lm_line8': (i32, [vp, i32, i32, i32, i32, i32]),
     'lm_trace_lines': (i32, [vp, i32, i32, vp, vp]),
     'lm_polyline_backproject': (i32, [vp, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp]),
+    'lm_polyline_backproject_z': (i32, [vp, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, i32]),
     'lm_skeletonize_lee_2d': (i64, [vp, i32, i32]),
     'lm_merge_create': (vp, []),
     'lm_merge_destroy': (None, [vp]),

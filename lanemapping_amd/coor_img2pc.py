@@ -15,9 +15,15 @@ from ._lib import lib, check
 from .io_utils import load_lane_seq, load_pc_2_img_transform_paras, save_seqs_json, save_seqs_txt
 
 
-def transform_coordinate_from_img_2_pc(params, img_seqs, img_seq_lens, bev_img):
+def transform_coordinate_from_img_2_pc(params, img_seqs, img_seq_lens, bev_img, vertex_z=None, fit='line'):
     """params: dict of `load_pc_2_img_transform_paras`; img_seqs [n_line, max_len, 2] (row, col); bev_img: HxWxC uint8 array
-    (or anything np.array() turns into one, e.g. a PIL image).  Returns seqs_3d [n_line, max_len, 3] float64."""
+    (or anything np.array() turns into one, e.g. a PIL image).  Returns seqs_3d [n_line, max_len, 3] float64.
+    vertex_z: [n_line, max_len] float32 tile-frame heights of the vertices (ops.drape_vertices), NaN = none: a vertex with a height
+    takes it instead of the tile's elevation channel and skips the empty-pixel fill.  fit: 'line' (the reference's least-squares line
+    over the vertex index) or 'none'.  The defaults are the reference's behaviour (`lm_polyline_backproject`); anything else runs
+    `lm_polyline_backproject_z`."""
+    if fit not in ('line', 'none'):
+        raise ValueError(f"fit={fit!r} must be 'line' or 'none'")
     img_seqs = np.ascontiguousarray(np.asarray(img_seqs, dtype=np.float64)[:, :, :2])
     n_line, max_len, _ = img_seqs.shape
     img = np.array(bev_img)                                   # copy: the elevation fill edits the tile like the reference
@@ -32,9 +38,20 @@ def transform_coordinate_from_img_2_pc(params, img_seqs, img_seq_lens, bev_img):
     off = np.array(params['las_read_offset'][:3], dtype=np.float64)
     out = np.zeros((n_line, max_len, 3), dtype=np.float64)
     vp = C.c_void_p
-    check(lib().lm_polyline_backproject(vp(img.ctypes.data), img.shape[0], img.shape[1], img.shape[2], vp(img_seqs.ctypes.data),
-                                        vp(lens.ctypes.data), n_line, max_len, vp(p13.ctypes.data), vp(off.ctypes.data),
-                                        vp(out.ctypes.data)))
+    if vertex_z is None and fit == 'line':
+        check(lib().lm_polyline_backproject(vp(img.ctypes.data), img.shape[0], img.shape[1], img.shape[2], vp(img_seqs.ctypes.data),
+                                            vp(lens.ctypes.data), n_line, max_len, vp(p13.ctypes.data), vp(off.ctypes.data),
+                                            vp(out.ctypes.data)))
+        return out
+    if vertex_z is None:
+        vz = np.full((n_line, max_len), np.nan, dtype=np.float32)
+    else:
+        vz = np.ascontiguousarray(np.asarray(vertex_z, dtype=np.float32))
+        if vz.shape != (n_line, max_len):
+            raise ValueError(f'vertex_z must have the shape {(n_line, max_len)} of the vertices, got {vz.shape}')
+    check(lib().lm_polyline_backproject_z(vp(img.ctypes.data), img.shape[0], img.shape[1], img.shape[2], vp(img_seqs.ctypes.data),
+                                          vp(lens.ctypes.data), n_line, max_len, vp(p13.ctypes.data), vp(off.ctypes.data),
+                                          vp(out.ctypes.data), vp(vz.ctypes.data), 1 if fit == 'line' else 0))
     return out
 
 

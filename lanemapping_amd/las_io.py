@@ -236,6 +236,46 @@ def intensity_window(lo_key, hi_key, count, stretch):
     return lo, hi, stretch.white / (hi - lo)
 
 
+class ElevationDrape:
+    """How the LAS -> map routes give their 3-D lane vertices a height (immutable; Runner.infer_las_strip_to_map / infer_las_to_map,
+    `elevation=`).  The height of a vertex is read off the points the rasteriser saw (ops.drape_vertices): the lower median, over the
+    (2 radius_px + 1)^2 pixels around the vertex pixel, of each pixel's smallest tile-frame height - instead of the 8-bit elevation of the
+    brightest return in the vertex pixel.
+
+      radius_px    0 .. 8: half the window side in pixels (default 4: 0.45 m x 0.45 m at 0.05 m per pixel)
+      min_pixels   a vertex with fewer non-empty window pixels (>= 1) falls back to the elevation channel of the tile, as without the
+                   argument
+      fit          'line': every line's heights are replaced by their least-squares line over the vertex index, as the reference does;
+                   'none': the heights stay as read, so a crest, dip or ramp inside a tile keeps its shape
+    min_pixels is a plain default, not a tuned value."""
+    __slots__ = ('radius_px', 'min_pixels', 'fit')
+
+    def __init__(self, radius_px=4, min_pixels=5, fit='line'):
+        if isinstance(radius_px, bool) or int(radius_px) != radius_px or not 0 <= int(radius_px) <= 8:
+            raise ValueError(f'ElevationDrape: radius_px={radius_px!r} must be a whole number of pixels in 0..8')
+        if isinstance(min_pixels, bool) or int(min_pixels) != min_pixels or int(min_pixels) < 1:
+            raise ValueError(f'ElevationDrape: min_pixels={min_pixels!r} must be a whole number >= 1')
+        if fit not in ('line', 'none'):
+            raise ValueError(f"ElevationDrape: fit={fit!r} must be 'line' or 'none'")
+        for k, v in (('radius_px', int(radius_px)), ('min_pixels', int(min_pixels)), ('fit', fit)):
+            object.__setattr__(self, k, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError('ElevationDrape is immutable')
+
+    def __delattr__(self, name):
+        raise AttributeError('ElevationDrape is immutable')
+
+    def __repr__(self):
+        return 'ElevationDrape(' + ', '.join(f'{k}={getattr(self, k)!r}' for k in self.__slots__) + ')'
+
+    def __eq__(self, other):
+        return isinstance(other, ElevationDrape) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
+
+    def __hash__(self):
+        return hash(tuple(getattr(self, k) for k in self.__slots__))
+
+
 def parse_header(data):
     """bytes -> dict of the header fields (raises LanemapHipError on non-LAS / LAZ / truncated files)."""
     h = LmLasHeader()

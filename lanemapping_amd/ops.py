@@ -843,6 +843,33 @@ def tile_intensity_window(points, tile_offsets, params, H=1152, W=1152, percenti
     return (window, count, hist) if want_hist else (window, count)
 
 
+def drape_vertices(points, tile_offsets, params, vertices, vertex_offsets, H=1152, W=1152, radius_px=4, want_pixel_min=False):
+    """Heights of polyline vertices read off the points (csrc/drape.hip), from the (points, tile_offsets, params) triple bev_raster_batch
+    takes: vertices [V,2] int32 host array of (row, col) pixels, tile 0's first; vertex_offsets: B+1 ints, vertex_offsets[0] = 0.
+    -> (z [V] f32, npix [V] int32) on the device, with want_pixel_min also pixel_min [V, 2R+1, 2R+1] f32 (NaN = empty).  pixel_min[v, i, j]
+    is the smallest tile-frame height vz of the points the rasteriser keeps for the vertex's tile in pixel (row + i - R, col + j - R), z[v]
+    the lower median of the npix[v] non-empty ones (NaN for none).  Exact and reproducible.  No synchronisation."""
+    import numpy as np
+    B, offs, par = _ground_args('drape_vertices', points, tile_offsets, params)
+    H, W, R = int(H), int(W), int(radius_px)
+    vert = np.ascontiguousarray(np.asarray(vertices, dtype=np.int32).reshape(-1, 2))
+    if len(vertex_offsets) != B + 1:
+        raise ValueError(f'drape_vertices: {len(vertex_offsets)} vertex_offsets for {B} tiles (B + 1 are needed)')
+    voffs = (C.c_long * (B + 1))(*[int(o) for o in vertex_offsets])
+    if voffs[B] != vert.shape[0]:
+        raise ValueError(f'drape_vertices: vertex_offsets end at {voffs[B]}, vertices has {vert.shape[0]} rows')
+    V, D = vert.shape[0], 2 * max(R, 0) + 1
+    need = lib().lm_drape_workspace_bytes(V, B, R)
+    ws = _ground_ws(points, max(need, 16))
+    z = torch.empty((V,), device=points.device, dtype=torch.float32)
+    npix = torch.empty((V,), device=points.device, dtype=torch.int32)
+    pmin = torch.empty((V, D, D), device=points.device, dtype=torch.float32) if want_pixel_min else None
+    # (need == 0: unsupported arguments; the call below refuses them with the argument's name)
+    check(lib().lm_drape_vertices(_stream(), _ptr(points) if points.numel() else None, offs, par, B, H, W, C.c_void_p(vert.ctypes.data), voffs, R,
+                                  _ptr(ws), ws.numel() if need else 0, _ptr(z), _ptr(npix), _ptr(pmin)))
+    return (z, npix, pmin) if want_pixel_min else (z, npix)
+
+
 def tile_ingest(u8_hwc):
     """[B,H,W,C>=3] uint8 (decoded PNG) -> [B,3,H,W] f32 = u8/255 (reference load_img contract)."""
     x = u8_hwc.contiguous()

@@ -377,8 +377,18 @@ class Runner:
         rpar, scales = self._stretch_intensity(st, names, points, offs, rpar, H, W, out_dir, used, strip)
         return raster_batch(names, plist, points, offs, rpar, scales)
 
+    def _las_elevation(self, elevation):
+        """The vertex heights of the LAS routes: the argument, else cfg['las_elevation'] (a dict of las_io.ElevationDrape arguments), else
+        none."""
+        from . import las_io
+        if elevation is None and self.cfg.get('las_elevation') is not None:
+            elevation = las_io.ElevationDrape(**dict(self.cfg.get('las_elevation')))
+        if elevation is not None and not isinstance(elevation, las_io.ElevationDrape):
+            raise TypeError(f'elevation must be a las_io.ElevationDrape, not {type(elevation).__name__}')
+        return elevation
+
     def infer_las_to_map(self, las_and_params, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None, ground=None,
-                         intensity=None):
+                         intensity=None, elevation=None):
         """LAS tiles -> map-level 3-D lane lines, every stage of the reference's offline chain on this stack:
 
           LAS file + tile parameter file (utils/io_utils.py:125-150)
@@ -400,9 +410,15 @@ class Runner:
         (ops.tile_intensity_window) and stretched (lm_bev_raster_batch_scaled); what was used is written to
         <work_dirs>/params/intensity.json as {tile name: [inten_lo, inten_hi, scale or null, count]}.  scope='strip' is refused here: the
         tiles arrive file by file.
+        elevation: a las_io.ElevationDrape (default: cfg['las_elevation'], a dict of its arguments; absent: nothing changes): after the
+        network, the height of every lane vertex is read off the points the rasteriser saw (ops.drape_vertices, one call and one
+        device-to-host read per batch: the lower median of the per-pixel minimum heights around the vertex pixel) instead of the tile's
+        8-bit elevation channel; a vertex with fewer than min_pixels filled pixels keeps the channel's value.  The 2-D JSON files do not
+        change.  What was used is written to <work_dirs>/params/elevation.json as {tile name: [vertices, draped, fallen back]}.
         Single rank (the merge is sequential over the sorted tiles)."""
         from . import las_io
         select, ground, intensity = self._las_select(select), self._las_ground(ground), self._las_intensity(intensity)
+        elevation = self._las_elevation(elevation)
         if intensity is not None and intensity.scope == 'strip':
             raise ValueError("intensity: scope='strip' needs the whole strip in one cloud (infer_las_strip_to_map); infer_las_to_map reads "
                              "its tiles file by file, use scope='tile'")
@@ -412,7 +428,7 @@ class Runner:
         B = int(batch_size or self.cfg.get('batch_size', 8))
         H, W = self.cfg.list_img_size_xy[1], self.cfg.list_img_size_xy[0]
         out_dir = work_dirs or self.cfg.get('work_dirs', './work_dirs')
-        raster_batch, close = self._las_chain(work_dirs, merge)
+        raster_batch, close = self._las_chain(work_dirs, merge, elevation)
         for i in range(0, len(las_and_params), B):
             chunk = las_and_params[i:i + B]
             pts, offs, rpar, names, plist = [], [0], [], [], []
@@ -430,42 +446,94 @@ class Runner:
             self._raster_stretched(raster_batch, intensity, names, plist, pts, offs, rpar, H, W, out_dir, used)
         return close()
 
-    def _las_chain(self, work_dirs, merge):
+    def _las_chain(self, work_dirs, merge, elevation=None):
         """The chain behind infer_las_to_map / infer_las_strip_to_map from the rasteriser on: -> (raster_batch, close).
         raster_batch(names, params, points, offsets, raster_params[, inten_scale]) rasterises one batch of tiles out of `points` and runs it through
-        the pipeline, the per-tile JSON and the back-projection; close() drains the pipeline, merges and returns (lines3d, merged)."""
+        the pipeline, the per-tile JSON and the back-projection; close() drains the pipeline, merges and returns (lines3d, merged).
+        elevation: a las_io.ElevationDrape or None.  With one, every batch keeps the (points, offsets, raster_params) the rasteriser saw
+        until its futures arrive; the vertices of all its tiles then get their heights in one ops.drape_vertices call."""
         from . import coor_img2pc, merge_lines as ml
         out_dir = work_dirs or self.cfg.get('work_dirs', './work_dirs')
         pc_dir = os.path.join(out_dir, 'out_pc_seq_json_dir')
         os.makedirs(pc_dir, exist_ok=True)
         pipe = TilePipeline(self.net)
         H, W = self.cfg.list_img_size_xy[1], self.cfg.list_img_size_xy[0]
-        queue, lines3d, pc_files = [], {}, []
+        queue, lines3d, pc_files, draped = [], {}, [], {}
+
+        def polylines(f, name):
+            """One tile's future -> its 2-D JSON on disk and (seqs [L, Vmax, 2], lens), None for a tile the reference skips."""
+            lanes, _ = f.result()
+            packed = io_utils.pack_lane_vertices(np.asarray(lanes, dtype=np.float64))
+            io_utils.save_lane_seq_2d(packed, os.path.join(out_dir, name + '.json'), with_pervertex_semantics=True)
+            recs = io_utils.lane_records(packed)
+            if len(recs) < 2:                           # load_lane_seq yields nothing for < 2 lines: the reference skips the tile
+                return None
+            lens = [r['seq_len'] for r in recs]
+            seqs = np.zeros((len(recs), max(lens), 2))
+            for i, r in enumerate(recs):
+                seqs[i, :lens[i]] = np.asarray(r['seq'])[:, 0:2]
+            return seqs, lens
+
+        def write_3d(name, pc, lens):
+            lines = [{'seq': pc[i, :lens[i], :], 'seq_len': lens[i], 'init_vertex': pc[i, 0, :], 'end_vertex': pc[i, lens[i] - 1, :]}
+                     for i in range(len(lens))]
+            io_utils.save_seqs_json(lines, os.path.join(pc_dir, name + '.json'))
+            io_utils.save_seqs_txt(lines, os.path.join(pc_dir, name + '.txt'))
+            pc_files.append(os.path.join(pc_dir, name + '.json'))
+            lines3d[name] = [l['seq'] for l in lines]
 
         def finish(futs):
+            if elevation is not None:
+                return finish_draped(futs)
             for f in futs:
                 name, params, u8 = queue.pop(0)
-                lanes, _ = f.result()
-                packed = io_utils.pack_lane_vertices(np.asarray(lanes, dtype=np.float64))
-                io_utils.save_lane_seq_2d(packed, os.path.join(out_dir, name + '.json'), with_pervertex_semantics=True)
-                recs = io_utils.lane_records(packed)
-                if len(recs) < 2:                       # load_lane_seq yields nothing for < 2 lines: the reference skips the tile
+                got = polylines(f, name)
+                if got is not None:
+                    write_3d(name, coor_img2pc.transform_coordinate_from_img_2_pc(params, got[0], got[1], u8), got[1])
+
+        def finish_draped(futs):
+            """The futures of one batch together: 2-D JSON, then one drape call over the vertices of all its tiles and one read-back,
+            then the back-projection of every tile with its vertex heights."""
+            if not futs:
+                return
+            entries = [queue.pop(0) for _ in futs]
+            kept = entries[0][3]
+            assert all(e[3] is kept for e in entries) and len(entries) == len(kept['rpar'])
+            tiles = [polylines(f, e[0]) for f, e in zip(futs, entries)]
+            vert, voffs = [], [0]
+            for got in tiles:
+                if got is not None:
+                    seqs, lens = got
+                    vert += [(int(seqs[i, v, 0]), int(seqs[i, v, 1])) for i in range(len(lens)) for v in range(lens[i])]
+                voffs.append(len(vert))
+            if vert:
+                z, npix = ops.drape_vertices(kept['points'], kept['offs'], kept['rpar'], np.asarray(vert, dtype=np.int32), voffs, H, W,
+                                             radius_px=elevation.radius_px)
+                both = torch.stack([z, npix.to(torch.float32)]).cpu().numpy()              # the one read-back
+                z = np.where(both[1] < elevation.min_pixels, np.float32(np.nan), both[0])
+            for j, (e, got) in enumerate(zip(entries, tiles)):
+                name, params, u8 = e[0:3]
+                draped[name] = [0, 0, 0]
+                if got is None:
                     continue
-                lens = [r['seq_len'] for r in recs]
-                seqs = np.zeros((len(recs), max(lens), 2))
-                for i, r in enumerate(recs):
-                    seqs[i, :lens[i]] = np.asarray(r['seq'])[:, 0:2]
-                pc = coor_img2pc.transform_coordinate_from_img_2_pc(params, seqs, lens, u8)
-                lines = [{'seq': pc[i, :lens[i], :], 'seq_len': lens[i], 'init_vertex': pc[i, 0, :], 'end_vertex': pc[i, lens[i] - 1, :]}
-                         for i in range(len(recs))]
-                io_utils.save_seqs_json(lines, os.path.join(pc_dir, name + '.json'))
-                io_utils.save_seqs_txt(lines, os.path.join(pc_dir, name + '.txt'))
-                pc_files.append(os.path.join(pc_dir, name + '.json'))
-                lines3d[name] = [l['seq'] for l in lines]
+                seqs, lens = got
+                vz = np.full(seqs.shape[0:2], np.nan, dtype=np.float32)
+                at = voffs[j]
+                for i, n in enumerate(lens):
+                    vz[i, :n] = z[at:at + n]
+                    at += n
+                n_draped = int(np.isfinite(vz).sum())
+                draped[name] = [voffs[j + 1] - voffs[j], n_draped, voffs[j + 1] - voffs[j] - n_draped]
+                write_3d(name, coor_img2pc.transform_coordinate_from_img_2_pc(params, seqs, lens, u8, vertex_z=vz, fit=elevation.fit), lens)
+            par_dir = os.path.join(out_dir, 'params')
+            os.makedirs(par_dir, exist_ok=True)
+            with open(os.path.join(par_dir, 'elevation.json'), 'w') as f:
+                json.dump(draped, f, indent=1)
 
         def raster_batch(names, params, points, offs, rpar, inten_scale=None):
+            kept = None if elevation is None else {'points': points, 'offs': [int(o) for o in offs], 'rpar': list(rpar)}
             for name, prm in zip(names, params):
-                queue.append([name, prm, None])
+                queue.append([name, prm, None] if kept is None else [name, prm, None, kept])
             if inten_scale is None:
                 tiles, u8 = ops.bev_raster_batch(points, offs, rpar, H, W, want_u8=True)
             else:
@@ -500,7 +568,7 @@ class Runner:
         return names, plist
 
     def infer_las_strip_to_map(self, las_paths, param_paths, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None,
-                               ground=None, intensity=None):
+                               ground=None, intensity=None, elevation=None):
         """A whole strip -> map-level lane lines: the LAS file(s) of the strip are read once, their points are binned into the tiles of
         the layout on the GPU (ops.strip_bin_points: the windows of `param_paths` may overlap and be rotated), and every batch of tiles
         then runs the chain of infer_las_to_map from the rasteriser on.  Same outputs under the same names; a tile is named by the
@@ -510,19 +578,21 @@ class Runner:
         ground: as for infer_las_to_map, applied per batch of tiles to the binned ranges, i.e. after `select` and the binning.
         intensity: as for infer_las_to_map, after `ground`.  scope='tile': per batch, on the ranges the rasteriser will see (after the
         height selection of `ground`).  scope='strip': one window for every tile, found once over all binned ranges before the batch
-        loop - BEFORE `ground`'s height selection, which runs per batch: points it later drops still count for the strip's window."""
+        loop - BEFORE `ground`'s height selection, which runs per batch: points it later drops still count for the strip's window.
+        elevation: as for infer_las_to_map, after the network, on the ranges the rasteriser saw (after `ground` and `intensity`)."""
         from . import las_io
         if isinstance(las_paths, (str, os.PathLike)):
             las_paths = [las_paths]
         names, plist = self._strip_layout(list(param_paths))
         select, ground, intensity = self._las_select(select), self._las_ground(ground), self._las_intensity(intensity)
+        elevation = self._las_elevation(elevation)
         used = {}
         if path_ckpt:
             self.load_ckpt(path_ckpt)
         B = int(batch_size or self.cfg.get('batch_size', 8))
         H, W = self.cfg.list_img_size_xy[1], self.cfg.list_img_size_xy[0]
         out_dir = work_dirs or self.cfg.get('work_dirs', './work_dirs')
-        raster_batch, close = self._las_chain(work_dirs, merge)
+        raster_batch, close = self._las_chain(work_dirs, merge, elevation)
         if plist:
             shift = plist[0]['las_read_offset']
             clouds, z_lo, z_hi = [], np.inf, -np.inf
