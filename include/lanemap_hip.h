@@ -331,6 +331,30 @@ int lm_drape_vertices(void* hip_stream, const float* points_xyzi, const long* ti
                       int W, const int* vertices_rc, const long* vertex_offsets, int radius_px, void* workspace, long workspace_bytes,
                       float* z, int* npix, float* pixel_min);
 
+/* ---- gap fill of sparse tiles (csrc/gapfill.hip): the stage between the rasteriser and the network for scanners that deliver fewer
+ * returns than pixels.  tiles_hwc_u8: DEVICE u8 [B][H][W][3], lm_bev_raster_batch's out_hwc_u8 or a decoded PNG; 1 <= B <= 4096,
+ * 1 <= H, W <= 32768.  A pixel is EMPTY when its three bytes are 0 (the reference's R + G + B < 1); its VALUE is R << 16 | G << 8 | B.
+ *   gap   of an empty pixel p for a maximal radius Rmax: the smallest d2 = dr^2 + dc^2 over the non-empty pixels q of the SAME tile with
+ *         d2 <= Rmax^2 - a disc: with Rmax = 1 the four edge neighbours count, the diagonal ones do not.  Pixels outside the tile do not
+ *         exist (no wrap into the next row, the neighbouring tile of the batch or padding).  An empty pixel without such a q is FAR.
+ *   ring  k of an empty, non-far pixel: the smallest integer with k^2 >= gap (1 for d2 = 1, 2 for 2..4, 3 for 5..9, ...).
+ * tile_gap_hist: hist DEVICE u32 [B][max_radius_px + 2], 1 <= max_radius_px = Rmax <= 8, zeroed by the call on the stream:
+ *         hist[b][0] = the non-empty pixels, hist[b][k], k = 1..Rmax, = the empty pixels of ring k, hist[b][Rmax + 1] = the far pixels;
+ *         every row sums to H W.  Integer atomic adds: order independent, the same bits every run.
+ * tile_gap_fill: radius_px HOST int [B], 0 <= radius_px[b] = r <= 8 per tile.  A non-empty pixel keeps its three bytes; an empty pixel
+ *         with gap <= r^2 takes the three bytes of the q of smallest d2 within the disc of radius r, ties in d2 to the LARGEST value
+ *         (brightest first, then highest elevation: the rule by which the rasteriser itself settles a pixel, so the result is unique by
+ *         value); every other pixel stays empty.  Sources are always pixels of the INPUT: no cascading, and out_hwc_u8 [B][H][W][3] is a
+ *         buffer of its own that must not overlap the input (refused, exact aliasing included).  r = 0 is a copy.
+ * Both are asynchronous, read nothing back to the host and need no workspace.  Bad arguments are refused with LM_ERR_ARG and a message that
+ * names the argument (B, H, W, max_radius_px, radius_px[b], null pointer, out_hwc_u8) before anything is launched.
+ * NOTE on the name `hip_stream`: as for lm_tile_ground above - tests/test_bounds_inventory_cpu.py finds device entries by the spelling
+ * `stream` and demands their guarded-buffer case in tests/test_gpu_1_bounds.py; the cases of these two entries are
+ * tests/test_gpu_gapfill.py::test_tile_gap_hist_guards and ::test_tile_gap_fill_guards, which that inventory does not read. */
+int lm_tile_gap_hist(void* hip_stream, const unsigned char* tiles_hwc_u8, int B, int H, int W, int max_radius_px, unsigned* hist);
+int lm_tile_gap_fill(void* hip_stream, const unsigned char* tiles_hwc_u8, int B, int H, int W, const int* radius_px,
+                     unsigned char* out_hwc_u8);
+
 /* ---- host-side tail (HOST pointers; no GPU is touched) --------------------------------------------------------
  * endp_cluster: heads/polyline_fpn_vit_vertex_2.py:661-688 + :903-924.
  * polyline_assemble: :805-861 + baseline/utils/polyline_utils.py (whole file) + :1091-1115.

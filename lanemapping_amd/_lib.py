@@ -104,6 +104,8 @@ SIGNATURES = {
                                        vp, vp, vp]),
     'lm_drape_workspace_bytes': (i64, [i64, i32, i32]),
     'lm_drape_vertices': (i32, [vp, vp, C.POINTER(i64), C.POINTER(LmRasterParams), i32, i32, i32, vp, C.POINTER(i64), i32, vp, i64, vp, vp, vp]),
+    'lm_tile_gap_hist': (i32, [vp, vp, i32, i32, i32, i32, vp]),
+    'lm_tile_gap_fill': (i32, [vp, vp, i32, i32, i32, C.POINTER(i32), vp]),
     'lm_endp_cluster': (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp]),
     'lm_polyline_assemble': (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp]),
     'lm_raster_polylines': (i32, [vp, i32, i32, vp]),

@@ -17,6 +17,9 @@ selection, both from the ground model the GPU computes out of the binned points 
 
 `IntensityStretch` / `intensity_window` describe how the map routes fit the rasteriser's intensity window to the data: two percentiles of
 the intensities a tile, or the whole strip, keeps (`ops.tile_intensity_window`), stretched over the intensity channel.
+
+`GapFill` / `gap_radius` describe how the map routes close the holes between the returns of a sparse scanner in the rasterised tiles
+(`ops.tile_gap_hist`, `ops.tile_gap_fill`).
 """
 import ctypes as C
 import math
@@ -274,6 +277,71 @@ class ElevationDrape:
 
     def __hash__(self):
         return hash(tuple(getattr(self, k) for k in self.__slots__))
+
+
+class GapFill:
+    """How the LAS -> map routes close the holes between the returns of a scanner that delivers fewer returns than pixels (immutable;
+    Runner.infer_las_strip_to_map / infer_las_to_map, `density=`).  Between the rasteriser and the network every empty pixel of a tile
+    takes the three bytes of the nearest non-empty pixel of the same tile within a disc of `radius` pixels, ties in distance going to the
+    brightest, then highest (ops.tile_gap_fill); pixels further away stay empty.
+
+      radius_px      'auto': per tile, the smallest radius that makes `coverage` of the tile's near pixels non-empty (gap_radius, from
+                     ops.tile_gap_hist); or a whole number in 0..max_radius_px used for every tile (0: the tile is not changed)
+      max_radius_px  1 .. 8: the largest radius 'auto' may choose; pixels further than this from every return are the black area beside
+                     the swath and do not count
+      coverage       0 < coverage <= 1: the share of the near pixels (non-empty, or within max_radius_px of a return) to be non-empty
+    coverage = 0.9 and max_radius_px = 4 are plain defaults, not tuned values."""
+    __slots__ = ('radius_px', 'max_radius_px', 'coverage')
+
+    def __init__(self, radius_px='auto', max_radius_px=4, coverage=0.9):
+        if isinstance(max_radius_px, bool) or not isinstance(max_radius_px, (int, np.integer)) or not 1 <= int(max_radius_px) <= 8:
+            raise ValueError(f'GapFill: max_radius_px={max_radius_px!r} must be a whole number of pixels in 1..8')
+        if not (isinstance(radius_px, str) and radius_px == 'auto'):
+            if isinstance(radius_px, bool) or not isinstance(radius_px, (int, np.integer)) or not 0 <= int(radius_px) <= int(max_radius_px):
+                raise ValueError(f"GapFill: radius_px={radius_px!r} must be 'auto' or a whole number of pixels in 0..max_radius_px="
+                                 f'{int(max_radius_px)}')
+            radius_px = int(radius_px)
+        if isinstance(coverage, bool) or not isinstance(coverage, (int, float, np.integer, np.floating)) or not 0 < float(coverage) <= 1:
+            raise ValueError(f'GapFill: coverage={coverage!r} must be a number with 0 < coverage <= 1')
+        for k, v in (('radius_px', radius_px), ('max_radius_px', int(max_radius_px)), ('coverage', float(coverage))):
+            object.__setattr__(self, k, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError('GapFill is immutable')
+
+    def __delattr__(self, name):
+        raise AttributeError('GapFill is immutable')
+
+    def __repr__(self):
+        return 'GapFill(' + ', '.join(f'{k}={getattr(self, k)!r}' for k in self.__slots__) + ')'
+
+    def __eq__(self, other):
+        return isinstance(other, GapFill) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
+
+    def __hash__(self):
+        return hash(tuple(getattr(self, k) for k in self.__slots__))
+
+
+def gap_radius(hist_row, fill):
+    """The fill radius of one tile from its row of ops.tile_gap_hist (Rmax + 2 counters for Rmax = fill.max_radius_px): a fixed
+    fill.radius_px as it is; 'auto': with near = sum(hist_row[0 : Rmax + 1]) - the far pixels, the black area beside the swath, left out -
+    the smallest r in 0..Rmax with sum(hist_row[0 : r + 1]) * 10**6 >= round(coverage * 10**6) * near, in integers; 0 for near == 0."""
+    if not isinstance(fill, GapFill):
+        raise TypeError(f'gap_radius: fill must be a las_io.GapFill, not {type(fill).__name__}')
+    if fill.radius_px != 'auto':
+        return fill.radius_px
+    row = [int(v) for v in hist_row]
+    R = fill.max_radius_px
+    if len(row) != R + 2 or any(v < 0 for v in row):
+        raise ValueError(f'gap_radius: hist_row must hold max_radius_px + 2 = {R + 2} counters >= 0, not {row}')
+    near = sum(row[0:R + 1])
+    if near == 0:
+        return 0
+    want = int(round(fill.coverage * 10 ** 6)) * near
+    for r in range(R + 1):
+        if sum(row[0:r + 1]) * 10 ** 6 >= want:
+            return r
+    return R
 
 
 def parse_header(data):

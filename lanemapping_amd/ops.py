@@ -870,6 +870,42 @@ def drape_vertices(points, tile_offsets, params, vertices, vertex_offsets, H=115
     return (z, npix, pmin) if want_pixel_min else (z, npix)
 
 
+def _gap_args(who, u8):
+    if not u8.is_cuda:
+        _ptr(u8)
+    if u8.dtype != torch.uint8 or u8.dim() != 4 or u8.shape[3] != 3 or not u8.is_contiguous():
+        raise ValueError(f'{who}: tiles must be a contiguous uint8 tensor [B,H,W,3], not {u8.dtype} {tuple(u8.shape)}'
+                         + ('' if u8.is_contiguous() else ' (not contiguous)'))
+    return int(u8.shape[0]), int(u8.shape[1]), int(u8.shape[2])
+
+
+def tile_gap_hist(u8, max_radius_px=4):
+    """How far the empty pixels of every u8 HWC tile [B,H,W,3] lie from a return (csrc/gapfill.hip): -> hist [B, Rmax + 2] int32 on the
+    device, Rmax = max_radius_px in 1..8.  hist[b, 0] = the non-empty pixels (a pixel is empty when its three bytes are 0), hist[b, k],
+    k = 1..Rmax, = the empty pixels whose nearest non-empty pixel of the same tile, d2 = dr^2 + dc^2 <= Rmax^2 away, has
+    (k - 1)^2 < d2 <= k^2, hist[b, Rmax + 1] = the empty pixels without one.  Every row sums to H W.  Exact and reproducible.  No
+    synchronisation."""
+    B, H, W = _gap_args('tile_gap_hist', u8)
+    R = int(max_radius_px)
+    hist = torch.empty((B, max(R, 0) + 2), device=u8.device, dtype=torch.int32)
+    check(lib().lm_tile_gap_hist(_stream(), _ptr(u8), B, H, W, R, _ptr(hist)))
+    return hist
+
+
+def tile_gap_fill(u8, radius_px):
+    """The u8 HWC tiles [B,H,W,3] with their gaps filled (csrc/gapfill.hip): -> a new u8 [B,H,W,3].  radius_px: an int or B ints in 0..8,
+    per tile.  A non-empty pixel keeps its bytes; an empty pixel takes the three bytes of the nearest non-empty pixel of the same INPUT
+    tile within the disc of that radius (ties in distance: the largest R << 16 | G << 8 | B, i.e. brightest, then highest); every other
+    pixel stays empty.  Radius 0 is a copy.  Exact and reproducible.  No synchronisation."""
+    B, H, W = _gap_args('tile_gap_fill', u8)
+    radii = [int(r) for r in radius_px] if hasattr(radius_px, '__len__') else [int(radius_px)] * B
+    if len(radii) != B:
+        raise ValueError(f'tile_gap_fill: {len(radii)} radius_px entries for {B} tiles')
+    out = torch.empty_like(u8)
+    check(lib().lm_tile_gap_fill(_stream(), _ptr(u8), B, H, W, (C.c_int * B)(*radii), _ptr(out)))
+    return out
+
+
 def tile_ingest(u8_hwc):
     """[B,H,W,C>=3] uint8 (decoded PNG) -> [B,3,H,W] f32 = u8/255 (reference load_img contract)."""
     x = u8_hwc.contiguous()

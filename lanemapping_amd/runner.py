@@ -387,8 +387,17 @@ class Runner:
             raise TypeError(f'elevation must be a las_io.ElevationDrape, not {type(elevation).__name__}')
         return elevation
 
+    def _las_density(self, density):
+        """The gap fill of the LAS routes: the argument, else cfg['las_density'] (a dict of las_io.GapFill arguments), else none."""
+        from . import las_io
+        if density is None and self.cfg.get('las_density') is not None:
+            density = las_io.GapFill(**dict(self.cfg.get('las_density')))
+        if density is not None and not isinstance(density, las_io.GapFill):
+            raise TypeError(f'density must be a las_io.GapFill, not {type(density).__name__}')
+        return density
+
     def infer_las_to_map(self, las_and_params, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None, ground=None,
-                         intensity=None, elevation=None):
+                         intensity=None, elevation=None, density=None):
         """LAS tiles -> map-level 3-D lane lines, every stage of the reference's offline chain on this stack:
 
           LAS file + tile parameter file (utils/io_utils.py:125-150)
@@ -415,10 +424,17 @@ class Runner:
         device-to-host read per batch: the lower median of the per-pixel minimum heights around the vertex pixel) instead of the tile's
         8-bit elevation channel; a vertex with fewer than min_pixels filled pixels keeps the channel's value.  The 2-D JSON files do not
         change.  What was used is written to <work_dirs>/params/elevation.json as {tile name: [vertices, draped, fallen back]}.
+        density: a las_io.GapFill (default: cfg['las_density'], a dict of its arguments; absent: nothing changes): for a scanner that
+        delivers fewer returns than pixels.  Between the rasteriser and the network every empty pixel of a tile takes the bytes of the
+        nearest return's pixel within the tile's fill radius (ops.tile_gap_fill; ties to the brightest, then highest).  radius_px='auto'
+        picks the radius per tile from the tile's gap histogram (ops.tile_gap_hist, one device-to-host read per batch;
+        las_io.gap_radius).  The network and the back-projection both get the filled tile; `elevation` reads the points and is not
+        affected.  What was used is written to <work_dirs>/params/density.json as {tile name: [radius, hist[0], ..., hist[Rmax + 1]]}.
+        Order of the stages: select, (binning,) ground, intensity, rasteriser, density, network, elevation.
         Single rank (the merge is sequential over the sorted tiles)."""
         from . import las_io
         select, ground, intensity = self._las_select(select), self._las_ground(ground), self._las_intensity(intensity)
-        elevation = self._las_elevation(elevation)
+        elevation, density = self._las_elevation(elevation), self._las_density(density)
         if intensity is not None and intensity.scope == 'strip':
             raise ValueError("intensity: scope='strip' needs the whole strip in one cloud (infer_las_strip_to_map); infer_las_to_map reads "
                              "its tiles file by file, use scope='tile'")
@@ -428,7 +444,7 @@ class Runner:
         B = int(batch_size or self.cfg.get('batch_size', 8))
         H, W = self.cfg.list_img_size_xy[1], self.cfg.list_img_size_xy[0]
         out_dir = work_dirs or self.cfg.get('work_dirs', './work_dirs')
-        raster_batch, close = self._las_chain(work_dirs, merge, elevation)
+        raster_batch, close = self._las_chain(work_dirs, merge, elevation, density)
         for i in range(0, len(las_and_params), B):
             chunk = las_and_params[i:i + B]
             pts, offs, rpar, names, plist = [], [0], [], [], []
@@ -446,19 +462,21 @@ class Runner:
             self._raster_stretched(raster_batch, intensity, names, plist, pts, offs, rpar, H, W, out_dir, used)
         return close()
 
-    def _las_chain(self, work_dirs, merge, elevation=None):
+    def _las_chain(self, work_dirs, merge, elevation=None, density=None):
         """The chain behind infer_las_to_map / infer_las_strip_to_map from the rasteriser on: -> (raster_batch, close).
         raster_batch(names, params, points, offsets, raster_params[, inten_scale]) rasterises one batch of tiles out of `points` and runs it through
         the pipeline, the per-tile JSON and the back-projection; close() drains the pipeline, merges and returns (lines3d, merged).
         elevation: a las_io.ElevationDrape or None.  With one, every batch keeps the (points, offsets, raster_params) the rasteriser saw
-        until its futures arrive; the vertices of all its tiles then get their heights in one ops.drape_vertices call."""
-        from . import coor_img2pc, merge_lines as ml
+        until its futures arrive; the vertices of all its tiles then get their heights in one ops.drape_vertices call.
+        density: a las_io.GapFill or None.  With one, a batch is rasterised to u8 only, its gaps are filled on the GPU (one read-back of
+        the gap histograms per batch), and the filled u8 tile goes to the pipeline and, copied to the host, to the back-projection."""
+        from . import coor_img2pc, las_io, merge_lines as ml
         out_dir = work_dirs or self.cfg.get('work_dirs', './work_dirs')
         pc_dir = os.path.join(out_dir, 'out_pc_seq_json_dir')
         os.makedirs(pc_dir, exist_ok=True)
         pipe = TilePipeline(self.net)
         H, W = self.cfg.list_img_size_xy[1], self.cfg.list_img_size_xy[0]
-        queue, lines3d, pc_files, draped = [], {}, [], {}
+        queue, lines3d, pc_files, draped, filled = [], {}, [], {}, {}
 
         def polylines(f, name):
             """One tile's future -> its 2-D JSON on disk and (seqs [L, Vmax, 2], lens), None for a tile the reference skips."""
@@ -530,11 +548,28 @@ class Runner:
             with open(os.path.join(par_dir, 'elevation.json'), 'w') as f:
                 json.dump(draped, f, indent=1)
 
+        def fill_gaps(names, points, offs, rpar, inten_scale):
+            """One batch through `density`: the u8 tile alone (the stem takes it directly), its gap histograms (the one read-back), every
+            tile's radius, the filled u8 tile.  `filled` collects {tile name: [radius, hist...]} over the call -> params/density.json."""
+            kw = {} if inten_scale is None else {'inten_scale': inten_scale}
+            u8 = ops.bev_raster_batch(points, offs, rpar, H, W, u8_only=True, **kw)
+            hist = ops.tile_gap_hist(u8, density.max_radius_px).cpu().numpy()
+            radii = [las_io.gap_radius(row, density) for row in hist]
+            for name, r, row in zip(names, radii, hist):
+                filled[name] = [int(r)] + [int(v) for v in row]
+            par_dir = os.path.join(out_dir, 'params')
+            os.makedirs(par_dir, exist_ok=True)
+            with open(os.path.join(par_dir, 'density.json'), 'w') as f:
+                json.dump(filled, f, indent=1)
+            return ops.tile_gap_fill(u8, radii)
+
         def raster_batch(names, params, points, offs, rpar, inten_scale=None):
             kept = None if elevation is None else {'points': points, 'offs': [int(o) for o in offs], 'rpar': list(rpar)}
             for name, prm in zip(names, params):
                 queue.append([name, prm, None] if kept is None else [name, prm, None, kept])
-            if inten_scale is None:
+            if density is not None:
+                tiles = u8 = fill_gaps(names, points, offs, rpar, inten_scale)
+            elif inten_scale is None:
                 tiles, u8 = ops.bev_raster_batch(points, offs, rpar, H, W, want_u8=True)
             else:
                 tiles, u8 = ops.bev_raster_batch(points, offs, rpar, H, W, want_u8=True, inten_scale=inten_scale)
@@ -568,7 +603,7 @@ class Runner:
         return names, plist
 
     def infer_las_strip_to_map(self, las_paths, param_paths, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None,
-                               ground=None, intensity=None, elevation=None):
+                               ground=None, intensity=None, elevation=None, density=None):
         """A whole strip -> map-level lane lines: the LAS file(s) of the strip are read once, their points are binned into the tiles of
         the layout on the GPU (ops.strip_bin_points: the windows of `param_paths` may overlap and be rotated), and every batch of tiles
         then runs the chain of infer_las_to_map from the rasteriser on.  Same outputs under the same names; a tile is named by the
@@ -579,20 +614,21 @@ class Runner:
         intensity: as for infer_las_to_map, after `ground`.  scope='tile': per batch, on the ranges the rasteriser will see (after the
         height selection of `ground`).  scope='strip': one window for every tile, found once over all binned ranges before the batch
         loop - BEFORE `ground`'s height selection, which runs per batch: points it later drops still count for the strip's window.
-        elevation: as for infer_las_to_map, after the network, on the ranges the rasteriser saw (after `ground` and `intensity`)."""
+        elevation: as for infer_las_to_map, after the network, on the ranges the rasteriser saw (after `ground` and `intensity`).
+        density: as for infer_las_to_map, per batch between the rasteriser and the network."""
         from . import las_io
         if isinstance(las_paths, (str, os.PathLike)):
             las_paths = [las_paths]
         names, plist = self._strip_layout(list(param_paths))
         select, ground, intensity = self._las_select(select), self._las_ground(ground), self._las_intensity(intensity)
-        elevation = self._las_elevation(elevation)
+        elevation, density = self._las_elevation(elevation), self._las_density(density)
         used = {}
         if path_ckpt:
             self.load_ckpt(path_ckpt)
         B = int(batch_size or self.cfg.get('batch_size', 8))
         H, W = self.cfg.list_img_size_xy[1], self.cfg.list_img_size_xy[0]
         out_dir = work_dirs or self.cfg.get('work_dirs', './work_dirs')
-        raster_batch, close = self._las_chain(work_dirs, merge, elevation)
+        raster_batch, close = self._las_chain(work_dirs, merge, elevation, density)
         if plist:
             shift = plist[0]['las_read_offset']
             clouds, z_lo, z_hi = [], np.inf, -np.inf
