@@ -38,6 +38,8 @@ int lm_ensure_dynamic_lds(const void* kernel, size_t bytes);   // per device and
 #define LM_LAUNCH_CHECK() LM_HIP(hipGetLastError())
 
 static inline int lm_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+static inline long lm_cdivl(long a, long b) { return (a + b - 1) / b; }
+static inline size_t lm_align256(size_t v) { return (v + 255) / 256 * 256; }   // workspace segments start on 256 bytes
 
 // activation codes shared by the GEMM/conv epilogues
 enum { LM_ACT_NONE = 0, LM_ACT_RELU = 1, LM_ACT_GELU = 2 };

@@ -1,12 +1,13 @@
 // Vertex heights read off the points: a pixel-scale ground model around the polyline vertices of every tile.  Input is the (points,
-// tile_offsets, params) triple lm_bev_raster_batch takes plus, per tile, a list of vertex pixels (vr, vc).  Membership is the rule of
-// ground.hip: a point counts for tile b exactly when lm_point_window (raster_xf.h, constants from lm_raster_derive) keeps it for b and
-// its tile-frame height vz is finite.  With R = radius_px and S = (2R + 1)^2:
-//   (a) window minima  vertex v owns S slots; slot (i, j), i, j in -R..R, holds the smallest key_of(vz) (the order-preserving u32 key of
-//                      ground.hip: -0.0 < +0.0, 0xFFFFFFFF = empty) over the tile's points of pixel (vr + i, vc + j).  A workgroup
-//                      streams one chunk of DCHUNK = 16,384 points of one tile (256 lanes x 64 coalesced 16-byte non-temporal loads, 8 in
-//                      flight per lane) and keeps the tile's vertices in LDS as a row-band index: the entries (vr, vc, vertex id) sorted
-//                      by band = vr / 8 (the head's row pitch) and the first entry of every band.  The host sorts (stable); the
+// tile_offsets, params) triple lm_bev_raster_batch takes plus, per tile, a list of vertex pixels (vr, vc), walked with the scaffold of
+// tile_points.h (tile constants, workgroup -> tile, streaming loop, key of a height, host prologue).  Membership is the rule of
+// ground.hip: a point counts for tile b exactly when raster.hip would keep it for b and its tile-frame height vz is finite.
+// With R = radius_px and S = (2R + 1)^2:
+//   (a) window minima  vertex v owns S slots; slot (i, j), i, j in -R..R, holds the smallest lm_key_of(vz) (-0.0 < +0.0, 0xFFFFFFFF =
+//                      empty) over the tile's points of pixel (vr + i, vc + j).  A workgroup streams one chunk of DCHUNK = 16,384
+//                      points of one tile (lm_stream_points: 256 lanes x 64 loads, 8 in flight per lane) and keeps the tile's vertices
+//                      in LDS as a row-band index: the entries (vr, vc, vertex id) sorted by band = vr / 8 (the head's row pitch)
+//                      and the first entry of every band.  The host sorts (stable); the
 //                      workgroup derives the band starts from the sorted entries while it copies them.  A point of row r walks the
 //                      entries of bands (r - R) / 8 .. (r + R) / 8, one contiguous range, and sends its key with an integer atomic min
 //                      straight to the slot in global memory for every vertex with |r - vr| <= R and |c - vc| <= R: one point serves
@@ -14,9 +15,9 @@
 //                      ever lowered by atomic min: order independent, the same bits every run.
 //   (b) median         one wave per vertex: z = the lower median (element (k - 1) / 2 of the k non-empty slots in ascending key order,
 //                      by rank counting with ties ranked by position), npix = k, z = NaN for k = 0.
-// Workgroup -> (tile, chunk) as in ground.hip; tiles without points or without vertices get no workgroup.  HBM traffic of (a): 16 N read.
+// Tiles without points or without vertices get no workgroup.  HBM traffic of (a): 16 N read.
 #include "common.h"
-#include "raster_xf.h"
+#include "tile_points.h"
 
 #include <cmath>
 #include <vector>
@@ -28,42 +29,20 @@ constexpr int D_PER_THREAD = 64;
 constexpr int DCHUNK = DT * D_PER_THREAD;    // points per workgroup of (a)
 constexpr int LB = 8;                        // loads in flight per lane
 constexpr int BAND = 8;                      // rows per band of the vertex index
-constexpr int MAX_B = 4096;
 constexpr int MAX_R = 8;
 constexpr int MAX_SLOTS = (2 * MAX_R + 1) * (2 * MAX_R + 1);
 constexpr int MAX_TILE_VERTICES = 16384;     // 128 KB of LDS entries
 constexpr int MAX_HW = 32768;                // vr and vc are packed into 16 bits each; at most 4097 band starts (16 KB of LDS)
-constexpr unsigned EMPTY = 0xFFFFFFFFu;
-constexpr unsigned QNAN_BITS = 0x7FC00000u;
 
-struct alignas(16) DrapeTile {               // the members of TileXf the window test reads + the tile's ranges: 96 bytes per tile
-    float m[9], t[3], off[2], irow, icol;
-    long start, count;                       // point range in the concatenated buffer
-    long cbase;                              // workgroups of the tiles before this one
+struct DrapeTile : LmTileRange {
     int vbase, nv;                           // vertex range of the tile
 };
+static_assert(sizeof(DrapeTile) == 96 && alignof(DrapeTile) == 16, "96 bytes per tile: lm_drape_workspace_bytes");
 
 struct DrapeEntry {
     unsigned rc;                             // vr << 16 | vc
     unsigned id;                             // index of the vertex in the call's concatenated list
 };
-
-__device__ __forceinline__ unsigned key_of(float v) {
-    const unsigned b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b ^ 0x80000000u);
-}
-__device__ __forceinline__ float value_of(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
-
-// the tile of workgroup `wg`: the last t with cbase[t] <= wg (a tile without workgroups shares its base with its successor)
-__device__ __forceinline__ int tile_of(const DrapeTile* __restrict__ tiles, int B, long wg) {
-    int lo = 0, hi = B;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (tiles[mid].cbase <= wg) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
 
 // (a) grid: sum over the tiles with vertices of ceil(count / DCHUNK); dynamic LDS = nb1 band starts (nb1 = bands + 1 rounded up to even)
 // + the entries of the largest tile
@@ -74,7 +53,7 @@ __global__ __launch_bounds__(DT) void drape_min_kernel(const f32x4* __restrict__
     unsigned* bstart = lds;                                     // [nb + 1]: first entry of every band, bstart[nb] = nv
     DrapeEntry* ent = reinterpret_cast<DrapeEntry*>(lds + nb1);
     const int tid = threadIdx.x;
-    const int t = tile_of(tiles, B, (long)blockIdx.x);
+    const int t = lm_tile_of(tiles, B, (long)blockIdx.x);
     const DrapeTile X = tiles[t];
     const long first = ((long)blockIdx.x - X.cbase) * DCHUNK;
     const long left = X.count - first;                          // >= 1
@@ -92,32 +71,19 @@ __global__ __launch_bounds__(DT) void drape_min_kernel(const f32x4* __restrict__
     __syncthreads();
     const int D = 2 * R + 1;
     const long S = (long)D * D;
-    const f32x4* base = pts + X.start + first;
-#pragma unroll 1
-    for (int j0 = 0; j0 < D_PER_THREAD; j0 += LB) {
-        if ((long)j0 * DT >= left) break;                      // workgroup-uniform
-        f32x4 p[LB];
-#pragma unroll
-        for (int j = 0; j < LB; ++j) {
-            const long i = (long)(j0 + j) * DT + tid;
-            p[j] = __builtin_nontemporal_load(base + (i < left ? i : left - 1));   // unconditional, tail lanes masked below
+    lm_stream_points<DT, D_PER_THREAD, LB>(pts + X.start + first, left, tid, [&](const f32x4 p, bool valid) {
+        int row, col;
+        float vz;
+        if (!(valid && lm_point_window(p, X, H, W, row, col, vz) && fabsf(vz) < INFINITY)) return;
+        const unsigned key = lm_key_of(vz);
+        const int r0 = row - R > 0 ? row - R : 0, r1 = row + R < H - 1 ? row + R : H - 1;
+        const unsigned e1 = bstart[r1 / BAND + 1];
+        for (unsigned e = bstart[r0 / BAND]; e < e1; ++e) {
+            const DrapeEntry v = ent[e];
+            const unsigned di = (unsigned)(row - (int)(v.rc >> 16) + R), dj = (unsigned)(col - (int)(v.rc & 0xFFFFu) + R);
+            if (di < (unsigned)D && dj < (unsigned)D) atomicMin(slots + ((long)v.id * S + (long)(di * (unsigned)D + dj)), key);
         }
-#pragma unroll
-        for (int j = 0; j < LB; ++j) {
-            const long i = (long)(j0 + j) * DT + tid;
-            int row, col;
-            float vz;
-            if (!(i < left && lm_point_window(p[j], X, H, W, row, col, vz) && fabsf(vz) < INFINITY)) continue;
-            const unsigned key = key_of(vz);
-            const int r0 = row - R > 0 ? row - R : 0, r1 = row + R < H - 1 ? row + R : H - 1;
-            const unsigned e1 = bstart[r1 / BAND + 1];
-            for (unsigned e = bstart[r0 / BAND]; e < e1; ++e) {
-                const DrapeEntry v = ent[e];
-                const unsigned di = (unsigned)(row - (int)(v.rc >> 16) + R), dj = (unsigned)(col - (int)(v.rc & 0xFFFFu) + R);
-                if (di < (unsigned)D && dj < (unsigned)D) atomicMin(slots + ((long)v.id * S + (long)(di * (unsigned)D + dj)), key);
-            }
-        }
-    }
+    });
 }
 
 // (b) grid: ceil(V / 4) workgroups, one wave per vertex
@@ -131,15 +97,15 @@ __global__ __launch_bounds__(DT) void drape_median_kernel(const unsigned* __rest
         for (int e = lane; e < S; e += 64) {
             const unsigned s = slots[v * S + e];
             k[e] = s;
-            if (pixel_min) pixel_min[v * S + e] = __uint_as_float(s == EMPTY ? QNAN_BITS : __float_as_uint(value_of(s)));
+            if (pixel_min) pixel_min[v * S + e] = __uint_as_float(s == LM_KEY_EMPTY ? LM_QNAN_BITS : __float_as_uint(lm_value_of(s)));
         }
     }
     __syncthreads();
     if (v >= V) return;
     int n = 0;
-    for (int f = 0; f < S; ++f) n += k[f] != EMPTY;
+    for (int f = 0; f < S; ++f) n += k[f] != LM_KEY_EMPTY;
     if (n == 0) {
-        if (lane == 0) z[v] = __uint_as_float(QNAN_BITS), npix[v] = 0;
+        if (lane == 0) z[v] = __uint_as_float(LM_QNAN_BITS), npix[v] = 0;
         return;
     }
     // the element of rank (n - 1) / 2; equal keys are ranked by their position, so exactly one element has each rank, and the empty
@@ -149,20 +115,17 @@ __global__ __launch_bounds__(DT) void drape_median_kernel(const unsigned* __rest
         const unsigned mine = k[e];
         int rank = 0;
         for (int f = 0; f < S; ++f) rank += (k[f] < mine) || (f < e && k[f] == mine);
-        if (rank == want) z[v] = value_of(mine), npix[v] = n;
+        if (rank == want) z[v] = lm_value_of(mine), npix[v] = n;
     }
 }
-
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-long cdivl(long a, long b) { return (a + b - 1) / b; }
 
 }  // namespace
 
 LM_API long lm_drape_workspace_bytes(long n_vertices, int B, int radius_px) {
-    if (n_vertices < 0 || n_vertices > 2147483647L || B < 0 || B > MAX_B || radius_px < 0 || radius_px > MAX_R) return 0;
+    if (n_vertices < 0 || n_vertices > 2147483647L || B < 0 || B > LM_MAX_TILES || radius_px < 0 || radius_px > MAX_R) return 0;
     const long S = (long)(2 * radius_px + 1) * (2 * radius_px + 1);
-    return (long)(align256((size_t)(B > 0 ? B : 1) * sizeof(DrapeTile)) + align256((size_t)n_vertices * sizeof(DrapeEntry)) +
-                  align256((size_t)n_vertices * (size_t)S * 4));
+    return (long)(lm_align256((size_t)(B > 0 ? B : 1) * sizeof(DrapeTile)) + lm_align256((size_t)n_vertices * sizeof(DrapeEntry)) +
+                  lm_align256((size_t)n_vertices * (size_t)S * 4));
 }
 
 // points: device [sum N][4]; tile_offsets: HOST [B+1]; params: HOST [B]; vertices_rc: HOST [V][2] (row, col); vertex_offsets: HOST [B+1],
@@ -174,35 +137,28 @@ LM_API int lm_drape_vertices(void* hip_stream, const float* points_xyzi, const l
     static thread_local std::vector<DrapeEntry> h_entries;
     static thread_local std::vector<int> h_fill;
     LM_REQUIRE(radius_px >= 0 && radius_px <= MAX_R, "drape_vertices: radius_px=%d, 0 to %d are supported", radius_px, MAX_R);
-    LM_REQUIRE(B >= 0 && B <= MAX_B, "drape_vertices: B=%d tiles, 0 to %d are supported", B, MAX_B);
     LM_REQUIRE(H > 0 && W > 0 && H <= MAX_HW && W <= MAX_HW, "drape_vertices: bad tile size H=%d W=%d (1 to %d)", H, W, MAX_HW);
-    if (B == 0) return LM_OK;
-    LM_REQUIRE(tile_offsets && params && vertex_offsets, "drape_vertices: null pointer (tile_offsets / params / vertex_offsets)");
-    LM_REQUIRE(tile_offsets[0] >= 0, "drape_vertices: tile_offsets[0] is negative");
-    LM_REQUIRE(vertex_offsets[0] == 0, "drape_vertices: vertex_offsets[0] must be 0");
-    const int nb = (int)cdivl(H, BAND);
+    const int nb = (int)lm_cdivl(H, BAND);
     int max_nv = 0;
-    long wg = 0;
-    h_tiles.resize((size_t)B);
-    for (int b = 0; b < B; ++b) {
-        const long n = tile_offsets[b + 1] - tile_offsets[b], nv = vertex_offsets[b + 1] - vertex_offsets[b];
-        LM_REQUIRE(n >= 0, "drape_vertices: tile_offsets must be non-decreasing (tile %d)", b);
+    const auto tile_vertices = [&](int b, DrapeTile& T, long& wgs) -> int {
+        if (b == 0) {                                           // behind the shared checks: B is refused by its own name first
+            LM_REQUIRE(vertex_offsets, "drape_vertices: null pointer (vertex_offsets)");
+            LM_REQUIRE(vertex_offsets[0] == 0, "drape_vertices: vertex_offsets[0] must be 0");
+        }
+        const long nv = vertex_offsets[b + 1] - vertex_offsets[b];
         LM_REQUIRE(nv >= 0, "drape_vertices: vertex_offsets must be non-decreasing (tile %d)", b);
         LM_REQUIRE(nv <= MAX_TILE_VERTICES, "drape_vertices: %ld vertices in tile %d, at most %d per tile are supported", nv, b,
                    MAX_TILE_VERTICES);
         LM_REQUIRE(vertex_offsets[b + 1] <= 2147483647L, "drape_vertices: more than 2^31 - 1 vertices");
-        LM_REQUIRE(params[b].img_reso[0] > 0 && params[b].img_reso[1] > 0, "drape_vertices: bad resolution (tile %d)", b);
-        TileXf X;
-        lm_raster_derive(params[b], tile_offsets[b], n, X);     // the rasteriser's own routine: the same float constants
-        DrapeTile& T = h_tiles[(size_t)b];
-        for (int i = 0; i < 9; ++i) T.m[i] = X.m[i];
-        for (int i = 0; i < 3; ++i) T.t[i] = X.t[i];
-        T.off[0] = X.off[0], T.off[1] = X.off[1], T.irow = X.irow, T.icol = X.icol;
-        T.start = tile_offsets[b], T.count = n, T.cbase = wg, T.vbase = (int)vertex_offsets[b], T.nv = (int)nv;
-        if (nv > 0) wg += cdivl(n, DCHUNK);
+        T.vbase = (int)vertex_offsets[b], T.nv = (int)nv;
+        if (nv == 0) wgs = 0;                                   // nothing to find: no workgroup, whatever its points
         if (nv > max_nv) max_nv = (int)nv;
-    }
-    const long N = tile_offsets[B] - tile_offsets[0], V = vertex_offsets[B];
+        return LM_OK;
+    };
+    long wg, N;
+    if (int e = lm_tile_ranges("drape_vertices", tile_offsets, params, B, 0, H, W, DCHUNK, h_tiles, &wg, &N, tile_vertices)) return e;
+    if (B == 0) return LM_OK;
+    const long V = vertex_offsets[B];
     LM_REQUIRE(N <= 2147483647L, "drape_vertices: %ld points, at most 2^31 - 1 are supported", N);
     LM_REQUIRE(wg <= 2147483647L, "drape_vertices: too many workgroups");
     if (V == 0) return LM_OK;
@@ -225,17 +181,16 @@ LM_API int lm_drape_vertices(void* hip_stream, const float* points_xyzi, const l
         }
     }
     LM_REQUIRE(workspace && z && npix, "drape_vertices: null pointer (workspace / z / npix)");
-    LM_REQUIRE(points_xyzi || N == 0, "drape_vertices: null points");
-    LM_REQUIRE(((uintptr_t)points_xyzi & 15) == 0 && ((uintptr_t)workspace & 15) == 0, "drape_vertices: points and workspace must be 16-byte aligned");
+    if (int e = lm_tile_points_check("drape_vertices", points_xyzi, N, workspace)) return e;
     LM_REQUIRE(lm_drape_workspace_bytes(V, B, radius_px) <= workspace_bytes, "drape_vertices: workspace too small (%ld B needed)",
                lm_drape_workspace_bytes(V, B, radius_px));
     const int D = 2 * radius_px + 1, S = D * D;
     hipStream_t s = (hipStream_t)hip_stream;
     char* w = (char*)workspace;
     DrapeTile* d_tiles = (DrapeTile*)w;
-    w += align256((size_t)B * sizeof(DrapeTile));
+    w += lm_align256((size_t)B * sizeof(DrapeTile));
     DrapeEntry* d_entries = (DrapeEntry*)w;
-    w += align256((size_t)V * sizeof(DrapeEntry));
+    w += lm_align256((size_t)V * sizeof(DrapeEntry));
     unsigned* slots = (unsigned*)w;
     LM_HIP(hipMemsetAsync(slots, 0xFF, (size_t)V * (size_t)S * 4, s));
     if (wg > 0) {
@@ -248,7 +203,7 @@ LM_API int lm_drape_vertices(void* hip_stream, const float* points_xyzi, const l
                            d_entries, slots, H, W, radius_px, nb, nb1);
         LM_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(drape_median_kernel, dim3((unsigned)cdivl(V, DT / 64)), dim3(DT), 0, s, slots, (int)V, S, z, npix, pixel_min);
+    hipLaunchKernelGGL(drape_median_kernel, dim3((unsigned)lm_cdivl(V, DT / 64)), dim3(DT), 0, s, slots, (int)V, S, z, npix, pixel_min);
     LM_LAUNCH_CHECK();
     return LM_OK;
 }

@@ -1,15 +1,14 @@
 // Per-tile ground model of the strip route: a coarse grid of ground heights under every tile, out of the points already binned for the
 // rasteriser, and the selection of points by their height above it.  Input of both entries is the (points, tile_offsets, params) triple
-// lm_bev_raster_batch takes; membership is the rasteriser's own window test, lm_point_window (raster_xf.h), on constants from the
-// rasteriser's own host routine (lm_raster_derive): a point counts for tile b exactly when raster.hip would keep it for b.  A point
-// whose vz (the tile-frame height the rasteriser turns into G) is not finite counts nowhere and is never selected.
+// lm_bev_raster_batch takes, walked with the scaffold of tile_points.h (tile constants, workgroup -> tile, streaming loop, key of a
+// height, host prologue): a point counts for tile b exactly when raster.hip would keep it for b.  A point whose vz (the tile-frame
+// height the rasteriser turns into G) is not finite counts nowhere and is never selected.
 //
 // The cell grid is Gy = ceil(H / cell_px) by Gx = ceil(W / cell_px); the cell of a point is (row / cell_px, col / cell_px).
-//   (a) cell minima   a workgroup streams one chunk of GCHUNK = 16,384 points of one tile (256 lanes x 64 coalesced 16-byte non-temporal
-//                     loads, 8 in flight per lane), keeps the tile's Gy Gx minima in LDS as order-preserving u32 keys of vz (float bits,
-//                     sign bit flipped for v >= +0, all bits flipped below; 0xFFFFFFFF = empty) under LDS atomic min, and flushes its
-//                     non-empty cells to keys [B][Gy][Gx] (memset to 0xFF) with integer atomic min: order independent, the same bits
-//                     every run.  The minimum is taken on the key: -0.0 < +0.0.
+//   (a) cell minima   a workgroup streams one chunk of GCHUNK = 16,384 points of one tile (lm_stream_points: 256 lanes x 64 loads, 8 in
+//                     flight per lane), keeps the tile's Gy Gx minima in LDS as keys of vz (lm_key_of; 0xFFFFFFFF = empty) under LDS
+//                     atomic min, and flushes its non-empty cells to keys [B][Gy][Gx] (memset to 0xFF) with integer atomic min: order
+//                     independent, the same bits every run.  The minimum is taken on the key: -0.0 < +0.0.
 //   (b) smoothing     one workgroup per tile: ground = lower median (element (k - 1) / 2 of the k keys in ascending order) of the
 //                     non-empty cells of the 3 x 3 neighbourhood clipped at the grid edge, NaN for k = 0; ground_min = the minimum of the
 //                     tile's finite ground cells, +inf when it has none.
@@ -17,11 +16,10 @@
 //                     nothing).  Stable compaction per tile, the scheme of lm_las_decode_select: count per block of SEL_BLOCK = 256 points
 //                     (blocks never straddle two tiles), exclusive scan (prim.hip), emit to block offset + ballot rank.  A workgroup
 //                     takes SEL_GROUP = 8 consecutive blocks of one tile so that 8 loads per lane are in flight.  No atomics.
-// Workgroup -> (tile, chunk) is a binary search over the per-tile prefix of chunk counts kept with the tile constants in a device buffer
-// (B up to 4096, any mix of tile sizes, one launch).  HBM traffic: (a) 16 N read, (c) 32 N read + 16 kept written.
+// HBM traffic: (a) 16 N read, (c) 32 N read + 16 kept written.
 #include "common.h"
 #include "prim.h"
-#include "raster_xf.h"
+#include "tile_points.h"
 
 #include <cmath>
 #include <vector>
@@ -35,34 +33,12 @@ constexpr int LB = 8;                        // loads in flight per lane
 constexpr int SEL_BLOCK = 256;               // points per counted block of (c)
 constexpr int SEL_GROUP = 8;                 // blocks per workgroup of (c)
 constexpr int SEL_CHUNK = SEL_BLOCK * SEL_GROUP;
-constexpr int MAX_B = 4096;
 constexpr int MAX_CELLS = 32768;             // 128 KB of LDS keys
-constexpr unsigned EMPTY = 0xFFFFFFFFu;
-constexpr unsigned QNAN_BITS = 0x7FC00000u;
 
-struct alignas(16) GroundTile {              // the members of TileXf the window test reads + the tile's ranges: 96 bytes per tile
-    float m[9], t[3], off[2], irow, icol;
-    long start, count;                       // point range in the concatenated buffer
-    long cbase;                              // workgroups of the tiles before this one (chunks of (a), block groups of (c))
+struct GroundTile : LmTileRange {            // cbase: chunks of (a), block groups of (c)
     long bbase;                              // 256-point blocks of the tiles before this one (c)
 };
-
-__device__ __forceinline__ unsigned key_of(float v) {
-    const unsigned b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b ^ 0x80000000u);
-}
-__device__ __forceinline__ float value_of(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
-
-// the tile of workgroup `wg`: the last t with cbase[t] <= wg (an empty tile shares its base with its successor and is never chosen)
-__device__ __forceinline__ int tile_of(const GroundTile* __restrict__ tiles, int B, long wg) {
-    int lo = 0, hi = B;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (tiles[mid].cbase <= wg) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
+static_assert(sizeof(GroundTile) == 96 && alignof(GroundTile) == 16, "96 bytes per tile: lm_*_workspace_bytes");
 
 // window test + finite height -> the point's cell; cdiv divides by cell_px
 __device__ __forceinline__ bool point_cell(const f32x4 p, const GroundTile& X, int H, int W, const LmFastDiv& cdiv, int Gx, int& cell,
@@ -79,35 +55,22 @@ __global__ __launch_bounds__(GT) void ground_min_kernel(const f32x4* __restrict_
                                                         unsigned* __restrict__ keys, int H, int W, LmFastDiv cdiv, int Gx, int ncell) {
     extern __shared__ unsigned cmin[];
     const int tid = threadIdx.x;
-    const int t = tile_of(tiles, B, (long)blockIdx.x);
+    const int t = lm_tile_of(tiles, B, (long)blockIdx.x);
     const GroundTile X = tiles[t];
     const long first = ((long)blockIdx.x - X.cbase) * GCHUNK;
     const long left = X.count - first;                          // >= 1
-    for (int i = tid; i < ncell; i += GT) cmin[i] = EMPTY;
+    for (int i = tid; i < ncell; i += GT) cmin[i] = LM_KEY_EMPTY;
     __syncthreads();
-    const f32x4* base = pts + X.start + first;
-#pragma unroll 1
-    for (int j0 = 0; j0 < G_PER_THREAD; j0 += LB) {
-        if ((long)j0 * GT >= left) break;                      // workgroup-uniform
-        f32x4 p[LB];
-#pragma unroll
-        for (int j = 0; j < LB; ++j) {
-            const long i = (long)(j0 + j) * GT + tid;
-            p[j] = __builtin_nontemporal_load(base + (i < left ? i : left - 1));   // unconditional, tail lanes masked below
-        }
-#pragma unroll
-        for (int j = 0; j < LB; ++j) {
-            const long i = (long)(j0 + j) * GT + tid;
-            int cell;
-            float vz;
-            if (i < left && point_cell(p[j], X, H, W, cdiv, Gx, cell, vz)) atomicMin(&cmin[cell], key_of(vz));
-        }
-    }
+    lm_stream_points<GT, G_PER_THREAD, LB>(pts + X.start + first, left, tid, [&](const f32x4 p, bool valid) {
+        int cell;
+        float vz;
+        if (valid && point_cell(p, X, H, W, cdiv, Gx, cell, vz)) atomicMin(&cmin[cell], lm_key_of(vz));
+    });
     __syncthreads();
     unsigned* dst = keys + (long)t * ncell;
     for (int i = tid; i < ncell; i += GT) {
         const unsigned k = cmin[i];
-        if (k != EMPTY) atomicMin(dst + i, k);
+        if (k != LM_KEY_EMPTY) atomicMin(dst + i, k);
     }
 }
 
@@ -118,9 +81,9 @@ __global__ __launch_bounds__(GT) void ground_smooth_kernel(const unsigned* __res
     const int tid = threadIdx.x, ncell = Gy * Gx;
     const long tile0 = (long)blockIdx.x * ncell;
     const unsigned* k = keys + tile0;
-    if (tid == 0) tmin = EMPTY;
+    if (tid == 0) tmin = LM_KEY_EMPTY;
     __syncthreads();
-    unsigned mine = EMPTY;
+    unsigned mine = LM_KEY_EMPTY;
     for (int c = tid; c < ncell; c += GT) {
         const int cy = c / Gx, cx = c - cy * Gx;
         unsigned v[9];
@@ -128,26 +91,26 @@ __global__ __launch_bounds__(GT) void ground_smooth_kernel(const unsigned* __res
 #pragma unroll
         for (int e = 0; e < 9; ++e) {
             const int y = cy + e / 3 - 1, x = cx + e % 3 - 1;
-            v[e] = (y >= 0 && y < Gy && x >= 0 && x < Gx) ? k[y * Gx + x] : EMPTY;
-            n += v[e] != EMPTY;
+            v[e] = (y >= 0 && y < Gy && x >= 0 && x < Gx) ? k[y * Gx + x] : LM_KEY_EMPTY;
+            n += v[e] != LM_KEY_EMPTY;
         }
         // the element of rank (n - 1) / 2; equal keys are ranked by their position, so exactly one element has each rank
         const int want = (n - 1) / 2;
-        unsigned res = EMPTY;
+        unsigned res = LM_KEY_EMPTY;
 #pragma unroll
         for (int e = 0; e < 9; ++e) {
             int rank = 0;
 #pragma unroll
             for (int f = 0; f < 9; ++f) rank += (v[f] < v[e]) || (f < e && v[f] == v[e]);
-            if (v[e] != EMPTY && rank == want) res = v[e];
+            if (v[e] != LM_KEY_EMPTY && rank == want) res = v[e];
         }
-        ground[tile0 + c] = __uint_as_float(res == EMPTY ? QNAN_BITS : __float_as_uint(value_of(res)));
-        if (cell_min) cell_min[tile0 + c] = __uint_as_float(k[c] == EMPTY ? QNAN_BITS : __float_as_uint(value_of(k[c])));
+        ground[tile0 + c] = __uint_as_float(res == LM_KEY_EMPTY ? LM_QNAN_BITS : __float_as_uint(lm_value_of(res)));
+        if (cell_min) cell_min[tile0 + c] = __uint_as_float(k[c] == LM_KEY_EMPTY ? LM_QNAN_BITS : __float_as_uint(lm_value_of(k[c])));
         mine = res < mine ? res : mine;
     }
-    if (mine != EMPTY) atomicMin(&tmin, mine);
+    if (mine != LM_KEY_EMPTY) atomicMin(&tmin, mine);
     __syncthreads();
-    if (tid == 0) ground_min[blockIdx.x] = tmin == EMPTY ? INFINITY : value_of(tmin);
+    if (tid == 0) ground_min[blockIdx.x] = tmin == LM_KEY_EMPTY ? INFINITY : lm_value_of(tmin);
 }
 
 // (c) grid: sum over tiles of ceil(count / SEL_CHUNK).  EMIT = false: counts[bbase + block] = kept points of the block;
@@ -158,7 +121,7 @@ __global__ __launch_bounds__(GT) void ground_select_kernel(const f32x4* __restri
                                                            float h_lo, float h_hi, unsigned* __restrict__ counts, f32x4* __restrict__ out) {
     __shared__ unsigned wcnt[SEL_GROUP][GT / 64];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int t = tile_of(tiles, B, (long)blockIdx.x);
+    const int t = lm_tile_of(tiles, B, (long)blockIdx.x);
     const GroundTile X = tiles[t];
     const long grp = (long)blockIdx.x - X.cbase;
     const long left = X.count - grp * SEL_CHUNK;                // >= 1
@@ -213,48 +176,31 @@ __global__ __launch_bounds__(GT) void ground_offsets_kernel(const unsigned* __re
     if (t == B) out_offsets[B] = (long)scanned[nblocks];
 }
 
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-long cdivl(long a, long b) { return (a + b - 1) / b; }
-
 }  // namespace
 
-// shared argument checks + the per-tile constants; per = points per workgroup (cbase), bbase in blocks of SEL_BLOCK
+// cell_px (named before the offsets are read), then the shared prologue; per = points per workgroup (cbase), bbase in blocks of SEL_BLOCK
 static int derive_tiles(const char* who, const long* tile_offsets, const LmRasterParams* params, int B, int H, int W, int cell_px, long per,
                         std::vector<GroundTile>& out, long* n_wg, long* n_blocks, long* n_points) {
-    LM_REQUIRE(B >= 1 && B <= MAX_B, "%s: B=%d tiles, 1 to %d are supported", who, B, MAX_B);
-    LM_REQUIRE(tile_offsets && params, "%s: null pointer (tile_offsets / params)", who);
-    LM_REQUIRE(H > 0 && W > 0, "%s: bad tile size H=%d W=%d", who, H, W);
     LM_REQUIRE(cell_px >= 8 && cell_px <= 128, "%s: cell_px=%d, 8 to 128 are supported", who, cell_px);
-    LM_REQUIRE(cdivl(H, cell_px) * cdivl(W, cell_px) <= MAX_CELLS, "%s: cell_px=%d gives %ld cells per tile, at most %d are supported", who,
-               cell_px, cdivl(H, cell_px) * cdivl(W, cell_px), MAX_CELLS);
-    LM_REQUIRE(tile_offsets[0] >= 0, "%s: tile_offsets[0] is negative", who);
-    out.resize((size_t)B);
-    long wg = 0, blocks = 0;
-    for (int b = 0; b < B; ++b) {
-        const long n = tile_offsets[b + 1] - tile_offsets[b];
-        LM_REQUIRE(n >= 0, "%s: tile_offsets must be non-decreasing (tile %d)", who, b);
-        LM_REQUIRE(params[b].img_reso[0] > 0 && params[b].img_reso[1] > 0, "%s: bad resolution (tile %d)", who, b);
-        TileXf X;
-        lm_raster_derive(params[b], tile_offsets[b], n, X);     // the rasteriser's own routine: the same float constants
-        GroundTile& T = out[(size_t)b];
-        for (int i = 0; i < 9; ++i) T.m[i] = X.m[i];
-        for (int i = 0; i < 3; ++i) T.t[i] = X.t[i];
-        T.off[0] = X.off[0], T.off[1] = X.off[1], T.irow = X.irow, T.icol = X.icol;
-        T.start = tile_offsets[b], T.count = n, T.cbase = wg, T.bbase = blocks;
-        wg += cdivl(n, per);
-        blocks += cdivl(n, SEL_BLOCK);
-    }
-    const long N = tile_offsets[B] - tile_offsets[0];
-    LM_REQUIRE(N <= 2147483647L, "%s: %ld points, at most 2^31 - 1 are supported", who, N);
-    *n_wg = wg, *n_blocks = blocks, *n_points = N;
+    LM_REQUIRE(lm_cdivl(H, cell_px) * lm_cdivl(W, cell_px) <= MAX_CELLS, "%s: cell_px=%d gives %ld cells per tile, at most %d are supported",
+               who, cell_px, lm_cdivl(H, cell_px) * lm_cdivl(W, cell_px), MAX_CELLS);
+    long blocks = 0;
+    const auto tile_blocks = [&](int, GroundTile& T, long&) -> int {
+        T.bbase = blocks;
+        blocks += lm_cdivl(T.count, SEL_BLOCK);
+        return LM_OK;
+    };
+    if (int e = lm_tile_ranges(who, tile_offsets, params, B, 1, H, W, per, out, n_wg, n_points, tile_blocks)) return e;
+    LM_REQUIRE(*n_points <= 2147483647L, "%s: %ld points, at most 2^31 - 1 are supported", who, *n_points);
+    *n_blocks = blocks;
     return LM_OK;
 }
 
 LM_API long lm_tile_ground_workspace_bytes(int B, int H, int W, int cell_px) {
-    if (B < 1 || B > MAX_B || H <= 0 || W <= 0 || cell_px < 8 || cell_px > 128) return 0;
-    const long ncell = cdivl(H, cell_px) * cdivl(W, cell_px);
+    if (B < 1 || B > LM_MAX_TILES || H <= 0 || W <= 0 || cell_px < 8 || cell_px > 128) return 0;
+    const long ncell = lm_cdivl(H, cell_px) * lm_cdivl(W, cell_px);
     if (ncell > MAX_CELLS) return 0;
-    return (long)(align256((size_t)B * sizeof(GroundTile)) + align256((size_t)B * ncell * 4));
+    return (long)(lm_align256((size_t)B * sizeof(GroundTile)) + lm_align256((size_t)B * ncell * 4));
 }
 
 // points: device [sum N][4]; tile_offsets: HOST [B+1]; params: HOST [B]; ground [B][Gy][Gx], ground_min [B], cell_min [B][Gy][Gx] or NULL:
@@ -265,15 +211,14 @@ LM_API int lm_tile_ground(void* hip_stream, const float* points_xyzi, const long
     long n_wg, n_blocks, N;
     if (int e = derive_tiles("tile_ground", tile_offsets, params, B, H, W, cell_px, GCHUNK, h_tiles, &n_wg, &n_blocks, &N)) return e;
     LM_REQUIRE(workspace && ground && ground_min, "tile_ground: null pointer (workspace / ground / ground_min)");
-    LM_REQUIRE(points_xyzi || N == 0, "tile_ground: null points");
-    LM_REQUIRE(((uintptr_t)points_xyzi & 15) == 0 && ((uintptr_t)workspace & 15) == 0, "tile_ground: points and workspace must be 16-byte aligned");
+    if (int e = lm_tile_points_check("tile_ground", points_xyzi, N, workspace)) return e;
     LM_REQUIRE(lm_tile_ground_workspace_bytes(B, H, W, cell_px) <= workspace_bytes, "tile_ground: workspace too small (%ld B needed)",
                lm_tile_ground_workspace_bytes(B, H, W, cell_px));
-    const int Gy = (int)cdivl(H, cell_px), Gx = (int)cdivl(W, cell_px), ncell = Gy * Gx;
+    const int Gy = (int)lm_cdivl(H, cell_px), Gx = (int)lm_cdivl(W, cell_px), ncell = Gy * Gx;
     hipStream_t s = (hipStream_t)hip_stream;
     char* w = (char*)workspace;
     GroundTile* d_tiles = (GroundTile*)w;
-    w += align256((size_t)B * sizeof(GroundTile));
+    w += lm_align256((size_t)B * sizeof(GroundTile));
     unsigned* keys = (unsigned*)w;
     LM_HIP(hipMemsetAsync(keys, 0xFF, (size_t)B * ncell * 4, s));
     if (n_wg > 0) {
@@ -290,9 +235,9 @@ LM_API int lm_tile_ground(void* hip_stream, const float* points_xyzi, const long
 }
 
 LM_API long lm_ground_select_workspace_bytes(long N, int B) {
-    if (N < 0 || N > 2147483647L || B < 1 || B > MAX_B) return 0;
+    if (N < 0 || N > 2147483647L || B < 1 || B > LM_MAX_TILES) return 0;
     const long L = N / SEL_BLOCK + B + 1;                       // at most this many blocks + the terminating entry
-    return (long)(align256((size_t)B * sizeof(GroundTile)) + align256((size_t)L * 4) + align256(lm_prim_scan_temp_bytes(L)));
+    return (long)(lm_align256((size_t)B * sizeof(GroundTile)) + lm_align256((size_t)L * 4) + lm_align256(lm_prim_scan_temp_bytes(L)));
 }
 
 // ground: device [B][Gy][Gx] (lm_tile_ground's, same H, W, cell_px); points_out: device [tile_offsets[B] - tile_offsets[0]][4];
@@ -313,16 +258,16 @@ LM_API int lm_ground_select(void* hip_stream, const float* points_xyzi, const lo
                "ground_select: points, points_out and workspace must be 16-byte aligned, out_offsets 8-byte");
     LM_REQUIRE(lm_ground_select_workspace_bytes(N, B) <= workspace_bytes, "ground_select: workspace too small (%ld B needed)",
                lm_ground_select_workspace_bytes(N, B));
-    const int Gx = (int)cdivl(W, cell_px), ncell = (int)cdivl(H, cell_px) * Gx;
+    const int Gx = (int)lm_cdivl(W, cell_px), ncell = (int)lm_cdivl(H, cell_px) * Gx;
     const long L = n_blocks + 1;                                // <= N / 256 + B + 1
     hipStream_t s = (hipStream_t)hip_stream;
     char* w = (char*)workspace;
     GroundTile* d_tiles = (GroundTile*)w;
-    w += align256((size_t)B * sizeof(GroundTile));
+    w += lm_align256((size_t)B * sizeof(GroundTile));
     unsigned* counts = (unsigned*)w;
-    w += align256((size_t)(N / SEL_BLOCK + B + 1) * 4);
+    w += lm_align256((size_t)(N / SEL_BLOCK + B + 1) * 4);
     void* scan_tmp = w;
-    const size_t scan_bytes = align256(lm_prim_scan_temp_bytes(N / SEL_BLOCK + B + 1));
+    const size_t scan_bytes = lm_align256(lm_prim_scan_temp_bytes(N / SEL_BLOCK + B + 1));
     const LmFastDiv cdiv = lm_fastdiv_make((unsigned)cell_px);
     const f32x4* pts = reinterpret_cast<const f32x4*>(points_xyzi);
     LM_HIP(hipMemcpyAsync(d_tiles, h_tiles.data(), (size_t)B * sizeof(GroundTile), hipMemcpyHostToDevice, s));

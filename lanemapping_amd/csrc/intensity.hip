@@ -1,16 +1,16 @@
 // Intensity window of the LAS routes: two order statistics (percentiles) of the intensities of the points a tile, or a group of tiles,
 // keeps, out of the points already binned for the rasteriser.  Input is the (points, tile_offsets, params) triple lm_bev_raster_batch
-// takes; membership is the rasteriser's own window test, lm_point_window (raster_xf.h), on constants from the rasteriser's own host
-// routine (lm_raster_derive).  A point counts for tile b exactly when raster.hip would keep it for b and its intensity is not NaN.
+// takes, walked with the scaffold of tile_points.h (tile constants, workgroup -> tile, streaming loop, host prologue).  A point counts
+// for tile b exactly when raster.hip would keep it for b and its intensity is not NaN.
 //
 // Key of a point: k = (int)floorf(fminf(fmaxf(i, 0), 65535)), 0 .. 65535 (LAS intensities are u16: the key is the intensity).  With n
 // counted points in group g, window[g][0] is the key of 0-based rank (n - 1) q_lo_ppm / 1,000,000 (64-bit floor division) in ascending
 // order, window[g][1] the same with q_hi_ppm: lower order statistics, values that occur in the data.  n = 0: (-1, -1).
 //
 // Exact in two levels of 4096 x 16 keys, all counters integers added with integer atomics (order independent: the same bits on every run):
-//   (a) coarse   a workgroup streams a span of ICPW chunks of ICHUNK = 16,384 points of one tile (256 lanes x 64 coalesced 16-byte
-//                non-temporal loads per chunk, 8 in flight per lane; the loop of ground_min_kernel), counts k >> 4 in 4096 LDS counters
-//                and flushes its non-zero counters to hist[group][4096].
+//   (a) coarse   a workgroup streams a span of ICPW chunks of ICHUNK = 16,384 points of one tile (lm_stream_points: 256 lanes x 64 loads
+//                per chunk, 8 in flight per lane), counts k >> 4 in 4096 LDS counters and flushes its non-zero counters to
+//                hist[group][4096].
 //   (b) locate   one workgroup per group: n, the two ranks, the coarse bin each rank falls into and the rank left inside that bin.
 //   (c) fine     the same stream again; a point whose k >> 4 is one of its group's two located bins counts k & 15 in 2 x 16 LDS
 //                counters, flushed to fine[group][2][16].  The predicate and the bytes are those of (a), so the 16 counters of a located
@@ -18,10 +18,9 @@
 //   (d) resolve  one thread per group walks the 16 counters: window, count.
 // Same-address LDS atomics: a saturated scanner puts a large share of a wave's 64 points on one key.  wave_count() first lets the
 // lowest active lane add the number of lanes that share its counter (two such rounds), only the rest add one each.
-// Workgroup -> (tile, span) is the binary search of ground.hip over a per-tile prefix kept with the tile constants in a device buffer
-// (B up to 4096, any mix of tile sizes, one launch).  HBM traffic: 16 N read in (a) and in (c).  No host synchronisation, no scratch.
+// HBM traffic: 16 N read in (a) and in (c).  No host synchronisation, no scratch.
 #include "common.h"
-#include "raster_xf.h"
+#include "tile_points.h"
 
 #include <cmath>
 #include <vector>
@@ -35,31 +34,17 @@ constexpr int ICPW = 4;                      // chunks per workgroup: one flush 
 constexpr long ISPAN = (long)ICHUNK * ICPW;
 constexpr int LB = 8;                        // loads in flight per lane
 constexpr int NBIN = 4096;                   // coarse bins of 16 keys
-constexpr int MAX_B = 4096;
 constexpr unsigned NO_BIN = 0xFFFFFFFFu;     // no key has this coarse bin
 
-struct alignas(16) IntenTile {               // the members of TileXf the window test reads + the tile's range and group: 96 bytes per tile
-    float m[9], t[3], off[2], irow, icol;
-    long start, count;                       // point range in the concatenated buffer
-    long cbase;                              // workgroups of the tiles before this one
+struct IntenTile : LmTileRange {
     int group, pad;
 };
+static_assert(sizeof(IntenTile) == 96 && alignof(IntenTile) == 16, "96 bytes per tile: lm_tile_intensity_workspace_bytes");
 
 struct Located {                             // per group, written by (b)
     unsigned bin[2];                         // coarse bin of the lower / upper rank, NO_BIN for an empty group
     unsigned rem[2];                         // rank inside that bin
 };
-
-// the tile of workgroup `wg`: the last t with cbase[t] <= wg (an empty tile shares its base with its successor and is never chosen)
-__device__ __forceinline__ int tile_of(const IntenTile* __restrict__ tiles, int B, long wg) {
-    int lo = 0, hi = B;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (tiles[mid].cbase <= wg) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
 
 // window test + intensity not NaN -> the key
 __device__ __forceinline__ bool point_key(const f32x4 p, const IntenTile& X, int H, int W, int& key) {
@@ -94,7 +79,7 @@ __global__ __launch_bounds__(IT) void inten_count_kernel(const f32x4* __restrict
     __shared__ unsigned cnt[FINE ? 32 : NBIN];
     constexpr int NC = FINE ? 32 : NBIN;
     const int tid = threadIdx.x;
-    const int t = tile_of(tiles, B, (long)blockIdx.x);
+    const int t = lm_tile_of(tiles, B, (long)blockIdx.x);
     const IntenTile X = tiles[t];
     const long first = ((long)blockIdx.x - X.cbase) * ISPAN;
     const long rest = X.count - first;                          // >= 1
@@ -106,30 +91,17 @@ __global__ __launch_bounds__(IT) void inten_count_kernel(const f32x4* __restrict
     }
     for (int i = tid; i < NC; i += IT) cnt[i] = 0;
     __syncthreads();
-    const f32x4* base = pts + X.start + first;
-#pragma unroll 1
-    for (int j0 = 0; j0 < I_PER_THREAD * ICPW; j0 += LB) {
-        if ((long)j0 * IT >= left) break;                      // workgroup-uniform
-        f32x4 p[LB];
-#pragma unroll
-        for (int j = 0; j < LB; ++j) {
-            const long i = (long)(j0 + j) * IT + tid;
-            p[j] = __builtin_nontemporal_load(base + (i < left ? i : left - 1));   // unconditional, tail lanes masked below
+    lm_stream_points<IT, I_PER_THREAD * ICPW, LB>(pts + X.start + first, left, tid, [&](const f32x4 p, bool valid) {
+        int key = 0;
+        const bool on = valid && point_key(p, X, H, W, key);   // (no early return: wave_count is wave-collective)
+        const unsigned bin = (unsigned)key >> 4;
+        if (!FINE) {
+            wave_count(cnt, (int)bin, on);
+        } else {
+            wave_count(cnt, key & 15, on && bin == bin_lo);
+            wave_count(cnt + 16, key & 15, on && bin == bin_hi);
         }
-#pragma unroll
-        for (int j = 0; j < LB; ++j) {
-            const long i = (long)(j0 + j) * IT + tid;
-            int key = 0;
-            const bool on = i < left && point_key(p[j], X, H, W, key);
-            const unsigned bin = (unsigned)key >> 4;
-            if (!FINE) {
-                wave_count(cnt, (int)bin, on);
-            } else {
-                wave_count(cnt, key & 15, on && bin == bin_lo);
-                wave_count(cnt + 16, key & 15, on && bin == bin_hi);
-            }
-        }
-    }
+    });
     __syncthreads();
     unsigned* dst = out + (long)X.group * NC;
     for (int i = tid; i < NC; i += IT) {
@@ -207,14 +179,12 @@ __global__ __launch_bounds__(IT) void inten_resolve_kernel(const unsigned* __res
     }
 }
 
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
 }  // namespace
 
 LM_API long lm_tile_intensity_workspace_bytes(int B, int G) {
-    if (B < 1 || B > MAX_B || G < 1 || G > B) return 0;
-    return (long)(align256((size_t)B * sizeof(IntenTile)) + align256((size_t)G * NBIN * 4) + align256((size_t)G * sizeof(Located)) +
-                  align256((size_t)G * 32 * 4));
+    if (B < 1 || B > LM_MAX_TILES || G < 1 || G > B) return 0;
+    return (long)(lm_align256((size_t)B * sizeof(IntenTile)) + lm_align256((size_t)G * NBIN * 4) + lm_align256((size_t)G * sizeof(Located)) +
+                  lm_align256((size_t)G * 32 * 4));
 }
 
 // points: device [sum N][4]; tile_offsets: HOST [B+1]; params: HOST [B]; group: HOST [B] or NULL; window [G][2] int32, count [G] int64,
@@ -223,38 +193,23 @@ LM_API int lm_tile_intensity_window(void* hip_stream, const float* points_xyzi, 
                                     int H, int W, const int* group, int G, int q_lo_ppm, int q_hi_ppm, void* workspace,
                                     long workspace_bytes, int* window, long* count, unsigned* coarse_hist) {
     static thread_local std::vector<IntenTile> h_tiles;
-    LM_REQUIRE(B >= 1 && B <= MAX_B, "tile_intensity_window: B=%d tiles, 1 to %d are supported", B, MAX_B);
+    LM_REQUIRE(B >= 1 && B <= LM_MAX_TILES, "tile_intensity_window: B=%d tiles, 1 to %d are supported", B, LM_MAX_TILES);   // G is judged against it
     LM_REQUIRE(G >= 1 && G <= B, "tile_intensity_window: G=%d groups, 1 to B=%d are supported", G, B);
     LM_REQUIRE(group || G == B, "tile_intensity_window: group is null (tile b is group b), so G=%d must equal B=%d", G, B);
-    LM_REQUIRE(tile_offsets && params, "tile_intensity_window: null pointer (tile_offsets / params)");
     LM_REQUIRE(workspace && window && count, "tile_intensity_window: null pointer (workspace / window / count)");
-    LM_REQUIRE(H > 0 && W > 0, "tile_intensity_window: bad tile size H=%d W=%d", H, W);
     LM_REQUIRE(q_lo_ppm >= 0 && q_lo_ppm <= 1000000, "tile_intensity_window: q_lo_ppm=%d is outside 0..1000000", q_lo_ppm);
     LM_REQUIRE(q_hi_ppm >= 0 && q_hi_ppm <= 1000000, "tile_intensity_window: q_hi_ppm=%d is outside 0..1000000", q_hi_ppm);
     LM_REQUIRE(q_lo_ppm <= q_hi_ppm, "tile_intensity_window: q_lo_ppm=%d > q_hi_ppm=%d", q_lo_ppm, q_hi_ppm);
-    LM_REQUIRE(tile_offsets[0] >= 0, "tile_intensity_window: tile_offsets[0] is negative");
-    h_tiles.resize((size_t)B);
-    long n_wg = 0;
-    for (int b = 0; b < B; ++b) {
-        const long n = tile_offsets[b + 1] - tile_offsets[b];
-        LM_REQUIRE(n >= 0, "tile_intensity_window: tile_offsets must be non-decreasing (tile %d)", b);
-        LM_REQUIRE(params[b].img_reso[0] > 0 && params[b].img_reso[1] > 0, "tile_intensity_window: bad resolution (tile %d)", b);
+    long n_wg, N;
+    const auto tile_group = [&](int b, IntenTile& T, long&) -> int {
         const int g = group ? group[b] : b;
         LM_REQUIRE(g >= 0 && g < G, "tile_intensity_window: group[%d]=%d is outside 0..G-1=%d", b, g, G - 1);
-        TileXf X;
-        lm_raster_derive(params[b], tile_offsets[b], n, X);     // the rasteriser's own routine: the same float constants
-        IntenTile& T = h_tiles[(size_t)b];
-        for (int i = 0; i < 9; ++i) T.m[i] = X.m[i];
-        for (int i = 0; i < 3; ++i) T.t[i] = X.t[i];
-        T.off[0] = X.off[0], T.off[1] = X.off[1], T.irow = X.irow, T.icol = X.icol;
-        T.start = tile_offsets[b], T.count = n, T.cbase = n_wg, T.group = g, T.pad = 0;
-        n_wg += (n + ISPAN - 1) / ISPAN;
-    }
-    const long N = tile_offsets[B] - tile_offsets[0];
+        T.group = g, T.pad = 0;
+        return LM_OK;
+    };
+    if (int e = lm_tile_ranges("tile_intensity_window", tile_offsets, params, B, 1, H, W, ISPAN, h_tiles, &n_wg, &N, tile_group)) return e;
     LM_REQUIRE(N < 4294967296L, "tile_intensity_window: tile_offsets span %ld points, fewer than 2^32 are supported (32-bit counters)", N);
-    LM_REQUIRE(points_xyzi || N == 0, "tile_intensity_window: null points");
-    LM_REQUIRE(((uintptr_t)points_xyzi & 15) == 0 && ((uintptr_t)workspace & 15) == 0,
-               "tile_intensity_window: points and workspace must be 16-byte aligned");
+    if (int e = lm_tile_points_check("tile_intensity_window", points_xyzi, N, workspace)) return e;
     LM_REQUIRE(((uintptr_t)window & 3) == 0 && ((uintptr_t)count & 7) == 0 && ((uintptr_t)coarse_hist & 3) == 0,
                "tile_intensity_window: window and coarse_hist must be 4-byte aligned, count 8-byte");
     LM_REQUIRE(lm_tile_intensity_workspace_bytes(B, G) <= workspace_bytes, "tile_intensity_window: workspace too small (%ld B needed)",
@@ -262,11 +217,11 @@ LM_API int lm_tile_intensity_window(void* hip_stream, const float* points_xyzi, 
     hipStream_t s = (hipStream_t)hip_stream;
     char* w = (char*)workspace;
     IntenTile* d_tiles = (IntenTile*)w;
-    w += align256((size_t)B * sizeof(IntenTile));
+    w += lm_align256((size_t)B * sizeof(IntenTile));
     unsigned* hist = coarse_hist ? coarse_hist : (unsigned*)w;  // the caller's histogram is the one the passes count into
-    w += align256((size_t)G * NBIN * 4);
+    w += lm_align256((size_t)G * NBIN * 4);
     Located* loc = (Located*)w;
-    w += align256((size_t)G * sizeof(Located));
+    w += lm_align256((size_t)G * sizeof(Located));
     unsigned* fine = (unsigned*)w;
     const f32x4* pts = reinterpret_cast<const f32x4*>(points_xyzi);
     LM_HIP(hipMemsetAsync(hist, 0, (size_t)G * NBIN * 4, s));

@@ -268,8 +268,6 @@ __global__ __launch_bounds__(256) void bicubic_kernel(const float* __restrict__ 
     *reinterpret_cast<float4*>(y + (((long)b * Ho + oy) * Wo + ox) * C + c4 * 4) = acc;
 }
 
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
 size_t sort_temp_bytes(long n) { return lm_prim_sort_temp_bytes(n); }       // (prim.hip: the library's own radix sort and scan)
 size_t scan_temp_bytes(long n) { return lm_prim_scan_temp_bytes(n); }
 
@@ -278,7 +276,7 @@ size_t scan_temp_bytes(long n) { return lm_prim_scan_temp_bytes(n); }
 LM_API long lm_voxelize_workspace_bytes(long n_points) {
     const long n = n_points > 0 ? n_points : 1;
     const size_t t1 = sort_temp_bytes(n), t2 = scan_temp_bytes(n);
-    return (long)(8 * align256((size_t)n * 4) + align256(t1 > t2 ? t1 : t2));
+    return (long)(8 * lm_align256((size_t)n * 4) + lm_align256(t1 > t2 ? t1 : t2));
 }
 
 // points [n,4] f32 (x, y, z, intensity) of ONE sample -> rows [*row_base, *row_end) of feats [cap_rows, ldf] (mean of the
@@ -310,7 +308,7 @@ LM_API int lm_voxelize_hard(void* stream, const float* points, long n, const flo
         G.g[a] = grid_xyz[a];
         LM_REQUIRE(G.vs[a] > 0.f, "voxelize: voxel size must be positive");
     }
-    const size_t seg = align256((size_t)n * 4);
+    const size_t seg = lm_align256((size_t)n * 4);
     char* w = (char*)workspace;
     unsigned *keys_in = (unsigned*)w, *keys_out = (unsigned*)(w + seg), *vals_in = (unsigned*)(w + 2 * seg),
              *vals_out = (unsigned*)(w + 3 * seg), *flags = (unsigned*)(w + 4 * seg), *rank = (unsigned*)(w + 5 * seg);
@@ -367,7 +365,7 @@ LM_API int lm_sparse_grid_build(void* stream, const int* coords, long n, int* gr
 
 LM_API long lm_sparse_conv_outputs_workspace_bytes(long out_cells) {
     const long n = out_cells > 0 ? out_cells : 1;
-    return (long)(2 * align256((size_t)n * 4) + align256(scan_temp_bytes(n)));
+    return (long)(2 * lm_align256((size_t)n * 4) + lm_align256(scan_temp_bytes(n)));
 }
 
 // Active output sites of a SparseConv3d (kernel / stride / padding in z, y, x order) over the input rows `in_coords`:
@@ -386,7 +384,7 @@ LM_API int lm_sparse_conv_outputs(void* stream, const int* in_coords, long n_in,
         cv.p[a] = ksp_zyx9[6 + a];
         LM_REQUIRE(cv.k[a] >= 1 && cv.s[a] >= 1 && cv.p[a] >= 0, "sparse_conv_outputs: bad kernel geometry");
     }
-    const size_t seg = align256((size_t)cells * 4);
+    const size_t seg = lm_align256((size_t)cells * 4);
     char* w = (char*)workspace;
     int *flags = (int*)w, *ids = (int*)(w + seg);
     void* temp = w + 2 * seg;
@@ -698,7 +696,7 @@ struct LmLasSelect {          // include/lanemap_hip.h
 LM_API long lm_las_select_workspace_bytes(long n) {
     if (n < 0 || n > 2147483647L) return 0;
     const long L = sel_blocks(n) + 1;
-    return (long)(align256((size_t)L * 4) + align256(scan_temp_bytes(L)) + align256((size_t)256 * (n ? sel_groups(n) : 1) * 4));
+    return (long)(lm_align256((size_t)L * 4) + lm_align256(scan_temp_bytes(L)) + lm_align256((size_t)256 * (n ? sel_groups(n) : 1) * 4));
 }
 
 // lm_las_decode_points restricted to the records that pass `select`: out_xyzi[0 .. *kept) = the rows the plain decode writes for them,
@@ -737,9 +735,9 @@ LM_API int lm_las_decode_select(void* hip_stream, const unsigned char* records, 
     const int groups = (int)sel_groups(n);
     char* w = (char*)workspace;
     unsigned* counts = (unsigned*)w;
-    w += align256((size_t)L * 4);
+    w += lm_align256((size_t)L * 4);
     void* scan_tmp = w;
-    const size_t scan_bytes = align256(scan_temp_bytes(L));
+    const size_t scan_bytes = lm_align256(scan_temp_bytes(L));
     w += scan_bytes;
     unsigned* hist_part = class_hist ? (unsigned*)w : nullptr;
     const size_t lds = ((size_t)256 * record_len + 3) / 4 * 4;

@@ -104,8 +104,6 @@ __global__ __launch_bounds__(256) void scan_tile_kernel(const unsigned* __restri
     }
 }
 
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
 // ---------------------------------------------------------------------------------------------------------------- radix sort
 __global__ __launch_bounds__(256) void sort_hist_kernel(const unsigned* __restrict__ keys, long n, int shift, unsigned mask, unsigned nblocks,
                                                         unsigned* __restrict__ hist) {
@@ -194,7 +192,7 @@ __global__ __launch_bounds__(256) void sort_scatter_kernel(const unsigned* __res
 
 size_t lm_prim_scan_temp_bytes(long n) {
     size_t b = 0;
-    for (long m = (n + TILE - 1) / TILE; m > 1; m = (m + TILE - 1) / TILE) b += align256((size_t)m * 4);
+    for (long m = (n + TILE - 1) / TILE; m > 1; m = (m + TILE - 1) / TILE) b += lm_align256((size_t)m * 4);
     return b + 256;
 }
 
@@ -211,7 +209,7 @@ int lm_prim_exclusive_scan_u32(hipStream_t s, const unsigned* in, unsigned* out,
     unsigned* sums = (unsigned*)temp;
     hipLaunchKernelGGL(scan_tile_sums_kernel, dim3((unsigned)nb), dim3(256), 0, s, in, n, sums);
     LM_LAUNCH_CHECK();
-    const size_t used = align256((size_t)nb * 4);
+    const size_t used = lm_align256((size_t)nb * 4);
     const int rc = lm_prim_exclusive_scan_u32(s, sums, sums, nb, (char*)temp + used, temp_bytes - used);      // (depth <= 3)
     if (rc != LM_OK) return rc;
     hipLaunchKernelGGL(scan_tile_kernel, dim3((unsigned)nb), dim3(256), 0, s, in, out, n, (const unsigned*)sums);
@@ -221,7 +219,7 @@ int lm_prim_exclusive_scan_u32(hipStream_t s, const unsigned* in, unsigned* out,
 
 size_t lm_prim_sort_temp_bytes(long n) {
     const long nb = (n + TILE - 1) / TILE;
-    return align256((size_t)(nb > 0 ? nb : 1) * 256 * 4) + lm_prim_scan_temp_bytes((nb > 0 ? nb : 1) * 256);
+    return lm_align256((size_t)(nb > 0 ? nb : 1) * 256 * 4) + lm_prim_scan_temp_bytes((nb > 0 ? nb : 1) * 256);
 }
 
 int lm_prim_sort_pairs_u32(hipStream_t s, unsigned* keys, unsigned* keys_alt, unsigned* vals, unsigned* vals_alt, long n, int end_bit,
@@ -234,7 +232,7 @@ int lm_prim_sort_pairs_u32(hipStream_t s, unsigned* keys, unsigned* keys_alt, un
     LM_REQUIRE(lm_prim_sort_temp_bytes(n) <= temp_bytes, "sort_pairs: scratch too small");
     const unsigned nb = (unsigned)((n + TILE - 1) / TILE);
     unsigned* hist = (unsigned*)temp;
-    const size_t hbytes = align256((size_t)nb * 256 * 4);
+    const size_t hbytes = lm_align256((size_t)nb * 256 * 4);
     unsigned *ki = keys, *ko = keys_alt, *vi = vals, *vo = vals_alt;
     for (int shift = 0; shift < end_bit; shift += 8) {
         // the last pass only looks at the bits below end_bit: keys may carry payload above it ([begin, end) semantics of the contract)
@@ -261,7 +259,7 @@ LM_API int lm_exclusive_scan_u32(void* stream, const unsigned* in, unsigned* out
     return lm_prim_exclusive_scan_u32((hipStream_t)stream, in, out, n, workspace, (size_t)workspace_bytes);
 }
 
-LM_API long lm_sort_pairs_workspace_bytes(long n) { return (long)(lm_prim_sort_temp_bytes(n > 0 ? n : 1) + 2 * align256((size_t)(n > 0 ? n : 1) * 4)); }
+LM_API long lm_sort_pairs_workspace_bytes(long n) { return (long)(lm_prim_sort_temp_bytes(n > 0 ? n : 1) + 2 * lm_align256((size_t)(n > 0 ? n : 1) * 4)); }
 
 // Stable sort of (key, value) pairs by the low end_bit bits of the keys; keys_io / vals_io are sorted in place (device pointers).
 LM_API int lm_sort_pairs_u32(void* stream, unsigned* keys_io, unsigned* vals_io, long n, int end_bit, void* workspace, long workspace_bytes) {
@@ -269,7 +267,7 @@ LM_API int lm_sort_pairs_u32(void* stream, unsigned* keys_io, unsigned* vals_io,
                lm_sort_pairs_workspace_bytes(n));
     if (n == 0) return LM_OK;
     LM_REQUIRE(workspace, "sort_pairs: null workspace");
-    const size_t seg = align256((size_t)n * 4);
+    const size_t seg = lm_align256((size_t)n * 4);
     char* w = (char*)workspace;
     unsigned *ka = (unsigned*)w, *va = (unsigned*)(w + seg), *kr = nullptr, *vr = nullptr;
     const int rc = lm_prim_sort_pairs_u32((hipStream_t)stream, keys_io, ka, vals_io, va, n, end_bit, w + 2 * seg, (size_t)workspace_bytes - 2 * seg,

@@ -1,5 +1,5 @@
-// Per-tile constants of the LAS -> BEV rule and its window test, shared by the rasteriser (raster.hip) and the strip binning (strip.hip):
-// a point belongs to a tile exactly when lm_point_window() says so, in both files, bit for bit.  Both are compiled with
+// Per-tile constants of the LAS -> BEV rule and its window test, shared by the rasteriser (raster.hip), the strip binning (strip.hip) and
+// the point-range kernels (tile_points.h): a point belongs to a tile exactly when lm_point_window() says so, in all of them, bit for bit.  All are compiled with
 // -ffp-contract=off (build.py EXACT_FP): the expressions below are evaluated as written.
 #pragma once
 #include "common.h"
@@ -24,7 +24,7 @@ struct TileXf {                        // derived per-tile constants (host, doub
 };
 
 // The window test: v = M (p - t), row / col by floor(x + .5), unsigned compare against H and W.  XF = TileXf or any struct with its
-// m, t, off, irow, icol members (the binning keeps only those, 64 bytes per tile, in a device buffer).
+// m, t, off, irow, icol members (LmWindowXf of tile_points.h keeps only those, 64 bytes per tile, in a device buffer).
 template <class XF>
 __device__ __forceinline__ bool lm_point_window(const f32x4 p, const XF& X, int H, int W, int& row, int& col, float& vz) {
     const float dx = p[0] - X.t[0], dy = p[1] - X.t[1], dz = p[2] - X.t[2];

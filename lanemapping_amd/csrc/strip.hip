@@ -20,7 +20,7 @@
 // HBM traffic = 16 N (count) + 16 N (scatter) + 16 sum(counts) + table; the per-wave table rows cost 4 T bytes per 32 KB of points.
 #include "common.h"
 #include "prim.h"
-#include "raster_xf.h"
+#include "tile_points.h"
 
 #include <cfloat>
 #include <cmath>
@@ -45,10 +45,6 @@ constexpr unsigned NO_TILE = 0xFFFFu;
 constexpr int MAX_T = 4096;
 constexpr long MAX_CELLS = 1L << 18;
 constexpr unsigned UNSET = 0xFFFFFFFFu;  // scatter cursor not yet read from the table (a real rank is < 2^31)
-
-struct alignas(16) StripXf {             // the members of TileXf the window test reads: 64 bytes per tile in a device buffer
-    float m[9], t[3], off[2], irow, icol;
-};
 
 struct GridDev {
     float x0, y0, inv, zlo, zhi;
@@ -79,7 +75,7 @@ struct WaveCtx {
 
 // grid: ceil(nwc / 4) workgroups; dynamic LDS = 4 * T words
 template <bool SCATTER>
-__global__ __launch_bounds__(SW) void strip_pass_kernel(const f32x4* __restrict__ pts, long N, const StripXf* __restrict__ xf, int T,
+__global__ __launch_bounds__(SW) void strip_pass_kernel(const f32x4* __restrict__ pts, long N, const LmWindowXf* __restrict__ xf, int T,
                                                         const u32x4* __restrict__ cells, GridDev G, int H, int W, unsigned* table, long nwc,
                                                         const long* __restrict__ offsets, f32x4* __restrict__ binned) {
     extern __shared__ unsigned strip_lds[];
@@ -185,7 +181,6 @@ __global__ __launch_bounds__(256) void strip_offsets_kernel(const unsigned* __re
     }
 }
 
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 long nwc_of(long N) { return (N + WCHUNK - 1) / WCHUNK; }
 
 struct Footprint {                       // one tile on the host, in double, from the float constants the device uses
@@ -328,8 +323,8 @@ LM_API int lm_strip_build_grid(const LmRasterParams* params, int T, int H, int W
 LM_API long lm_strip_bin_workspace_bytes(long N, int T) {
     if (N < 0 || T < 1 || T > MAX_T) return 0;
     const long L = (long)T * nwc_of(N) + 1;
-    return (long)(align256((size_t)T * sizeof(StripXf)) + align256((size_t)MAX_CELLS * CELL_CAP * 2) + align256((size_t)L * 4) +
-                  align256(lm_prim_scan_temp_bytes(L)));
+    return (long)(lm_align256((size_t)T * sizeof(LmWindowXf)) + lm_align256((size_t)MAX_CELLS * CELL_CAP * 2) + lm_align256((size_t)L * 4) +
+                  lm_align256(lm_prim_scan_temp_bytes(L)));
 }
 
 // points: device [N][4]; params: HOST [T]; counts [T], offsets [T+1]: device int64; offsets_host: HOST [T+1] (may be NULL);
@@ -345,31 +340,24 @@ LM_API int lm_strip_bin_points(void* hip_stream, const float* points_xyzi, long 
     LM_REQUIRE(lm_strip_bin_workspace_bytes(N, T) <= workspace_bytes, "strip_bin: workspace too small (%ld B needed)",
                lm_strip_bin_workspace_bytes(N, T));
     static thread_local std::vector<unsigned short> h_cells;
-    static thread_local std::vector<StripXf> h_xf;
+    static thread_local std::vector<LmWindowXf> h_xf;
     static thread_local std::vector<long> h_off;
     LmStripGrid grid;
     if (int e = build_grid(params, T, H, W, z_lo, z_hi, &grid, h_cells)) return e;
     const long ncell = (long)grid.nx * grid.ny;
     h_xf.resize((size_t)T);
-    for (int t = 0; t < T; ++t) {
-        TileXf X;
-        lm_raster_derive(params[t], 0, 0, X);                  // the rasteriser's own routine: the same float constants
-        StripXf& S = h_xf[(size_t)t];
-        for (int i = 0; i < 9; ++i) S.m[i] = X.m[i];
-        for (int i = 0; i < 3; ++i) S.t[i] = X.t[i];
-        S.off[0] = X.off[0], S.off[1] = X.off[1], S.irow = X.irow, S.icol = X.icol;
-    }
+    for (int t = 0; t < T; ++t) lm_window_xf(params[t], h_xf[(size_t)t]);
     hipStream_t s = (hipStream_t)hip_stream;
     const long nwc = nwc_of(N), L = (long)T * nwc + 1;
     char* w = (char*)workspace;
-    StripXf* d_xf = (StripXf*)w;
-    w += align256((size_t)T * sizeof(StripXf));
+    LmWindowXf* d_xf = (LmWindowXf*)w;
+    w += lm_align256((size_t)T * sizeof(LmWindowXf));
     u32x4* d_cells = (u32x4*)w;
-    w += align256((size_t)MAX_CELLS * CELL_CAP * 2);
+    w += lm_align256((size_t)MAX_CELLS * CELL_CAP * 2);
     unsigned* table = (unsigned*)w;
-    w += align256((size_t)L * 4);
+    w += lm_align256((size_t)L * 4);
     void* scan_tmp = w;
-    const size_t scan_bytes = align256(lm_prim_scan_temp_bytes(L));
+    const size_t scan_bytes = lm_align256(lm_prim_scan_temp_bytes(L));
     GridDev G;
     G.x0 = (float)grid.x0, G.y0 = (float)grid.y0, G.inv = (float)(1.0 / grid.cell);
     G.zlo = (float)z_lo, G.zhi = (float)z_hi;
@@ -380,7 +368,7 @@ LM_API int lm_strip_bin_points(void* hip_stream, const float* points_xyzi, long 
     const size_t lds = (size_t)WAVES * T * sizeof(unsigned);
     const unsigned nblk = (unsigned)((nwc + WAVES - 1) / WAVES);
     if (N > 0) {
-        LM_HIP(hipMemcpyAsync(d_xf, h_xf.data(), (size_t)T * sizeof(StripXf), hipMemcpyHostToDevice, s));
+        LM_HIP(hipMemcpyAsync(d_xf, h_xf.data(), (size_t)T * sizeof(LmWindowXf), hipMemcpyHostToDevice, s));
         LM_HIP(hipMemcpyAsync(d_cells, h_cells.data(), (size_t)ncell * CELL_CAP * 2, hipMemcpyHostToDevice, s));
         if (int e = lm_ensure_dynamic_lds((const void*)strip_pass_kernel<false>, lds)) return e;
         if (int e = lm_ensure_dynamic_lds((const void*)strip_pass_kernel<true>, lds)) return e;

@@ -641,6 +641,29 @@ def make_raster_params(quat=(1, 0, 0, 0), trans=(0, 0, 0), bev_img_offset=(0, 0)
 _raster_ws = {}
 
 
+def _workspace(points, need):
+    """The scratch buffer of the raster section: one per (device, stream), grown and never shrunk."""
+    key = (points.device, _stream().value)
+    ws = _raster_ws.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _raster_ws[key] = torch.empty(need, device=points.device, dtype=torch.uint8)
+    return ws
+
+
+def _tile_range_args(who, points, tile_offsets, params):
+    """The (points, tile_offsets, params) triple of bev_raster_batch, checked -> (B, offsets as C longs, params as a C array)."""
+    if not points.is_cuda:
+        _ptr(points)
+    assert points.dim() == 2 and points.shape[1] == 4 and points.is_contiguous() and points.dtype == torch.float32
+    B = len(params)
+    if len(tile_offsets) != B + 1:
+        raise ValueError(f'{who}: {len(tile_offsets)} tile_offsets for {B} tiles (B + 1 are needed)')
+    offs = (C.c_long * (B + 1))(*[int(o) for o in tile_offsets])
+    if B and offs[B] > points.shape[0]:
+        raise ValueError(f'{who}: tile_offsets end at {offs[B]}, points has {points.shape[0]} rows')
+    return B, offs, (LmRasterParams * B)(*params)
+
+
 def bev_raster_batch(points, tile_offsets, params, H=1152, W=1152, out=None, want_u8=False, u8_only=False, out_u8=None, inten_scale=None):
     """points [sum N,4] f32 (x,y,z,raw intensity) on device, tile_offsets: B+1 ints, params: list of LmRasterParams
     -> proj [B,3,H,W] f32 (= u8/255), optional u8 [B,H,W,3].  u8_only: only the u8 HWC tile is written (the stem takes it
@@ -653,11 +676,7 @@ def bev_raster_batch(points, tile_offsets, params, H=1152, W=1152, out=None, wan
     offs = (C.c_long * (B + 1))(*[int(o) for o in tile_offsets])
     par = (LmRasterParams * B)(*params)
     cap = max([offs[b + 1] - offs[b] for b in range(B)] + [0])
-    need = lib().lm_bev_raster_workspace_bytes(B, cap, H, W)
-    key = (points.device, _stream().value)
-    ws = _raster_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _raster_ws[key] = torch.empty(need, device=points.device, dtype=torch.uint8)
+    ws = _workspace(points, lib().lm_bev_raster_workspace_bytes(B, cap, H, W))
     want_u8 = want_u8 or u8_only or out_u8 is not None
     if out is None and not u8_only:
         out = torch.empty((B, 3, H, W), device=points.device, dtype=torch.float32)
@@ -727,10 +746,7 @@ def strip_bin_points(points, params, H=1152, W=1152, z_range=None, capacity=None
     need = lib().lm_strip_bin_workspace_bytes(N, T)
     if need <= 0:
         raise LanemapHipError(f'strip_bin_points: {T} tiles / {N} points are not supported (1 to 4096 tiles)')
-    key = (points.device, _stream().value)
-    ws = _raster_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _raster_ws[key] = torch.empty(need, device=points.device, dtype=torch.uint8)
+    ws = _workspace(points, need)
     meta = torch.empty(2 * T + 1, device=points.device, dtype=torch.int64)        # counts [T] | offsets [T+1]
     offs = (C.c_long * (T + 1))()
     cap = int(capacity) if capacity is not None else N + N // 4
@@ -748,38 +764,17 @@ def strip_bin_points(points, params, H=1152, W=1152, z_range=None, capacity=None
     return binned[:offs[T]], [int(o) for o in offs]
 
 
-def _ground_args(who, points, tile_offsets, params):
-    if not points.is_cuda:
-        _ptr(points)
-    assert points.dim() == 2 and points.shape[1] == 4 and points.is_contiguous() and points.dtype == torch.float32
-    B = len(params)
-    if len(tile_offsets) != B + 1:
-        raise ValueError(f'{who}: {len(tile_offsets)} tile_offsets for {B} tiles (B + 1 are needed)')
-    offs = (C.c_long * (B + 1))(*[int(o) for o in tile_offsets])
-    if B and offs[B] > points.shape[0]:
-        raise ValueError(f'{who}: tile_offsets end at {offs[B]}, points has {points.shape[0]} rows')
-    return B, offs, (LmRasterParams * B)(*params)
-
-
-def _ground_ws(points, need):
-    key = (points.device, _stream().value)
-    ws = _raster_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _raster_ws[key] = torch.empty(need, device=points.device, dtype=torch.uint8)
-    return ws
-
-
 def tile_ground(points, tile_offsets, params, H=1152, W=1152, cell_px=32, want_cell_min=False):
     """The coarse ground model under every tile (csrc/ground.hip), from the (points, tile_offsets, params) triple bev_raster_batch takes:
     -> (ground [B,Gy,Gx] f32, ground_min [B] f32) on the device, Gy = ceil(H / cell_px), Gx = ceil(W / cell_px).  A cell's raw value is
     the smallest tile-frame height vz of the points the rasteriser keeps for the tile in that cell; ground is the lower median of the
     non-empty cells of its 3 x 3 neighbourhood (NaN where all nine are empty), ground_min the tile's smallest finite ground (+inf: none).
     want_cell_min: -> (ground, ground_min, cell_min [B,Gy,Gx]), the raw minima, NaN = empty.  No synchronisation."""
-    B, offs, par = _ground_args('tile_ground', points, tile_offsets, params)
+    B, offs, par = _tile_range_args('tile_ground', points, tile_offsets, params)
     H, W, cell_px = int(H), int(W), int(cell_px)
     need = lib().lm_tile_ground_workspace_bytes(B, H, W, cell_px)
     Gy, Gx = (-(-H // cell_px), -(-W // cell_px)) if cell_px > 0 else (0, 0)
-    ws = _ground_ws(points, max(need, 16))
+    ws = _workspace(points, max(need, 16))
     ground = torch.empty((B, Gy, Gx), device=points.device, dtype=torch.float32)
     gmin = torch.empty((B,), device=points.device, dtype=torch.float32)
     cmin = torch.empty_like(ground) if want_cell_min else None
@@ -794,14 +789,14 @@ def ground_select(points, tile_offsets, params, ground, H=1152, W=1152, cell_px=
     point for the tile, vz is finite and lo <= vz - ground[b, cell] <= hi (infinite bounds switch a side off).  -> (points_out
     [sum kept, 4], offsets: B+1 host ints) as strip_bin_points returns them: each tile's kept points in their input order, the pair
     bev_raster_batch takes.  `ground` is tile_ground's for the same tiles, H, W and cell_px.  One device-to-host read of the offsets."""
-    B, offs, par = _ground_args('ground_select', points, tile_offsets, params)
+    B, offs, par = _tile_range_args('ground_select', points, tile_offsets, params)
     H, W, cell_px = int(H), int(W), int(cell_px)
     Gy, Gx = (-(-H // cell_px), -(-W // cell_px)) if cell_px > 0 else (0, 0)
     if tuple(ground.shape) != (B, Gy, Gx) or ground.dtype != torch.float32 or not ground.is_contiguous() or ground.device != points.device:
         raise ValueError(f'ground_select: ground must be a contiguous [{B},{Gy},{Gx}] float32 tensor on {points.device} (tile_ground\'s output)')
     N = int(offs[B] - offs[0]) if B else 0
     need = lib().lm_ground_select_workspace_bytes(max(N, 0), B)
-    ws = _ground_ws(points, max(need, 16))
+    ws = _workspace(points, max(need, 16))
     out = torch.empty((max(N, 0), 4), device=points.device, dtype=torch.float32)
     doffs = torch.empty((B + 1,), device=points.device, dtype=torch.int64)
     hoffs = (C.c_long * (B + 1))()
@@ -818,7 +813,7 @@ def tile_intensity_window(points, tile_offsets, params, H=1152, W=1152, percenti
     tile and its intensity is not NaN; its key is floor(clamp(intensity, 0, 65535)).  With n counted points in a group, window[g] holds the
     keys of 0-based ranks (n - 1) * ppm // 10**6 in ascending order for ppm = round(p * 10**4) of the two percentiles; n = 0: (-1, -1).
     group: B ints in 0..G-1 with G = max + 1 (None: every tile its own group).  Exact and reproducible.  No synchronisation."""
-    B, offs, par = _ground_args('tile_intensity_window', points, tile_offsets, params)
+    B, offs, par = _tile_range_args('tile_intensity_window', points, tile_offsets, params)
     H, W = int(H), int(W)
     if group is None:
         G, grp = B, None
@@ -833,7 +828,7 @@ def tile_intensity_window(points, tile_offsets, params, H=1152, W=1152, percenti
         G = max(ids + [0]) + 1
     q_lo, q_hi = (int(round(float(p) * 1e4)) for p in percentiles)
     need = lib().lm_tile_intensity_workspace_bytes(B, G)
-    ws = _ground_ws(points, max(need, 16))
+    ws = _workspace(points, max(need, 16))
     window = torch.empty((max(G, 0), 2), device=points.device, dtype=torch.int32)
     count = torch.empty((max(G, 0),), device=points.device, dtype=torch.int64)
     hist = torch.empty((max(G, 0), 4096), device=points.device, dtype=torch.int32) if want_hist else None
@@ -850,7 +845,7 @@ def drape_vertices(points, tile_offsets, params, vertices, vertex_offsets, H=115
     is the smallest tile-frame height vz of the points the rasteriser keeps for the vertex's tile in pixel (row + i - R, col + j - R), z[v]
     the lower median of the npix[v] non-empty ones (NaN for none).  Exact and reproducible.  No synchronisation."""
     import numpy as np
-    B, offs, par = _ground_args('drape_vertices', points, tile_offsets, params)
+    B, offs, par = _tile_range_args('drape_vertices', points, tile_offsets, params)
     H, W, R = int(H), int(W), int(radius_px)
     vert = np.ascontiguousarray(np.asarray(vertices, dtype=np.int32).reshape(-1, 2))
     if len(vertex_offsets) != B + 1:
@@ -860,7 +855,7 @@ def drape_vertices(points, tile_offsets, params, vertices, vertex_offsets, H=115
         raise ValueError(f'drape_vertices: vertex_offsets end at {voffs[B]}, vertices has {vert.shape[0]} rows')
     V, D = vert.shape[0], 2 * max(R, 0) + 1
     need = lib().lm_drape_workspace_bytes(V, B, R)
-    ws = _ground_ws(points, max(need, 16))
+    ws = _workspace(points, max(need, 16))
     z = torch.empty((V,), device=points.device, dtype=torch.float32)
     npix = torch.empty((V,), device=points.device, dtype=torch.int32)
     pmin = torch.empty((V, D, D), device=points.device, dtype=torch.float32) if want_pixel_min else None

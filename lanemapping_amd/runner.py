@@ -21,6 +21,7 @@ Tiles are PNG files (load_img contract, datasets/laserlane_proposals.py:85-98): 
 converted u8 -> f32/255 on the GPU (lm_tile_ingest_u8).  With torch.distributed initialised, tiles are sharded
 over the ranks (lanemapping_amd/shard.py) and rank 0 writes every file after one all-gather per batch.
 """
+import functools
 import glob
 import json
 import os
@@ -283,23 +284,29 @@ class Runner:
                 print(f'{k}={v}')
         return results
 
-    def _las_select(self, select):
-        """The point filter of the LAS readers: the argument, else cfg['las_select'] (a dict of las_io.PointFilter arguments), else none."""
+    def _las_option(self, arg, key, cls, value):
+        """A stage of the LAS routes (`arg` of infer_las_to_map): the argument, else cfg[key] (a dict of the arguments of las_io's class
+        `cls`), else none."""
         from . import las_io
-        if select is None and self.cfg.get('las_select') is not None:
-            select = las_io.PointFilter(**dict(self.cfg.get('las_select')))
-        if select is not None and not isinstance(select, las_io.PointFilter):
-            raise TypeError(f'select must be a las_io.PointFilter, not {type(select).__name__}')
-        return select
+        cls = getattr(las_io, cls)
+        if value is None and self.cfg.get(key) is not None:
+            value = cls(**dict(self.cfg.get(key)))
+        if value is not None and not isinstance(value, cls):
+            raise TypeError(f'{arg} must be a las_io.{cls.__name__}, not {type(value).__name__}')
+        return value
 
-    def _las_ground(self, ground):
-        """The terrain following of the LAS routes: the argument, else cfg['las_ground'] (a dict of las_io.GroundFilter arguments), else none."""
-        from . import las_io
-        if ground is None and self.cfg.get('las_ground') is not None:
-            ground = las_io.GroundFilter(**dict(self.cfg.get('las_ground')))
-        if ground is not None and not isinstance(ground, las_io.GroundFilter):
-            raise TypeError(f'ground must be a las_io.GroundFilter, not {type(ground).__name__}')
-        return ground
+    _las_select = functools.partialmethod(_las_option, 'select', 'las_select', 'PointFilter')              # the point filter of the readers
+    _las_ground = functools.partialmethod(_las_option, 'ground', 'las_ground', 'GroundFilter')             # the terrain following
+    _las_intensity = functools.partialmethod(_las_option, 'intensity', 'las_intensity', 'IntensityStretch')  # the intensity window
+    _las_elevation = functools.partialmethod(_las_option, 'elevation', 'las_elevation', 'ElevationDrape')  # the vertex heights
+    _las_density = functools.partialmethod(_las_option, 'density', 'las_density', 'GapFill')               # the gap fill
+
+    @staticmethod
+    def _params_dir(out_dir):
+        """<out_dir>/params, made if need be: where the LAS routes record what they used."""
+        par_dir = os.path.join(out_dir, 'params')
+        os.makedirs(par_dir, exist_ok=True)
+        return par_dir
 
     def _follow_ground(self, gf, names, plist, points, offs, rpar, H, W, out_dir):
         """One batch of tiles through a las_io.GroundFilter: -> (plist, points, offs, rpar) to rasterise and back-project with.  The ground
@@ -318,21 +325,10 @@ class Runner:
                 rpar[j].local_min_ele = p['local_min_ele']
         if gf.height_range is not None:
             points, offs = ops.ground_select(points, offs, rpar, ground, H, W, gf.cell_px, gf.height_range)
-        par_dir = os.path.join(out_dir, 'params')
-        os.makedirs(par_dir, exist_ok=True)
+        par_dir = self._params_dir(out_dir)
         for name, p in zip(names, plist):
             io_utils.save_pc_2_img_transform_paras(os.path.join(par_dir, name + '.txt'), p)
         return plist, points, offs, rpar
-
-    def _las_intensity(self, intensity):
-        """The intensity window of the LAS routes: the argument, else cfg['las_intensity'] (a dict of las_io.IntensityStretch arguments),
-        else none."""
-        from . import las_io
-        if intensity is None and self.cfg.get('las_intensity') is not None:
-            intensity = las_io.IntensityStretch(**dict(self.cfg.get('las_intensity')))
-        if intensity is not None and not isinstance(intensity, las_io.IntensityStretch):
-            raise TypeError(f'intensity must be a las_io.IntensityStretch, not {type(intensity).__name__}')
-        return intensity
 
     @staticmethod
     def _strip_intensity(st, points, offs, rpar, H, W):
@@ -363,9 +359,7 @@ class Runner:
             r.inten_lo, r.inten_hi = lo, hi
             scales.append(0.0 if scale is None else scale)
             used[name] = [lo, hi, scale, n]
-        par_dir = os.path.join(out_dir, 'params')
-        os.makedirs(par_dir, exist_ok=True)
-        with open(os.path.join(par_dir, 'intensity.json'), 'w') as f:
+        with open(os.path.join(self._params_dir(out_dir), 'intensity.json'), 'w') as f:
             json.dump(used, f, indent=1)
         return rpar, scales
 
@@ -376,25 +370,6 @@ class Runner:
             return raster_batch(names, plist, points, offs, rpar)
         rpar, scales = self._stretch_intensity(st, names, points, offs, rpar, H, W, out_dir, used, strip)
         return raster_batch(names, plist, points, offs, rpar, scales)
-
-    def _las_elevation(self, elevation):
-        """The vertex heights of the LAS routes: the argument, else cfg['las_elevation'] (a dict of las_io.ElevationDrape arguments), else
-        none."""
-        from . import las_io
-        if elevation is None and self.cfg.get('las_elevation') is not None:
-            elevation = las_io.ElevationDrape(**dict(self.cfg.get('las_elevation')))
-        if elevation is not None and not isinstance(elevation, las_io.ElevationDrape):
-            raise TypeError(f'elevation must be a las_io.ElevationDrape, not {type(elevation).__name__}')
-        return elevation
-
-    def _las_density(self, density):
-        """The gap fill of the LAS routes: the argument, else cfg['las_density'] (a dict of las_io.GapFill arguments), else none."""
-        from . import las_io
-        if density is None and self.cfg.get('las_density') is not None:
-            density = las_io.GapFill(**dict(self.cfg.get('las_density')))
-        if density is not None and not isinstance(density, las_io.GapFill):
-            raise TypeError(f'density must be a las_io.GapFill, not {type(density).__name__}')
-        return density
 
     def infer_las_to_map(self, las_and_params, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None, ground=None,
                          intensity=None, elevation=None, density=None):
@@ -543,9 +518,7 @@ class Runner:
                 n_draped = int(np.isfinite(vz).sum())
                 draped[name] = [voffs[j + 1] - voffs[j], n_draped, voffs[j + 1] - voffs[j] - n_draped]
                 write_3d(name, coor_img2pc.transform_coordinate_from_img_2_pc(params, seqs, lens, u8, vertex_z=vz, fit=elevation.fit), lens)
-            par_dir = os.path.join(out_dir, 'params')
-            os.makedirs(par_dir, exist_ok=True)
-            with open(os.path.join(par_dir, 'elevation.json'), 'w') as f:
+            with open(os.path.join(self._params_dir(out_dir), 'elevation.json'), 'w') as f:
                 json.dump(draped, f, indent=1)
 
         def fill_gaps(names, points, offs, rpar, inten_scale):
@@ -557,9 +530,7 @@ class Runner:
             radii = [las_io.gap_radius(row, density) for row in hist]
             for name, r, row in zip(names, radii, hist):
                 filled[name] = [int(r)] + [int(v) for v in row]
-            par_dir = os.path.join(out_dir, 'params')
-            os.makedirs(par_dir, exist_ok=True)
-            with open(os.path.join(par_dir, 'density.json'), 'w') as f:
+            with open(os.path.join(self._params_dir(out_dir), 'density.json'), 'w') as f:
                 json.dump(filled, f, indent=1)
             return ops.tile_gap_fill(u8, radii)
 

@@ -162,6 +162,36 @@ def test_vertex_cap_on_one_tile(dev):
     assert (rn > 0).all() and len(np.unique(rz.view(np.uint32))) > 1000
 
 
+def test_empty_tile_between_two_tiles_across_the_chunk_seam(dev):
+    """Three 64 x 64 tiles of 16,385 / 0 / 255 points - two workgroups, none, one - with vertices in the first and the last.  The last
+    point of either range is the lowest of its pixel and a vertex sits on that pixel: the first tile's point 16,384 is alone in its
+    tile's second chunk, and the third tile's workgroup follows the first tile's two, not the empty tile's none."""
+    T, R = 64, 2
+    tiles = [_axis_tile(), _far_tile(), _rot_tile()]
+    clouds, verts, voffs = [], [], [0]
+    for seed, n, p in ((51, DCHUNK + 1, tiles[0]), (0, 0, tiles[1]), (52, 255, tiles[2])):
+        c = _small_cloud(seed, n, p, spread=0.85) if n else np.zeros((0, 4), f32)
+        if n:
+            c[-1] = c[np.flatnonzero(gr.window(c, p, T, T)[0])[0]]      # a place inside the window ...
+            c[-1, 2] -= 1.0                                             # ... and a metre under everything else
+            on, row, col, vz = gr.window(c, p, T, T)
+            assert on[-1] and vz[-1] < vz[:-1][on[:-1]].min()
+            verts += [(int(row[-1]), int(col[-1])), (0, 0), (T - 1, T - 1), (30, 33)]
+        clouds.append(c)
+        voffs.append(len(verts))
+    pts = np.concatenate(clouds)
+    offs = [0, DCHUNK + 1, DCHUNK + 1, DCHUNK + 1 + 255]
+    verts = np.asarray(verts, np.int32)
+    z, npix, pmin = ops.drape_vertices(torch.from_numpy(pts).to(dev), offs, tiles, verts, voffs, T, T, radius_px=R, want_pixel_min=True)
+    rz, rn, rp = dr.drape_vertices(pts, offs, tiles, verts, voffs, T, T, R)
+    _same(pmin, rp, 'seam: pixel_min')
+    assert np.array_equal(npix.cpu().numpy(), rn), 'seam: npix'
+    _same(z, rz, 'seam: z')
+    for v, c, p in ((0, clouds[0], tiles[0]), (4, clouds[2], tiles[2])):
+        assert rp[v, R, R].view(np.uint32) == gr.window(c[-1:], p, T, T)[3].view(np.uint32)[0], 'the last point of the range is its pixel\'s minimum'
+        assert rn[v] > 1
+
+
 # ------------------------------------------------------------------------------------------------ 2. guards and refusals
 def _guard_case():
     axis, rot = _axis_tile(), _rot_tile()
