@@ -136,8 +136,10 @@ int lm_unpatchify(void* stream, const float* tokens, float* y_nhwc, int B, int G
 int lm_token_mix_mfma_f32(void* stream, const float* x, const float* wt, int ldw, const float* bias, const float* res, float* y,
                           int B, int M, int K, int N, int act);
 
-/* ---- attention core: softmax(q k^T * scale) v per (batch, head); qkv = [B*N][3*heads*64] (vitsegnet.py:58-68).  Any N >= 1: N >= 382
- * (ViT patches 6 / 4) streams K / V through LDS with an online softmax; deterministic, no workspace. */
+/* ---- attention core: softmax(q k^T * scale) v per (batch, head); qkv = [B*N][3*heads*64] (vitsegnet.py:58-68).  Any N >= 1, routed by N
+ * alone: 321 <= N <= 352 (the ViT block's 324 tokens) runs on the matrix cores with the whole head's K / V in LDS; every other N <= 380
+ * runs the VALU kernel, whose LDS (404 N + 9792 dynamic + 272 static bytes) reaches 163584 of the CU's 163840 bytes at N = 380; N >= 381
+ * (ViT patches 6 / 4) streams K / V through LDS with an online softmax.  Deterministic, no workspace. */
 int lm_attention_f32(void* stream, const float* qkv, float* out, int B, int N, int heads, int dim_head, float scale);
 /* the same with a key mask, valid [B][N] ints (N <= 64): per batch element only the flagged tokens are keys, compacted in token order
  * (row_shared_not_reduc_ref.py:199-215: the transformer runs over the data-dependent subset of the lane tokens) */
@@ -203,7 +205,10 @@ typedef struct {
     float inten_lo, inten_hi; /* 800, 33000 */
 } LmRasterParams;
 /* points: device [sum N][4] f32 {x,y,z,raw intensity}; tile_offsets: HOST [B+1] point index of each tile's first
- * record; params: HOST [B]; out_chw [B][3][H][W] f32 (= u8/255), out_hwc_u8 [B][H][W][3] (either may be NULL). */
+ * record; params: HOST [B]; out_chw [B][3][H][W] f32 (= u8/255), out_hwc_u8 [B][H][W][3] (either may be NULL).
+ * Tile size: H a multiple of 16 or 12 with at most 96 bands of that many rows, and one band image (rows * W * 4 bytes) within the CU's
+ * 160 KB of LDS: rows * W <= 40960, i.e. W <= 2560 where H is a multiple of 16 and W <= 3413 where H is a multiple of 12.  Any other
+ * size is refused with LM_ERR_ARG before anything is launched, and lm_bev_raster_workspace_bytes returns 0 for it. */
 long lm_bev_raster_workspace_bytes(int B, long max_points_per_tile, int H, int W);
 int lm_bev_raster_batch(void* stream, const float* points_xyzi, const long* tile_offsets, const LmRasterParams* params,
                         int B, void* workspace, long workspace_bytes, float* out_chw, unsigned char* out_hwc_u8,

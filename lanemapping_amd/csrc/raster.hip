@@ -273,14 +273,20 @@ static long nblk_of(long n) { return (n + CHUNK - 1) / CHUNK; }
 // Rows per band: the band kernel runs (bands x tiles) workgroups on 256 CUs x floor(160 KB / band image) slots; with 16-row bands a
 // 16-tile batch of 1152-row tiles is 1152 workgroups on 512 slots = 2.25 rounds (the third one a quarter full), with 12-row bands
 // 1536 on 512 = exactly 3 rounds of 3/4 the work each.  Picks the candidate with the least rounds x rows.  LM_RASTER_BAND_ROWS overrides.
+// A band is a candidate only while its image, rows x W u32 of dynamic LDS (raster_band_kernel has no static LDS), fits the CU's 160 KB:
+// rows * W <= MAX_BAND_PIX = 40960, i.e. W <= 2560 with 16-row bands and W <= 3413 with 12-row bands (the record's 16-bit pixel index
+// would allow 65536, the LDS does not).  The override obeys the same bound.
+constexpr long LDS_PER_WG = 160 * 1024;
+constexpr long MAX_BAND_PIX = LDS_PER_WG / (long)sizeof(unsigned);
 static int band_rows_for(int B, int H, int W) {
     static const int forced = [] { const char* e = getenv("LM_RASTER_BAND_ROWS"); return e ? atoi(e) : 0; }();
-    if (forced > 0 && H % forced == 0 && H / forced <= MAX_BANDS && (long)forced * W <= 65536 && forced % 4 == 0) return forced;
+    if (W <= 0 || H <= 0) return 0;
+    if (forced > 0 && H % forced == 0 && H / forced <= MAX_BANDS && (long)forced * W <= MAX_BAND_PIX && forced % 4 == 0) return forced;
     int best = 0;
     long best_cost = 0;
     for (int r : {16, 12}) {
-        if (H % r != 0 || H / r > MAX_BANDS || (long)r * W > 65536) continue;
-        const long lds = (long)r * W * 4, per_cu = lds > 0 ? (160 * 1024) / lds : 1;
+        if (H % r != 0 || H / r > MAX_BANDS || (long)r * W > MAX_BAND_PIX) continue;
+        const long lds = (long)r * W * 4, per_cu = LDS_PER_WG / lds;          // >= 1: the band fits
         const long slots = 256 * (per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu));     // 1024-thread workgroups: at most 2 per CU
         const long wgs = (long)(H / r) * (B < MAX_TILES ? B : MAX_TILES);
         const long cost = ((wgs + slots - 1) / slots) * r;
@@ -307,9 +313,11 @@ LM_API int lm_bev_raster_batch_scaled(void* hip_stream, const float* points_xyzi
                                       int B, void* workspace, long workspace_bytes, float* out_chw, unsigned char* out_hwc_u8,
                                       int H, int W, const float* inten_scale) {
     void* const stream = hip_stream;
-    LM_REQUIRE(tile_offsets && params && workspace && (out_chw || out_hwc_u8) && B >= 1, "bev_raster: null pointer");
-    const int band_rows = band_rows_for(B, H, W);
-    LM_REQUIRE(band_rows > 0 && W > 0, "bev_raster: H=%d must be a multiple of 16 or 12 (at most %d bands) and rows*W <= 65536", H, MAX_BANDS);
+    LM_REQUIRE(tile_offsets && params && (out_chw || out_hwc_u8) && B >= 1, "bev_raster: null pointer");
+    const int band_rows = band_rows_for(B, H, W);    // before the workspace: the size query returns 0 exactly where this refuses
+    LM_REQUIRE(band_rows > 0, "bev_raster: H=%d W=%d: H must be a multiple of 16 or 12 (at most %d bands) with rows*W <= %ld "
+               "(a band of 16 or 12 rows is rows*W*4 bytes of LDS, at most %ld)", H, W, MAX_BANDS, MAX_BAND_PIX, LDS_PER_WG);
+    LM_REQUIRE(workspace, "bev_raster: null pointer");
     const int nbands = H / band_rows;
     long nmax = 0;
     for (int b = 0; b < B; ++b) {

@@ -5,8 +5,8 @@
 // The projections themselves run on lm_conv2d_nhwc_mfma_f32.
 //
 // Three kernels: attention_mfma_kernel (below) for the ViT block's 324 tokens at patch 8, attention_flash_kernel (below) for the
-// longer sequences of patches 6 / 4 / 2 (N >= 382), and this VALU kernel for every other sequence length (the RowRef head's few lane
-// tokens, the 144 / 81 tokens of patches 12 / 16).
+// longer sequences of patches 6 / 4 / 2 (N >= 381: what the VALU kernel's LDS cannot hold), and this VALU kernel for every other
+// sequence length up to 380 (the RowRef head's few lane tokens, the 144 / 81 tokens of patches 12 / 16).
 // VALU kernel: one workgroup = one (batch, head, 36-query chunk).  K (then V, re-using the same LDS) for the
 // whole head is staged once: 324 x 64 fp32 = 83 KB of the CU's 160 KB LDS; the 36 x 324 score
 // block stays in LDS as well, so scores never touch HBM.  Fixed summation order => deterministic.
@@ -17,6 +17,16 @@ namespace {
 constexpr int DH = 64;
 constexpr int QC = 36;      // query rows per workgroup
 constexpr int KLD = DH + 1; // padded K/V row (floats): conflict-free column access
+// attention_kernel's STATIC LDS (kidx[64], kcount, padding), which a launch needs on top of its dynamic block.  It is the kernel's
+// .group_segment_fixed_size in the gfx950 code object: re-read it after any change to the kernel's __shared__ variables with
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -S vit.hip   (the .amdhsa.kernels entry of attention_kernel)
+constexpr size_t VALU_STATIC_LDS = 272;
+constexpr size_t LDS_PER_WG = 160 * 1024;   // what one workgroup can be granted on gfx950, static + dynamic
+// dynamic LDS of attention_kernel for N keys: K / V [N][KLD], scores [QC][N + 4], Q [QC][DH] = 404 N + 9792 bytes
+constexpr size_t valu_dynamic_lds(int N) { return ((size_t)N * KLD + (size_t)QC * (N + 4) + QC * DH) * sizeof(float); }
+constexpr bool valu_fits(int N) { return valu_dynamic_lds(N) + VALU_STATIC_LDS <= LDS_PER_WG; }
+static_assert(valu_fits(380) && !valu_fits(381), "the VALU kernel holds 380 keys (163312 + 272 B), not 381 (163716 + 272 B > 163840)");
+static_assert(valu_fits(64), "the masked entry's 64 tokens fit");
 
 // valid (optional, [B][NT] ints, NT <= 64 tokens per batch element): only the tokens with a non-zero flag take part as KEYS, in token
 // order - the scores, the softmax and P V are computed on the compacted key list exactly as if the call had been made on the valid
@@ -224,7 +234,7 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(const float* __rest
     }
 }
 
-// ---- Flash-style MFMA kernel for long sequences (every N the two kernels above cannot hold: N >= 382) --------------------------
+// ---- Flash-style MFMA kernel for long sequences (every N the two kernels above cannot hold: N >= 381) --------------------------
 // One workgroup = (batch, head, 4 query tiles of 32), one wave per query tile, Q fragments in registers exactly as in
 // attention_mfma_kernel.  K and V stream through LDS in stages of FKB = 64 keys (two MFMA key blocks of 32; keys >= N are zero rows
 // and masked to -inf), and the softmax is online: per 32-key block the lane's query takes the block max (its 16 registers plus
@@ -341,8 +351,8 @@ LM_API int lm_attention_f32(void* stream, const float* qkv, float* out, int B, i
         LM_LAUNCH_CHECK();
         return LM_OK;
     }
-    const size_t lds = ((size_t)N * KLD + (size_t)QC * (N + 4) + QC * DH) * sizeof(float);
-    if (lds > 160 * 1024) {                 // N >= 382 (patch sizes 6, 4, 2: 576, 1296, 5184 tokens): stream K / V
+    LM_REQUIRE(N >= 1, "attention: N=%d must be at least 1", N);
+    if (!valu_fits(N)) {                    // N >= 381 (patch sizes 6, 4, 2: 576, 1296, 5184 tokens): stream K / V
         const size_t lds_f = (size_t)FKB * (KP + VP) * sizeof(float);
         if (int e = lm_ensure_dynamic_lds((const void*)attention_flash_kernel, lds_f)) return e;
         hipLaunchKernelGGL(attention_flash_kernel, dim3(lm_cdiv(lm_cdiv(N, 32), 4), heads, B), dim3(256), lds_f, (hipStream_t)stream, qkv,
@@ -350,6 +360,7 @@ LM_API int lm_attention_f32(void* stream, const float* qkv, float* out, int B, i
         LM_LAUNCH_CHECK();
         return LM_OK;
     }
+    const size_t lds = valu_dynamic_lds(N);   // static + dynamic <= 160 KB: N <= 380
     if (int e = lm_ensure_dynamic_lds((const void*)attention_kernel, lds)) return e;
     hipLaunchKernelGGL(attention_kernel, dim3(lm_cdiv(N, QC), heads, B), dim3(256), lds, (hipStream_t)stream, qkv, out, N, heads, scale,
                        (const int*)nullptr);
@@ -363,7 +374,7 @@ LM_API int lm_attention_masked_f32(void* stream, const float* qkv, float* out, c
                                    float scale) {
     LM_REQUIRE(qkv && out && valid, "attention_masked: null pointer");
     LM_REQUIRE(dim_head == DH && N >= 1 && N <= 64, "attention_masked: dim_head=%d must be %d, N=%d at most 64", dim_head, DH, N);
-    const size_t lds = ((size_t)N * KLD + (size_t)QC * (N + 4) + QC * DH) * sizeof(float);
+    const size_t lds = valu_dynamic_lds(N);   // N <= 64: 35648 + 272 B
     if (int e = lm_ensure_dynamic_lds((const void*)attention_kernel, lds)) return e;
     hipLaunchKernelGGL(attention_kernel, dim3(lm_cdiv(N, QC), heads, B), dim3(256), lds, (hipStream_t)stream, qkv, out, N, heads, scale, valid);
     LM_LAUNCH_CHECK();
