@@ -37,6 +37,12 @@ class LmLasSelect(C.Structure):
     _fields_ = [('class_mask', C.c_uint * 8), ('drop_flags', C.c_uint), ('returns', C.c_int), ('z_lo', C.c_float), ('z_hi', C.c_float)]
 
 
+class LmLineGrid(C.Structure):
+    """Point-to-segment lookup grid of the labelling (include/lanemap_hip.h)."""
+    _fields_ = [('x0', C.c_double), ('y0', C.c_double), ('cell', C.c_double), ('nx', C.c_int), ('ny', C.c_int), ('min_line', C.c_int),
+                ('max_line', C.c_int), ('n_segments', C.c_long), ('n_entries', C.c_long), ('half_width', C.c_float)]
+
+
 # name -> (restype, argtypes); every entry must be declared in include/lanemap_hip.h
 SIGNATURES = {
     'lm_abi_version': (i32, []),
@@ -146,6 +152,10 @@ SIGNATURES = {
     'lm_las_select_workspace_bytes': (i64, [i64]),
     'lm_las_decode_select': (i32, [vp, vp, i32, i32, i64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), f32, f32,
                                    i32, C.POINTER(LmLasSelect), vp, i64, vp, vp, vp]),
+    'lm_line_index_build': (i32, [vp, i64, f32, C.c_double, C.POINTER(LmLineGrid), vp, i64, vp, i64]),
+    'lm_label_points': (i32, [vp, vp, i64, vp, i64, C.POINTER(LmLineGrid), vp, vp, f32, f32, f32, vp, vp]),
+    'lm_las_label_records': (i32, [vp, vp, i32, i32, i64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                   C.POINTER(LmLasSelect), vp, i64, C.POINTER(LmLineGrid), vp, vp, f32, f32, f32, i32, i32, vp, vp, vp, i32]),
     'lm_png_info': (i32, [vp, i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
     'lm_png_decode_u8': (i32, [vp, i64, vp, i64]),
     'lm_png_decode_files_u8': (i32, [C.POINTER(C.c_char_p), i32, vp, i32, i32, i32, i32]),

@@ -20,9 +20,13 @@ the intensities a tile, or the whole strip, keeps (`ops.tile_intensity_window`),
 
 `GapFill` / `gap_radius` describe how the map routes close the holes between the returns of a sparse scanner in the rasterised tiles
 (`ops.tile_gap_hist`, `ops.tile_gap_fill`).
+
+`MarkingLabels` / `line_segments` / `label_las` are the way back: the returns of a file labelled by the lane lines found in it
+(`ops.line_index`, `ops.label_points`, `lm_las_label_records`), and the file written again with the markings classified.
 """
 import ctypes as C
 import math
+import os
 
 import numpy as np
 import torch
@@ -342,6 +346,160 @@ def gap_radius(hist_row, fill):
         if sum(row[0:r + 1]) * 10 ** 6 >= want:
             return r
     return R
+
+
+class MarkingLabels:
+    """How the LAS -> map routes label the returns of their input by the lines they found (immutable; Runner.infer_las_strip_to_map /
+    infer_las_to_map, `label=`; label_las).  A return is labelled with line k (counted from 1 in the order of the lines) when it lies within
+    half_width of the line in the plane and within z_tol of it in height, the nearest line winning (the rule: include/lanemap_hip.h).
+
+      half_width      metres (finite, >= 0): half the width of the band around a line in which a return counts as its paint
+      z_tol           metres (>= 0, may be infinite): the height band; it only keeps a carriageway from labelling the one under or over it
+      min_intensity   None, or the smallest raw intensity a labelled return has (paint is bright)
+      marking_class   the classification a labelled record gets, 0..255; None: 64 on point formats 6-10 (the first user-definable class of
+                      LAS 1.4), 31 on formats 0-5 (the largest class their five bits hold)
+      line_ids        True: the point source ID of a labelled record becomes its line number (at most 65535 lines)
+    half_width = 0.15 and z_tol = 0.5 are plain defaults, not tuned values."""
+    __slots__ = ('half_width', 'z_tol', 'min_intensity', 'marking_class', 'line_ids')
+
+    def __init__(self, half_width=0.15, z_tol=0.5, min_intensity=None, marking_class=None, line_ids=True):
+        num = (int, float, np.integer, np.floating)
+        if isinstance(half_width, bool) or not isinstance(half_width, num) or not (0.0 <= float(half_width) < math.inf):
+            raise ValueError(f'MarkingLabels: half_width={half_width!r} must be a finite number >= 0')
+        if isinstance(z_tol, bool) or not isinstance(z_tol, num) or not float(z_tol) >= 0.0:
+            raise ValueError(f'MarkingLabels: z_tol={z_tol!r} must be a number >= 0')
+        if min_intensity is not None:
+            if isinstance(min_intensity, bool) or not isinstance(min_intensity, num) or math.isnan(float(min_intensity)):
+                raise ValueError(f'MarkingLabels: min_intensity={min_intensity!r} must be None or a number')
+            min_intensity = float(min_intensity)
+        if marking_class is not None:
+            if isinstance(marking_class, bool) or not isinstance(marking_class, (int, np.integer)) or not 0 <= int(marking_class) <= 255:
+                raise ValueError(f'MarkingLabels: marking_class={marking_class!r} must be None or a class in 0..255')
+            marking_class = int(marking_class)
+        for k, v in (('half_width', float(half_width)), ('z_tol', float(z_tol)), ('min_intensity', min_intensity),
+                     ('marking_class', marking_class), ('line_ids', bool(line_ids))):
+            object.__setattr__(self, k, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError('MarkingLabels is immutable')
+
+    def __delattr__(self, name):
+        raise AttributeError('MarkingLabels is immutable')
+
+    def __repr__(self):
+        return 'MarkingLabels(' + ', '.join(f'{k}={getattr(self, k)!r}' for k in self.__slots__) + ')'
+
+    def __eq__(self, other):
+        return isinstance(other, MarkingLabels) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
+
+    def __hash__(self):
+        return hash(tuple(getattr(self, k) for k in self.__slots__))
+
+    def for_format(self, point_format):
+        """-> the classification labelled records of a file of this point data record format get: marking_class, or its default for the
+        format.  Formats 0-5 store the classification in five bits: a class above 31 asked of such a file is refused."""
+        if not 0 <= int(point_format) <= 10:
+            raise ValueError(f'MarkingLabels: unknown point data record format {point_format}')
+        if self.marking_class is None:
+            return 64 if int(point_format) >= 6 else 31
+        if int(point_format) <= 5 and self.marking_class > 31:
+            raise ValueError(f'MarkingLabels: marking_class={self.marking_class} does not exist in point format {point_format} '
+                             '(formats 0-5 hold 0..31)')
+        return self.marking_class
+
+
+def line_segments(lines, shift=None):
+    """Lines (a list of [n_i,3] float64 arrays in the LAS frame: what infer_las_*_to_map returns) -> the [S,8] float32 segment table of
+    the labelling: per consecutive vertex pair ax, ay, az, dx, dy, dz, inv, line.  Every vertex minus `shift` in float64, rounded to
+    float32; d = the float32 difference of the rounded endpoints; inv = 1 / (dx*dx + dy*dy) in float32, 0 where that is 0; line = the
+    int32 bit pattern of (line index + 1).  Line order, then vertex order; a line with fewer than two vertices gives no segment."""
+    sh = np.zeros(3) if shift is None else np.asarray(shift, dtype=np.float64).reshape(3)
+    rows = []
+    for k, line in enumerate(lines):
+        v = np.asarray(line, dtype=np.float64)
+        if v.size == 0:
+            continue
+        if v.ndim != 2 or v.shape[1] != 3:
+            raise ValueError(f'line_segments: line {k} has shape {v.shape}, not [n,3]')
+        if v.shape[0] < 2:
+            continue
+        v = (v - sh).astype(np.float32)
+        a, d = v[:-1], v[1:] - v[:-1]
+        len2 = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]
+        inv = np.zeros_like(len2)
+        np.divide(np.float32(1.0), len2, out=inv, where=len2 != 0)
+        seg = np.empty((len(a), 8), dtype=np.float32)
+        seg[:, 0:3], seg[:, 3:6], seg[:, 6] = a, d, inv
+        seg[:, 7] = np.full(len(a), k + 1, dtype=np.int32).view(np.float32)
+        rows.append(seg)
+    return np.concatenate(rows) if rows else np.zeros((0, 8), dtype=np.float32)
+
+
+def label_records(records_u8, header, index, labels, shift=None, select=None, n_lines=None, want_line=False):
+    """One lm_las_label_records call on the DEVICE records of a file (padded to a multiple of 4 bytes; `header`: parse_header's dict)
+    against an ops.line_index: -> (patched records, counts [n_lines + 1] int64 device tensor[, line [n] int32]).  Asynchronous."""
+    from . import ops
+    if not isinstance(labels, MarkingLabels):
+        raise TypeError(f'las_io.label_records: labels must be a MarkingLabels, not {type(labels).__name__}')
+    if select is not None and not isinstance(select, PointFilter):
+        raise TypeError(f'las_io.label_records: select must be a PointFilter, not {type(select).__name__}')
+    if not records_u8.is_cuda:
+        raise LanemapHipError('las_io.label_records needs the records on an MI355X (HIP) device; no CPU fallback exists')
+    fmt, rl, n = header['point_format'], header['record_len'], header['n_points']
+    cls = labels.for_format(fmt)
+    sel = select.for_format(fmt).as_struct() if select is not None else None
+    L = index.n_lines if n_lines is None else int(n_lines)
+    if index.half_width != np.float32(labels.half_width):
+        raise ValueError(f'las_io.label_records: the index was built for half_width={index.half_width}, labels ask {labels.half_width}')
+    dev = records_u8.device
+    out = torch.empty_like(records_u8)
+    counts = torch.empty((L + 1,), device=dev, dtype=torch.int64)
+    line = torch.empty((n,), device=dev, dtype=torch.int32) if want_line else None
+    d3 = lambda v: (C.c_double * 3)(*[float(x) for x in v])
+    mi = math.nan if labels.min_intensity is None else labels.min_intensity
+    check(lib().lm_las_label_records(C.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index)), C.c_void_p(records_u8.data_ptr()), int(rl),
+                                     int(fmt), int(n), d3(header['scale']), d3(header['offset']), d3(shift) if shift is not None else None,
+                                     C.byref(sel) if sel is not None else None, *index.args(), labels.z_tol, mi, cls,
+                                     int(labels.line_ids), C.c_void_p(out.data_ptr()), C.c_void_p(line.data_ptr()) if want_line else None,
+                                     C.c_void_p(counts.data_ptr()), L))
+    return (out, counts, line) if want_line else (out, counts)
+
+
+def label_las(path, out_path, lines, labels, shift, select=None, device='cuda:0'):
+    """The LAS file `path` written again as `out_path` with the returns of the `lines` (list of [n,3] float64, LAS frame) classified:
+    the records are uploaded, labelled in one lm_las_label_records call (the rule and what is patched: include/lanemap_hip.h) and read back
+    once, together with the counts.  out_path = the input's bytes up to offset_to_points (header and VLRs), the patched records, whatever
+    followed them (EVLRs).  shift: the read offset of the frame the float32 arithmetic runs in (the las_read_offset the lines were found
+    with); select: the PointFilter the file was read with - a record that fails it is never relabelled.
+    -> {'records': n, 'labelled': records with a label, 'per_line': [count of line 1, ...]}."""
+    from . import ops
+    if not isinstance(labels, MarkingLabels):
+        raise TypeError(f'las_io.label_las: labels must be a MarkingLabels, not {type(labels).__name__}')
+    device = torch.device(device)
+    data = np.fromfile(path, dtype=np.uint8)
+    h = parse_header(data)
+    n, rl, off = h['n_points'], h['record_len'], h['offset_to_points']
+    labels.for_format(h['point_format'])                                  # refused before anything is uploaded
+    if select is not None:
+        if not isinstance(select, PointFilter):
+            raise TypeError(f'las_io.label_las: select must be a PointFilter, not {type(select).__name__}')
+        select.for_format(h['point_format'])
+    lines = list(lines)
+    index = ops.line_index(line_segments(lines, shift), labels.half_width, device=device)
+    nbytes = n * rl
+    padded = np.zeros(((nbytes + 3) // 4 * 4,), dtype=np.uint8)
+    padded[:nbytes] = data[off:off + nbytes]
+    rec = torch.from_numpy(padded).to(device, non_blocking=True)
+    out, counts = label_records(rec, h, index, labels, shift, select, n_lines=len(lines))
+    both = torch.cat([out, counts.view(torch.uint8)]).cpu().numpy()        # the one read-back
+    counts = both[len(padded):].view(np.int64)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, 'wb') as f:
+        f.write(data[:off].tobytes())
+        f.write(both[:nbytes].tobytes())
+        f.write(data[off + nbytes:].tobytes())
+    per_line = [int(c) for c in counts[1:]]
+    return {'records': int(n), 'labelled': int(sum(per_line)), 'per_line': per_line}
 
 
 def parse_header(data):

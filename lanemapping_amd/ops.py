@@ -11,7 +11,7 @@ import math
 
 import torch
 
-from ._lib import lib, check, LmRasterParams, LmStripGrid, LanemapHipError
+from ._lib import lib, check, LmRasterParams, LmStripGrid, LmLineGrid, LanemapHipError
 
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
 
@@ -717,6 +717,74 @@ def strip_grid(params, H=1152, W=1152, z_range=None):
     cells = np.empty((g.ny, g.nx, 8), dtype=np.uint16)
     check(lib().lm_strip_build_grid(par, T, H, W, z_lo, z_hi, C.byref(g), C.c_void_p(cells.ctypes.data), g.nx * g.ny))
     return {'x0': g.x0, 'y0': g.y0, 'cell': g.cell, 'nx': g.nx, 'ny': g.ny}, cells
+
+
+class LineIndex:
+    """The segment table of las_io.line_segments with its lookup grid (lm_line_index_build), on the device: what label_points and
+    las_io.label_records take.  segments [S,8] f32, cell_start [nx ny + 1] and cell_segs [n_entries] int32 are device tensors; grid is
+    the host LmLineGrid; half_width the float32 half width the lists were built for; n_lines the largest line a segment carries."""
+
+    def __init__(self, segments, cell_start, cell_segs, grid, half_width):
+        self.segments, self.cell_start, self.cell_segs, self.grid, self.half_width = segments, cell_start, cell_segs, grid, half_width
+        self.n_segments, self.n_lines = int(segments.shape[0]), int(grid.max_line)
+
+    def args(self):
+        """-> the (segments, S, grid, cell_start, cell_segs, half_width) run of arguments of the two device entries."""
+        S = self.n_segments
+        return (_ptr(self.segments) if S else None, S, C.byref(self.grid), _ptr(self.cell_start) if S else None,
+                _ptr(self.cell_segs) if S else None, float(self.half_width))
+
+
+def line_index_host(segments, half_width, cell=None):
+    """lm_line_index_build on the host (no GPU): segments [S,8] float32 numpy (las_io.line_segments) -> (LmLineGrid, cell_start
+    [nx ny + 1] int32, cell_segs [n_entries] int32).  cell: the cell size in metres; None: max(1 m, 2 half_width).  The two-call protocol:
+    the first call sizes the lists, the second fills them."""
+    import numpy as np
+    seg = np.ascontiguousarray(segments, dtype=np.float32)
+    if seg.ndim != 2 or seg.shape[1] != 8:
+        raise ValueError(f'line_index: segments must be [S,8] float32 (las_io.line_segments), not {seg.shape}')
+    S, g = int(seg.shape[0]), LmLineGrid()
+    if cell is not None and not float(cell) > 0.0:
+        raise ValueError(f'line_index: cell={cell!r} must be a size > 0 (None: the default)')
+    cell = 0.0 if cell is None else float(cell)                              # (0: the entry's default)
+    sp = C.c_void_p(seg.ctypes.data) if S else None
+    check(lib().lm_line_index_build(sp, S, float(half_width), cell, C.byref(g), None, 0, None, 0))
+    cell_start = np.zeros(g.nx * g.ny + 1, dtype=np.int32)
+    cell_segs = np.zeros(max(int(g.n_entries), 1), dtype=np.int32)
+    check(lib().lm_line_index_build(sp, S, float(half_width), cell, C.byref(g), C.c_void_p(cell_start.ctypes.data), cell_start.size,
+                                    C.c_void_p(cell_segs.ctypes.data), cell_segs.size))
+    return g, cell_start, cell_segs[:int(g.n_entries)]
+
+
+def line_index(segments, half_width, cell=None, device='cuda:0'):
+    """segments [S,8] float32 numpy (las_io.line_segments) -> a LineIndex on `device`: the table and the grid's lists uploaded once, to
+    label any number of clouds with.  cell: see line_index_host; it changes the cost of a lookup, never a label."""
+    import numpy as np
+    seg = np.ascontiguousarray(segments, dtype=np.float32)
+    g, cell_start, cell_segs = line_index_host(seg, half_width, cell)
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise LanemapHipError('lanemapping_amd ops need tensors on an MI355X (HIP) device; no CPU fallback exists')
+    up = lambda a: torch.from_numpy(np.array(a, order='C', copy=True)).to(device)      # (a copy: the caller's array may be read-only)
+    return LineIndex(up(seg), up(cell_start), up(cell_segs), g, np.float32(half_width))
+
+
+def label_points(points, index, z_tol, min_intensity=None, want_dist2=False):
+    """points [N,4] f32 on device (x, y, z, intensity in the frame of the index' segments) -> line [N] int32: 0, or the number (from 1) of
+    the line whose band the point lies in, the nearest winning (the rule: include/lanemap_hip.h).  want_dist2: -> (line, dist2 [N] f32),
+    the squared horizontal distance to the winner, +inf without one.  No synchronisation."""
+    if not points.is_cuda:
+        raise LanemapHipError('lanemapping_amd ops need tensors on an MI355X (HIP) device; no CPU fallback exists')
+    assert points.dim() == 2 and points.shape[1] == 4 and points.is_contiguous() and points.dtype == torch.float32
+    if not isinstance(index, LineIndex):
+        raise TypeError(f'label_points: index must be an ops.LineIndex (ops.line_index), not {type(index).__name__}')
+    N = int(points.shape[0])
+    line = torch.empty((N,), device=points.device, dtype=torch.int32)
+    dist2 = torch.empty((N,), device=points.device, dtype=torch.float32) if want_dist2 else None
+    mi = math.nan if min_intensity is None else float(min_intensity)
+    check(lib().lm_label_points(_stream(), _ptr(points) if N else None, N, *index.args(), float(z_tol), mi, _ptr(line) if N else None,
+                                _ptr(dist2) if (want_dist2 and N) else None))
+    return (line, dist2) if want_dist2 else line
 
 
 def _tilted(p):

@@ -300,6 +300,7 @@ class Runner:
     _las_intensity = functools.partialmethod(_las_option, 'intensity', 'las_intensity', 'IntensityStretch')  # the intensity window
     _las_elevation = functools.partialmethod(_las_option, 'elevation', 'las_elevation', 'ElevationDrape')  # the vertex heights
     _las_density = functools.partialmethod(_las_option, 'density', 'las_density', 'GapFill')               # the gap fill
+    _las_label = functools.partialmethod(_las_option, 'label', 'las_label', 'MarkingLabels')               # the labelled LAS files
 
     @staticmethod
     def _params_dir(out_dir):
@@ -307,6 +308,39 @@ class Runner:
         par_dir = os.path.join(out_dir, 'params')
         os.makedirs(par_dir, exist_ok=True)
         return par_dir
+
+    @staticmethod
+    def _label_plan(paths):
+        """The input files of a `label=` call, each once (a file listed with several parameter files is labelled once, with the first
+        listing's read offset), in input order.  The outputs are named by the input's basename: two different files that share one would
+        overwrite each other in labelled/ and labels.json and are refused, before anything is read."""
+        seen, plan = {}, []
+        for path in paths:
+            real, base = os.path.realpath(path), os.path.basename(path)
+            if seen.setdefault(base, real) != real:
+                raise ValueError(f'label: {seen[base]} and {real} share the basename {base!r}, under which both would be written to '
+                                 'labelled/; rename one of them')
+            if real not in plan:
+                plan.append(real)
+        return plan
+
+    def _label_inputs(self, labels, files, result, out_dir):
+        """The last stage of the LAS routes: every input file (files: (path, shift, select) in input order) labelled against the lines the
+        call returns - `merged`, or the tiles' 3-D lines in tile-name order when nothing was merged - and written to
+        <out_dir>/labelled/<basename>; what was done goes to <out_dir>/params/labels.json as {file: [records, labelled, [per-line counts]]}."""
+        from . import las_io
+        lines3d, merged = result
+        lines = list(merged) if len(merged) else [l for name in sorted(lines3d) for l in lines3d[name]]
+        done, todo = {}, self._label_plan([f[0] for f in files])
+        for path, shift, select in files:
+            if os.path.realpath(path) not in todo:
+                continue                                                   # (listed before: labelled once)
+            todo.remove(os.path.realpath(path))
+            base = os.path.basename(path)
+            r = las_io.label_las(path, os.path.join(out_dir, 'labelled', base), lines, labels, shift, select=select, device=self.device)
+            done[base] = [r['records'], r['labelled'], r['per_line']]
+        with open(os.path.join(self._params_dir(out_dir), 'labels.json'), 'w') as f:
+            json.dump(done, f, indent=1)
 
     def _follow_ground(self, gf, names, plist, points, offs, rpar, H, W, out_dir):
         """One batch of tiles through a las_io.GroundFilter: -> (plist, points, offs, rpar) to rasterise and back-project with.  The ground
@@ -372,7 +406,7 @@ class Runner:
         return raster_batch(names, plist, points, offs, rpar, scales)
 
     def infer_las_to_map(self, las_and_params, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None, ground=None,
-                         intensity=None, elevation=None, density=None):
+                         intensity=None, elevation=None, density=None, label=None):
         """LAS tiles -> map-level 3-D lane lines, every stage of the reference's offline chain on this stack:
 
           LAS file + tile parameter file (utils/io_utils.py:125-150)
@@ -405,11 +439,21 @@ class Runner:
         picks the radius per tile from the tile's gap histogram (ops.tile_gap_hist, one device-to-host read per batch;
         las_io.gap_radius).  The network and the back-projection both get the filled tile; `elevation` reads the points and is not
         affected.  What was used is written to <work_dirs>/params/density.json as {tile name: [radius, hist[0], ..., hist[Rmax + 1]]}.
-        Order of the stages: select, (binning,) ground, intensity, rasteriser, density, network, elevation.
+        label: a las_io.MarkingLabels (default: cfg['las_label'], a dict of its arguments; absent: nothing changes): after the merge every
+        input LAS file is labelled against the lines the call returns (`merged`, or the tiles' lines when nothing was merged): one
+        lm_las_label_records call per file, with the file's own las_read_offset and `select` - a record `select` dropped is never
+        relabelled.  The file comes back as <work_dirs>/labelled/<basename of the input> with the classification (and, with line_ids, the
+        point source ID) of the labelled records patched and every other byte as it was; what was done is written to
+        <work_dirs>/params/labels.json as {file: [records, labelled, [per-line counts]]}.  A file listed several times is labelled once
+        (with the read offset of its first listing); two different files with one basename are refused with a ValueError before anything
+        runs.  The return value does not change.
+        Order of the stages: select, (binning,) ground, intensity, rasteriser, density, network, elevation, (merge,) label.
         Single rank (the merge is sequential over the sorted tiles)."""
         from . import las_io
         select, ground, intensity = self._las_select(select), self._las_ground(ground), self._las_intensity(intensity)
-        elevation, density = self._las_elevation(elevation), self._las_density(density)
+        elevation, density, label = self._las_elevation(elevation), self._las_density(density), self._las_label(label)
+        if label is not None:
+            self._label_plan([p for p, _ in las_and_params])              # (a basename collision is refused before anything runs)
         if intensity is not None and intensity.scope == 'strip':
             raise ValueError("intensity: scope='strip' needs the whole strip in one cloud (infer_las_strip_to_map); infer_las_to_map reads "
                              "its tiles file by file, use scope='tile'")
@@ -420,11 +464,13 @@ class Runner:
         H, W = self.cfg.list_img_size_xy[1], self.cfg.list_img_size_xy[0]
         out_dir = work_dirs or self.cfg.get('work_dirs', './work_dirs')
         raster_batch, close = self._las_chain(work_dirs, merge, elevation, density)
+        inputs = []
         for i in range(0, len(las_and_params), B):
             chunk = las_and_params[i:i + B]
             pts, offs, rpar, names, plist = [], [0], [], [], []
             for las_path, param_path in chunk:
                 params = io_utils.load_pc_2_img_transform_paras(param_path)
+                inputs.append((las_path, params['las_read_offset'], select))
                 p, _ = las_io.read_las_raw(las_path, self.device, shift=params['las_read_offset'], select=select)
                 pts.append(p)
                 offs.append(offs[-1] + p.shape[0])
@@ -435,7 +481,10 @@ class Runner:
             if ground is not None:
                 plist, pts, offs, rpar = self._follow_ground(ground, names, plist, pts, offs, rpar, H, W, out_dir)
             self._raster_stretched(raster_batch, intensity, names, plist, pts, offs, rpar, H, W, out_dir, used)
-        return close()
+        result = close()
+        if label is not None:
+            self._label_inputs(label, inputs, result, out_dir)
+        return result
 
     def _las_chain(self, work_dirs, merge, elevation=None, density=None):
         """The chain behind infer_las_to_map / infer_las_strip_to_map from the rasteriser on: -> (raster_batch, close).
@@ -574,7 +623,7 @@ class Runner:
         return names, plist
 
     def infer_las_strip_to_map(self, las_paths, param_paths, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None,
-                               ground=None, intensity=None, elevation=None, density=None):
+                               ground=None, intensity=None, elevation=None, density=None, label=None):
         """A whole strip -> map-level lane lines: the LAS file(s) of the strip are read once, their points are binned into the tiles of
         the layout on the GPU (ops.strip_bin_points: the windows of `param_paths` may overlap and be rotated), and every batch of tiles
         then runs the chain of infer_las_to_map from the rasteriser on.  Same outputs under the same names; a tile is named by the
@@ -586,13 +635,16 @@ class Runner:
         height selection of `ground`).  scope='strip': one window for every tile, found once over all binned ranges before the batch
         loop - BEFORE `ground`'s height selection, which runs per batch: points it later drops still count for the strip's window.
         elevation: as for infer_las_to_map, after the network, on the ranges the rasteriser saw (after `ground` and `intensity`).
-        density: as for infer_las_to_map, per batch between the rasteriser and the network."""
+        density: as for infer_las_to_map, per batch between the rasteriser and the network.
+        label: as for infer_las_to_map, last: every file of `las_paths` is labelled with the layout's las_read_offset and `select`."""
         from . import las_io
         if isinstance(las_paths, (str, os.PathLike)):
             las_paths = [las_paths]
         names, plist = self._strip_layout(list(param_paths))
         select, ground, intensity = self._las_select(select), self._las_ground(ground), self._las_intensity(intensity)
-        elevation, density = self._las_elevation(elevation), self._las_density(density)
+        elevation, density, label = self._las_elevation(elevation), self._las_density(density), self._las_label(label)
+        if label is not None:
+            self._label_plan(las_paths)                                    # (a basename collision is refused before anything runs)
         used = {}
         if path_ckpt:
             self.load_ckpt(path_ckpt)
@@ -622,7 +674,10 @@ class Runner:
                 if ground is not None:
                     batch = self._follow_ground(ground, names[i:j], *batch, H, W, out_dir)
                 self._raster_stretched(raster_batch, intensity, names[i:j], *batch, H, W, out_dir, used, strip)
-        return close()
+        result = close()
+        if label is not None and plist:
+            self._label_inputs(label, [(path, plist[0]['las_read_offset'], select) for path in las_paths], result, out_dir)
+        return result
 
     def infer_lane_geometry_segmentation_segmentor(self, path_ckpt=None, mode_view=False, write_lane_vertex=False,
                                                    *, tiles=None, batch_size=None, gt_avail=None):
