@@ -570,6 +570,55 @@ int lm_las_label_records(void* hip_stream, const unsigned char* records, int rec
                          float min_intensity, int marking_class, int write_line_id, unsigned char* records_out, int* line,
                          unsigned long* counts, int L);
 
+/* ---- the marking profile (csrc/profile.hip): every lane line profiled from the returns the labelling rule gives it - per station bin
+ * along the line the count, the summed intensity and the lateral spread of its returns; paint runs, dash pattern, width and brightness are
+ * read off the bins on the host (las_io.marking_summary).
+ * HOST TABLES (las_io.line_stations(lines, shift, bin)), rows in exactly the order of the segment table:
+ *     stations [S][4] f32 = s0, len, rlen, 0.  len64 = sqrt(dx dx + dy dy) in f64 from the f32 dx, dy of the segment row; s0 = the f64
+ *         running sum of the len64 of the earlier segments of the same line, rounded to f32; len = (f32)len64; rlen = (f32)(1 / len64), or 0
+ *         where len64 == 0.
+ *     bin_start [L + 1] int32, a CSR table: line k (from 1) owns the bins bin_start[k-1] .. bin_start[k] - 1; a line with segments owns
+ *         max(1, ceil(total len64 / bin)) bins, a line with fewer than two vertices none.  bin is finite and > 0.
+ * PER POINT.  Eligibility, the hit test and the winner are exactly the labelling rule's above (smallest d2, ties to the smaller line, then
+ * to the smaller segment index).  For a point whose winner is segment s of line k, with the clamped t and px, py of that rule, plain f32,
+ * no contraction:
+ *     st = s0 + t len
+ *     b  = min((int)(st inv_bin), nb_k - 1)                  inv_bin = (f32)(1 / bin), nb_k the number of bins of line k
+ *     o  = (dx py - dy px) rlen                              the signed offset, left of the line positive; 0 on a zero-length segment
+ *     q  = (int)rintf(o 1024.f)
+ *     iq = (unsigned)fminf(fmaxf(rintf(i), 0.f), 65535.f)    a NaN intensity gives 0
+ * OUTPUT.  bins [n_bins][6] int64 = n, sum iq, sum q, sum q q, min q, max q per bin; an empty bin reads 0, 0, 0, 0, 2^31 - 1, -2^31.
+ * Everything is an integer sum, minimum or maximum: the result does not depend on the order of the points or of the adds, and every run
+ * writes the same bits.  No float atomic is used.  half_width above 16 m is refused, so that |q| <= 2^14 + 1 and the sums of 2^31 points
+ * stay far inside 64 bits.  WITHOUT a min_intensity a bin counts returns, not paint: width and dash pattern then measure the band and the
+ * point density, so a threshold between asphalt and paint is needed for them to mean anything.
+ * line_profile_points: points_xyzi DEVICE [N][4] f32, then the index arguments of lm_label_points.
+ * las_line_profile_records: the inputs of lm_las_label_records up to `select`, then the index.  The records are only read: staged through
+ *         LDS and decoded as there; a record that `select` drops contributes nothing.
+ * Both: stations DEVICE [S][4] f32 (16-byte aligned); bin_start DEVICE [L + 1] int32, what the kernel reads; bin_start_host its HOST copy,
+ *         what the call checks (from 0, not descending, bin_start_host[L] == n_bins) - the host cannot see a device table without a
+ *         read-back, so the table travels twice, as `grid` travels beside cell_start.  TRUST: the device tables are the caller's word;
+ *         whatever they hold, the kernels read bin_start only in [0, L] and write bins only in [0, n_bins).  accumulate = 0: the call
+ *         initialises bins on the stream first; accumulate = 1: it adds to what is there - the files of a strip go into one profile this
+ *         way.  Asynchronous, no workspace, nothing read back.  N = 0, S = 0 or n_bins = 0 is LM_OK.
+ *         The wave merges before it goes to memory: per distinct bin among its lanes one reduction and one row of six 64-bit integer
+ *         atomics; a wave without a candidate leaves early as in the label kernels.
+ * Refused with LM_ERR_ARG and a message that names the argument, before anything is launched or written: what lm_label_points /
+ * lm_las_label_records refuse of the shared arguments; half_width > 16; bin <= 0 or not finite; accumulate outside 0, 1; segments whose
+ * lines leave 1 .. L; n_bins != bin_start_host[L]; a bin_start_host that does not start at 0 or descends; null buffers; a misaligned
+ * buffer, named alone ("bins is not 8-byte aligned").
+ * NOTE on the name `hip_stream`: as for lm_label_points above; the guarded-buffer cases of these two entries are
+ * tests/test_gpu_profile.py::test_profile_points_guards and ::test_profile_records_guards. */
+int lm_line_profile_points(void* hip_stream, const float* points_xyzi, long N, const float* segments, long S, const LmLineGrid* grid,
+                           const int* cell_start, const int* cell_segs, float half_width, const float* stations, const int* bin_start,
+                           const int* bin_start_host, int L, double bin, float z_tol, float min_intensity, int accumulate, long* bins,
+                           long n_bins);
+int lm_las_line_profile_records(void* hip_stream, const unsigned char* records, int record_len, int point_format, long n,
+                                const double* scale, const double* offset, const double* shift, const LmLasSelect* select,
+                                const float* segments, long S, const LmLineGrid* grid, const int* cell_start, const int* cell_segs,
+                                float half_width, const float* stations, const int* bin_start, const int* bin_start_host, int L, double bin,
+                                float z_tol, float min_intensity, int accumulate, long* bins, long n_bins);
+
 /* ---- PNG tile ingest (replaces PIL in `load_img`, baseline/datasets/laserlane_proposals.py:85-98 and laserlane.py:214-219:
  * np.array(Image.open(path)) -> uint8 HWC).  Host code, no third-party library (PIL runs zlib; the DEFLATE decoder here is
  * csrc/inflate.h), 8-bit non-interlaced grey / grey+alpha / RGB / RGBA only; palette, 16-bit and Adam7 files are refused; chunk CRCs

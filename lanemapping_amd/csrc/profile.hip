@@ -1,0 +1,318 @@
+// The marking profile: every lane line profiled from the returns that the labelling rule gives it - per station bin along the line the
+// number of returns, their summed intensity, and the sum, sum of squares, minimum and maximum of their lateral offset.  What a lane map's
+// user asks next after the labels: which lines are dashed, how wide the paint is, how bright (las_io.marking_summary is the host policy on
+// top of the bins).
+//
+// The rule (one definition: the two kernels here, include/lanemap_hip.h and tests/profile_ref.py).  Eligibility, the hit test and the
+// winner are label.hip's (label_rule.h).  Beside the segment table the host cuts a station table (las_io.line_stations): rows s0, len,
+// rlen, 0 of float32 in the order of the segments - s0 the arc length of the line up to the segment, len its length in the plane, rlen
+// 1 / len or 0 - and bin_start [L + 1], the CSR table of the bins each line owns.  For a point whose winner is segment s of line k, with
+// the clamped t and px, py of the labelling rule, plain float32, no contraction (build.py EXACT_FP):
+//     st = s0 + t*len
+//     b  = min((int)(st * inv_bin), nb_k - 1)                        inv_bin = (float)(1 / bin), nb_k = bin_start[k] - bin_start[k-1]
+//     o  = (dx*py - dy*px) * rlen                                    the signed offset, left of the line positive
+//     q  = (int)rintf(o * 1024.f)
+//     iq = (unsigned)fminf(fmaxf(rintf(i), 0.f), 65535.f)            a NaN intensity: 0
+// and bins[bin_start[k-1] + b] takes n += 1, sum iq, sum q, sum q*q, min q, max q.  Everything is an integer sum, minimum or maximum: the
+// result does not depend on the order of the points or of the adds, and every run writes the same bits.  No float atomic anywhere.
+//
+// Where the time goes.  Reads and search are label.hip's; the new part is the accumulation.  Paint returns arrive in scanner order: the
+// lanes of a wave that hit anything mostly hit the same one to three bins, and most waves hit nothing and leave through the same
+// wave-uniform exit as the label kernels.  So the lanes are merged inside the wave before anything goes to memory: loop over the distinct
+// bins present in the wave (ballot, first set lane), reduce the six quantities across the lanes of that bin, and lanes 0 .. 5 issue the
+// six 64-bit integer atomics of the bin's row (48 contiguous bytes).  A bin held by one lane alone skips the reduction.
+#include "common.h"
+#include "label_rule.h"
+#include "las_record.h"
+
+#include <cmath>
+#include <map>
+#include <mutex>
+#include <utility>
+
+struct LmLasSelect {          // include/lanemap_hip.h
+    unsigned class_mask[8];
+    unsigned drop_flags;
+    int returns;
+    float z_lo, z_hi;
+};
+
+namespace {
+
+constexpr int PER = 4;                   // points per lane of profile_points_kernel, as label_points_kernel
+constexpr int CHUNK = 256 * PER;
+constexpr int REC_GROUPS = 4096;         // cap on the workgroups of the record kernel
+constexpr float MAX_HALF_WIDTH = 16.f;   // |q| <= 16 * 1024 + 1: q*q < 2^29, and 2^31 of them stay far inside 64 bits
+
+struct ProfDev {
+    const float4* stations;              // [S]: s0 len rlen 0
+    const int* bin_start;                // [L + 1]
+    long long* bins;                     // [n_bins][6]
+    int L, n_bins;
+    float inv_bin;
+};
+
+// the bin (absolute, -1: none), q and iq of a point whose winner is segment s of line ln at t.  bin_start and stations are device tables
+// the host cannot see: whatever they hold, a bin outside [0, n_bins) is never returned and bin_start is never read outside [0, L].
+__device__ __forceinline__ int profile_bin(const float4 p, const IndexDev& I, const ProfDev& P, int ln, int s, float t, int& q, unsigned& iq) {
+    q = 0, iq = 0u;
+    if (ln <= 0 || ln > P.L) return -1;
+    const int base = P.bin_start[ln - 1], nb = P.bin_start[ln] - base;
+    if (base < 0 || nb <= 0 || nb > P.n_bins - base) return -1;
+    const float4 A = I.seg[2 * s], D = I.seg[2 * s + 1], T = P.stations[s];
+    const float px = p.x - A.x, py = p.y - A.y;
+    const float st = T.x + t * T.y;
+    int b = (int)(st * P.inv_bin);
+    b = b < nb - 1 ? b : nb - 1;
+    b = b > 0 ? b : 0;                                                 // (st >= 0 in a table of las_io.line_stations)
+    const float o = (A.w * py - D.x * px) * T.z;
+    q = (int)rintf(o * 1024.f);
+    iq = (unsigned)fminf(fmaxf(rintf(p.w), 0.f), 65535.f);
+    return base + b;
+}
+
+// Wave-uniform: every lane of the wave calls it, B = -1 where the lane has nothing.  Per distinct bin of the wave one reduction and
+// one row of six atomics.
+__device__ __forceinline__ void profile_merge(long long* __restrict__ bins, int B, int q, unsigned iq) {
+    const int lane = (int)__lane_id();
+    unsigned long long todo = __ballot(B >= 0);
+    while (todo) {
+        const int leader = __ffsll(todo) - 1;
+        const int lb = __shfl(B, leader);
+        const bool mine = B == lb;
+        const unsigned long long m = __ballot(mine);
+        unsigned long long n = 1, siq, sqq;
+        long long sq;
+        int mn, mx;
+        if (__popcll(m) == 1) {                                        // one lane alone: its values, read off the leader
+            const int ql = __shfl(q, leader);
+            siq = (unsigned)__shfl((int)iq, leader);
+            sq = ql, sqq = (unsigned long long)((long long)ql * ql), mn = mx = ql;
+        } else {
+            n = (unsigned long long)__popcll(m);
+            unsigned a_iq = mine ? iq : 0u;                            // 64 * 65535 and 64 * 16385 fit 32 bits; q*q needs 64
+            int a_q = mine ? q : 0;
+            unsigned long long a_qq = mine ? (unsigned long long)((long long)q * q) : 0ull;
+            mn = mine ? q : 2147483647, mx = mine ? q : (-2147483647 - 1);
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) {
+                a_iq += (unsigned)__shfl_xor((int)a_iq, d);
+                a_q += __shfl_xor(a_q, d);
+                a_qq += (unsigned long long)__shfl_xor((long long)a_qq, d);
+                const int on = __shfl_xor(mn, d), ox = __shfl_xor(mx, d);
+                mn = on < mn ? on : mn, mx = ox > mx ? ox : mx;
+            }
+            siq = a_iq, sq = a_q, sqq = a_qq;
+        }
+        long long* row = bins + (long)lb * 6;
+        if (lane < 4) {
+            const unsigned long long v = lane == 0 ? n : lane == 1 ? siq : lane == 2 ? (unsigned long long)sq : sqq;
+            atomicAdd(reinterpret_cast<unsigned long long*>(row) + lane, v);
+        } else if (lane == 4) {
+            atomicMin(row + 4, (long long)mn);
+        } else if (lane == 5) {
+            atomicMax(row + 5, (long long)mx);
+        }
+        todo &= ~m;
+    }
+}
+
+// grid: ceil(n_bins * 6 / 256)
+__global__ __launch_bounds__(256) void profile_init_kernel(long long* __restrict__ bins, long words) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < words) {
+        const int c = (int)(i % 6);
+        bins[i] = c < 4 ? 0LL : c == 4 ? 2147483647LL : -2147483648LL;
+    }
+}
+
+// grid: ceil(N / 1024) workgroups
+__global__ __launch_bounds__(256) void profile_points_kernel(const lab_f32x4* __restrict__ pts, long N, IndexDev I, ProfDev P) {
+    const long first = (long)blockIdx.x * CHUNK;
+    const long left = N - first;                               // >= 1
+    float4 p[PER];
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        const long i = (long)j * 256 + threadIdx.x;
+        const lab_f32x4 v = __builtin_nontemporal_load(pts + first + (i < left ? i : left - 1));   // unconditional, tail lanes masked below
+        p[j] = float4{v[0], v[1], v[2], v[3]};
+    }
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        const long i = (long)j * 256 + threadIdx.x;
+        int a = 0, b = 0;
+        if (i < left) label_range(p[j], I, a, b);
+        if (__ballot(b > a) == 0) continue;                    // wave-uniform: a wave beside the lines leaves here
+        float best, t;
+        int s;
+        const int ln = label_search_t<true>(p[j], I, a, b, best, s, t);
+        int q = 0, B = -1;
+        unsigned iq = 0u;
+        if (ln > 0) B = profile_bin(p[j], I, P, ln, s, t, q, iq);
+        profile_merge(P.bins, B, q, iq);
+    }
+}
+
+// grid: min(blocks of 256 records, the workgroups resident at once) workgroups; dynamic LDS = 256 records.  Per block: stage, decode into
+// registers, barrier (the stage is free again), search and accumulate.  The records are only read.
+__global__ __launch_bounds__(256) void las_profile_kernel(const unsigned* __restrict__ rec, int record_len, long n, long nblk, LasXf X, LasSel S,
+                                                          int use_sel, IndexDev I, ProfDev P) {
+    extern __shared__ unsigned prof_stage[];
+    for (long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+        const int cnt = las_stage_block(rec, record_len, n, blk, prof_stage);
+        float4 p = {0.f, 0.f, 0.f, 0.f};
+        int a = 0, b = 0;
+        if ((int)threadIdx.x < cnt) {
+            const unsigned char* r = reinterpret_cast<const unsigned char*>(prof_stage) + (int)threadIdx.x * record_len;
+            bool pass = true;
+            unsigned cls;
+            if (use_sel) pass = las_record_keep(r, X, S, cls, p);
+            else p = las_record_xyzi(r, X);
+            if (pass) label_range(p, I, a, b);                 // a record that `select` drops contributes nothing
+        }
+        __syncthreads();                                       // every record is in registers: the next block may be staged
+        if (__ballot(b > a) == 0) continue;
+        float best, t;
+        int s;
+        const int ln = label_search_t<true>(p, I, a, b, best, s, t);
+        int q = 0, B = -1;
+        unsigned iq = 0u;
+        if (ln > 0) B = profile_bin(p, I, P, ln, s, t, q, iq);
+        profile_merge(P.bins, B, q, iq);
+    }
+}
+
+// Workgroups of las_profile_kernel the current device holds at once for `lds` bytes of dynamic LDS (as label.hip's: asked of the runtime
+// once per (device, lds) and kept; the number only sizes the grid).
+int resident_groups(size_t lds, long& groups) {
+    static std::mutex mu;
+    static std::map<std::pair<int, size_t>, long> known;
+    int dev_id = 0;
+    LM_HIP(hipGetDevice(&dev_id));
+    std::lock_guard<std::mutex> lock(mu);
+    const auto it = known.find({dev_id, lds});
+    if (it != known.end()) {
+        groups = it->second;
+        return LM_OK;
+    }
+    int per_cu = 0, cus = 0;
+    LM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, las_profile_kernel, 256, lds));
+    LM_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev_id));
+    groups = (long)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 256);
+    groups = groups < REC_GROUPS ? groups : REC_GROUPS;
+    known[{dev_id, lds}] = groups;
+    return LM_OK;
+}
+
+// the arguments both entries share, checked before anything is launched or written
+int check_profile(const char* who, const LmLineGrid* grid, long S, const void* segments, const void* cell_start, const void* cell_segs,
+                  float half_width, const float* stations, const int* bin_start, const int* bin_start_host, int L, double bin, float z_tol,
+                  int accumulate, long* bins, long n_bins, IndexDev& I, ProfDev& P) {
+    if (int e = check_index(who, grid, S, segments, cell_start, cell_segs, half_width, z_tol, I)) return e;
+    LM_REQUIRE(half_width <= MAX_HALF_WIDTH, "%s: half_width=%g, at most %g m is supported (the offsets are summed in 1/1024 m)", who,
+               (double)half_width, (double)MAX_HALF_WIDTH);
+    LM_REQUIRE(bin > 0 && bin < HUGE_VAL, "%s: bin=%g must be a finite length > 0", who, bin);
+    LM_REQUIRE(accumulate == 0 || accumulate == 1, "%s: accumulate=%d is neither 0 nor 1", who, accumulate);
+    LM_REQUIRE(L >= 0, "%s: L=%d lines", who, L);
+    LM_REQUIRE(S == 0 || (grid->min_line >= 1 && grid->max_line <= L), "%s: segments carry lines %d .. %d, outside 1 .. L=%d", who,
+               S ? grid->min_line : 0, S ? grid->max_line : 0, L);
+    LM_REQUIRE(bin_start_host, "%s: null pointer (bin_start_host)", who);
+    LM_REQUIRE(bin_start_host[0] == 0, "%s: bin_start[0]=%d must be 0", who, bin_start_host[0]);
+    for (int k = 0; k < L; ++k)
+        LM_REQUIRE(bin_start_host[k + 1] >= bin_start_host[k], "%s: bin_start[%d]=%d is below bin_start[%d]=%d", who, k + 1,
+                   bin_start_host[k + 1], k, bin_start_host[k]);
+    LM_REQUIRE(n_bins == (long)bin_start_host[L], "%s: n_bins=%ld, but bin_start[L]=%d", who, n_bins, bin_start_host[L]);
+    LM_REQUIRE(S == 0 || (stations && bin_start), "%s: null pointer (stations, bin_start)", who);
+    LM_REQUIRE(n_bins == 0 || bins, "%s: null pointer (bins)", who);
+    LM_REQUIRE(((uintptr_t)stations & 15) == 0, "%s: stations is not 16-byte aligned", who);
+    LM_REQUIRE(((uintptr_t)bin_start & 3) == 0, "%s: bin_start is not 4-byte aligned", who);
+    LM_REQUIRE(((uintptr_t)bins & 7) == 0, "%s: bins is not 8-byte aligned", who);
+    P = ProfDev{reinterpret_cast<const float4*>(stations), bin_start, reinterpret_cast<long long*>(bins), L, (int)n_bins,
+                (float)(1.0 / bin)};
+    return LM_OK;
+}
+
+int init_bins(const ProfDev& P, hipStream_t s) {
+    const long words = (long)P.n_bins * 6;
+    if (words == 0) return LM_OK;
+    hipLaunchKernelGGL(profile_init_kernel, dim3((unsigned)lm_cdivl(words, 256)), dim3(256), 0, s, P.bins, words);
+    LM_LAUNCH_CHECK();
+    return LM_OK;
+}
+
+}  // namespace
+
+// points_xyzi: DEVICE [N][4] f32; the index arguments of lm_label_points; stations DEVICE [S][4] f32, bin_start DEVICE [L + 1] int32,
+// bin_start_host its HOST copy (what the call checks); bins DEVICE [n_bins][6] int64.  Asynchronous, no workspace.
+LM_API int lm_line_profile_points(void* hip_stream, const float* points_xyzi, long N, const float* segments, long S, const LmLineGrid* grid,
+                                  const int* cell_start, const int* cell_segs, float half_width, const float* stations,
+                                  const int* bin_start, const int* bin_start_host, int L, double bin, float z_tol, float min_intensity,
+                                  int accumulate, long* bins, long n_bins) {
+    IndexDev I;
+    ProfDev P;
+    if (int e = check_profile("line_profile_points", grid, S, segments, cell_start, cell_segs, half_width, stations, bin_start, bin_start_host,
+                              L, bin, z_tol, accumulate, bins, n_bins, I, P))
+        return e;
+    LM_REQUIRE(N >= 0 && N <= 2147483647L, "line_profile_points: N=%ld points, at most 2^31 - 1 are supported", N);
+    LM_REQUIRE(N == 0 || points_xyzi, "line_profile_points: null pointer (points_xyzi)");
+    LM_REQUIRE(((uintptr_t)points_xyzi & 15) == 0, "line_profile_points: points_xyzi is not 16-byte aligned");
+    I.min_inten = min_intensity;
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (!accumulate)
+        if (int e = init_bins(P, s)) return e;
+    if (N == 0 || S == 0 || n_bins == 0) return LM_OK;
+    hipLaunchKernelGGL(profile_points_kernel, dim3((unsigned)lm_cdivl(N, CHUNK)), dim3(256), 0, s, reinterpret_cast<const lab_f32x4*>(points_xyzi),
+                       N, I, P);
+    LM_LAUNCH_CHECK();
+    return LM_OK;
+}
+
+// records: DEVICE, n record_len bytes rounded up to a multiple of 4, 4-byte aligned, only read; the rest as above.
+LM_API int lm_las_line_profile_records(void* hip_stream, const unsigned char* records, int record_len, int point_format, long n,
+                                       const double* scale, const double* offset, const double* shift, const LmLasSelect* select,
+                                       const float* segments, long S, const LmLineGrid* grid, const int* cell_start, const int* cell_segs,
+                                       float half_width, const float* stations, const int* bin_start, const int* bin_start_host, int L,
+                                       double bin, float z_tol, float min_intensity, int accumulate, long* bins, long n_bins) {
+    static const int min_len[11] = {20, 28, 26, 34, 57, 63, 30, 36, 38, 59, 67};
+    const char* who = "las_line_profile_records";
+    LM_REQUIRE(point_format >= 0 && point_format <= 10, "%s: unknown point data record format point_format=%d", who, point_format);
+    LM_REQUIRE(record_len >= min_len[point_format] && record_len <= 160, "%s: bad record_len=%d for format %d (%d .. 160)", who, record_len,
+               point_format, min_len[point_format]);
+    LM_REQUIRE(n >= 0 && n <= 2147483647L, "%s: n=%ld records, at most 2^31 - 1 are supported", who, n);
+    IndexDev I;
+    ProfDev P;
+    if (int e = check_profile(who, grid, S, segments, cell_start, cell_segs, half_width, stations, bin_start, bin_start_host, L, bin, z_tol,
+                              accumulate, bins, n_bins, I, P))
+        return e;
+    LM_REQUIRE(scale && offset && (n == 0 || records), "%s: null pointer (scale, offset, records)", who);
+    LM_REQUIRE(((uintptr_t)records & 3) == 0, "%s: records is not 4-byte aligned", who);
+    LasSel Sel{};
+    if (select) {
+        LM_REQUIRE(select->returns >= 0 && select->returns <= 3, "%s: select returns=%d is none of all (0), first (1), last (2), single (3)", who,
+                   select->returns);
+        LM_REQUIRE(select->drop_flags < 16u, "%s: select drop_flags=%u has bits beyond synthetic | key-point | withheld | overlap", who,
+                   select->drop_flags);
+        LM_REQUIRE(select->z_lo == select->z_lo && select->z_hi == select->z_hi, "%s: select z_lo / z_hi must not be NaN", who);
+        for (int k = 0; k < 8; ++k) Sel.cls[k] = select->class_mask[k];
+        Sel.drop = select->drop_flags, Sel.returns = select->returns, Sel.z_lo = select->z_lo, Sel.z_hi = select->z_hi;
+    }
+    Sel.fmt6 = point_format >= 6;
+    I.min_inten = min_intensity;
+    hipStream_t s = (hipStream_t)hip_stream;
+    const bool work = n > 0 && S > 0 && n_bins > 0;
+    const long nblk = (n + 255) / 256;
+    const size_t lds = ((size_t)256 * record_len + 3) / 4 * 4;
+    long resident = 0;
+    if (work)
+        if (int e = resident_groups(lds, resident)) return e;
+    if (!accumulate)
+        if (int e = init_bins(P, s)) return e;
+    if (!work) return LM_OK;
+    const double sh[3] = {shift ? shift[0] : 0.0, shift ? shift[1] : 0.0, shift ? shift[2] : 0.0};
+    const LasXf X{scale[0], scale[1], scale[2], offset[0] - sh[0], offset[1] - sh[1], offset[2] - sh[2], 0.f, 1.f, 0};   // raw intensity
+    const unsigned groups = (unsigned)(nblk < resident ? nblk : resident);
+    hipLaunchKernelGGL(las_profile_kernel, dim3(groups), dim3(256), lds, s, reinterpret_cast<const unsigned*>(records), record_len, n, nblk, X,
+                       Sel, select ? 1 : 0, I, P);
+    LM_LAUNCH_CHECK();
+    return LM_OK;
+}

@@ -23,6 +23,10 @@ the intensities a tile, or the whole strip, keeps (`ops.tile_intensity_window`),
 
 `MarkingLabels` / `line_segments` / `label_las` are the way back: the returns of a file labelled by the lane lines found in it
 (`ops.line_index`, `ops.label_points`, `lm_las_label_records`), and the file written again with the markings classified.
+
+`MarkingSurvey` / `line_stations` / `survey_las` / `marking_summary` profile the lines from the same returns: per station bin along every
+line the count, intensity and lateral spread of its returns (`ops.line_profile`, `lm_las_line_profile_records`), and on the host the paint
+runs, dash pattern, width and brightness read off the bins.
 """
 import ctypes as C
 import math
@@ -500,6 +504,229 @@ def label_las(path, out_path, lines, labels, shift, select=None, device='cuda:0'
         f.write(data[off + nbytes:].tobytes())
     per_line = [int(c) for c in counts[1:]]
     return {'records': int(n), 'labelled': int(sum(per_line)), 'per_line': per_line}
+
+
+class MarkingSurvey:
+    """How the LAS -> map routes profile the lane lines they found from the returns of their input (immutable;
+    Runner.infer_las_strip_to_map / infer_las_to_map, `survey=`; survey_las, marking_summary).  The returns the labelling rule gives a line
+    (within half_width in the plane and z_tol in height, the nearest line winning) are accumulated per station bin along the line (the
+    rule: include/lanemap_hip.h); marking_summary then reads paint runs, width and intensity off the bins.
+
+      bin             metres (finite, > 0): the length of a station bin along a line
+      half_width      metres (finite, 0 .. 16): half the width of the band around a line whose returns are profiled
+      z_tol           metres (>= 0, may be infinite): the height band
+      min_intensity   None, or the smallest raw intensity a profiled return has.  WITHOUT it a bin counts returns, not paint: every bin of
+                      a line over asphalt is 'painted', the width is the width of the band and the dash pattern that of the point density.
+                      A threshold between asphalt and paint is needed for width, runs and type to mean anything
+      min_points      a bin counts as painted when it holds at least this many returns (whole number >= 1)
+      max_gap         metres (finite, >= 0): runs of painted bins separated by at most this length of unpainted bins are joined
+      solid_cover     0 < solid_cover <= 1: a line whose painted share reaches it is 'solid'
+    All defaults are plain defaults, not tuned values."""
+    __slots__ = ('bin', 'half_width', 'z_tol', 'min_intensity', 'min_points', 'max_gap', 'solid_cover')
+
+    def __init__(self, bin=0.25, half_width=0.3, z_tol=0.5, min_intensity=None, min_points=3, max_gap=0.5, solid_cover=0.8):
+        num = (int, float, np.integer, np.floating)
+        if isinstance(bin, bool) or not isinstance(bin, num) or not (0.0 < float(bin) < math.inf):
+            raise ValueError(f'MarkingSurvey: bin={bin!r} must be a finite length > 0')
+        if isinstance(half_width, bool) or not isinstance(half_width, num) or not (0.0 <= float(half_width) <= 16.0):
+            raise ValueError(f'MarkingSurvey: half_width={half_width!r} must be a number in 0 .. 16 (metres)')
+        if isinstance(z_tol, bool) or not isinstance(z_tol, num) or not float(z_tol) >= 0.0:
+            raise ValueError(f'MarkingSurvey: z_tol={z_tol!r} must be a number >= 0')
+        if min_intensity is not None:
+            if isinstance(min_intensity, bool) or not isinstance(min_intensity, num) or math.isnan(float(min_intensity)):
+                raise ValueError(f'MarkingSurvey: min_intensity={min_intensity!r} must be None or a number')
+            min_intensity = float(min_intensity)
+        if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)) or int(min_points) < 1:
+            raise ValueError(f'MarkingSurvey: min_points={min_points!r} must be a whole number >= 1')
+        if isinstance(max_gap, bool) or not isinstance(max_gap, num) or not (0.0 <= float(max_gap) < math.inf):
+            raise ValueError(f'MarkingSurvey: max_gap={max_gap!r} must be a finite length >= 0')
+        if isinstance(solid_cover, bool) or not isinstance(solid_cover, num) or not (0.0 < float(solid_cover) <= 1.0):
+            raise ValueError(f'MarkingSurvey: solid_cover={solid_cover!r} must be a number with 0 < solid_cover <= 1')
+        for k, v in (('bin', float(bin)), ('half_width', float(half_width)), ('z_tol', float(z_tol)), ('min_intensity', min_intensity),
+                     ('min_points', int(min_points)), ('max_gap', float(max_gap)), ('solid_cover', float(solid_cover))):
+            object.__setattr__(self, k, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError('MarkingSurvey is immutable')
+
+    def __delattr__(self, name):
+        raise AttributeError('MarkingSurvey is immutable')
+
+    def __repr__(self):
+        return 'MarkingSurvey(' + ', '.join(f'{k}={getattr(self, k)!r}' for k in self.__slots__) + ')'
+
+    def __eq__(self, other):
+        return isinstance(other, MarkingSurvey) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
+
+    def __hash__(self):
+        return hash(tuple(getattr(self, k) for k in self.__slots__))
+
+
+def line_stations(lines, shift=None, bin=0.25):
+    """Lines (as line_segments takes them) -> (stations [S,4] float32, bin_start [L + 1] int32): the station table of the marking profile,
+    its rows in exactly the order of line_segments(lines, shift), and the CSR table of the bins each of the L = len(lines) lines owns.
+    Row s0, len, rlen, 0: len64 = sqrt(dx^2 + dy^2) in float64 from the float32 dx, dy of the segment row; s0 = the float64 running sum
+    of the len64 of the earlier segments of the same line, rounded to float32; len = float32(len64); rlen = float32(1 / len64), 0 where
+    len64 == 0.  Line k (from 1) owns the bins bin_start[k-1] .. bin_start[k] - 1: max(1, ceil(total len64 / bin)) of them for a line with
+    segments, none for a line with fewer than two vertices."""
+    if isinstance(bin, bool) or not isinstance(bin, (int, float, np.integer, np.floating)) or not (0.0 < float(bin) < math.inf):
+        raise ValueError(f'line_stations: bin={bin!r} must be a finite length > 0')
+    bin = float(bin)
+    lines = list(lines)
+    seg = line_segments(lines, shift)
+    of_line = np.ascontiguousarray(seg[:, 7]).view(np.int32)
+    stations = np.zeros((len(seg), 4), dtype=np.float32)
+    bin_start = np.zeros(len(lines) + 1, dtype=np.int64)
+    for k in range(len(lines)):
+        rows = np.nonzero(of_line == k + 1)[0]                              # (consecutive, in vertex order)
+        nb = 0
+        if len(rows):
+            d = seg[rows, 3:5].astype(np.float64)
+            len64 = np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1])
+            run = np.concatenate([[0.0], np.add.accumulate(len64)])         # sequential float64 sums
+            stations[rows, 0] = run[:-1].astype(np.float32)
+            stations[rows, 1] = len64.astype(np.float32)
+            rlen = np.zeros_like(len64)
+            np.divide(1.0, len64, out=rlen, where=len64 != 0)
+            stations[rows, 2] = rlen.astype(np.float32)
+            nb = max(1, int(math.ceil(run[-1] / bin)))
+        bin_start[k + 1] = bin_start[k] + nb
+    if bin_start[-1] > 2147483647:
+        raise ValueError(f'line_stations: {int(bin_start[-1])} bins of {bin} m, at most 2^31 - 1 are supported (choose a larger bin)')
+    return stations, bin_start.astype(np.int32)
+
+
+def profile_records(records_u8, header, index, stations, survey, shift=None, select=None, out=None):
+    """One lm_las_line_profile_records call on the DEVICE records of a file (padded to a multiple of 4 bytes; `header`: parse_header's
+    dict) against an ops.LineIndex and the ops.LineStations of the same segments: -> bins [n_bins, 6] int64 device tensor (see
+    ops.line_profile).  The records are only read; a record `select` drops contributes nothing.  out: the bins of an earlier call to add to
+    - the files of a strip go into one profile this way.  Asynchronous."""
+    from . import ops
+    if not isinstance(survey, MarkingSurvey):
+        raise TypeError(f'las_io.profile_records: survey must be a MarkingSurvey, not {type(survey).__name__}')
+    if select is not None and not isinstance(select, PointFilter):
+        raise TypeError(f'las_io.profile_records: select must be a PointFilter, not {type(select).__name__}')
+    if not records_u8.is_cuda:
+        raise LanemapHipError('las_io.profile_records needs the records on an MI355X (HIP) device; no CPU fallback exists')
+    if not isinstance(index, ops.LineIndex) or not isinstance(stations, ops.LineStations):
+        raise TypeError('las_io.profile_records: index must be an ops.LineIndex and stations an ops.LineStations')
+    fmt, rl, n = header['point_format'], header['record_len'], header['n_points']
+    sel = select.for_format(fmt).as_struct() if select is not None else None
+    if index.half_width != np.float32(survey.half_width):
+        raise ValueError(f'las_io.profile_records: the index was built for half_width={index.half_width}, the survey asks {survey.half_width}')
+    if stations.bin != survey.bin or stations.n_segments != index.n_segments:
+        raise ValueError(f'las_io.profile_records: the stations were cut for bin={stations.bin} and {stations.n_segments} segments, the survey '
+                         f'asks bin={survey.bin}, the index holds {index.n_segments}')
+    dev = records_u8.device
+    bins = ops._profile_out('las_io.profile_records', stations, out, dev)
+    d3 = lambda v: (C.c_double * 3)(*[float(x) for x in v])
+    mi = math.nan if survey.min_intensity is None else survey.min_intensity
+    check(lib().lm_las_line_profile_records(C.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index)), C.c_void_p(records_u8.data_ptr()),
+                                            int(rl), int(fmt), int(n), d3(header['scale']), d3(header['offset']),
+                                            d3(shift) if shift is not None else None, C.byref(sel) if sel is not None else None,
+                                            *index.args(), *stations.args(), survey.z_tol, mi, int(out is not None),
+                                            C.c_void_p(bins.data_ptr()) if stations.n_bins else None, stations.n_bins))
+    return bins
+
+
+def survey_files(files, lines, survey, device='cuda:0'):
+    """The marking profile of `lines` (list of [n,3] float64, LAS frame) from the LAS files `files`, a list of (path, shift, select): every
+    file is uploaded and profiled in one lm_las_line_profile_records call with its own read offset and PointFilter, all into one bins
+    tensor, which is read back once.  The bins each line owns (bin_start) are those of the first file's frame; where another file's shift
+    rounds a line's length into one bin more, the rule's clamp to the line's last bin holds.
+    -> (bins [n_bins, 6] int64 numpy, bin_start [L + 1] int32 numpy)."""
+    from . import ops
+    if not isinstance(survey, MarkingSurvey):
+        raise TypeError(f'las_io.survey_files: survey must be a MarkingSurvey, not {type(survey).__name__}')
+    device = torch.device(device)
+    lines, files = list(lines), list(files)
+    tables, bin_start, bins = {}, None, None
+    for path, shift, select in files:
+        if select is not None and not isinstance(select, PointFilter):
+            raise TypeError(f'las_io.survey_files: select must be a PointFilter, not {type(select).__name__}')
+        data = np.fromfile(path, dtype=np.uint8)
+        h = parse_header(data)
+        n, rl, off = h['n_points'], h['record_len'], h['offset_to_points']
+        if select is not None:
+            select.for_format(h['point_format'])
+        key = None if shift is None else tuple(float(v) for v in shift)
+        if key not in tables:
+            st, bs = line_stations(lines, shift, survey.bin)
+            bin_start = bs if bin_start is None else bin_start
+            tables[key] = (ops.line_index(line_segments(lines, shift), survey.half_width, device=device),
+                           ops.line_stations(st, bin_start, survey.bin, device=device))
+        index, stations = tables[key]
+        nbytes = n * rl
+        padded = np.zeros(((nbytes + 3) // 4 * 4,), dtype=np.uint8)
+        padded[:nbytes] = data[off:off + nbytes]
+        rec = torch.from_numpy(padded).to(device, non_blocking=True)
+        bins = profile_records(rec, h, index, stations, survey, shift, select, out=bins)
+    if bins is None:                                                        # no file: the empty profile of the lines
+        bin_start = line_stations(lines, None, survey.bin)[1]
+        host = np.zeros((int(bin_start[-1]), 6), dtype=np.int64)
+        host[:, 4], host[:, 5] = 2 ** 31 - 1, -2 ** 31
+        return host, bin_start
+    return bins.cpu().numpy(), bin_start                                    # the one read-back
+
+
+def survey_las(paths, lines, survey, shift, select=None, device='cuda:0'):
+    """survey_files for files that share one read offset `shift` (the las_read_offset the lines were found with) and one PointFilter:
+    one call per file into one bins tensor, then one read-back.  -> (bins [n_bins, 6] int64 numpy, bin_start [L + 1] int32 numpy);
+    marking_summary(bins, bin_start, survey) reads the markings off them."""
+    if isinstance(paths, (str, os.PathLike)):
+        paths = [paths]
+    return survey_files([(p, shift, select) for p in paths], lines, survey, device)
+
+
+def marking_summary(bins, bin_start, survey):
+    """The markings read off a profile (host, integers and float64): bins [n_bins, 6] int64 (n, sum iq, sum q, sum q^2, min q, max q) and
+    bin_start [L + 1] -> one dict per line:
+
+      length      metres: the line's bins times survey.bin (the last bin may reach past the line's end)
+      painted     the number of painted bins; a bin counts as painted when n >= survey.min_points
+      runs        [[start_m, end_m], ...]: the maximal runs of painted bins, after runs separated by at most survey.max_gap metres of
+                  unpainted bins are joined
+      cover       painted bins over bins (painted length over length; 0.0 for a line without bins)
+      type        'solid' when cover >= survey.solid_cover; else 'dashed' with at least two runs; 'none' without a run; else 'partial'
+      dash, gap   the median run length and the median length between consecutive runs, metres (None without a run / below two runs)
+      width       metres: the median over the painted bins of (max q - min q) / 1024 (None without a painted bin)
+      intensity   sum iq / n over the painted bins (None without a painted bin)
+    Without survey.min_intensity a bin counts returns, not paint (see MarkingSurvey)."""
+    if not isinstance(survey, MarkingSurvey):
+        raise TypeError(f'marking_summary: survey must be a las_io.MarkingSurvey, not {type(survey).__name__}')
+    bins = np.asarray(bins)
+    bs = np.asarray(bin_start, dtype=np.int64)
+    if bins.ndim != 2 or bins.shape[1] != 6 or bins.dtype != np.int64 or bs.ndim != 1 or len(bs) < 1 or bs[0] != 0 or (np.diff(bs) < 0).any() \
+            or bs[-1] != len(bins):
+        raise ValueError(f'marking_summary: bins must be [bin_start[L], 6] int64 and bin_start a CSR table from 0, not {bins.shape} '
+                         f'{bins.dtype} and {bs.tolist() if len(bs) < 8 else bs.shape}')
+    w = survey.bin
+    gap_bins = int(math.floor(survey.max_gap / w + 1e-9))                   # the longest hole, in bins, that is joined
+    out = []
+    for k in range(len(bs) - 1):
+        b = bins[bs[k]:bs[k + 1]]
+        nb = len(b)
+        on = b[:, 0] >= survey.min_points
+        idx = np.nonzero(on)[0]
+        runs = []
+        for i in idx:
+            i = int(i)
+            if runs and i - runs[-1][1] - 1 <= gap_bins:
+                runs[-1][1] = i
+            else:
+                runs.append([i, i])
+        painted = int(on.sum())
+        cover = painted / nb if nb else 0.0
+        runs_m = [[i0 * w, (i1 + 1) * w] for i0, i1 in runs]
+        gaps_m = [(runs[j + 1][0] - runs[j][1] - 1) * w for j in range(len(runs) - 1)]
+        kind = 'solid' if (nb and cover >= survey.solid_cover) else 'dashed' if len(runs) >= 2 else 'none' if not runs else 'partial'
+        n_sum = int(b[on, 0].sum())
+        out.append({'length': nb * w, 'painted': painted, 'runs': runs_m, 'cover': cover, 'type': kind,
+                    'dash': float(np.median([(i1 - i0 + 1) * w for i0, i1 in runs])) if runs else None,
+                    'gap': float(np.median(gaps_m)) if gaps_m else None,
+                    'width': float(np.median((b[on, 5] - b[on, 4]).astype(np.float64) / 1024.0)) if painted else None,
+                    'intensity': int(b[on, 1].sum()) / n_sum if painted else None})
+    return out
 
 
 def parse_header(data):

@@ -787,6 +787,72 @@ def label_points(points, index, z_tol, min_intensity=None, want_dist2=False):
     return (line, dist2) if want_dist2 else line
 
 
+class LineStations:
+    """The station table of las_io.line_stations on the device, beside the LineIndex of the same segments: what line_profile and
+    las_io.profile_records take.  stations [S,4] f32 and bin_start [L + 1] int32 are device tensors; bin_start_host the same table as a
+    numpy array (the entries check it on the host); bin the bin length in metres; n_lines = L, n_bins = bin_start[L]."""
+
+    def __init__(self, stations, bin_start, bin_start_host, bin):
+        self.stations, self.bin_start, self.bin_start_host, self.bin = stations, bin_start, bin_start_host, float(bin)
+        self.n_segments, self.n_lines, self.n_bins = int(stations.shape[0]), int(bin_start_host.shape[0]) - 1, int(bin_start_host[-1])
+
+    def args(self):
+        """-> the (stations, bin_start, bin_start_host, L, bin) run of arguments of the two device entries."""
+        return (_ptr(self.stations) if self.n_segments else None, _ptr(self.bin_start), C.c_void_p(self.bin_start_host.ctypes.data),
+                self.n_lines, self.bin)
+
+    def new_bins(self):
+        """-> an uninitialised [n_bins, 6] int64 tensor on the tables' device."""
+        return torch.empty((self.n_bins, 6), device=self.bin_start.device, dtype=torch.int64)
+
+
+def line_stations(stations, bin_start, bin, device='cuda:0'):
+    """(stations [S,4] float32, bin_start [L + 1] int32) numpy, as las_io.line_stations(lines, shift, bin) returns them -> a LineStations
+    on `device`, uploaded once to profile any number of clouds with."""
+    import numpy as np
+    st = np.ascontiguousarray(stations, dtype=np.float32)
+    bs = np.array(bin_start, dtype=np.int32, order='C', copy=True)
+    if st.ndim != 2 or st.shape[1] != 4 or bs.ndim != 1 or bs.shape[0] < 1:
+        raise ValueError(f'line_stations: stations must be [S,4] float32 and bin_start [L + 1] int32, not {st.shape} and {bs.shape}')
+    if not (math.isfinite(float(bin)) and float(bin) > 0.0):
+        raise ValueError(f'line_stations: bin={bin!r} must be a finite length > 0')
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise LanemapHipError('lanemapping_amd ops need tensors on an MI355X (HIP) device; no CPU fallback exists')
+    return LineStations(torch.from_numpy(st.copy()).to(device), torch.from_numpy(bs).to(device), bs, bin)
+
+
+def line_profile(points, index, stations, z_tol, min_intensity=None, out=None):
+    """points [N,4] f32 on device -> bins [n_bins, 6] int64 on device: per station bin of every line the columns n, sum iq, sum q,
+    sum q^2, min q, max q over the points the labelling rule gives that line (the rule: include/lanemap_hip.h; q the lateral offset in
+    1/1024 m, left positive; iq the intensity rounded into 0..65535); an empty bin reads 0, 0, 0, 0, 2^31 - 1, -2^31.  index: the
+    ops.LineIndex, stations: the ops.LineStations of the same segments.  out: a bins tensor of an earlier call to add to.  Integer sums,
+    minima and maxima only: the same bits whatever the order of the points.  No synchronisation."""
+    if not points.is_cuda:
+        raise LanemapHipError('lanemapping_amd ops need tensors on an MI355X (HIP) device; no CPU fallback exists')
+    assert points.dim() == 2 and points.shape[1] == 4 and points.is_contiguous() and points.dtype == torch.float32
+    if not isinstance(index, LineIndex):
+        raise TypeError(f'line_profile: index must be an ops.LineIndex (ops.line_index), not {type(index).__name__}')
+    if not isinstance(stations, LineStations):
+        raise TypeError(f'line_profile: stations must be an ops.LineStations (ops.line_stations), not {type(stations).__name__}')
+    if stations.n_segments != index.n_segments:
+        raise ValueError(f'line_profile: stations hold {stations.n_segments} rows, the index {index.n_segments} segments')
+    bins = _profile_out('line_profile', stations, out, points.device)
+    N = int(points.shape[0])
+    mi = math.nan if min_intensity is None else float(min_intensity)
+    check(lib().lm_line_profile_points(_stream(), _ptr(points) if N else None, N, *index.args(), *stations.args(), float(z_tol), mi,
+                                       int(out is not None), _ptr(bins) if stations.n_bins else None, stations.n_bins))
+    return bins
+
+
+def _profile_out(who, stations, out, device):
+    if out is None:
+        return stations.new_bins()
+    if tuple(out.shape) != (stations.n_bins, 6) or out.dtype != torch.int64 or not out.is_contiguous() or out.device != device:
+        raise ValueError(f'{who}: out must be a contiguous [{stations.n_bins},6] int64 tensor on {device}')
+    return out
+
+
 def _tilted(p):
     return p.quat[1] != 0.0 or p.quat[2] != 0.0
 

@@ -301,6 +301,7 @@ class Runner:
     _las_elevation = functools.partialmethod(_las_option, 'elevation', 'las_elevation', 'ElevationDrape')  # the vertex heights
     _las_density = functools.partialmethod(_las_option, 'density', 'las_density', 'GapFill')               # the gap fill
     _las_label = functools.partialmethod(_las_option, 'label', 'las_label', 'MarkingLabels')               # the labelled LAS files
+    _las_survey = functools.partialmethod(_las_option, 'survey', 'las_survey', 'MarkingSurvey')            # the marking profile
 
     @staticmethod
     def _params_dir(out_dir):
@@ -341,6 +342,26 @@ class Runner:
             done[base] = [r['records'], r['labelled'], r['per_line']]
         with open(os.path.join(self._params_dir(out_dir), 'labels.json'), 'w') as f:
             json.dump(done, f, indent=1)
+
+    def _survey_inputs(self, survey, files, result, out_dir):
+        """The stage after `label`: the lines the call returns - `merged`, or the tiles' 3-D lines in tile-name order when nothing was
+        merged - profiled from every input file (files: (path, shift, select) in input order; a file listed several times is surveyed
+        once, with its first listing's read offset): one lm_las_line_profile_records call per file into one bins tensor, one read-back.
+        The raw bins go to <out_dir>/params/markings.npy, what las_io.marking_summary reads off them to <out_dir>/params/markings.json
+        as {line number: summary}."""
+        from . import las_io
+        lines3d, merged = result
+        lines = list(merged) if len(merged) else [l for name in sorted(lines3d) for l in lines3d[name]]
+        seen, once = set(), []
+        for path, shift, select in files:
+            if os.path.realpath(path) not in seen:
+                seen.add(os.path.realpath(path))
+                once.append((path, shift, select))
+        bins, bin_start = las_io.survey_files(once, lines, survey, device=self.device)
+        par_dir = self._params_dir(out_dir)
+        np.save(os.path.join(par_dir, 'markings.npy'), bins)
+        with open(os.path.join(par_dir, 'markings.json'), 'w') as f:
+            json.dump({str(k + 1): m for k, m in enumerate(las_io.marking_summary(bins, bin_start, survey))}, f, indent=1)
 
     def _follow_ground(self, gf, names, plist, points, offs, rpar, H, W, out_dir):
         """One batch of tiles through a las_io.GroundFilter: -> (plist, points, offs, rpar) to rasterise and back-project with.  The ground
@@ -406,7 +427,7 @@ class Runner:
         return raster_batch(names, plist, points, offs, rpar, scales)
 
     def infer_las_to_map(self, las_and_params, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None, ground=None,
-                         intensity=None, elevation=None, density=None, label=None):
+                         intensity=None, elevation=None, density=None, label=None, survey=None):
         """LAS tiles -> map-level 3-D lane lines, every stage of the reference's offline chain on this stack:
 
           LAS file + tile parameter file (utils/io_utils.py:125-150)
@@ -447,11 +468,19 @@ class Runner:
         <work_dirs>/params/labels.json as {file: [records, labelled, [per-line counts]]}.  A file listed several times is labelled once
         (with the read offset of its first listing); two different files with one basename are refused with a ValueError before anything
         runs.  The return value does not change.
-        Order of the stages: select, (binning,) ground, intensity, rasteriser, density, network, elevation, (merge,) label.
+        survey: a las_io.MarkingSurvey (default: cfg['las_survey'], a dict of its arguments; absent: nothing changes): last, the lines the
+        call returns are profiled from the returns of every input file, each read once with its own las_read_offset and `select` (one
+        lm_las_line_profile_records call per file into one profile, one read-back): per station bin along every line the count, summed
+        intensity and lateral spread of the returns the labelling rule gives the line.  The raw bins are written to
+        <work_dirs>/params/markings.npy ([n_bins, 6] int64), what las_io.marking_summary reads off them - paint runs, dashed or solid,
+        width, intensity - to <work_dirs>/params/markings.json as {line number: summary}.  Without survey.min_intensity a bin counts
+        returns, not paint.  The return value does not change.
+        Order of the stages: select, (binning,) ground, intensity, rasteriser, density, network, elevation, (merge,) label, survey.
         Single rank (the merge is sequential over the sorted tiles)."""
         from . import las_io
         select, ground, intensity = self._las_select(select), self._las_ground(ground), self._las_intensity(intensity)
         elevation, density, label = self._las_elevation(elevation), self._las_density(density), self._las_label(label)
+        survey = self._las_survey(survey)
         if label is not None:
             self._label_plan([p for p, _ in las_and_params])              # (a basename collision is refused before anything runs)
         if intensity is not None and intensity.scope == 'strip':
@@ -484,6 +513,8 @@ class Runner:
         result = close()
         if label is not None:
             self._label_inputs(label, inputs, result, out_dir)
+        if survey is not None:
+            self._survey_inputs(survey, inputs, result, out_dir)
         return result
 
     def _las_chain(self, work_dirs, merge, elevation=None, density=None):
@@ -623,7 +654,7 @@ class Runner:
         return names, plist
 
     def infer_las_strip_to_map(self, las_paths, param_paths, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None,
-                               ground=None, intensity=None, elevation=None, density=None, label=None):
+                               ground=None, intensity=None, elevation=None, density=None, label=None, survey=None):
         """A whole strip -> map-level lane lines: the LAS file(s) of the strip are read once, their points are binned into the tiles of
         the layout on the GPU (ops.strip_bin_points: the windows of `param_paths` may overlap and be rotated), and every batch of tiles
         then runs the chain of infer_las_to_map from the rasteriser on.  Same outputs under the same names; a tile is named by the
@@ -636,13 +667,15 @@ class Runner:
         loop - BEFORE `ground`'s height selection, which runs per batch: points it later drops still count for the strip's window.
         elevation: as for infer_las_to_map, after the network, on the ranges the rasteriser saw (after `ground` and `intensity`).
         density: as for infer_las_to_map, per batch between the rasteriser and the network.
-        label: as for infer_las_to_map, last: every file of `las_paths` is labelled with the layout's las_read_offset and `select`."""
+        label: as for infer_las_to_map, after the merge: every file of `las_paths` is labelled with the layout's las_read_offset and `select`.
+        survey: as for infer_las_to_map, last: every file of `las_paths` is surveyed with the layout's las_read_offset and `select`."""
         from . import las_io
         if isinstance(las_paths, (str, os.PathLike)):
             las_paths = [las_paths]
         names, plist = self._strip_layout(list(param_paths))
         select, ground, intensity = self._las_select(select), self._las_ground(ground), self._las_intensity(intensity)
         elevation, density, label = self._las_elevation(elevation), self._las_density(density), self._las_label(label)
+        survey = self._las_survey(survey)
         if label is not None:
             self._label_plan(las_paths)                                    # (a basename collision is refused before anything runs)
         used = {}
@@ -677,6 +710,8 @@ class Runner:
         result = close()
         if label is not None and plist:
             self._label_inputs(label, [(path, plist[0]['las_read_offset'], select) for path in las_paths], result, out_dir)
+        if survey is not None and plist:
+            self._survey_inputs(survey, [(path, plist[0]['las_read_offset'], select) for path in las_paths], result, out_dir)
         return result
 
     def infer_lane_geometry_segmentation_segmentor(self, path_ckpt=None, mode_view=False, write_lane_vertex=False,
