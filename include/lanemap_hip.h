@@ -52,6 +52,8 @@ int lm_conv2d_nhwc_mfma_resup_f32(void* stream, const float* x, int ldx, const f
  *   wu_frag[xi][u][nt][lane][e] = U[xi][nt*32 + (lane & 31)][8 u + 4 (lane >> 5) + e], CoutP % 64 == 0, Cin % 16 == 0.
  * wu (twin): U as [36][CoutP][Cin].  gn_partial: [B][lm_winograd44_gn_chunks][Cout][2] doubles -> lm_gn_finalize. */
 int lm_winograd44_supported(int H, int W, int Cin, int dil);
+/* the same for an input of pixel stride ldx floats: 0 as well when an image of it spans 2^31 bytes or more (32-bit offsets in the patch loads) */
+int lm_winograd44_supported_ld(int H, int W, int Cin, int dil, int ldx);
 int lm_winograd44_gn_chunks(int H, int W, int dil);
 long lm_winograd44_tiles(int B, int H, int W, int dil);
 long lm_winograd44_twin_workspace_bytes(int B, int H, int W, int Cin, int CoutP, int dil);

@@ -53,6 +53,7 @@ SIGNATURES = {
     'lm_conv2d_nhwc_mfma_resup_f32': (i32, [vp, vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, vp, i32,
                                             i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32]),
     'lm_winograd44_supported': (i32, [i32, i32, i32, i32]),
+    'lm_winograd44_supported_ld': (i32, [i32, i32, i32, i32, i32]),
     'lm_winograd44_gn_chunks': (i32, [i32, i32, i32]),
     'lm_winograd44_tiles': (i64, [i32, i32, i32, i32]),
     'lm_winograd44_twin_workspace_bytes': (i64, [i32, i32, i32, i32, i32, i32]),

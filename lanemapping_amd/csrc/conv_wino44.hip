@@ -22,8 +22,8 @@
 // planes of V (LDS) and its own nine planes of U (global -> registers, ring of 6 register sets 5 steps ahead): no operand is fetched
 // twice inside a workgroup.  Per 16-channel unit of the input:
 //   1. the RAW 6 x 6 patches of the 32 tiles (6 patch rows x 144 cells of 16 channels; horizontally adjacent tiles share two columns)
-//      arrive in LDS through global_load_lds gathers straight from the NHWC tensor (zero block for padding), requested two units ahead,
-//      double-buffered;
+//      arrive in LDS through LDS-DMA gathers straight from the NHWC tensor (buffer loads: a padding cell carries an offset the
+//      resource's range check refuses, which writes zeros - QPADOFF), requested two units ahead, double-buffered;
 //   2. per 8-channel half (a SLOT of nine steps, one per xi of the wave: one A fragment from LDS, two B fragments, 8 MFMAs = 4 k steps
 //      x 2 channel blocks): the 256 threads compute V = B^T d B of the NEXT half once (thread = tile x channel pair x half of the first
 //      pass: 30 ds_read_b64, 72 packed FMAs / adds, 18 ds_write_b64 into V[xi][channel pair][tile][2], 36 KB, single-buffered) in pieces
@@ -79,7 +79,14 @@ constexpr int QVF = 36 * 256;                   // floats of the V buffer: 36 pl
 constexpr int QBD = 5, QRING = 6;               // B fragments run QBD steps ahead in a ring of QRING register sets
 static_assert(6 * (QNCELL / 16) * QGRP <= QRAWF && QNCELL % 16 == 0, "patch loads cover the unit");
 
-__device__ __attribute__((aligned(16))) float g_w44_zeros[1024 + 32];   // zero source for padding cells, any channel unit (Cin <= 1024)
+// Patch loads go through a buffer resource that covers the workgroup's image (base = its first pixel, num_records = the bytes of the
+// OPERAND inside it: up to the last pixel's channel Cin - 1, whatever lies behind it in a wider tensor or behind the allocation): a load
+// is one 32-bit byte offset per lane, fixed for the workgroup, plus the unit's byte offset in the instruction's scalar offset - no vector
+// arithmetic in the loop.  A padding cell carries QPADOFF: at or above 2^31 the resource's range check refuses it for every unit however
+// the scalar offset enters the check (alone the vector offset is already >= num_records; added to a scalar offset < 2^31 the 32-bit sum
+// does not wrap), the load returns zeros and touches no memory.
+constexpr unsigned QPADOFF = 0x80000000u;
+typedef __amdgpu_buffer_rsrc_t w44_rsrc_t;
 
 struct W44Geom {
     int B, H, W, dil, Ty, Tx;   // Ty x Tx tiles of 4 x 4 outputs per (image, phase); dil * dil phases
@@ -279,14 +286,14 @@ __global__ __launch_bounds__(256) void wino44_split_frag_kernel(const f32x4* __r
 // ===================================================================================================================================
 // The fused kernel
 struct W44Params {
-    const float* x; const float* U; const float* scale; const float* shift; const float* res; float* y; const float* zeros;
+    const float* x; const float* U; const float* scale; const float* shift; const float* res; float* y;
     int ldx, ldr, ldy, C, Cout, NT, act;      // NT = CoutP / 32 channel blocks in U
     int n_inner;                               // workgroup order: N tile inner
     LmFastDiv dnt;                             // / number of N tiles
     double* gn_part;
     W44Geom g;
-    float post;                                // SPLIT: 1 / (power-of-two scale of U), folded into the epilogue's scale (exact); else 1.  (Last:
-};                                             // the exact kernel's argument offsets - and with them its code - are what they were)
+    float post;                                // SPLIT: 1 / (power-of-two scale of U), folded into the epilogue's scale (exact); else 1
+};
 
 // packed fp32 pairs (two channels of a lane).  Plain asm (not volatile): the scheduler may move them, the arithmetic is fixed.
 // (the multiplier b is one of three wave-uniform constant pairs: an SGPR-pair operand - with a "v" constraint every use cost a v_mov_b64)
@@ -313,6 +320,10 @@ __device__ __forceinline__ f32x2 pk_sub(const f32x2 a, const f32x2 b) {
 
 struct W44K {
     f32x2 c2, c4, c5;
+};
+template <int V>
+struct W44Int {
+    static constexpr int value = V;
 };
 
 // w44_bt on channel pairs.  Source order = issue order (the scheduler leaves opaque asm statements where they stand and puts an s_nop
@@ -343,16 +354,17 @@ __device__ __forceinline__ void pk_bt(const f32x2 (&d)[6], f32x2 (&t)[6], const 
 // Step k of a slot:   0: read cols 0, 1 | store late 0, 1        1: pass 1 of cols 0, 1 | read cols 2, 3 | store late 2, 3
 //   2: pass 1 of cols 2, 3 | read cols 4, 5 | store late 4, 5     3: pass 1 of cols 4, 5 | store late 6, 7      4: pass 2 of row A
 //   -- mid barrier --   5: pass 2 of row B | store A 0..2         6: pass 2 of row C | store A 3..5             7: store B early (4)
-// rawrow = raw buffer + 8 * half + (LOWER ? one patch row : 0); roff[c] = float offset of patch column c of the tile (+ 2 * channel pair).
+// col[c] = patch column c of the thread's tile (and channel pair) in the raw buffer, at the half's eight channels and the thread's first
+// patch row (LOWER: row 1): LM_QCOLS in wino44_kernel.
 struct W44Xf {
     f32x2 e[6][5];           // [patch column][patch row 0..4 (LOWER: 1..5)] - two columns live at a time
     f32x2 w[3][6];           // first-pass results by class: [A, B, C][column]
     f32x2 tA[6], tB[6], tC[6];     // second-pass results; the late planes - (B, j = 2), (B, 5), (C, 0..5) - stay here over the end of the slot
 };                                 // and are stored in steps 0..3 of the next one, before steps 5 / 6 compute their successors
 template <int C>
-__device__ __forceinline__ void w44_preread(W44Xf& d, const float* rawrow, const int (&roff)[6]) {
+__device__ __forceinline__ void w44_preread(W44Xf& d, const float* const (&col)[6]) {
     constexpr int ROWF = (QNCELL / 16) * QGRP;
-    const float* s = rawrow + roff[C];
+    const float* s = col[C];
 #pragma unroll
     for (int r = 0; r < 5; ++r) d.e[C][r] = *reinterpret_cast<const f32x2*>(s + r * ROWF);
 }
@@ -397,17 +409,17 @@ __device__ __forceinline__ void w44_vstore(float* v, int j, const f32x2 t) {
     }
 }
 template <int K, bool SPLIT>
-__device__ __forceinline__ void w44_xf_lds(W44Xf& d, const float* rawrow, const int (&roff)[6], float* vA, float* vB, float* vC) {
+__device__ __forceinline__ void w44_xf_lds(W44Xf& d, const float* const (&col)[6], float* vA, float* vB, float* vC) {
     auto st = [](float* v, int j, const f32x2 t) { w44_vstore<SPLIT>(v, j, t); };
     if constexpr (K == 0) {
         st(vB, 2, d.tB[2]); st(vB, 5, d.tB[5]);
-        w44_preread<0>(d, rawrow, roff); w44_preread<1>(d, rawrow, roff);
+        w44_preread<0>(d, col); w44_preread<1>(d, col);
     } else if constexpr (K == 1) {
         st(vC, 0, d.tC[0]); st(vC, 1, d.tC[1]);
-        w44_preread<2>(d, rawrow, roff); w44_preread<3>(d, rawrow, roff);
+        w44_preread<2>(d, col); w44_preread<3>(d, col);
     } else if constexpr (K == 2) {
         st(vC, 2, d.tC[2]); st(vC, 3, d.tC[3]);
-        w44_preread<4>(d, rawrow, roff); w44_preread<5>(d, rawrow, roff);
+        w44_preread<4>(d, col); w44_preread<5>(d, col);
     } else if constexpr (K == 3) {
         st(vC, 4, d.tC[4]); st(vC, 5, d.tC[5]);
     } else if constexpr (K == 5) {
@@ -436,10 +448,10 @@ __device__ __forceinline__ void w44_xf_valu(W44Xf& d, bool lower, const W44K& k)
 // the whole transform of one slot at once (prologue: V(0) has nobody to hide behind): every plane stored; the first slot stores the late
 // ones again in its steps 0..3 (the same bits)
 template <bool SPLIT>
-__device__ __forceinline__ void w44_xf_all(W44Xf& d, const float* rawrow, const int (&roff)[6], float* vA, float* vB, float* vC, bool lower,
+__device__ __forceinline__ void w44_xf_all(W44Xf& d, const float* const (&col)[6], float* vA, float* vB, float* vC, bool lower,
                                            const W44K& k) {
-    w44_preread<0>(d, rawrow, roff); w44_preread<1>(d, rawrow, roff); w44_preread<2>(d, rawrow, roff);
-    w44_preread<3>(d, rawrow, roff); w44_preread<4>(d, rawrow, roff); w44_preread<5>(d, rawrow, roff);
+    w44_preread<0>(d, col); w44_preread<1>(d, col); w44_preread<2>(d, col);
+    w44_preread<3>(d, col); w44_preread<4>(d, col); w44_preread<5>(d, col);
     w44_xf_valu<1>(d, lower, k); w44_xf_valu<2>(d, lower, k); w44_xf_valu<3>(d, lower, k);
     w44_xf_valu<4>(d, lower, k); w44_xf_valu<5>(d, lower, k); w44_xf_valu<6>(d, lower, k);
 #pragma unroll
@@ -452,10 +464,17 @@ __device__ __forceinline__ void w44_xf_all(W44Xf& d, const float* rawrow, const 
 
 // B fragment loads bypass the compiler's wait-count bookkeeping: explicit s_waitcnt vmcnt(N), tied to the destination
 // registers through "+v" operands.
+// The base goes through an SALU copy inside the statement: under SGPR pressure the compiler keeps some of these pointers in the lanes of
+// a VGPR and fetches them with v_readlane_b32 right in front of the statement, and a VMEM instruction that reads an SGPR within five wait
+// states of a VALU write of it gets the old value (the compiler pads its own loads, not the inside of an asm statement): the loads of
+// the odd-unit tail went to wild addresses.  An SALU read of a VALU-written SGPR is interlocked, and an SALU write needs no wait states
+// in front of a VMEM read.
 __device__ __forceinline__ void q_bload2(f32x4 (&b)[2], unsigned voff, const float* sbase) {
-    asm volatile("global_load_dwordx4 %0, %2, %3\n\t"
-                 "global_load_dwordx4 %1, %2, %3 offset:1024"
-                 : "=&v"(b[0]), "=&v"(b[1]) : "v"(voff), "s"(sbase) : "memory");
+    unsigned long base;
+    asm volatile("s_mov_b64 %2, %4\n\t"
+                 "global_load_dwordx4 %0, %3, %2\n\t"
+                 "global_load_dwordx4 %1, %3, %2 offset:1024"
+                 : "=&v"(b[0]), "=&v"(b[1]), "=&s"(base) : "v"(voff), "s"(sbase) : "memory");
 }
 template <int N>
 __device__ __forceinline__ void q_bwait(f32x4 (&b)[2]) {
@@ -495,13 +514,42 @@ static_assert(q_dma0(17) + q_ndma(17) == QLPW, "the second phase issues every pa
 // A fragment of one xi: V plane [4 channel pairs][32 tiles][2] - the 16 lanes of a ds_write_b64 group of the transform (16 tiles of one
 // channel pair) and the 32 lanes of a read pass here cover contiguous bytes: conflict-free on both sides ([2 k halves][32 tiles][4] with
 // one ds_read_b128 made the transform's stores two-way conflicted).  Lane (tile, k half) takes pairs 2 k and 2 k + 1: channels 4 k .. 4 k + 3
+// (exact kernel: v1 = v + 64 comes from a base register of its own - see w44_lds_hide - so that the two reads stay two ds_read_b64 with
+// 16-bit offsets: merged into a ds_read2_b64, whose offsets end at 2 KB, most planes needed a v_add for a new base)
 template <bool SPLIT>
-__device__ __forceinline__ f32x4 q_aread(const float* v) {
+__device__ __forceinline__ f32x4 q_aread(const float* v, const float* v1) {
     if constexpr (SPLIT) {       // v = plane + 64 (lane >> 5) + tile: hi words of pairs 2 k, 2 k + 1, then their lo words (two ds_read2_b32)
         return f32x4{v[0], v[32], v[128], v[160]};
     } else {
-        const f32x2 lo = *reinterpret_cast<const f32x2*>(v), hi = *reinterpret_cast<const f32x2*>(v + 64);
+        const f32x2 lo = *reinterpret_cast<const f32x2*>(v), hi = *reinterpret_cast<const f32x2*>(v1);
         return f32x4{lo[0], lo[1], hi[0], hi[1]};
+    }
+}
+
+// An LDS address computed once, as a register the optimiser cannot see through (the empty asm): left to fold the addresses of the loop
+// into one base plus large constants it re-derived them with VALU instructions inside the loop (a v_add per pair of reads it merged into
+// a ds_read2 whose offsets did not fit, a shift-and-add per buffer parity), and a VALU instruction beside the fp32 MFMAs costs matrix
+// time wherever it stands.  What is added to the result must fit the 16-bit offset field of a ds instruction.
+__device__ __forceinline__ float* w44_lds_hide(float* p) {
+    typedef __attribute__((address_space(3))) float lds_float;
+    unsigned a = (unsigned)(unsigned long)(lds_float*)p;
+    asm volatile("" : "+v"(a));
+    return (float*)(lds_float*)(unsigned long)a;
+}
+
+// The seven MFMAs of a step that follow its first one (exact kernel).  The steps in front of a barrier inside a unit (4 and 13: the mid
+// barrier of a slot, 8: the end of the first slot) leave them to the loop, which issues them BEHIND the barrier and the first A-fragment
+// read of what follows: their operands are in registers, and they cover that read's latency (the last step of a unit keeps its MFMAs:
+// what follows it is the next round of the loop).
+constexpr bool w44_deferred(int S) { return S == 4 || S == 8 || S == 13; }
+template <int S>
+__device__ __forceinline__ void w44_step_rest(f32x16& acc0, f32x16& acc1, const f32x4 (&b)[2], const f32x4& a_cur) {
+    constexpr bool VACC = S % 9 == 8;
+    q_mfma<VACC>(acc1, a_cur[0], b[1][0]);
+#pragma unroll
+    for (int t = 1; t < 4; ++t) {
+        q_mfma<VACC>(acc0, a_cur[t], b[0][t]);
+        q_mfma<VACC>(acc1, a_cur[t], b[1][t]);
     }
 }
 
@@ -511,17 +559,16 @@ __device__ __forceinline__ f32x4 q_aread(const float* v) {
 // steps 4 and 8 leave it to the loop), the LDS part of this step's transform share, then its VALU part.
 template <int S, bool SPLIT>
 __device__ __forceinline__ void w44_step(f32x16& acc0, f32x16& acc1, f32x4 (&bq)[QRING][2], unsigned bvoff, const float* bpre,
-                                         const float* anext, const f32x4& a_cur, f32x4& a_nxt, const float* const (&gsrc)[QLPW], long goff,
-                                         float* rawld, int wave, W44Xf& xf, const float* prerow, const int (&roff)[6], float* vA, float* vB,
+                                         const float* anext, const float* anext1, const f32x4& a_cur, f32x4& a_nxt, const w44_rsrc_t grsrc, const unsigned (&gvoff)[QLPW], int gsoff,
+                                         float* rawld, int wave, W44Xf& xf, const float* const (&col)[6], float* vA, float* vB,
                                          float* vC, bool lower, const W44K& kk) {
-    typedef __attribute__((address_space(1))) const void gptr_t;
     typedef __attribute__((address_space(3))) void lptr_t;
     constexpr int K = S % 9;
     q_bload2(bq[(S + QBD) % QRING], bvoff, bpre);
 #pragma unroll
     for (int i = 0; i < q_ndma(S); ++i) {
         constexpr int L0 = q_dma0(S);
-        __builtin_amdgcn_global_load_lds((gptr_t*)(gsrc[L0 + i] + goff), (lptr_t*)(rawld + ((L0 + i) * 4 + wave) * QGRP), 16, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(grsrc, (lptr_t*)(rawld + ((L0 + i) * 4 + wave) * QGRP), 16, gvoff[L0 + i], gsoff, 0, 0);
     }
     f32x4 (&b)[2] = bq[S % QRING];
     q_bwait<q_nwait(S)>(b);
@@ -534,8 +581,8 @@ __device__ __forceinline__ void w44_step(f32x16& acc0, f32x16& acc1, f32x4 (&bq)
     //  SPLIT: an fp16 MFMA is 8 passes on a pipe of its own, and the step's VALU work (transform + split, ~110 cycles) is of the order of
     //  its six MFMAs (192 cycles): the scheduler interleaves them - see the group pattern at the end of the step)
     if constexpr (!SPLIT) __builtin_amdgcn_sched_barrier(0);
-    if constexpr (K != 4 && K != 8) a_nxt = q_aread<SPLIT>(anext);
-    w44_xf_lds<K, SPLIT>(xf, prerow, roff, vA, vB, vC);
+    if constexpr (K != 4 && K != 8) a_nxt = q_aread<SPLIT>(anext, anext1);
+    w44_xf_lds<K, SPLIT>(xf, col, vA, vB, vC);
     if constexpr (!SPLIT) __builtin_amdgcn_sched_barrier(0);
     w44_xf_valu<K>(xf, lower, kk);
     if constexpr (!SPLIT) __builtin_amdgcn_sched_barrier(0);
@@ -553,13 +600,8 @@ __device__ __forceinline__ void w44_step(f32x16& acc0, f32x16& acc1, f32x4 (&bq)
                 __builtin_amdgcn_sched_group_barrier(0x300, 3, 0);
             }
         }
-    } else {
-        q_mfma<VACC>(acc1, a_cur[0], b[1][0]);
-#pragma unroll
-        for (int t = 1; t < 4; ++t) {
-            q_mfma<VACC>(acc0, a_cur[t], b[0][t]);
-            q_mfma<VACC>(acc1, a_cur[t], b[1][t]);
-        }
+    } else if constexpr (!w44_deferred(S)) {
+        w44_step_rest<S>(acc0, acc1, b, a_cur);
     }
     __builtin_amdgcn_sched_barrier(0);
 }
@@ -606,7 +648,6 @@ __global__ __launch_bounds__(256) void wino44_kernel(W44Params p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];      // raw[2][QRAWF] | V[QVF]; the epilogue's exchange buffer over all of it
     float* const raw0 = smem;
     float* const Vbuf = smem + 2 * QRAWF;
-    typedef __attribute__((address_space(1))) const void gptr_t;
     typedef __attribute__((address_space(3))) void lptr_t;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -672,13 +713,16 @@ __global__ __launch_bounds__(256) void wino44_kernel(W44Params p) {
     // patch loads: load s of wave w fills chunks (s * 4 + w) * 64 .. + 63 of the raw buffer; chunk = 16 B = channel quad cq of a cell;
     // cell = patch row r x position pos; position = 16 (slot >> 2) + 4 c + (slot & 3) for column c (0..3) of tile slot `slot`: the cells
     // one column of consecutive tiles needs are neighbours in LDS; the 16 cells of a load are contiguous, consecutive loads QGRP floats apart
-    const float* gsrc[QLPW];
+    unsigned gvoff[QLPW];
     const int img_pix0 = bi * g.H * g.W;
+    // (the entry point keeps an image's operand bytes below 2^31; built from kernel arguments and the block index only: provably uniform)
+    const w44_rsrc_t grsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x) + (long)img_pix0 * p.ldx, 0,
+                                                               (int)((((long)g.H * g.W - 1) * p.ldx + p.C) * 4), 0x00020000);
     // Round 5: the set-up was 7.6 k cycles of address arithmetic per workgroup (profiles/r4_wino44_phase_profile_final.txt,
     // profiles/r5_wino44_fixed_costs_experiments.txt; 7.0 k with every cell served from the zero block: not memory) - the run search, nine run-time divisions and four exec-masked regions per load.  Now lane l describes
     // tile SLOT l once (x / y pixel of its patch cell (0, 0), patch columns it may fetch: 4 (tiles left in its run) + 2, 0 without a run);
     // a load covers the four slots 4 gq .. 4 gq + 3 of one patch row (q = 4 s + wave = 9 r + gq: wave-uniform) and looks its slot up
-    // with three ds_bpermute_b32; masks instead of selects keep the 64-bit offset out of divergent branches.
+    // with three ds_bpermute_b32; the byte offset of the cell inside the image is one select away from QPADOFF.
     int tab_x, tab_y, tab_n;
     {
         int n = sn[0], yb = iy0[0], xb = ix0[0], s0 = 0;
@@ -705,13 +749,10 @@ __global__ __launch_bounds__(256) void wino44_kernel(W44Params p) {
         const int nn = __builtin_amdgcn_ds_bpermute(idx, tab_n);
         const int yy = y0 + r * g.dil, xx = x0 + gccd;
         const bool ok = (r < 6) & (gcc < nn) & ((unsigned)yy < (unsigned)g.H) & ((unsigned)xx < (unsigned)g.W);
-        const long m = -(long)ok;                         // all ones: the cell exists
-        const long eoff = ((long)(img_pix0 + yy * g.W + xx) * p.ldx) & m;
-        const unsigned long base = (unsigned long)p.zeros + (((unsigned long)p.x - (unsigned long)p.zeros) & (unsigned long)m);
-        gsrc[s_] = (const float*)base + eoff + gcq4;
+        gvoff[s_] = ok ? ((unsigned)(yy * g.W + xx) * (unsigned)p.ldx + (unsigned)gcq4) * 4u : QPADOFF;
         // unit 0's patch load s goes out as soon as its source is known: issuing a load of cold, scattered lines stalls ~140 cycles
         // (profiles/r4_wino44_residual_issue_experiment.txt) - the address arithmetic of load s + 1 runs meanwhile
-        __builtin_amdgcn_global_load_lds((gptr_t*)gsrc[s_], (lptr_t*)(raw0 + (s_ * 4 + wave) * QGRP), 16, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(grsrc, (lptr_t*)(raw0 + (s_ * 4 + wave) * QGRP), 16, gvoff[s_], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
     }
     // transform share: tile = lane & 31, LOWER = wave >> 1 (wave-uniform).  Bank layout of the raw reads (round 5, measured with
@@ -737,16 +778,37 @@ __global__ __launch_bounds__(256) void wino44_kernel(W44Params p) {
         tvoff = SPLIT ? cp * 32 + tl : cp * 64 + tl * 2;
     }
     const bool lower = (wave >> 1) != 0;
+    // Every LDS address of the loop is one of the hidden bases below (w44_lds_hide) plus a constant.
+    // Raw patches, [buffer = unit parity][columns 0 and 2, columns 1 and 3, column 4, column 5] from the thread's first patch row (LOWER
+    // threads read rows 1..5): roff[c] = roff[0] + 64 c for c < 4 and roff[5] = roff[4] + 64 (pos & 15 = (slot & 3) + 4 c has no carry),
+    // but two neighbouring columns on one base would be merged into a ds_read2_b64 again.
+    const float* rbo[2][4];
+    {
+        const int lowoff = lower ? (QNCELL / 16) * QGRP : 0;
+#pragma unroll
+        for (int par = 0; par < 2; ++par) {
+            rbo[par][0] = w44_lds_hide(raw0 + par * QRAWF + lowoff + roff[0]);
+            rbo[par][1] = w44_lds_hide(raw0 + par * QRAWF + lowoff + roff[1]);
+            rbo[par][2] = w44_lds_hide(raw0 + par * QRAWF + lowoff + roff[4]);
+            rbo[par][3] = w44_lds_hide(raw0 + par * QRAWF + lowoff + roff[5]);
+        }
+    }
+    // column pointers of w44_preread for the buffer of parity PAR, channels HALF8 .. HALF8 + 7 of the unit
+#define LM_QCOL(PAR, K, F) rbo[PAR][K] + (F)
+#define LM_QCOLS(PAR, HALF8)                                                                                                  \
+    {LM_QCOL(PAR, 0, HALF8), LM_QCOL(PAR, 1, HALF8), LM_QCOL(PAR, 0, 128 + (HALF8)), LM_QCOL(PAR, 1, 128 + (HALF8)), \
+     LM_QCOL(PAR, 2, HALF8), LM_QCOL(PAR, 3, HALF8)}
     // plane rows of this thread by class (A: i % 3 == 0, B: == 1, C: == 2): upper threads i = 0, 1, 2; lower threads i = 3, 4, 5
-    float* const vA = Vbuf + (lower ? 3 : 0) * (6 * 256) + tvoff;
-    float* const vB = Vbuf + (lower ? 4 : 1) * (6 * 256) + tvoff;
-    float* const vC = Vbuf + (lower ? 5 : 2) * (6 * 256) + tvoff;
+    float* const vA = w44_lds_hide(Vbuf + (lower ? 3 : 0) * (6 * 256) + tvoff);
+    float* const vB = w44_lds_hide(Vbuf + (lower ? 4 : 1) * (6 * 256) + tvoff);
+    float* const vC = w44_lds_hide(Vbuf + (lower ? 5 : 2) * (6 * 256) + tvoff);
     const W44K kk = {f32x2{2.f, 2.f}, f32x2{4.f, 4.f}, f32x2{5.f, 5.f}};
     // MFMA operands: A = V plane xi, channel pairs 2 (lane >> 5) and 2 (lane >> 5) + 1 of tile lane & 31; this wave's planes xi = xi00 + 6 ii + jj
     const int qa = wave >> 1, qb = wave & 1;
     const int xi00 = 18 * qa + 3 * qb;
-    const float* const Vq = SPLIT ? Vbuf + xi00 * 256 + (lane >> 5) * 64 + (lane & 31)
-                                  : Vbuf + xi00 * 256 + (lane >> 5) * 128 + (lane & 31) * 2;       // channel pairs 2 (lane >> 5) and 2 (lane >> 5) + 1
+    const float* const Vq = w44_lds_hide(SPLIT ? Vbuf + xi00 * 256 + (lane >> 5) * 64 + (lane & 31)
+                                               : Vbuf + xi00 * 256 + (lane >> 5) * 128 + (lane & 31) * 2);       // channel pairs 2 (lane >> 5) and 2 (lane >> 5) + 1
+    const float* const Vq1 = SPLIT ? Vq : w44_lds_hide(Vbuf + xi00 * 256 + (lane >> 5) * 128 + (lane & 31) * 2 + 64);
     const int nun = p.C / 16;                                    // 16-channel units
     const unsigned bvoff = (unsigned)lane * 16u;
     const long ustride = (long)p.NT * 256;                       // floats between 8-channel halves in U
@@ -762,48 +824,62 @@ __global__ __launch_bounds__(256) void wino44_kernel(W44Params p) {
             for (int r = 0; r < 16; ++r) acc[k][b][r] = 0.f;
     f32x4 bq[QRING][2];
     W44Xf xf;
-    const int lowoff = lower ? (QNCELL / 16) * QGRP : 0;               // LOWER threads read patch rows 1..5
     // prologue: (raw unit 0 was requested while the sources were computed,) B of steps 0 .. QBD-1, THEN raw unit 1: the wait below leaves unit 1's loads (the youngest) in flight - they
     // are only needed before the second slot, and being older than every load of the loop they do not enter its wait counts
 #define LM_QXI(K) (6 * ((K) / 3) + (K) % 3)
 #pragma unroll
     for (int k = 0; k < QBD; ++k) q_bload2(bq[k], bvoff, bbase + (long)LM_QXI(k) * xstride);
     {
-        const long goff1 = nun > 1 ? 16 : 0;
+        const int gsoff1 = nun > 1 ? 64 : 0;
 #pragma unroll
         for (int s_ = 0; s_ < QLPW; ++s_)
-            __builtin_amdgcn_global_load_lds((gptr_t*)(gsrc[s_] + goff1), (lptr_t*)(raw0 + QRAWF + (s_ * 4 + wave) * QGRP), 16, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(grsrc, (lptr_t*)(raw0 + QRAWF + (s_ * 4 + wave) * QGRP), 16, gvoff[s_], gsoff1, 0, 0);
     }
     q_bwait<QLPW>(bq[0]);                      // unit 0 and the first B fragments have landed (this wave's part; the barrier collects all parts)
     __builtin_amdgcn_s_barrier();
     // V(0): the only transform with nothing to hide behind
-    w44_xf_all<SPLIT>(xf, raw0 + lowoff, roff, vA, vB, vC, lower, kk);
+    {
+        const float* const col0[6] = LM_QCOLS(0, 0);
+        w44_xf_all<SPLIT>(xf, col0, vA, vB, vC, lower, kk);
+    }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
 
     // B fragments of step S5 = S + QBD of the unit (S5 >= 18: first slot of the next unit)
 #define LM_QBPRE(S5) ((S5) < 18 ? bu + (long)((S5) / 9) * ustride + (long)LM_QXI((S5) % 9) * xstride : bu_next + (long)LM_QXI((S5) - 18) * xstride)
+#define LM_QANEXT(S) (LM_QXI(((S) % 9) + 1 < 9 ? ((S) % 9) + 1 : 0) * 256)
 #define LM_QSTEP(S, AC, AN) \
-    w44_step<S, SPLIT>(acc[(S) % 9][0], acc[(S) % 9][1], bq, bvoff, LM_QBPRE((S) + QBD), Vq + LM_QXI(((S) % 9) + 1 < 9 ? ((S) % 9) + 1 : 0) * 256, \
-                AC, AN, gsrc, goff, rawc_w, wave, xf, (S) < 9 ? rawc + 8 + lowoff : rawn + lowoff, roff, vA, vB, vC, lower, kk)
+    w44_step<S, SPLIT>(acc[(S) % 9][0], acc[(S) % 9][1], bq, bvoff, LM_QBPRE((S) + QBD), Vq + LM_QANEXT(S), Vq1 + LM_QANEXT(S), \
+                AC, AN, grsrc, gvoff, gsoff, rawc_w, wave, xf, (S) < 9 ? colc : coln, vA, vB, vC, lower, kk)
     // the barrier in the middle of a slot: this wave's late stores (steps 0..3) are done; behind it every wave's are, and the early
     // planes are free (every wave has read V(s)'s in steps 0..4)
 #define LM_QMID(AN)                                          \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       \
     __builtin_amdgcn_s_barrier();                            \
-    AN = q_aread<SPLIT>(Vq + LM_QXI(5) * 256);
-    for (int u = 0; u < nun; ++u) {
-        const float* const rawc = raw0 + (u & 1) * QRAWF;              // unit u
-        float* const rawc_w = raw0 + (u & 1) * QRAWF;                  // ... and the destination of unit u + 2's patch loads (second slot)
-        const float* const rawn = raw0 + ((u + 1) & 1) * QRAWF;        // unit u + 1 (pre-read in the second slot)
-        const long goff = u + 2 < nun ? (long)(u + 2) * 16 : 0;            // (nothing left to fetch: harmless re-read of unit 0)
+    AN = q_aread<SPLIT>(Vq + LM_QXI(5) * 256, Vq1 + LM_QXI(5) * 256); \
+    __builtin_amdgcn_sched_barrier(0);
+    // the deferred MFMAs of step S (w44_deferred), behind the barrier and the A-fragment read that follow the step
+#define LM_QREST(S, AC)                                                                               \
+    if constexpr (!SPLIT) {                                                                           \
+        w44_step_rest<S>(acc[(S) % 9][0], acc[(S) % 9][1], bq[(S) % QRING], AC);                      \
+        __builtin_amdgcn_sched_barrier(0);                                                            \
+    }
+    // one 16-channel unit; PAR = u & 1 is a compile-time constant (the loop below is unrolled over two units), so the buffer a step
+    // reads or fills is a constant offset and not an address computed in the loop
+    auto unit = [&](auto par_, const int u) __attribute__((always_inline)) {
+        constexpr int PAR = decltype(par_)::value;
+        const float* const colc[6] = LM_QCOLS(PAR, 8);                 // unit u, second half (transformed in the first slot)
+        const float* const coln[6] = LM_QCOLS(PAR ^ 1, 0);             // unit u + 1, first half (pre-read in the second slot)
+        float* const rawc_w = raw0 + PAR * QRAWF;                      // destination of unit u + 2's patch loads (second slot)
+        const int gsoff = u + 2 < nun ? (u + 2) * 64 : 0;                  // bytes (nothing left to fetch: harmless re-read of unit 0)
         const float* const bu = bbase + (long)(2 * u) * ustride;
         const float* const bu_next = bbase + (long)(u + 1 < nun ? 2 * (u + 1) : 0) * ustride;
         f32x4 a0, a1;
         // ---- slot 2 u: channels 16 u .. 16 u + 7 multiplied, channels 16 u + 8 .. 16 u + 15 transformed behind the MFMAs
-        a0 = q_aread<SPLIT>(Vq);
+        a0 = q_aread<SPLIT>(Vq, Vq1);
         LM_QSTEP(0, a0, a1); LM_QSTEP(1, a1, a0); LM_QSTEP(2, a0, a1); LM_QSTEP(3, a1, a0); LM_QSTEP(4, a0, a1);
         LM_QMID(a1)
+        LM_QREST(4, a0)
         LM_QSTEP(5, a1, a0); LM_QSTEP(6, a0, a1); LM_QSTEP(7, a1, a0); LM_QSTEP(8, a0, a1);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         // unit u + 1 (patch loads of the previous unit's second slot, or of the prologue) is pre-read in the slot that follows: every
@@ -811,15 +887,28 @@ __global__ __launch_bounds__(256) void wino44_kernel(W44Params p) {
         q_bwait<2 * 9>(bq[0]);
         __builtin_amdgcn_s_barrier();          // V(2 u + 1)'s early planes complete
         // ---- slot 2 u + 1: channels 16 u + 8 .. multiplied, the next unit's first half transformed, unit u + 2's patches requested
-        a0 = q_aread<SPLIT>(Vq);
-        LM_QSTEP(9, a0, a1);  LM_QSTEP(10, a1, a0); LM_QSTEP(11, a0, a1); LM_QSTEP(12, a1, a0); LM_QSTEP(13, a0, a1);
-        LM_QMID(a1)
-        LM_QSTEP(14, a1, a0); LM_QSTEP(15, a0, a1); LM_QSTEP(16, a1, a0); LM_QSTEP(17, a0, a1);
+        // (into a1: a0 still feeds the deferred MFMAs of step 8; the registers change roles for this slot)
+        a1 = q_aread<SPLIT>(Vq, Vq1);
+        __builtin_amdgcn_sched_barrier(0);
+        LM_QREST(8, a0)
+        LM_QSTEP(9, a1, a0);  LM_QSTEP(10, a0, a1); LM_QSTEP(11, a1, a0); LM_QSTEP(12, a0, a1); LM_QSTEP(13, a1, a0);
+        LM_QMID(a0)
+        LM_QREST(13, a1)
+        LM_QSTEP(14, a0, a1); LM_QSTEP(15, a1, a0); LM_QSTEP(16, a0, a1); LM_QSTEP(17, a1, a0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
+    };
+    for (int u = 0; u + 1 < nun; u += 2) {
+        unit(W44Int<0>{}, u);
+        unit(W44Int<1>{}, u + 1);
     }
+    if (nun & 1) unit(W44Int<0>{}, nun - 1);
+#undef LM_QCOLS
+#undef LM_QCOL
+#undef LM_QREST
 #undef LM_QMID
 #undef LM_QSTEP
+#undef LM_QANEXT
 #undef LM_QBPRE
 #undef LM_QXI
     static_assert(18 % QRING == 0 && QBD < QRING, "eighteen steps per unit walk the ring a whole number of times");
@@ -828,7 +917,10 @@ __global__ __launch_bounds__(256) void wino44_kernel(W44Params p) {
 
     // ---- epilogue: the products of one 32-channel block go to LDS as M[xi][tile][32 channels] (144 KB; straight from the accumulator
     // registers), every thread takes one (tile, channel quad): 36 ds_read_b128, A^T M A (rows first, then columns: w44_at), tail, 16 stores
-    const int etile = tid >> 3, ecq = tid & 7;
+    // (the thread's index is taken anew from the hardware here: every register the loop does not need is one it does not have - the
+    // index and what the compiler derived from it early for this part were spilled to scratch memory over the loop)
+    const int elane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)), etid = wave * 64 + elane;
+    const int etile = etid >> 3, ecq = etid & 7;
     int epix0;
     int eny = 0, enx = 0;                                   // valid output rows / columns of this thread's tile (0: no tile)
     {
@@ -845,7 +937,7 @@ __global__ __launch_bounds__(256) void wino44_kernel(W44Params p) {
             enx = min(4, (int)lm_fastdiv((unsigned)(g.W - ox + g.dil - 1), g.ddil));
         }
     }
-    float* const mw = smem + xi00 * 1024 + (4 * (lane >> 5)) * 32 + (lane & 31);      // this wave's planes, this lane's origin
+    float* const mw = smem + xi00 * 1024 + (4 * (elane >> 5)) * 32 + (elane & 31);      // this wave's planes, this lane's origin
     const float* const mr = smem + etile * 32 + ecq * 4;
     f32x4 gsum[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, gsq[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
     const bool full = eny == 4 && enx == 4;
@@ -952,17 +1044,17 @@ __global__ __launch_bounds__(256) void wino44_kernel(W44Params p) {
                     gsq[blk][e] += __shfl_xor(gsq[blk][e], o);
                 }
         __syncthreads();
-        if (lane < 8) {
+        if (elane < 8) {
 #pragma unroll
             for (int blk = 0; blk < 2; ++blk) {
-                *reinterpret_cast<f32x4*>(smem + (((wave * 2 + blk) * 8 + lane) * 2) * 4) = gsum[blk];
-                *reinterpret_cast<f32x4*>(smem + (((wave * 2 + blk) * 8 + lane) * 2 + 1) * 4) = gsq[blk];
+                *reinterpret_cast<f32x4*>(smem + (((wave * 2 + blk) * 8 + elane) * 2) * 4) = gsum[blk];
+                *reinterpret_cast<f32x4*>(smem + (((wave * 2 + blk) * 8 + elane) * 2 + 1) * 4) = gsq[blk];
             }
         }
         __syncthreads();
-        if (tid < 16) {
+        if (etid < 16) {
 #pragma clang fp contract(off)
-            const int blk = tid >> 3, cq = tid & 7;
+            const int blk = etid >> 3, cq = etid & 7;
             const int n = n0 + blk * 32 + cq * 4;
             f32x4 s = {0.f, 0.f, 0.f, 0.f}, q = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -988,27 +1080,21 @@ __global__ __launch_bounds__(256) void wino44_kernel(W44Params p) {
 // runs of adjacent tiles a 32-tile block can touch: floor((QBM - 2) / Tx) + 2
 bool w44_ok(const W44Geom& g) { return (QBM - 2) / g.Tx + 2 <= QSEG; }
 
-int w44_zeros(const float** out) {      // per device (a process may drive several)
-    static const float* cache[64] = {nullptr};
-    int dev = 0;
-    LM_HIP(hipGetDevice(&dev));
-    LM_REQUIRE(dev >= 0 && dev < 64, "conv_wino44: device index %d", dev);
-    if (!cache[dev]) {
-        void* sym = nullptr;
-        LM_HIP(hipGetSymbolAddress(&sym, HIP_SYMBOL(g_w44_zeros)));
-        cache[dev] = (const float*)sym;
-    }
-    *out = cache[dev];
-    return LM_OK;
-}
+// the patch loads address an image through 32-bit byte offsets (buffer resource per image): bytes from its first pixel to the end of its
+// last pixel's operand channels
+bool w44_image_ok(int H, int W, int Cin, int ldx) { return ((long)H * W - 1) * ldx * 4 + (long)Cin * 4 < (1L << 31); }
 
 }  // namespace
 
-// 1 if lm_conv3x3_winograd44_f32 covers the shape
-LM_API int lm_winograd44_supported(int H, int W, int Cin, int dil) {
-    if (dil < 1 || H < 1 || W < 1 || Cin < 16 || Cin % 16 != 0 || Cin > 1024) return 0;
-    return w44_ok(geom44(1, H, W, dil)) ? 1 : 0;
+// 1 if lm_conv3x3_winograd44_f32 covers the shape with an input of pixel stride ldx (floats): an image whose operand spans 2^31 bytes or
+// more is refused (32-bit offsets in the patch loads) - the callers take the direct kernel for it
+LM_API int lm_winograd44_supported_ld(int H, int W, int Cin, int dil, int ldx) {
+    if (dil < 1 || H < 1 || W < 1 || Cin < 16 || Cin % 16 != 0 || Cin > 1024 || ldx < Cin) return 0;
+    return w44_ok(geom44(1, H, W, dil)) && w44_image_ok(H, W, Cin, ldx) ? 1 : 0;
 }
+
+// the same for a dense input (ldx = Cin)
+LM_API int lm_winograd44_supported(int H, int W, int Cin, int dil) { return lm_winograd44_supported_ld(H, W, Cin, dil, Cin); }
 
 // 32-tile chunks per image of the GroupNorm partial sums written by lm_conv3x3_winograd44_f32 (-> lm_gn_finalize's nchunk)
 LM_API int lm_winograd44_gn_chunks(int H, int W, int dil) { return dil < 1 ? 0 : geom44(1, H, W, dil).Tpad / 32; }
@@ -1030,6 +1116,7 @@ static int w44_launch(void* stream, const float* x, int ldx, const float* wu_fra
                       int Cin, int Cout, int dil, int act, double* gn_partial, float split_post) {
     LM_REQUIRE(x && wu_frag && y, "conv_wino44: null pointer");
     LM_REQUIRE(lm_winograd44_supported(H, W, Cin, dil) && B > 0, "conv_wino44: unsupported shape (H=%d W=%d Cin=%d dil=%d)", H, W, Cin, dil);
+    LM_REQUIRE(w44_image_ok(H, W, Cin, ldx), "conv_wino44: an image of the input spans 2^31 bytes or more (H=%d W=%d ldx=%d): use the direct kernel", H, W, ldx);
     LM_REQUIRE(CoutP >= Cout && CoutP % QBN == 0, "conv_wino44: CoutP=%d must be Cout=%d rounded up to %d", CoutP, Cout, QBN);
     LM_REQUIRE(ldx >= Cin && ldx % 4 == 0 && ldy >= Cout, "conv_wino44: bad leading dimension");
     LM_REQUIRE(act == LM_ACT_NONE || act == LM_ACT_RELU, "conv_wino44: activation %d not supported", act);
@@ -1040,7 +1127,6 @@ static int w44_launch(void* stream, const float* x, int ldx, const float* wu_fra
     p.x = x; p.U = wu_frag; p.scale = scale; p.shift = shift; p.res = res; p.y = y;
     p.ldx = ldx; p.ldr = ldr; p.ldy = ldy; p.C = Cin; p.Cout = Cout; p.NT = CoutP / 32; p.act = act;
     p.gn_part = gn_partial;
-    if (int e = w44_zeros(&p.zeros)) return e;
     // N tile inner: the N tiles of an M block run side by side on one XCD and share the input lines in its L2; U (2.4 MB per N tile at
     // Cin = 256) then streams from the Infinity Cache.  Measured at B = 16 against N outer: 256->256@288^2 4.06 vs 4.25 ms, 256->512@144^2
     // 2.08 vs 2.16, 256->256 d2@144^2 1.146 vs 1.162.  LANEMAP_W44_ORDER=0 selects N outer (experiments).

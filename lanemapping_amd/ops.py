@@ -39,16 +39,22 @@ def new_act(B, C_, H, W, device, dtype=torch.float32):
     return torch.empty((B, H, W, C_), device=device, dtype=dtype).permute(0, 3, 1, 2)
 
 
-def as_nhwc(x):
-    """Return (tensor, ld): x itself if it is NHWC-stored (channel stride 1, pixel-major rows, pixel
-    stride ld >= C), else an NHWC copy."""
+def nhwc_ld(x):
+    """Pixel stride of x [B,C,H,W] if it is NHWC-stored (channel stride 1, pixel-major rows, pixel stride >= C), else None."""
     B, C_, H, W = x.shape
     sb, sc, sh, sw = x.stride()
     ok = (sc == 1 or C_ == 1) and sw >= C_ and (sh == W * sw or H == 1) and (sb == H * W * sw or B == 1)
-    if not ok:
+    return sw if ok else None
+
+
+def as_nhwc(x):
+    """Return (tensor, ld): x itself if it is NHWC-stored (channel stride 1, pixel-major rows, pixel
+    stride ld >= C), else an NHWC copy."""
+    ld = nhwc_ld(x)
+    if ld is None:
         x = x.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-        sw = C_
-    return x, sw
+        ld = x.shape[1]
+    return x, ld
 
 
 # ------------------------------------------------------------------------------- weight packing
@@ -207,8 +213,16 @@ def _hooked(kind, flops, launch, executed=None):
         launch()
 
 
-def wino44_supported(H, W, cin, dil=1):
-    return bool(lib().lm_winograd44_supported(int(H), int(W), int(cin), int(dil)))
+def wino44_supported(H, W, cin, dil=1, ldx=None):
+    """ldx: pixel stride of the input in floats (default: dense, cin).  The Winograd kernel addresses an image through 32-bit byte
+    offsets: an image that spans 2^31 bytes or more (a narrow channel slice of a very wide tensor) is not covered."""
+    return bool(lib().lm_winograd44_supported_ld(int(H), int(W), int(cin), int(dil), int(cin if ldx is None else ldx)))
+
+
+def wino44_covers(x, dil=1):
+    """wino44_supported for the tensor x [B,C,H,W] as conv_wino44 would see it (as_nhwc: its own pixel stride when it is NHWC-stored,
+    a dense copy otherwise) - what the callers that fall back to the direct kernel ask."""
+    return wino44_supported(x.shape[2], x.shape[3], x.shape[1], dil, nhwc_ld(x))
 
 
 def conv_wino44(x, wf, cout, dil=1, scale=None, shift=None, res=None, act=ACT_NONE, out=None, gn_eps=None, gn_split=1):

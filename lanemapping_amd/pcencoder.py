@@ -181,7 +181,7 @@ class FPNEncoder(PackedModule):
     def _c3(x, P, wkey, cout, stride, dil, **epi):
         """3x3 convolution, pad = dilation: Winograd F(4x4,3x3) when its fragments were packed and the shape is covered, else the
         direct kernel."""
-        if (wkey + 'q') in P and stride == 1 and ops.wino44_supported(x.shape[2], x.shape[3], x.shape[1], dil):
+        if (wkey + 'q') in P and stride == 1 and ops.wino44_covers(x, dil):
             return ops.conv_wino44(x, P[wkey + 'q'], cout, dil, **epi)
         return ops.conv_mfma(x, P[wkey], cout, 3, 3, stride, dil, dil, **epi)
 
@@ -198,7 +198,7 @@ class FPNEncoder(PackedModule):
     def _conv_stats(self, P, src, conv, cout, gn):
         """conv3x3 + bias with the GroupNorm statistics coming out of the conv epilogue."""
         eps = getattr(self, gn).eps
-        if (conv + '.wq') in P and ops.wino44_supported(src.shape[2], src.shape[3], src.shape[1], 1):
+        if (conv + '.wq') in P and ops.wino44_covers(src):
             return ops.conv_wino44(src, P[conv + '.wq'], cout, 1, shift=P[conv + '.b'], gn_eps=eps)
         if (src.shape[2] * src.shape[3]) % 128 == 0:      # whole 128-row tiles per image: statistics from the direct kernel's epilogue
             return ops.conv_mfma_gnstats(src, P[conv + '.w'], cout, 3, 3, 1, 1, 1, P[conv + '.b'], eps)
@@ -268,12 +268,12 @@ class FPNEncoder(PackedModule):
         if 'semantic_branch_ab.wq' in P:
             ch = self.semantic_branch.out_channels
             for i, src in enumerate((p2, p3)):
-                if ops.wino44_supported(src.shape[2], src.shape[3], src.shape[1], 1):
+                if ops.wino44_covers(src):
                     t, st = ops.conv_wino44(src, P['semantic_branch_ab.wq'], 2 * ch, 1, shift=P['semantic_branch_ab.b'],
                                             gn_eps=self.gn11.eps, gn_split=2)              # statistics per branch half: [2, B, ch, 2]
                     pre_a[i], pre_b[i] = (t[:, :ch], st[0]), (t[:, ch:], st[1])
         a4 = b4 = None
-        if 'conv23.wq' in P and ops.wino44_supported(p4.shape[2], p4.shape[3], p4.shape[1], 1):
+        if 'conv23.wq' in P and ops.wino44_covers(p4):
             c4o = self.conv2.out_channels
             t, st = ops.conv_wino44(p4, P['conv23.wq'], 2 * c4o, 1, shift=P['conv23.b'], gn_eps=self.gn12.eps, gn_split=2)
             a4, b4 = (t[:, :c4o], st[0]), (t[:, c4o:], st[1])
