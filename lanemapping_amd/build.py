@@ -1,4 +1,5 @@
-"""Build liblanemap_hip.so (gfx950) in-tree with hipcc.  `python -m lanemapping_amd.build`."""
+"""Build liblanemap_hip.so (gfx950) in-tree with hipcc, and beside it liblanemap_diag.so, the LDS diagnostics of the tests
+(tests/hip, never linked into the product library).  `python -m lanemapping_amd.build`."""
 import os
 import subprocess
 import sys
@@ -6,6 +7,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'liblanemap_hip.so')
+DIAG_SRC = os.path.join(os.path.dirname(HERE), 'tests', 'hip')
+DIAG_LIB = os.path.join(HERE, 'liblanemap_diag.so')
+DIAG_SOURCES = ['lds_state.hip']        # same compiler and flags as SOURCES; linked with errors.cpp's helpers into a library of their own
 SOURCES = ['errors.cpp', 'conv_mfma.hip', 'conv_wino44.hip', 'conv_direct.hip', 'norm_resize.hip', 'vit.hip', 'mixer.hip', 'head.hip', 'head_endpoint.hip',
            'decode.hip', 'raster.hip', 'strip.hip', 'ground.hip', 'intensity.hip', 'drape.hip', 'gapfill.hip', 'rowref.hip', 'prim.hip', 'lidar.hip', 'label.hip', 'profile.hip', 'postproc.cpp', 'backproject.cpp', 'png_reader.cpp', 'lane_json.cpp', 'merge_lines.cpp', 'skeleton.cpp']
 
@@ -17,11 +21,18 @@ EXACT_FP = {'raster.hip', 'strip.hip', 'ground.hip', 'intensity.hip', 'drape.hip
 EXTRA_FLAGS = {'conv_wino44.hip': ['-fno-slp-vectorize']}
 
 
+def _diag_sources():
+    """The diagnostics sources that are there: the package also builds where the tests directory is another one, or absent - then the
+    product library alone."""
+    return [f for f in DIAG_SOURCES if os.path.exists(os.path.join(DIAG_SRC, f))]
+
+
 def _stale():
-    if not os.path.exists(LIB):
+    diag = _diag_sources()
+    if not os.path.exists(LIB) or (diag and not os.path.exists(DIAG_LIB)):
         return True
-    t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.abspath(__file__)]
+    t = min([os.path.getmtime(LIB)] + ([os.path.getmtime(DIAG_LIB)] if diag else []))
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(DIAG_SRC, f) for f in diag] + [os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -32,16 +43,21 @@ def build(force=False, verbose=True):
     objs = []
     procs = []
     os.makedirs(os.path.join(HERE, 'build'), exist_ok=True)
-    for src in SOURCES:
+    diag_objs = [os.path.join(HERE, 'build', 'errors.cpp.o')]
+    diag_sources = _diag_sources()
+    for src in SOURCES + diag_sources:
+        diag = src in diag_sources
         obj = os.path.join(HERE, 'build', src + '.o')
         cmd = [hipcc, '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fvisibility=hidden',
-               '-x', 'hip', '-c', os.path.join(CSRC, src), '-o', obj]
+               '-x', 'hip', '-c', os.path.join(DIAG_SRC if diag else CSRC, src), '-o', obj]
+        if diag:
+            cmd.insert(4, '-I' + CSRC)
         if src in EXACT_FP:
             cmd.insert(4, '-ffp-contract=off')
         for fl in EXTRA_FLAGS.get(src, []):
             cmd.insert(4, fl)
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
-        objs.append(obj)
+        (diag_objs if diag else objs).append(obj)
     for src, p in procs:
         out, _ = p.communicate()
         if p.returncode != 0:
@@ -51,8 +67,10 @@ def build(force=False, verbose=True):
             sys.stderr.write(out.decode())
     cmd = [hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', LIB] + objs
     subprocess.check_call(cmd)
+    if diag_sources:
+        subprocess.check_call([hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', DIAG_LIB] + diag_objs)
     if verbose:
-        print(f'built {LIB}')
+        print(f'built {LIB}' + (f' and {DIAG_LIB}' if diag_sources else ''))
     return LIB
 
 

@@ -7,9 +7,13 @@ write changes it, and a logical element that still holds it was never written).
 
 guarded_runs() runs a case three times - guards benign (0), guards poisoned, and at batch 3 with elements 0 and 2 poisoned - and checks
 the canaries of every output after each run, bit-identical logical outputs between the first two, and element 1 of the batch-3 run
-bit-identical to the batch-1 run.
+bit-identical to the batch-1 run.  It then repeats the benign batch-1 run with every CU's LDS pre-filled with each non-zero word of
+lds_state.WORDS (NaN / all ones, +Inf): the canaries hold and the logical outputs keep the bits of the benign run, so no output depends
+on an LDS cell the launch did not write itself (tests/lds_state.py).
 """
 import torch
+
+from lds_state import WORDS, poisoned as lds_poisoned
 
 NAN = float('nan')
 INF = float('inf')
@@ -102,4 +106,15 @@ def guarded_runs(run, name, batch=True):
             mid = got[(3, True)][k][0][rpe:2 * rpe]
             assert torch.equal(bits, mid), (f'{name} [{k}]: batch element 1 of 3 (neighbours poisoned) differs from the batch-1 call in '
                                             f'{int((bits != mid).sum())} words')
+    for word in WORDS[1:]:
+        with lds_poisoned(word) as lds:
+            outs = run(1, False)
+            torch.cuda.synchronize()
+        assert lds.fills > 0, f'{name}: the run after LDS = 0x{word:08X} enqueued no fill'
+        for k, (s, _) in outs.items():
+            s.check_canary(f'{name} [{k}, B=1, benign guards, LDS pre-filled with 0x{word:08X}]')
+            lb, bits = s.logical_bits(), got[(1, False)][k][0]
+            diff = (lb != bits).reshape(-1)
+            assert not bool(diff.any()), (f'{name} [{k}]: LDS pre-filled with 0x{word:08X} changed {int(diff.sum())} logical output words, first '
+                                          f'at flat index {int(diff.nonzero()[0])}: an LDS cell this launch never wrote reaches the output')
     return {k: v[2] for k, v in got[(1, False)].items()}

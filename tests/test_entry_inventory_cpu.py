@@ -11,9 +11,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # queries (workspace sizes, chunk / tile counts): their results size the launches that the tests do check
 NOT_DIRECTLY_TESTED = {
     'lm_winograd44_tiles': 'query: Winograd tile count (profiling FLOP count in conv_wino44)',
-    'lm_endp_topk_workspace_bytes': 'query: workspace size of lm_endp_topk',
-    'lm_scan_workspace_bytes': 'query: workspace size of the exclusive scan',
-    'lm_sort_pairs_workspace_bytes': 'query: workspace size of the pair sort',
 }
 
 

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import label_ref as lr
+import lds_state
 from guards import Slab, guarded_runs
 from lanemapping_amd import io_utils, las_io, ops
 from lanemapping_amd._lib import lib
@@ -301,8 +302,9 @@ def test_counts_of_more_lines_than_the_lds_histogram_holds(dev, tmp_path):
     index = ops.line_index(seg, lr.HW, device=dev)
     assert index.n_lines == L
     labels = MarkingLabels(lr.HW, lr.ZTOL)
-    for attempt in range(2):                                             # integer adds: the same counts every run
-        rc, d_out, line, counts = _label_call(dev, torch.from_numpy(flat).to(dev), 28, 1, n, index, L, labels)
+    for word in lds_state.WORDS:                                         # integer adds: the same counts every run, whatever LDS held before
+        with lds_state.poisoned(word):                                   # (0xFFFFFFFF / +Inf in the LDS histogram the kernel must clear itself)
+            rc, d_out, line, counts = _label_call(dev, torch.from_numpy(flat).to(dev), 28, 1, n, index, L, labels)
         assert rc == 0, lib().lm_last_error()
         assert np.array_equal(line.cpu().numpy(), want_line)
         assert np.array_equal(counts.cpu().numpy(), np.bincount(want_line, minlength=L + 1))

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import lds_state
 from lanemapping_amd import io_utils, ops, synth
 from lanemapping_amd._lib import LanemapHipError, LmRasterParams, lib
 
@@ -266,6 +267,11 @@ def test_strip_bin_guards(dev):
     rc, out = run(total - 1)
     assert rc == 4 and b'binned holds' in L.lm_last_error()
     assert bool((out == CANARY).all()), 'a refused call wrote to binned'
+    for word in lds_state.WORDS:                                   # whatever LDS held before (tests/lds_state.py): the tile table with its
+        with lds_state.poisoned(word) as lds:                      # UNSET sentinel and the per-wave counters are the launch's own.  run()
+            rc, out = run(total)                                   # holds counts and offsets to the host cut, binned follows here
+        assert lds.fills == 1 and rc == 0, L.lm_last_error()
+        assert np.array_equal(out.cpu().numpy().view(np.uint32).reshape(-1, 4), want.view(np.uint32)), f'binned after LDS = 0x{word:08X}'
 
 
 def test_wrapper_retries_once_when_its_guess_is_short(dev):
