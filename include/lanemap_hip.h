@@ -621,6 +621,38 @@ int lm_las_line_profile_records(void* hip_stream, const unsigned char* records, 
                                 float half_width, const float* stations, const int* bin_start, const int* bin_start_host, int L, double bin,
                                 float z_tol, float min_intensity, int accumulate, long* bins, long n_bins);
 
+/* ---- the colour of the markings (csrc/profile.hip): white or yellow, from the 16-bit R, G, B triple that colourised deliveries carry per
+ * return.  Point formats 2, 3, 5, 7, 8 and 10 hold it as three u16 LE at byte 20 (format 2), 28 (3, 5) or 30 (7, 8, 10) of the record;
+ * formats 0, 1, 4, 6 and 9 have no colour.
+ * THE RULE (one definition: las_profile_kernel<true>, this text, tests/colour_ref.py).  Eligibility, the hit test, the winner, the station
+ * bin b and the row bin_start[k-1] + b are exactly the marking profile's above, min_intensity and `select` included: a record that `select`
+ * drops contributes nothing.  For a return that lands in a bin, with its R, G, B:
+ *     BLACK     R == 0 && G == 0 && B == 0 (colourisation leaves such triples where no camera saw the point): n_black += 1, nothing else
+ *     COLOURED  any other triple: n_c += 1, sum R += R, sum G += G, sum B += B
+ *     YELLOW    a coloured return with 2048 B < blue_q (R + G): n_yellow += 1.  blue_q = round(1024 yellow_ratio), an integer in 1 .. 1024:
+ *               "blue is below yellow_ratio of the mean of red and green".  Both sides fit 32 bits; equality is not yellow; the test does
+ *               not depend on the scale of the triple, so 8-bit values stored in the 16-bit fields need no special case.
+ * OUTPUT.  colours [n_bins][6] int64 = n_c, sum R, sum G, sum B, n_yellow, n_black per bin; an empty bin reads six zeros.  Integer sums only:
+ * the result does not depend on the order of the records or of the adds, every run writes the same bits, no float atomic is used.
+ * las_line_colour_records: the arguments of lm_las_line_profile_records, blue_q after min_intensity, colours after bins.  The records are
+ *         read ONCE: the same kernel, instantiated with the colour part, writes both tensors, and bins holds bit for bit what
+ *         lm_las_line_profile_records writes for the same arguments.  accumulate covers both tensors: 0 initialises both on the stream
+ *         first, 1 adds to both.  The wave merges the colour row as it merges the profile's: per distinct bin among its lanes the three sums
+ *         by cross-lane adds (64 x 65535 fits 32 bits), the three counts by ballots, then the row's 64-bit integer atomics (an add of 0 is
+ *         left out).  Asynchronous, no workspace, nothing read back.  n = 0, S = 0 or n_bins = 0 is LM_OK after the initialisation.
+ * Refused with LM_ERR_ARG and a message that names the argument, before anything is launched or written: everything
+ * lm_las_line_profile_records refuses; a point_format without colour ("point_format=1 carries no RGB"); blue_q outside 1 .. 1024; a null
+ * colours with n_bins > 0; a colours that is not 8-byte aligned, named alone; colours overlapping bins.
+ * NOT HERE: a points entry.  Decoded clouds ([N][4] xyzi) carry no colour; giving them one means changing the compaction of
+ * lm_las_decode_select, which is another change.
+ * NOTE on the name `hip_stream`: as for lm_label_points above; the guarded-buffer case of this entry is
+ * tests/test_gpu_colour.py::test_colour_records_guards. */
+int lm_las_line_colour_records(void* hip_stream, const unsigned char* records, int record_len, int point_format, long n,
+                               const double* scale, const double* offset, const double* shift, const LmLasSelect* select,
+                               const float* segments, long S, const LmLineGrid* grid, const int* cell_start, const int* cell_segs,
+                               float half_width, const float* stations, const int* bin_start, const int* bin_start_host, int L, double bin,
+                               float z_tol, float min_intensity, int blue_q, int accumulate, long* bins, long* colours, long n_bins);
+
 /* ---- PNG tile ingest (replaces PIL in `load_img`, baseline/datasets/laserlane_proposals.py:85-98 and laserlane.py:214-219:
  * np.array(Image.open(path)) -> uint8 HWC).  Host code, no third-party library (PIL runs zlib; the DEFLATE decoder here is
  * csrc/inflate.h), 8-bit non-interlaced grey / grey+alpha / RGB / RGBA only; palette, 16-bit and Adam7 files are refused; chunk CRCs

@@ -21,6 +21,16 @@
 // wave-uniform exit as the label kernels.  So the lanes are merged inside the wave before anything goes to memory: loop over the distinct
 // bins present in the wave (ballot, first set lane), reduce the six quantities across the lanes of that bin, and lanes 0 .. 5 issue the
 // six 64-bit integer atomics of the bin's row (48 contiguous bytes).  A bin held by one lane alone skips the reduction.
+//
+// The colour of the markings (lm_las_line_colour_records).  Point formats 2, 3, 5, 7, 8 and 10 carry a 16-bit R, G, B triple per return
+// (at byte 20, 28, 28, 30, 30, 30).  For a return that lands in a bin the same pass over the records also fills colours[bin] = n_c, sum R,
+// sum G, sum B, n_yellow, n_black: a triple of three zeros is BLACK (no camera saw the point) and adds 1 to n_black and nothing else; any
+// other triple is COLOURED and votes yellow when 2048 B < blue_q (R + G), blue_q in 1 .. 1024 (both sides fit 32 bits; equality is not
+// yellow; the test does not depend on the scale of the triple).  Integer sums again: the same bits in every run.
+// las_profile_kernel is a template for this: <false> is the profile kernel as it was, instruction for instruction; <true> reads the three
+// colour words of the lane's staged record before the barrier that frees the stage and runs a second wave merge after profile_merge.  One
+// kernel name, because every kernel with LDS owns a case in the LDS-state tests under its name; a separate colour pass would also read
+// every record twice.
 #include "common.h"
 #include "label_rule.h"
 #include "las_record.h"
@@ -28,6 +38,7 @@
 #include <cmath>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 
 struct LmLasSelect {          // include/lanemap_hip.h
@@ -51,6 +62,15 @@ struct ProfDev {
     int L, n_bins;
     float inv_bin;
 };
+
+struct ColourDev : ProfDev {             // what las_profile_kernel<true> takes instead
+    long long* colours;                  // [n_bins][6]
+    int rgb_off;                         // byte offset of R in a record
+    unsigned blue_q;                     // 1 .. 1024
+};
+
+template <bool COLOUR>
+using ProfArg = std::conditional_t<COLOUR, ColourDev, ProfDev>;
 
 // the bin (absolute, -1: none), q and iq of a point whose winner is segment s of line ln at t.  bin_start and stations are device tables
 // the host cannot see: whatever they hold, a bin outside [0, n_bins) is never returned and bin_start is never read outside [0, L].
@@ -117,6 +137,42 @@ __device__ __forceinline__ void profile_merge(long long* __restrict__ bins, int 
     }
 }
 
+// Wave-uniform like profile_merge, for the colour row: r, g, b the triple of the lane's return (anything where B = -1).  The three sums by
+// __shfl_xor (64 * 65535 fits 32 bits; a black return adds three zeros), the three counts by ballots; lanes 0 .. 5 issue the row's
+// atomics, an add of 0 is left out.
+__device__ __forceinline__ void colour_merge(long long* __restrict__ colours, int B, unsigned r, unsigned g, unsigned b, unsigned blue_q) {
+    const int lane = (int)__lane_id();
+    const bool black = (r | g | b) == 0u;
+    const bool yellow = !black && 2048u * b < blue_q * (r + g);       // <= 2048 * 65535 and <= 1024 * 131070: no overflow
+    unsigned long long todo = __ballot(B >= 0);
+    while (todo) {
+        const int leader = __ffsll(todo) - 1;
+        const int lb = __shfl(B, leader);
+        const bool mine = B == lb;
+        const unsigned long long m = __ballot(mine);
+        const unsigned long long nk = (unsigned long long)__popcll(__ballot(mine && black));
+        const unsigned long long ny = (unsigned long long)__popcll(__ballot(mine && yellow));
+        const unsigned long long nc = (unsigned long long)__popcll(m) - nk;
+        unsigned sr, sg, sb;
+        if (__popcll(m) == 1) {                                        // one lane alone: its triple, read off the leader
+            sr = (unsigned)__shfl((int)r, leader), sg = (unsigned)__shfl((int)g, leader), sb = (unsigned)__shfl((int)b, leader);
+        } else {
+            sr = mine ? r : 0u, sg = mine ? g : 0u, sb = mine ? b : 0u;
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) {
+                sr += (unsigned)__shfl_xor((int)sr, d);
+                sg += (unsigned)__shfl_xor((int)sg, d);
+                sb += (unsigned)__shfl_xor((int)sb, d);
+            }
+        }
+        if (lane < 6) {
+            const unsigned long long v = lane == 0 ? nc : lane == 1 ? sr : lane == 2 ? sg : lane == 3 ? sb : lane == 4 ? ny : nk;
+            if (v) atomicAdd(reinterpret_cast<unsigned long long*>(colours + (long)lb * 6) + lane, v);
+        }
+        todo &= ~m;
+    }
+}
+
 // grid: ceil(n_bins * 6 / 256)
 __global__ __launch_bounds__(256) void profile_init_kernel(long long* __restrict__ bins, long words) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
@@ -124,6 +180,12 @@ __global__ __launch_bounds__(256) void profile_init_kernel(long long* __restrict
         const int c = (int)(i % 6);
         bins[i] = c < 4 ? 0LL : c == 4 ? 2147483647LL : -2147483648LL;
     }
+}
+
+// grid: ceil(words / 256)
+__global__ __launch_bounds__(256) void colour_init_kernel(long long* __restrict__ colours, long words) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < words) colours[i] = 0LL;
 }
 
 // grid: ceil(N / 1024) workgroups
@@ -154,14 +216,17 @@ __global__ __launch_bounds__(256) void profile_points_kernel(const lab_f32x4* __
 }
 
 // grid: min(blocks of 256 records, the workgroups resident at once) workgroups; dynamic LDS = 256 records.  Per block: stage, decode into
-// registers, barrier (the stage is free again), search and accumulate.  The records are only read.
+// registers, barrier (the stage is free again), search and accumulate.  The records are only read.  COLOUR: P is a ColourDev, the lane also
+// takes the R, G, B of its own staged record into registers before the barrier, and the colour row is merged after the profile's.
+template <bool COLOUR>
 __global__ __launch_bounds__(256) void las_profile_kernel(const unsigned* __restrict__ rec, int record_len, long n, long nblk, LasXf X, LasSel S,
-                                                          int use_sel, IndexDev I, ProfDev P) {
+                                                          int use_sel, IndexDev I, ProfArg<COLOUR> P) {
     extern __shared__ unsigned prof_stage[];
     for (long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
         const int cnt = las_stage_block(rec, record_len, n, blk, prof_stage);
         float4 p = {0.f, 0.f, 0.f, 0.f};
         int a = 0, b = 0;
+        unsigned cr = 0u, cg = 0u, cb = 0u;
         if ((int)threadIdx.x < cnt) {
             const unsigned char* r = reinterpret_cast<const unsigned char*>(prof_stage) + (int)threadIdx.x * record_len;
             bool pass = true;
@@ -169,6 +234,10 @@ __global__ __launch_bounds__(256) void las_profile_kernel(const unsigned* __rest
             if (use_sel) pass = las_record_keep(r, X, S, cls, p);
             else p = las_record_xyzi(r, X);
             if (pass) label_range(p, I, a, b);                 // a record that `select` drops contributes nothing
+            if constexpr (COLOUR) {                            // rgb_off + 6 <= the format's minimum record_len: inside the lane's own record
+                const unsigned char* c = r + P.rgb_off;
+                cr = (unsigned)c[0] | ((unsigned)c[1] << 8), cg = (unsigned)c[2] | ((unsigned)c[3] << 8), cb = (unsigned)c[4] | ((unsigned)c[5] << 8);
+            }
         }
         __syncthreads();                                       // every record is in registers: the next block may be staged
         if (__ballot(b > a) == 0) continue;
@@ -179,11 +248,13 @@ __global__ __launch_bounds__(256) void las_profile_kernel(const unsigned* __rest
         unsigned iq = 0u;
         if (ln > 0) B = profile_bin(p, I, P, ln, s, t, q, iq);
         profile_merge(P.bins, B, q, iq);
+        if constexpr (COLOUR) colour_merge(P.colours, B, cr, cg, cb, P.blue_q);
     }
 }
 
-// Workgroups of las_profile_kernel the current device holds at once for `lds` bytes of dynamic LDS (as label.hip's: asked of the runtime
-// once per (device, lds) and kept; the number only sizes the grid).
+// Workgroups of las_profile_kernel<COLOUR> the current device holds at once for `lds` bytes of dynamic LDS (as label.hip's: asked of the
+// runtime once per (device, lds) and instantiation, and kept; the number only sizes the grid).
+template <bool COLOUR>
 int resident_groups(size_t lds, long& groups) {
     static std::mutex mu;
     static std::map<std::pair<int, size_t>, long> known;
@@ -196,7 +267,7 @@ int resident_groups(size_t lds, long& groups) {
         return LM_OK;
     }
     int per_cu = 0, cus = 0;
-    LM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, las_profile_kernel, 256, lds));
+    LM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, las_profile_kernel<COLOUR>, 256, lds));
     LM_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev_id));
     groups = (long)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 256);
     groups = groups < REC_GROUPS ? groups : REC_GROUPS;
@@ -240,6 +311,14 @@ int init_bins(const ProfDev& P, hipStream_t s) {
     return LM_OK;
 }
 
+int init_colours(const ColourDev& P, hipStream_t s) {
+    const long words = (long)P.n_bins * 6;
+    if (words == 0) return LM_OK;
+    hipLaunchKernelGGL(colour_init_kernel, dim3((unsigned)lm_cdivl(words, 256)), dim3(256), 0, s, P.colours, words);
+    LM_LAUNCH_CHECK();
+    return LM_OK;
+}
+
 }  // namespace
 
 // points_xyzi: DEVICE [N][4] f32; the index arguments of lm_label_points; stations DEVICE [S][4] f32, bin_start DEVICE [L + 1] int32,
@@ -267,20 +346,24 @@ LM_API int lm_line_profile_points(void* hip_stream, const float* points_xyzi, lo
     return LM_OK;
 }
 
-// records: DEVICE, n record_len bytes rounded up to a multiple of 4, 4-byte aligned, only read; the rest as above.
-LM_API int lm_las_line_profile_records(void* hip_stream, const unsigned char* records, int record_len, int point_format, long n,
-                                       const double* scale, const double* offset, const double* shift, const LmLasSelect* select,
-                                       const float* segments, long S, const LmLineGrid* grid, const int* cell_start, const int* cell_segs,
-                                       float half_width, const float* stations, const int* bin_start, const int* bin_start_host, int L,
-                                       double bin, float z_tol, float min_intensity, int accumulate, long* bins, long n_bins) {
+namespace {
+
+// The two record entries.  COLOUR: blue_q and colours are checked after everything the profile entry refuses, both tensors are initialised,
+// and las_profile_kernel<true> fills both in its one pass over the records.
+template <bool COLOUR>
+int las_profile_records(const char* who, void* hip_stream, const unsigned char* records, int record_len, int point_format, long n,
+                        const double* scale, const double* offset, const double* shift, const LmLasSelect* select, const float* segments, long S,
+                        const LmLineGrid* grid, const int* cell_start, const int* cell_segs, float half_width, const float* stations,
+                        const int* bin_start, const int* bin_start_host, int L, double bin, float z_tol, float min_intensity, int blue_q,
+                        int accumulate, long* bins, long* colours, long n_bins) {
     static const int min_len[11] = {20, 28, 26, 34, 57, 63, 30, 36, 38, 59, 67};
-    const char* who = "las_line_profile_records";
+    static const int rgb_off[11] = {-1, -1, 20, 28, -1, 28, -1, 30, 30, -1, 30};      // rgb_off + 6 <= min_len wherever there is colour
     LM_REQUIRE(point_format >= 0 && point_format <= 10, "%s: unknown point data record format point_format=%d", who, point_format);
     LM_REQUIRE(record_len >= min_len[point_format] && record_len <= 160, "%s: bad record_len=%d for format %d (%d .. 160)", who, record_len,
                point_format, min_len[point_format]);
     LM_REQUIRE(n >= 0 && n <= 2147483647L, "%s: n=%ld records, at most 2^31 - 1 are supported", who, n);
     IndexDev I;
-    ProfDev P;
+    ProfArg<COLOUR> P;
     if (int e = check_profile(who, grid, S, segments, cell_start, cell_segs, half_width, stations, bin_start, bin_start_host, L, bin, z_tol,
                               accumulate, bins, n_bins, I, P))
         return e;
@@ -296,6 +379,15 @@ LM_API int lm_las_line_profile_records(void* hip_stream, const unsigned char* re
         for (int k = 0; k < 8; ++k) Sel.cls[k] = select->class_mask[k];
         Sel.drop = select->drop_flags, Sel.returns = select->returns, Sel.z_lo = select->z_lo, Sel.z_hi = select->z_hi;
     }
+    if constexpr (COLOUR) {
+        LM_REQUIRE(rgb_off[point_format] >= 0, "%s: point_format=%d carries no RGB (formats 2, 3, 5, 7, 8 and 10 do)", who, point_format);
+        LM_REQUIRE(blue_q >= 1 && blue_q <= 1024, "%s: blue_q=%d must lie in 1 .. 1024", who, blue_q);
+        LM_REQUIRE(n_bins == 0 || colours, "%s: null pointer (colours)", who);
+        LM_REQUIRE(((uintptr_t)colours & 7) == 0, "%s: colours is not 8-byte aligned", who);
+        const uintptr_t b0 = (uintptr_t)bins, c0 = (uintptr_t)colours, bytes = (uintptr_t)n_bins * 48;
+        LM_REQUIRE(n_bins == 0 || b0 + bytes <= c0 || c0 + bytes <= b0, "%s: colours overlaps bins", who);
+        P.colours = reinterpret_cast<long long*>(colours), P.rgb_off = rgb_off[point_format], P.blue_q = (unsigned)blue_q;
+    }
     Sel.fmt6 = point_format >= 6;
     I.min_inten = min_intensity;
     hipStream_t s = (hipStream_t)hip_stream;
@@ -304,15 +396,43 @@ LM_API int lm_las_line_profile_records(void* hip_stream, const unsigned char* re
     const size_t lds = ((size_t)256 * record_len + 3) / 4 * 4;
     long resident = 0;
     if (work)
-        if (int e = resident_groups(lds, resident)) return e;
-    if (!accumulate)
+        if (int e = resident_groups<COLOUR>(lds, resident)) return e;
+    if (!accumulate) {
         if (int e = init_bins(P, s)) return e;
+        if constexpr (COLOUR)
+            if (int e = init_colours(P, s)) return e;
+    }
     if (!work) return LM_OK;
     const double sh[3] = {shift ? shift[0] : 0.0, shift ? shift[1] : 0.0, shift ? shift[2] : 0.0};
     const LasXf X{scale[0], scale[1], scale[2], offset[0] - sh[0], offset[1] - sh[1], offset[2] - sh[2], 0.f, 1.f, 0};   // raw intensity
     const unsigned groups = (unsigned)(nblk < resident ? nblk : resident);
-    hipLaunchKernelGGL(las_profile_kernel, dim3(groups), dim3(256), lds, s, reinterpret_cast<const unsigned*>(records), record_len, n, nblk, X,
-                       Sel, select ? 1 : 0, I, P);
+    hipLaunchKernelGGL(las_profile_kernel<COLOUR>, dim3(groups), dim3(256), lds, s, reinterpret_cast<const unsigned*>(records), record_len, n, nblk,
+                       X, Sel, select ? 1 : 0, I, P);
     LM_LAUNCH_CHECK();
     return LM_OK;
+}
+
+}  // namespace
+
+// records: DEVICE, n record_len bytes rounded up to a multiple of 4, 4-byte aligned, only read; the rest as above.
+LM_API int lm_las_line_profile_records(void* hip_stream, const unsigned char* records, int record_len, int point_format, long n,
+                                       const double* scale, const double* offset, const double* shift, const LmLasSelect* select,
+                                       const float* segments, long S, const LmLineGrid* grid, const int* cell_start, const int* cell_segs,
+                                       float half_width, const float* stations, const int* bin_start, const int* bin_start_host, int L,
+                                       double bin, float z_tol, float min_intensity, int accumulate, long* bins, long n_bins) {
+    return las_profile_records<false>("las_line_profile_records", hip_stream, records, record_len, point_format, n, scale, offset, shift, select,
+                                      segments, S, grid, cell_start, cell_segs, half_width, stations, bin_start, bin_start_host, L, bin, z_tol,
+                                      min_intensity, 0, accumulate, bins, nullptr, n_bins);
+}
+
+// as above, point formats 2, 3, 5, 7, 8, 10; colours DEVICE [n_bins][6] int64, disjoint from bins.  One pass over the records fills both.
+LM_API int lm_las_line_colour_records(void* hip_stream, const unsigned char* records, int record_len, int point_format, long n,
+                                      const double* scale, const double* offset, const double* shift, const LmLasSelect* select,
+                                      const float* segments, long S, const LmLineGrid* grid, const int* cell_start, const int* cell_segs,
+                                      float half_width, const float* stations, const int* bin_start, const int* bin_start_host, int L,
+                                      double bin, float z_tol, float min_intensity, int blue_q, int accumulate, long* bins, long* colours,
+                                      long n_bins) {
+    return las_profile_records<true>("las_line_colour_records", hip_stream, records, record_len, point_format, n, scale, offset, shift, select,
+                                     segments, S, grid, cell_start, cell_segs, half_width, stations, bin_start, bin_start_host, L, bin, z_tol,
+                                     min_intensity, blue_q, accumulate, bins, colours, n_bins);
 }

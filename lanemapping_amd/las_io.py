@@ -27,6 +27,10 @@ the intensities a tile, or the whole strip, keeps (`ops.tile_intensity_window`),
 `MarkingSurvey` / `line_stations` / `survey_las` / `marking_summary` profile the lines from the same returns: per station bin along every
 line the count, intensity and lateral spread of its returns (`ops.line_profile`, `lm_las_line_profile_records`), and on the host the paint
 runs, dash pattern, width and brightness read off the bins.
+
+`MarkingColour` / `rgb_offset` / `survey_colour_las` / `marking_colours` add the colour of a marking, white or yellow, from the R, G, B
+triple that point formats 2, 3, 5, 7, 8 and 10 carry per return: the same pass over the records fills a second table per station bin
+(`lm_las_line_colour_records`), and the host reads a colour per line and per paint run off it.
 """
 import ctypes as C
 import math
@@ -726,6 +730,222 @@ def marking_summary(bins, bin_start, survey):
                     'gap': float(np.median(gaps_m)) if gaps_m else None,
                     'width': float(np.median((b[on, 5] - b[on, 4]).astype(np.float64) / 1024.0)) if painted else None,
                     'intensity': int(b[on, 1].sum()) / n_sum if painted else None})
+    return out
+
+
+RGB_OFFSET = {2: 20, 3: 28, 5: 28, 7: 30, 8: 30, 10: 30}      # byte offset of the u16 LE R, G, B triple (LAS 1.4 R15, tables 10 .. 18)
+
+
+def rgb_offset(point_format):
+    """-> the byte offset of the 16-bit R, G, B triple in a record of this point data record format (2: 20; 3, 5: 28; 7, 8, 10: 30), or
+    None for a format without colour (0, 1, 4, 6, 9)."""
+    if isinstance(point_format, bool) or not isinstance(point_format, (int, np.integer)) or not 0 <= int(point_format) <= 10:
+        raise ValueError(f'rgb_offset: unknown point data record format {point_format!r}')
+    return RGB_OFFSET.get(int(point_format))
+
+
+class MarkingColour:
+    """How the LAS -> map routes tell white markings from yellow ones (immutable; Runner.infer_las_strip_to_map / infer_las_to_map,
+    `colour=` beside `survey=`; survey_colour_las, marking_colours).  The returns of a line's station bins (MarkingSurvey's rule) that
+    carry a colour - any R, G, B triple but three zeros, which colourisation leaves where no camera saw the point - are counted and
+    summed per bin, and each votes yellow when its blue lies below yellow_ratio of the mean of its red and green (the rule:
+    include/lanemap_hip.h).
+
+      yellow_ratio    0 < yellow_ratio <= 1: a coloured return votes yellow when B < yellow_ratio (R + G) / 2, evaluated in integers as
+                      2048 B < blue_q (R + G) with blue_q = round(1024 yellow_ratio), at least 1
+      yellow_share    0 < yellow_share <= 1: a line, or a paint run, is 'yellow' when at least this share of its coloured returns votes
+                      yellow, else 'white'
+      min_coloured    a line or run with fewer coloured returns than this is 'unknown' (whole number >= 1)
+    The three defaults are plain defaults, not tuned values."""
+    __slots__ = ('yellow_ratio', 'yellow_share', 'min_coloured')
+
+    def __init__(self, yellow_ratio=0.75, yellow_share=0.5, min_coloured=10):
+        num = (int, float, np.integer, np.floating)
+        if isinstance(yellow_ratio, bool) or not isinstance(yellow_ratio, num) or not (0.0 < float(yellow_ratio) <= 1.0):
+            raise ValueError(f'MarkingColour: yellow_ratio={yellow_ratio!r} must be a number with 0 < yellow_ratio <= 1')
+        if isinstance(yellow_share, bool) or not isinstance(yellow_share, num) or not (0.0 < float(yellow_share) <= 1.0):
+            raise ValueError(f'MarkingColour: yellow_share={yellow_share!r} must be a number with 0 < yellow_share <= 1')
+        if isinstance(min_coloured, bool) or not isinstance(min_coloured, (int, np.integer)) or int(min_coloured) < 1:
+            raise ValueError(f'MarkingColour: min_coloured={min_coloured!r} must be a whole number >= 1')
+        for k, v in (('yellow_ratio', float(yellow_ratio)), ('yellow_share', float(yellow_share)), ('min_coloured', int(min_coloured))):
+            object.__setattr__(self, k, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError('MarkingColour is immutable')
+
+    def __delattr__(self, name):
+        raise AttributeError('MarkingColour is immutable')
+
+    def __repr__(self):
+        return 'MarkingColour(' + ', '.join(f'{k}={getattr(self, k)!r}' for k in self.__slots__) + ')'
+
+    def __eq__(self, other):
+        return isinstance(other, MarkingColour) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
+
+    def __hash__(self):
+        return hash(tuple(getattr(self, k) for k in self.__slots__))
+
+    @property
+    def blue_q(self):
+        """The integer lm_las_line_colour_records takes: round(1024 yellow_ratio), halves up, in 1 .. 1024."""
+        return min(1024, max(1, int(math.floor(1024.0 * self.yellow_ratio + 0.5))))
+
+
+def profile_colour_records(records_u8, header, index, stations, survey, colour, shift=None, select=None, out=None):
+    """One lm_las_line_colour_records call on the DEVICE records of a file, as profile_records: -> (bins, colours), two [n_bins, 6] int64
+    device tensors filled in one pass over the records - bins bit for bit profile_records', colours = n_c, sum R, sum G, sum B, n_yellow,
+    n_black per station bin (the rule: include/lanemap_hip.h).  out: the (bins, colours) pair of an earlier call to add to.  A header
+    whose point format has no colour is refused with a ValueError.  Asynchronous."""
+    from . import ops
+    who = 'las_io.profile_colour_records'
+    if not isinstance(survey, MarkingSurvey):
+        raise TypeError(f'{who}: survey must be a MarkingSurvey, not {type(survey).__name__}')
+    if not isinstance(colour, MarkingColour):
+        raise TypeError(f'{who}: colour must be a MarkingColour, not {type(colour).__name__}')
+    if select is not None and not isinstance(select, PointFilter):
+        raise TypeError(f'{who}: select must be a PointFilter, not {type(select).__name__}')
+    if not records_u8.is_cuda:
+        raise LanemapHipError(f'{who} needs the records on an MI355X (HIP) device; no CPU fallback exists')
+    if not isinstance(index, ops.LineIndex) or not isinstance(stations, ops.LineStations):
+        raise TypeError(f'{who}: index must be an ops.LineIndex and stations an ops.LineStations')
+    fmt, rl, n = header['point_format'], header['record_len'], header['n_points']
+    if rgb_offset(fmt) is None:
+        raise ValueError(f'{who}: point format {fmt} carries no RGB (formats {sorted(RGB_OFFSET)} do)')
+    sel = select.for_format(fmt).as_struct() if select is not None else None
+    if index.half_width != np.float32(survey.half_width):
+        raise ValueError(f'{who}: the index was built for half_width={index.half_width}, the survey asks {survey.half_width}')
+    if stations.bin != survey.bin or stations.n_segments != index.n_segments:
+        raise ValueError(f'{who}: the stations were cut for bin={stations.bin} and {stations.n_segments} segments, the survey '
+                         f'asks bin={survey.bin}, the index holds {index.n_segments}')
+    dev = records_u8.device
+    if out is not None and not (isinstance(out, (tuple, list)) and len(out) == 2):
+        raise ValueError(f'{who}: out must be the (bins, colours) pair of an earlier call')
+    bins = ops._profile_out(who, stations, None if out is None else out[0], dev)
+    colours = ops._profile_out(who, stations, None if out is None else out[1], dev)
+    d3 = lambda v: (C.c_double * 3)(*[float(x) for x in v])
+    mi = math.nan if survey.min_intensity is None else survey.min_intensity
+    nb = stations.n_bins
+    check(lib().lm_las_line_colour_records(C.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index)), C.c_void_p(records_u8.data_ptr()),
+                                           int(rl), int(fmt), int(n), d3(header['scale']), d3(header['offset']),
+                                           d3(shift) if shift is not None else None, C.byref(sel) if sel is not None else None,
+                                           *index.args(), *stations.args(), survey.z_tol, mi, colour.blue_q, int(out is not None),
+                                           C.c_void_p(bins.data_ptr()) if nb else None, C.c_void_p(colours.data_ptr()) if nb else None, nb))
+    return bins, colours
+
+
+def survey_colour_files(files, lines, survey, colour, device='cuda:0'):
+    """survey_files with the colour table: every file of `files`, a list of (path, shift, select), is uploaded and goes through one
+    lm_las_line_colour_records call into one (bins, colours) pair, which is read back once.  All headers are read before anything is
+    uploaded: a file whose point format has no colour is refused with a ValueError that names the file and its format.
+    -> (bins [n_bins, 6] int64 numpy, colours [n_bins, 6] int64 numpy, bin_start [L + 1] int32 numpy)."""
+    from . import ops
+    if not isinstance(survey, MarkingSurvey):
+        raise TypeError(f'las_io.survey_colour_files: survey must be a MarkingSurvey, not {type(survey).__name__}')
+    if not isinstance(colour, MarkingColour):
+        raise TypeError(f'las_io.survey_colour_files: colour must be a MarkingColour, not {type(colour).__name__}')
+    device = torch.device(device)
+    lines, files = list(lines), list(files)
+    for path, shift, select in files:
+        if select is not None and not isinstance(select, PointFilter):
+            raise TypeError(f'las_io.survey_colour_files: select must be a PointFilter, not {type(select).__name__}')
+        require_colour(path)
+    tables, bin_start, pair = {}, None, None
+    for path, shift, select in files:
+        data = np.fromfile(path, dtype=np.uint8)
+        h = parse_header(data)
+        n, rl, off = h['n_points'], h['record_len'], h['offset_to_points']
+        if select is not None:
+            select.for_format(h['point_format'])
+        key = None if shift is None else tuple(float(v) for v in shift)
+        if key not in tables:
+            st, bs = line_stations(lines, shift, survey.bin)
+            bin_start = bs if bin_start is None else bin_start
+            tables[key] = (ops.line_index(line_segments(lines, shift), survey.half_width, device=device),
+                           ops.line_stations(st, bin_start, survey.bin, device=device))
+        index, stations = tables[key]
+        nbytes = n * rl
+        padded = np.zeros(((nbytes + 3) // 4 * 4,), dtype=np.uint8)
+        padded[:nbytes] = data[off:off + nbytes]
+        rec = torch.from_numpy(padded).to(device, non_blocking=True)
+        pair = profile_colour_records(rec, h, index, stations, survey, colour, shift, select, out=pair)
+    if pair is None:                                                        # no file: the empty tables of the lines
+        bin_start = line_stations(lines, None, survey.bin)[1]
+        host = np.zeros((int(bin_start[-1]), 6), dtype=np.int64)
+        host[:, 4], host[:, 5] = 2 ** 31 - 1, -2 ** 31
+        return host, np.zeros_like(host), bin_start
+    both = torch.stack(pair).cpu().numpy()                                  # the one read-back
+    return both[0], both[1], bin_start
+
+
+def require_colour(path):
+    """-> the point data record format of the LAS file `path`, read off the public header block alone (byte 104, the low six bits, as
+    lm_las_parse_header reads it); a format without R, G, B is refused with a ValueError that names the file and the format.  What is
+    no LAS file at all is left to parse_header, which refuses it when the file is read."""
+    with open(path, 'rb') as f:
+        head = f.read(105)
+    fmt = head[104] & 0x3F if len(head) == 105 and head[:4] == b'LASF' else None
+    if fmt is not None and fmt <= 10 and rgb_offset(fmt) is None:
+        raise ValueError(f'colour: {path} is of point format {fmt}, which carries no RGB (formats {sorted(RGB_OFFSET)} do)')
+    return fmt
+
+
+def survey_colour_las(paths, lines, survey, colour, shift, select=None, device='cuda:0'):
+    """survey_colour_files for files that share one read offset `shift` and one PointFilter, as survey_las: -> (bins, colours, bin_start);
+    marking_summary(bins, bin_start, survey) and marking_colours(bins, colours, bin_start, survey, colour) read the markings off them."""
+    if isinstance(paths, (str, os.PathLike)):
+        paths = [paths]
+    return survey_colour_files([(p, shift, select) for p in paths], lines, survey, colour, device)
+
+
+def marking_colours(bins, colours, bin_start, survey, colour):
+    """The colour of the markings read off the two tables of survey_colour_las (host, integers and float64): bins [n_bins, 6] int64, colours
+    [n_bins, 6] int64 (n_c, sum R, sum G, sum B, n_yellow, n_black) and bin_start [L + 1] -> one dict per line:
+
+      coloured, yellow, black   the sums of n_c, n_yellow, n_black over the line's painted bins (painted as in marking_summary: n >=
+                                survey.min_points)
+      rgb          [sum R / n_c, sum G / n_c, sum B / n_c] over the painted bins, the raw values, not rescaled; None when nothing is coloured
+      colour       'unknown' when coloured < colour.min_coloured; 'yellow' when yellow >= colour.yellow_share * coloured (compared exactly,
+                   as integers times the share's own rational value); else 'white'
+      run_colours  the same three-way answer per paint run, in the order of marking_summary's `runs` (the same joining over
+                   survey.max_gap), each from the painted bins of its run: a line that turns from white to yellow says so."""
+    from fractions import Fraction
+    if not isinstance(survey, MarkingSurvey):
+        raise TypeError(f'marking_colours: survey must be a las_io.MarkingSurvey, not {type(survey).__name__}')
+    if not isinstance(colour, MarkingColour):
+        raise TypeError(f'marking_colours: colour must be a las_io.MarkingColour, not {type(colour).__name__}')
+    bins, colours = np.asarray(bins), np.asarray(colours)
+    bs = np.asarray(bin_start, dtype=np.int64)
+    if bins.ndim != 2 or bins.shape[1] != 6 or bins.dtype != np.int64 or bs.ndim != 1 or len(bs) < 1 or bs[0] != 0 or (np.diff(bs) < 0).any() \
+            or bs[-1] != len(bins):
+        raise ValueError(f'marking_colours: bins must be [bin_start[L], 6] int64 and bin_start a CSR table from 0, not {bins.shape} '
+                         f'{bins.dtype} and {bs.tolist() if len(bs) < 8 else bs.shape}')
+    if colours.shape != bins.shape or colours.dtype != np.int64:
+        raise ValueError(f'marking_colours: colours must be {list(bins.shape)} int64 like bins, not {list(colours.shape)} {colours.dtype}')
+    share = Fraction(colour.yellow_share)                                   # the float's exact value
+    gap_bins = int(math.floor(survey.max_gap / survey.bin + 1e-9))
+
+    def decide(n_c, n_y):
+        return 'unknown' if n_c < colour.min_coloured else 'yellow' if n_y >= share * n_c else 'white'
+
+    out = []
+    for k in range(len(bs) - 1):
+        b, c = bins[bs[k]:bs[k + 1]], colours[bs[k]:bs[k + 1]]
+        on = b[:, 0] >= survey.min_points
+        runs = []
+        for i in np.nonzero(on)[0]:
+            i = int(i)
+            if runs and i - runs[-1][1] - 1 <= gap_bins:
+                runs[-1][1] = i
+            else:
+                runs.append([i, i])
+        n_c, n_y, n_k = (int(c[on, j].sum()) for j in (0, 4, 5))
+        sums = [int(c[on, j].sum()) for j in (1, 2, 3)]
+        run_colours = []
+        for i0, i1 in runs:
+            sel = on[i0:i1 + 1]
+            run_colours.append(decide(int(c[i0:i1 + 1][sel, 0].sum()), int(c[i0:i1 + 1][sel, 4].sum())))
+        out.append({'coloured': n_c, 'yellow': n_y, 'black': n_k, 'rgb': [s / n_c for s in sums] if n_c else None,
+                    'colour': decide(n_c, n_y), 'run_colours': run_colours})
     return out
 
 

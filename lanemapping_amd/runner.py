@@ -302,6 +302,19 @@ class Runner:
     _las_density = functools.partialmethod(_las_option, 'density', 'las_density', 'GapFill')               # the gap fill
     _las_label = functools.partialmethod(_las_option, 'label', 'las_label', 'MarkingLabels')               # the labelled LAS files
     _las_survey = functools.partialmethod(_las_option, 'survey', 'las_survey', 'MarkingSurvey')            # the marking profile
+    _las_colour = functools.partialmethod(_las_option, 'colour', 'las_colour', 'MarkingColour')            # white or yellow, beside the profile
+
+    @staticmethod
+    def _colour_plan(colour, survey, paths):
+        """`colour=` is read off the survey's pass over the records: without `survey=` it is refused, and so is an input file whose point
+        format carries no R, G, B (the header of every file is read here) - before anything runs."""
+        from . import las_io
+        if colour is None:
+            return
+        if survey is None:
+            raise ValueError('colour: the colours are accumulated by the survey of the markings; pass survey= (a las_io.MarkingSurvey) with it')
+        for path in paths:
+            las_io.require_colour(path)
 
     @staticmethod
     def _params_dir(out_dir):
@@ -343,12 +356,15 @@ class Runner:
         with open(os.path.join(self._params_dir(out_dir), 'labels.json'), 'w') as f:
             json.dump(done, f, indent=1)
 
-    def _survey_inputs(self, survey, files, result, out_dir):
+    def _survey_inputs(self, survey, files, result, out_dir, colour=None):
         """The stage after `label`: the lines the call returns - `merged`, or the tiles' 3-D lines in tile-name order when nothing was
         merged - profiled from every input file (files: (path, shift, select) in input order; a file listed several times is surveyed
         once, with its first listing's read offset): one lm_las_line_profile_records call per file into one bins tensor, one read-back.
         The raw bins go to <out_dir>/params/markings.npy, what las_io.marking_summary reads off them to <out_dir>/params/markings.json
-        as {line number: summary}."""
+        as {line number: summary}.
+        colour: a las_io.MarkingColour or None.  With one the call per file is lm_las_line_colour_records - still one pass over every file
+        and one read-back -, the colour table goes to <out_dir>/params/marking_colours.npy, and every line's summary in markings.json also
+        carries the keys of las_io.marking_colours.  markings.npy holds the same bytes either way."""
         from . import las_io
         lines3d, merged = result
         lines = list(merged) if len(merged) else [l for name in sorted(lines3d) for l in lines3d[name]]
@@ -357,11 +373,19 @@ class Runner:
             if os.path.realpath(path) not in seen:
                 seen.add(os.path.realpath(path))
                 once.append((path, shift, select))
-        bins, bin_start = las_io.survey_files(once, lines, survey, device=self.device)
+        if colour is None:
+            bins, bin_start = las_io.survey_files(once, lines, survey, device=self.device)
+            summary = las_io.marking_summary(bins, bin_start, survey)
+        else:
+            bins, colours, bin_start = las_io.survey_colour_files(once, lines, survey, colour, device=self.device)
+            summary = [{**m, **c} for m, c in zip(las_io.marking_summary(bins, bin_start, survey),
+                                                  las_io.marking_colours(bins, colours, bin_start, survey, colour))]
         par_dir = self._params_dir(out_dir)
         np.save(os.path.join(par_dir, 'markings.npy'), bins)
+        if colour is not None:
+            np.save(os.path.join(par_dir, 'marking_colours.npy'), colours)
         with open(os.path.join(par_dir, 'markings.json'), 'w') as f:
-            json.dump({str(k + 1): m for k, m in enumerate(las_io.marking_summary(bins, bin_start, survey))}, f, indent=1)
+            json.dump({str(k + 1): m for k, m in enumerate(summary)}, f, indent=1)
 
     def _follow_ground(self, gf, names, plist, points, offs, rpar, H, W, out_dir):
         """One batch of tiles through a las_io.GroundFilter: -> (plist, points, offs, rpar) to rasterise and back-project with.  The ground
@@ -427,7 +451,7 @@ class Runner:
         return raster_batch(names, plist, points, offs, rpar, scales)
 
     def infer_las_to_map(self, las_and_params, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None, ground=None,
-                         intensity=None, elevation=None, density=None, label=None, survey=None):
+                         intensity=None, elevation=None, density=None, label=None, survey=None, colour=None):
         """LAS tiles -> map-level 3-D lane lines, every stage of the reference's offline chain on this stack:
 
           LAS file + tile parameter file (utils/io_utils.py:125-150)
@@ -475,14 +499,22 @@ class Runner:
         <work_dirs>/params/markings.npy ([n_bins, 6] int64), what las_io.marking_summary reads off them - paint runs, dashed or solid,
         width, intensity - to <work_dirs>/params/markings.json as {line number: summary}.  Without survey.min_intensity a bin counts
         returns, not paint.  The return value does not change.
+        colour: a las_io.MarkingColour (default: cfg['las_colour'], a dict of its arguments; absent: nothing changes), with `survey`
+        only: the survey's pass over the records (then one lm_las_line_colour_records call per file, still one read-back) also counts,
+        per station bin, the returns that carry a colour, sums their R, G, B and counts those that vote yellow.  The table is written to
+        <work_dirs>/params/marking_colours.npy ([n_bins, 6] int64), markings.npy keeps its bytes, and every line of markings.json also
+        gets the keys of las_io.marking_colours: coloured, yellow, black, rgb, colour ('white', 'yellow' or 'unknown') and run_colours.
+        Refused with a ValueError before anything runs: colour without survey; an input file of a point format without R, G, B (0, 1,
+        4, 6, 9).  The return value does not change.
         Order of the stages: select, (binning,) ground, intensity, rasteriser, density, network, elevation, (merge,) label, survey.
         Single rank (the merge is sequential over the sorted tiles)."""
         from . import las_io
         select, ground, intensity = self._las_select(select), self._las_ground(ground), self._las_intensity(intensity)
         elevation, density, label = self._las_elevation(elevation), self._las_density(density), self._las_label(label)
-        survey = self._las_survey(survey)
+        survey, colour = self._las_survey(survey), self._las_colour(colour)
         if label is not None:
             self._label_plan([p for p, _ in las_and_params])              # (a basename collision is refused before anything runs)
+        self._colour_plan(colour, survey, [p for p, _ in las_and_params])
         if intensity is not None and intensity.scope == 'strip':
             raise ValueError("intensity: scope='strip' needs the whole strip in one cloud (infer_las_strip_to_map); infer_las_to_map reads "
                              "its tiles file by file, use scope='tile'")
@@ -514,7 +546,7 @@ class Runner:
         if label is not None:
             self._label_inputs(label, inputs, result, out_dir)
         if survey is not None:
-            self._survey_inputs(survey, inputs, result, out_dir)
+            self._survey_inputs(survey, inputs, result, out_dir, colour)
         return result
 
     def _las_chain(self, work_dirs, merge, elevation=None, density=None):
@@ -654,7 +686,7 @@ class Runner:
         return names, plist
 
     def infer_las_strip_to_map(self, las_paths, param_paths, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None,
-                               ground=None, intensity=None, elevation=None, density=None, label=None, survey=None):
+                               ground=None, intensity=None, elevation=None, density=None, label=None, survey=None, colour=None):
         """A whole strip -> map-level lane lines: the LAS file(s) of the strip are read once, their points are binned into the tiles of
         the layout on the GPU (ops.strip_bin_points: the windows of `param_paths` may overlap and be rotated), and every batch of tiles
         then runs the chain of infer_las_to_map from the rasteriser on.  Same outputs under the same names; a tile is named by the
@@ -668,16 +700,18 @@ class Runner:
         elevation: as for infer_las_to_map, after the network, on the ranges the rasteriser saw (after `ground` and `intensity`).
         density: as for infer_las_to_map, per batch between the rasteriser and the network.
         label: as for infer_las_to_map, after the merge: every file of `las_paths` is labelled with the layout's las_read_offset and `select`.
-        survey: as for infer_las_to_map, last: every file of `las_paths` is surveyed with the layout's las_read_offset and `select`."""
+        survey: as for infer_las_to_map, last: every file of `las_paths` is surveyed with the layout's las_read_offset and `select`.
+        colour: as for infer_las_to_map, in the survey's pass over the files of `las_paths`."""
         from . import las_io
         if isinstance(las_paths, (str, os.PathLike)):
             las_paths = [las_paths]
         names, plist = self._strip_layout(list(param_paths))
         select, ground, intensity = self._las_select(select), self._las_ground(ground), self._las_intensity(intensity)
         elevation, density, label = self._las_elevation(elevation), self._las_density(density), self._las_label(label)
-        survey = self._las_survey(survey)
+        survey, colour = self._las_survey(survey), self._las_colour(colour)
         if label is not None:
             self._label_plan(las_paths)                                    # (a basename collision is refused before anything runs)
+        self._colour_plan(colour, survey, las_paths)
         used = {}
         if path_ckpt:
             self.load_ckpt(path_ckpt)
@@ -711,7 +745,7 @@ class Runner:
         if label is not None and plist:
             self._label_inputs(label, [(path, plist[0]['las_read_offset'], select) for path in las_paths], result, out_dir)
         if survey is not None and plist:
-            self._survey_inputs(survey, [(path, plist[0]['las_read_offset'], select) for path in las_paths], result, out_dir)
+            self._survey_inputs(survey, [(path, plist[0]['las_read_offset'], select) for path in las_paths], result, out_dir, colour)
         return result
 
     def infer_lane_geometry_segmentation_segmentor(self, path_ckpt=None, mode_view=False, write_lane_vertex=False,
