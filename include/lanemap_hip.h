@@ -653,6 +653,71 @@ int lm_las_line_colour_records(void* hip_stream, const unsigned char* records, i
                                float half_width, const float* stations, const int* bin_start, const int* bin_start_host, int L, double bin,
                                float z_tol, float min_intensity, int blue_q, int accumulate, long* bins, long* colours, long n_bins);
 
+/* ---- the paint no lane line explains (csrc/residue.hip): stop bars, crossing bars, arrows, hatching, chevrons and lines the network
+ * missed are bright paint in the same returns as the lines, and label, profile and colour above see only paint that lies ON a line.  This
+ * stage takes the strip's returns and the lines the call returns, keeps the bright road-level returns that no line explains (the RESIDUE),
+ * puts them on a sparse map-frame grid, finds the connected blobs of that grid on the device and describes every blob by exact integer
+ * footprint statistics.  The host policy (las_io.residue_summary) turns those into centre, area, length, width, fill and the heading
+ * against the nearest line; calling a blob "arrow" or "zebra" is left to the user.
+ * THE RULE (one definition: this text; the kernels and tests/residue_ref.py restate it).
+ * PER POINT, plain f32, no contraction (build.py EXACT_FP).  Inputs: a line index (lm_line_index_build) built with half_width = REACH
+ * (at most 16 m), z_tol, a finite min_intensity (required: "WITHOUT a min_intensity a bin counts returns, not paint" above - here the
+ * whole road would be one blob), clear with 0 <= clear < reach, and a grid of nx x ny cells of size `cell` whose origin x0, y0 is the index
+ * grid's f32 origin; inv = (f32)(1 / cell).
+ *     ln, d2  = the labelling rule's winner and its squared distance; eligibility, the hit test and z_tol are exactly that rule's
+ *     RESIDUE = ln > 0 && d2 > clear2                          clear2 = clear clear, squared once in f32; d2 == clear2 is no residue
+ *     cx = (int)((x - x0) inv);  cy = (int)((y - y0) inv)
+ *     key = (int64)cy nx + cx  for a residue point with 0 <= cx < nx and 0 <= cy < ny, else -1
+ *     iq  = (unsigned)fminf(fmaxf(rintf(i), 0.f), 65535.f)     the profile's intensity rule, for a point with a key >= 0; else 0
+ * A residue point lies within reach and within z_tol in height of some line - signs, vehicles and bridges stay out - and farther than
+ * clear from every line that would hit it.  nx, ny come from the host (ops.residue_grid) so that the grid covers the index grid's box:
+ * every point the index accepts then has 0 <= cx < nx, 0 <= cy < ny, and the kernel's range test never bites.  nx or ny above 2^20 is
+ * refused: a cell index stays exact in f32, and with at most 2^22 occupied cells sum cx^2 < 2^62 stays inside 64 bits.
+ * CELLS: the distinct keys >= 0 over all clouds of the call in ascending order, m = 0 .. M-1.
+ * COMPONENTS: two cells are joined when they are neighbours on (cx, cy) under `connectivity`, 8 or 4 - on (cx, cy), not on the key: key
+ * and key + 1 are no neighbours when cx = nx - 1.  root[m] = the smallest cell index of the component of m; components are numbered
+ * 0 .. K-1 in ascending root.
+ * STATISTICS: stats [K][12] int64 = n_cells, n_points, sum iq, sum cx, sum cy, sum cx^2, sum cx cy, sum cy^2, min cx, max cx, min cy,
+ * max cy.  Moments and extents are taken over the cells, each once - the footprint, not the point density -, n_points and sum iq over the
+ * points.  Integer sums, minima and maxima only, no float atomic: the result does not depend on the order of points, cells or adds.
+ * residue_keys: points_xyzi DEVICE [N][4] f32, then the index arguments of lm_label_points (half_width = the reach).  key DEVICE [N] int64;
+ *         iq DEVICE [N] int32 or NULL.  label_points_kernel's streaming shape, four 16-byte loads in flight per lane; a wave with no
+ *         candidate leaves through the ballot.  N = 0 or S = 0 (every key -1) is LM_OK.  Asynchronous, no workspace, nothing read back.
+ * cell_components: keys DEVICE [M] int64, ascending and distinct; root DEVICE [M] int32; err DEVICE [1] int32.  THE FORM CHOSEN IS THE
+ *         LOCK-FREE UNION-FIND, and the entry READS NOTHING BACK: three launches - parent[m] = m; a lane per cell looks the neighbours
+ *         with a smaller key (four for 8-connectivity, two for 4) up by binary search in keys[0, m) and joins each it finds: find both
+ *         roots, order them, old = atomicMin(&parent[larger], smaller); old == larger: done, else go on with old; then a compression
+ *         launch of its own.  parent[x] <= x holds throughout, so the final root is the smallest index of the component whatever the
+ *         interleaving.  NO WAITING: no kernel waits for another workgroup - no flags, tickets or spinning; every loop advances by the
+ *         lane's own action.  CAPPED LOOPS: a root chase follows at most M links, a join retries at most 2 M times (each retry lowers
+ *         the larger index); a lane that exhausts a cap sets err[0] with an atomic and leaves - a bug is a non-zero err (zeroed by the
+ *         call on the stream first), never a hang.  VISIBILITY: inside the union and compression launches every word of parent is read
+ *         with an agent-scope atomic load or as the return value of an atomic and written only with atomics (one L2 per XCD); the three
+ *         launches are published to each other by their boundaries.  keys is read-only and read with plain loads.  TRUST: the host cannot
+ *         check a device table; whatever keys holds the entry reads keys[0, M) only, writes root[0, M) only and terminates - unsorted
+ *         or duplicate keys give garbage inside root.
+ * residue_stats: comp DEVICE [M] int32 (dense ids 0 .. K-1), keys DEVICE [M] int64 with the grid's nx, ny (cx = key % nx, cy = key / nx),
+ *         cell_points and cell_iq DEVICE [M] int64 (points and summed iq per cell), stats DEVICE [K][12] int64, initialised by the call on
+ *         the stream (zeros, 2^31 - 1 / -2^31 for the extents).  One pass, a lane per cell: the lanes of a wave that share a component are
+ *         merged by cross-lane operations before one row of integer atomics per distinct component goes to memory, as las_profile_kernel
+ *         merges per distinct bin; the cells are sorted by key, so the lanes of a wave mostly share a component.  M above 2^22 is refused.
+ *         TRUST: a comp outside [0, K) or a key outside the grid contributes nothing; stats is written in [0, K) only.
+ * None of the kernels uses LDS.  Compacting the keys >= 0, concatenating the clouds, the unique cells with their counts, the per-cell sum
+ * of iq (an int64 index_add_) and the dense component ids are torch calls in ops.paint_residue.
+ * Refused with LM_ERR_ARG and a message that names the argument, before anything is launched or written: what lm_label_points refuses of
+ * the index arguments (a grid built for another half_width among them); a min_intensity that is not finite; clear < 0 or >= the reach; a
+ * reach above 16; cell <= 0 or not finite; nx or ny above 2^20; connectivity other than 4 and 8; M above the limits; K > M; a null buffer
+ * with N, M or K > 0; a misaligned buffer, named alone ("key is not 8-byte aligned").
+ * NOT HERE: a raw-records entry.  The clouds come from las_io.read_las_raw(path, device, shift, select), so `select` applies as everywhere.
+ * NOTE on the name `hip_stream`: as for lm_label_points above; the guarded-buffer cases of these three entries are
+ * tests/test_gpu_residue.py::test_residue_keys_guards, ::test_cell_components_guards and ::test_residue_stats_guards. */
+int lm_residue_keys(void* hip_stream, const float* points_xyzi, long N, const float* segments, long S, const LmLineGrid* grid,
+                    const int* cell_start, const int* cell_segs, float half_width, float z_tol, float min_intensity, float clear,
+                    double cell, int nx, int ny, long* key, int* iq);
+int lm_cell_components(void* hip_stream, const long* keys, long M, int nx, int ny, int connectivity, int* root, int* err);
+int lm_residue_stats(void* hip_stream, const int* comp, const long* keys, int nx, int ny, const long* cell_points, const long* cell_iq,
+                     long M, long K, long* stats);
+
 /* ---- PNG tile ingest (replaces PIL in `load_img`, baseline/datasets/laserlane_proposals.py:85-98 and laserlane.py:214-219:
  * np.array(Image.open(path)) -> uint8 HWC).  Host code, no third-party library (PIL runs zlib; the DEFLATE decoder here is
  * csrc/inflate.h), 8-bit non-interlaced grey / grey+alpha / RGB / RGBA only; palette, 16-bit and Adam7 files are refused; chunk CRCs

@@ -11,11 +11,11 @@ DIAG_SRC = os.path.join(os.path.dirname(HERE), 'tests', 'hip')
 DIAG_LIB = os.path.join(HERE, 'liblanemap_diag.so')
 DIAG_SOURCES = ['lds_state.hip']        # same compiler and flags as SOURCES; linked with errors.cpp's helpers into a library of their own
 SOURCES = ['errors.cpp', 'conv_mfma.hip', 'conv_wino44.hip', 'conv_direct.hip', 'norm_resize.hip', 'vit.hip', 'mixer.hip', 'head.hip', 'head_endpoint.hip',
-           'decode.hip', 'raster.hip', 'strip.hip', 'ground.hip', 'intensity.hip', 'drape.hip', 'gapfill.hip', 'rowref.hip', 'prim.hip', 'lidar.hip', 'label.hip', 'profile.hip', 'postproc.cpp', 'backproject.cpp', 'png_reader.cpp', 'lane_json.cpp', 'merge_lines.cpp', 'skeleton.cpp']
+           'decode.hip', 'raster.hip', 'strip.hip', 'ground.hip', 'intensity.hip', 'drape.hip', 'gapfill.hip', 'rowref.hip', 'prim.hip', 'lidar.hip', 'label.hip', 'profile.hip', 'residue.hip', 'postproc.cpp', 'backproject.cpp', 'png_reader.cpp', 'lane_json.cpp', 'merge_lines.cpp', 'skeleton.cpp']
 
 
 # integer-output kernels whose fp32 index math must match the C oracle bit for bit
-EXACT_FP = {'raster.hip', 'strip.hip', 'ground.hip', 'intensity.hip', 'drape.hip', 'lidar.hip', 'label.hip', 'profile.hip', 'backproject.cpp', 'merge_lines.cpp'}
+EXACT_FP = {'raster.hip', 'strip.hip', 'ground.hip', 'intensity.hip', 'drape.hip', 'lidar.hip', 'label.hip', 'profile.hip', 'residue.hip', 'backproject.cpp', 'merge_lines.cpp'}
 # per-source extra flags.  conv_wino44.hip: the SLP vectoriser packs the Winograd transform's adds into v_pk_add_f32 plus a dozen
 # v_mov shuffles per group; packed f32 VALU beside MFMAs costs issue slots (MI355X_MICROARCH.md, filler price list)
 EXTRA_FLAGS = {'conv_wino44.hip': ['-fno-slp-vectorize']}

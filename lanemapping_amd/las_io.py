@@ -31,6 +31,10 @@ runs, dash pattern, width and brightness read off the bins.
 `MarkingColour` / `rgb_offset` / `survey_colour_las` / `marking_colours` add the colour of a marking, white or yellow, from the R, G, B
 triple that point formats 2, 3, 5, 7, 8 and 10 carry per return: the same pass over the records fills a second table per station bin
 (`lm_las_line_colour_records`), and the host reads a colour per line and per paint run off it.
+
+`PaintResidue` / `residue_files` / `residue_summary` inventory the paint that no line explains - stop bars, crossing bars, arrows,
+hatching, a line the network missed: the bright road-level returns away from every line, gridded, labelled into connected blobs and
+described on the GPU (`ops.paint_residue`), and on the host the centre, size, fill and heading of every blob against its nearest line.
 """
 import ctypes as C
 import math
@@ -946,6 +950,175 @@ def marking_colours(bins, colours, bin_start, survey, colour):
             run_colours.append(decide(int(c[i0:i1 + 1][sel, 0].sum()), int(c[i0:i1 + 1][sel, 4].sum())))
         out.append({'coloured': n_c, 'yellow': n_y, 'black': n_k, 'rgb': [s / n_c for s in sums] if n_c else None,
                     'colour': decide(n_c, n_y), 'run_colours': run_colours})
+    return out
+
+
+class PaintResidue:
+    """How the LAS -> map routes inventory the paint that no lane line explains (immutable; Runner.infer_las_strip_to_map /
+    infer_las_to_map, `residue=`; residue_files, residue_summary).  A return is RESIDUE when it is bright, lies within `reach` in the plane
+    and z_tol in height of some line the call found - so signs, vehicles and bridges stay out - and farther than `clear` from the nearest
+    such line (the rule: include/lanemap_hip.h).  The residue is put on a grid of `cell` metres, the connected blobs of the grid are
+    found and described on the GPU, and residue_summary reads centre, size and heading off every blob large enough.
+
+      min_intensity   REQUIRED, finite: the smallest raw intensity of a paint return.  Without a threshold between asphalt and paint the
+                      whole road is one blob, so there is no default
+      clear           metres, 0 <= clear < reach: returns within it of their nearest line are that line's paint, not residue
+      reach           metres, clear < reach <= 16: how far from a line paint is looked for
+      z_tol           metres (>= 0, may be infinite): the height band around the line
+      cell            metres (finite, > 0): the size of a grid cell
+      connectivity    8 or 4: which cells count as neighbours
+      min_cells       a blob is reported when it covers at least this many cells ... (whole number >= 1)
+      min_points      ... and holds at least this many returns (whole number >= 1)
+      elongated       a blob whose length / width reaches it has a direction; below it the blob is 'compact' (finite, >= 1)
+      angle_tol_deg   degrees in 0 .. 45: an elongated blob within it of the nearest segment's direction is 'along', within it of the
+                      normal 'across', else 'oblique'
+    All defaults are plain defaults, not tuned values."""
+    __slots__ = ('min_intensity', 'clear', 'reach', 'z_tol', 'cell', 'connectivity', 'min_cells', 'min_points', 'elongated', 'angle_tol_deg')
+
+    def __init__(self, min_intensity, clear=0.3, reach=6.0, z_tol=0.5, cell=0.1, connectivity=8, min_cells=20, min_points=20, elongated=2.0,
+                 angle_tol_deg=30.0):
+        num = (int, float, np.integer, np.floating)
+        isnum = lambda v: not isinstance(v, bool) and isinstance(v, num)
+        if not isnum(min_intensity) or not math.isfinite(float(min_intensity)):
+            raise ValueError(f'PaintResidue: min_intensity={min_intensity!r} must be a finite number (without one the whole road is one blob)')
+        if not isnum(reach) or not (0.0 < float(reach) <= 16.0):
+            raise ValueError(f'PaintResidue: reach={reach!r} must be a number with 0 < reach <= 16 (metres)')
+        if not isnum(clear) or not (0.0 <= float(clear) < float(reach)):
+            raise ValueError(f'PaintResidue: clear={clear!r} must be a number with 0 <= clear < reach={reach!r}')
+        if not isnum(z_tol) or not float(z_tol) >= 0.0:
+            raise ValueError(f'PaintResidue: z_tol={z_tol!r} must be a number >= 0')
+        if not isnum(cell) or not (0.0 < float(cell) < math.inf):
+            raise ValueError(f'PaintResidue: cell={cell!r} must be a finite size > 0')
+        if isinstance(connectivity, bool) or connectivity not in (4, 8):
+            raise ValueError(f'PaintResidue: connectivity={connectivity!r} is neither 4 nor 8')
+        for name, v in (('min_cells', min_cells), ('min_points', min_points)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
+                raise ValueError(f'PaintResidue: {name}={v!r} must be a whole number >= 1')
+        if not isnum(elongated) or not (1.0 <= float(elongated) < math.inf):
+            raise ValueError(f'PaintResidue: elongated={elongated!r} must be a finite ratio >= 1')
+        if not isnum(angle_tol_deg) or not (0.0 <= float(angle_tol_deg) <= 45.0):
+            raise ValueError(f'PaintResidue: angle_tol_deg={angle_tol_deg!r} must be a number in 0 .. 45 (degrees)')
+        for k, v in (('min_intensity', float(min_intensity)), ('clear', float(clear)), ('reach', float(reach)), ('z_tol', float(z_tol)),
+                     ('cell', float(cell)), ('connectivity', int(connectivity)), ('min_cells', int(min_cells)), ('min_points', int(min_points)),
+                     ('elongated', float(elongated)), ('angle_tol_deg', float(angle_tol_deg))):
+            object.__setattr__(self, k, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError('PaintResidue is immutable')
+
+    def __delattr__(self, name):
+        raise AttributeError('PaintResidue is immutable')
+
+    def __repr__(self):
+        return 'PaintResidue(' + ', '.join(f'{k}={getattr(self, k)!r}' for k in self.__slots__) + ')'
+
+    def __eq__(self, other):
+        return isinstance(other, PaintResidue) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
+
+    def __hash__(self):
+        return hash(tuple(getattr(self, k) for k in self.__slots__))
+
+
+def residue_index_cell(residue):
+    """The cell of the line index residue_files builds, metres.  The index' default, max(1 m, 2 half_width), is sized for the narrow band
+    of the labelling; with half_width = reach it lists every segment within reach + a cell's diagonal of the cell, so a large cell
+    makes every bright point test several times the segments that can hit it.  The cell decides the cost, never the result."""
+    return max(1.0, residue.reach / 4.0)
+
+
+def residue_files(files, lines, residue, device='cuda:0'):
+    """The paint residue of `lines` (list of [n,3] float64, LAS frame) in the LAS files `files`, a list of (path, shift, select) like
+    survey_files takes: every file is read once with its own PointFilter (read_las_raw), all clouds go through one ops.paint_residue
+    call, and the result is read back once.  The grid lives in ONE frame, that of the first file's read offset: a file listed with
+    another offset is decoded against the first one (the decode subtracts the offset in float64, so nothing is lost as long as the
+    files lie within float32 reach of it).  -> an ops.ResidueBlobs of numpy arrays (cells [M,2] int32, comp [M] int32, stats [K,12]
+    int64, grid); grid['shift'] is the frame, what residue_summary needs."""
+    from . import ops
+    if not isinstance(residue, PaintResidue):
+        raise TypeError(f'las_io.residue_files: residue must be a PaintResidue, not {type(residue).__name__}')
+    device = torch.device(device)
+    lines, files = list(lines), list(files)
+    for _, _, select in files:
+        if select is not None and not isinstance(select, PointFilter):
+            raise TypeError(f'las_io.residue_files: select must be a PointFilter, not {type(select).__name__}')
+    frame = None if not files or files[0][1] is None else [float(v) for v in files[0][1]]
+    index = ops.line_index(line_segments(lines, frame), residue.reach, cell=residue_index_cell(residue), device=device)
+    clouds = [read_las_raw(path, device, frame, select)[0] for path, _, select in files]
+    out = ops.paint_residue(clouds, index, residue.z_tol, residue.min_intensity, residue.clear, residue.cell, residue.connectivity).numpy()
+    out.grid['shift'] = [0.0, 0.0, 0.0] if frame is None else frame
+    return out
+
+
+def _nearest_segment(c, seg):
+    """The segment of seg [S,4] float64 (ax, ay, dx, dy) nearest to the point c in the plane: -> (index, signed lateral offset of c, left
+    positive, direction of the segment in degrees), by brute force."""
+    px, py = c[0] - seg[:, 0], c[1] - seg[:, 1]
+    l2 = seg[:, 2] ** 2 + seg[:, 3] ** 2
+    t = np.clip(np.divide(px * seg[:, 2] + py * seg[:, 3], l2, out=np.zeros_like(l2), where=l2 > 0), 0.0, 1.0)
+    d = np.hypot(px - t * seg[:, 2], py - t * seg[:, 3])
+    d = np.where(l2 > 0, d, np.inf) if (l2 > 0).any() else d               # a doubled vertex has no direction: another segment if there is one
+    s = int(np.argmin(d))
+    ln = math.sqrt(l2[s])
+    off = (seg[s, 2] * py[s] - seg[s, 3] * px[s]) / ln if ln > 0 else float(d[s])
+    return s, float(off), math.degrees(math.atan2(seg[s, 3], seg[s, 2]))
+
+
+def residue_summary(result, lines, residue, shift=None):
+    """The blobs read off a paint residue (host, Python integers and float64): result an ops.ResidueBlobs of numpy arrays (residue_files),
+    lines the lines it was computed against (LAS frame), shift the frame of its grid (default: result.grid['shift'], else none) -> one
+    dict per component with n_cells >= residue.min_cells and n_points >= residue.min_points, in component order:
+
+      blob        the component's number, from 1 (its row of stats, its value + 1 in comp)
+      centre      [x, y] in the LAS frame: the mean of the cell centres
+      cells, points, area (cells cell^2, m^2), intensity (sum iq / points)
+      length, width   metres: sqrt(12 l + 1) cell for the larger and the smaller eigenvalue l of the covariance of the cell indices -
+                  exact for a filled axis-parallel rectangle of whole cells
+      fill        area / (length width): 1 for a filled rectangle, lower for an outline, an arrow, a diagonal
+      heading     degrees in [0, 180): the principal axis, counter-clockwise from +x
+      bbox        [x_min, y_min, x_max, y_max] of the cells in the LAS frame
+      line        the number (from 1) of the line nearest to the centre in the plane, None without a line
+      offset      metres: the signed lateral offset of the centre from that line's nearest segment, left positive
+      shape       'compact' when length / width < residue.elongated; else 'along' / 'across' when the axis lies within
+                  residue.angle_tol_deg of the nearest segment's direction / of its normal; else 'oblique'"""
+    if not isinstance(residue, PaintResidue):
+        raise TypeError(f'residue_summary: residue must be a las_io.PaintResidue, not {type(residue).__name__}')
+    stats, grid = np.asarray(result.stats), result.grid
+    if stats.ndim != 2 or stats.shape[1] != 12 or stats.dtype != np.int64:
+        raise ValueError(f'residue_summary: stats must be [K,12] int64, not {stats.shape} {stats.dtype}')
+    if shift is None:
+        shift = grid.get('shift')
+    sh = np.zeros(3) if shift is None else np.asarray(shift, dtype=np.float64).reshape(3)
+    cell, x0, y0 = float(grid['cell']), float(grid['x0']) + sh[0], float(grid['y0']) + sh[1]
+    rows, of_line = [], []
+    for k, line in enumerate(lines):
+        v = np.asarray(line, dtype=np.float64)
+        if v.ndim == 2 and v.shape[0] >= 2:
+            rows.append(np.concatenate([v[:-1, :2], v[1:, :2] - v[:-1, :2]], axis=1))
+            of_line += [k + 1] * (v.shape[0] - 1)
+    seg = np.concatenate(rows) if rows else np.zeros((0, 4))
+    out = []
+    for k in range(len(stats)):
+        n, npts, siq, sx, sy, sxx, sxy, syy, x_lo, x_hi, y_lo, y_hi = (int(v) for v in stats[k])
+        if n < residue.min_cells or npts < residue.min_points:
+            continue
+        # the covariance of the cell indices from exact integers: (n sum x^2 - (sum x)^2) / n^2
+        vxx, vxy, vyy = (n * sxx - sx * sx) / (n * n), (n * sxy - sx * sy) / (n * n), (n * syy - sy * sy) / (n * n)
+        mid, rad = 0.5 * (vxx + vyy), math.hypot(0.5 * (vxx - vyy), vxy)
+        length, width = math.sqrt(12.0 * (mid + rad) + 1.0) * cell, math.sqrt(max(12.0 * (mid - rad), 0.0) + 1.0) * cell
+        heading = math.degrees(0.5 * math.atan2(2.0 * vxy, vxx - vyy)) % 180.0
+        centre = [x0 + (sx / n + 0.5) * cell, y0 + (sy / n + 0.5) * cell]
+        area = n * cell * cell
+        line, offset, shape = None, None, 'compact' if length / width < residue.elongated else 'oblique'
+        if len(seg):
+            s, offset, along = _nearest_segment(centre, seg)
+            line = of_line[s]
+            if shape != 'compact':
+                turn = abs((heading - along + 90.0) % 180.0 - 90.0)         # the angle between two undirected axes, 0 .. 90
+                shape = 'along' if turn <= residue.angle_tol_deg else 'across' if turn >= 90.0 - residue.angle_tol_deg else 'oblique'
+        out.append({'blob': k + 1, 'centre': centre, 'cells': n, 'points': npts, 'area': area, 'intensity': siq / npts, 'length': length,
+                    'width': width, 'fill': area / (length * width), 'heading': heading,
+                    'bbox': [x0 + x_lo * cell, y0 + y_lo * cell, x0 + (x_hi + 1) * cell, y0 + (y_hi + 1) * cell], 'line': line,
+                    'offset': offset, 'shape': shape})
     return out
 
 

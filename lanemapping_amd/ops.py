@@ -867,6 +867,134 @@ def _profile_out(who, stations, out, device):
     return out
 
 
+RESIDUE_MAX_SIDE, RESIDUE_MAX_CELLS = 1 << 20, 1 << 22
+STATS_COLUMNS = ('n_cells', 'n_points', 'sum_iq', 'sum_cx', 'sum_cy', 'sum_cx2', 'sum_cxcy', 'sum_cy2', 'min_cx', 'max_cx', 'min_cy', 'max_cy')
+
+
+def residue_grid(index, cell=0.1):
+    """The host grid of the paint residue over the box of an ops.LineIndex (no GPU): -> dict x0, y0 (the index grid's float32 origin),
+    cell (metres), nx, ny - enough cells to cover the index grid's box, so that every point the labelling rule can hit has a cell.  Refused:
+    a cell that is no finite size > 0; nx or ny above 2^20 (a cell index must stay exact in float32)."""
+    import numpy as np
+    if not isinstance(index, LineIndex):
+        raise TypeError(f'residue_grid: index must be an ops.LineIndex (ops.line_index), not {type(index).__name__}')
+    if isinstance(cell, bool) or not isinstance(cell, (int, float, np.integer, np.floating)) or not (0.0 < float(cell) < math.inf):
+        raise ValueError(f'residue_grid: cell={cell!r} must be a finite size > 0')
+    cell, g = float(cell), index.grid
+    inv = float(np.float32(1.0 / cell))
+    # a point the index accepts has (x - x0) < nx_index * cell_index up to a few float32 roundings: 1e-6 relative and two cells cover them
+    side = lambda n: int(math.floor(n * g.cell * inv * (1.0 + 1e-6))) + 2 if index.n_segments else 0
+    nx, ny = side(g.nx), side(g.ny)
+    if nx > RESIDUE_MAX_SIDE or ny > RESIDUE_MAX_SIDE:
+        raise ValueError(f'residue_grid: nx={nx}, ny={ny} cells of {cell} m, at most 2^20 a side are supported (choose a larger cell)')
+    return {'x0': float(np.float32(g.x0)), 'y0': float(np.float32(g.y0)), 'cell': cell, 'nx': nx, 'ny': ny}
+
+
+def residue_keys(points, index, z_tol, min_intensity, clear, grid, want_iq=True):
+    """points [N,4] f32 on device -> (key [N] int64, iq [N] int32 or None): the residue cell of every point on `grid` (residue_grid), -1
+    where the point is no residue - not within the index' half_width (the reach) and z_tol of a line, below min_intensity, or within
+    `clear` of its nearest line (the rule: include/lanemap_hip.h).  No synchronisation."""
+    if not points.is_cuda:
+        raise LanemapHipError('lanemapping_amd ops need tensors on an MI355X (HIP) device; no CPU fallback exists')
+    assert points.dim() == 2 and points.shape[1] == 4 and points.is_contiguous() and points.dtype == torch.float32
+    if not isinstance(index, LineIndex):
+        raise TypeError(f'residue_keys: index must be an ops.LineIndex (ops.line_index), not {type(index).__name__}')
+    N = int(points.shape[0])
+    key = torch.empty((N,), device=points.device, dtype=torch.int64)
+    iq = torch.empty((N,), device=points.device, dtype=torch.int32) if want_iq else None
+    check(lib().lm_residue_keys(_stream(), _ptr(points) if N else None, N, *index.args(), float(z_tol), float(min_intensity), float(clear),
+                                float(grid['cell']), int(grid['nx']), int(grid['ny']), _ptr(key) if N else None,
+                                _ptr(iq) if (want_iq and N) else None))
+    return key, iq
+
+
+def cell_components(keys, nx, ny, connectivity=8):
+    """keys [M] int64 on device, ascending and distinct cells cy * nx + cx of an nx x ny grid -> (root [M] int32, err [1] int32):
+    root[m] the smallest index of the cells connected with cell m under 4- or 8-connectivity on (cx, cy); err non-zero when a loop of
+    the union-find ran into its cap (a bug, never a hang).  No synchronisation."""
+    if not keys.is_cuda:
+        raise LanemapHipError('lanemapping_amd ops need tensors on an MI355X (HIP) device; no CPU fallback exists')
+    assert keys.dim() == 1 and keys.is_contiguous() and keys.dtype == torch.int64
+    M = int(keys.shape[0])
+    root = torch.empty((M,), device=keys.device, dtype=torch.int32)
+    err = torch.empty((1,), device=keys.device, dtype=torch.int32)
+    check(lib().lm_cell_components(_stream(), _ptr(keys) if M else None, M, int(nx), int(ny), int(connectivity), _ptr(root) if M else None,
+                                   _ptr(err)))
+    return root, err
+
+
+def residue_stats(comp, keys, nx, ny, cell_points, cell_iq, K):
+    """comp [M] int32 (dense component ids 0 .. K-1), keys [M] int64, cell_points and cell_iq [M] int64 on device -> stats [K,12] int64,
+    the columns STATS_COLUMNS: cells, points and summed iq of every component, the first and second moments and the extents of its
+    cells (each cell once).  Integer sums, minima and maxima only.  No synchronisation."""
+    if not keys.is_cuda:
+        raise LanemapHipError('lanemapping_amd ops need tensors on an MI355X (HIP) device; no CPU fallback exists')
+    M = int(keys.shape[0])
+    for t, dt in ((comp, torch.int32), (keys, torch.int64), (cell_points, torch.int64), (cell_iq, torch.int64)):
+        assert t.dim() == 1 and t.shape[0] == M and t.is_contiguous() and t.dtype == dt and t.device == keys.device
+    stats = torch.empty((int(K), 12), device=keys.device, dtype=torch.int64)
+    p = lambda t: _ptr(t) if M else None
+    check(lib().lm_residue_stats(_stream(), p(comp), p(keys), int(nx), int(ny), p(cell_points), p(cell_iq), M, int(K),
+                                 _ptr(stats) if K else None))
+    return stats
+
+
+class ResidueBlobs:
+    """What paint_residue returns: cells [M,2] int32 (cx, cy of the occupied cells, ascending in cy * nx + cx), comp [M] int32 (the blob
+    of every cell, blobs numbered from 0 in the order of their first cell), stats [K,12] int64 (STATS_COLUMNS) and grid, the host dict of
+    residue_grid.  numpy(): the same with numpy arrays (the one read-back of the results)."""
+
+    def __init__(self, cells, comp, stats, grid):
+        self.cells, self.comp, self.stats, self.grid = cells, comp, stats, grid
+
+    def numpy(self):
+        if not isinstance(self.cells, torch.Tensor):
+            return self
+        M = int(self.cells.shape[0])
+        flat = torch.cat([self.cells.reshape(-1).to(torch.int64), self.comp.to(torch.int64), self.stats.reshape(-1)]).cpu().numpy()
+        return ResidueBlobs(flat[:2 * M].reshape(M, 2).astype('int32'), flat[2 * M:3 * M].astype('int32'),
+                            flat[3 * M:].reshape(-1, 12).copy(), dict(self.grid))
+
+
+def paint_residue(clouds, index, z_tol, min_intensity, clear, cell=0.1, connectivity=8):
+    """The paint no line explains.  clouds: a list of [N,4] f32 device tensors (x, y, z, raw intensity) in the frame of `index`, an
+    ops.LineIndex built with half_width = the reach.  The residue points of all clouds (residue_keys) are put on one grid, the occupied
+    cells are labelled into connected blobs (cell_components) and every blob gets its footprint statistics (residue_stats): -> a
+    ResidueBlobs of device tensors.  The result does not depend on the order of the clouds or of their points.  The keys are compacted,
+    made unique and counted with torch (an integer index_add_ sums iq per cell); the call itself reads one word back (the error word of
+    the union-find, with M and K known from the shapes).  Refused: more than 2^22 occupied cells.  The per-point pass is bound by the
+    candidate search: build the index with a cell well below 2 reach (las_io.residue_index_cell), the default cell of line_index is
+    sized for the narrow band of the labelling."""
+    if not isinstance(index, LineIndex):
+        raise TypeError(f'paint_residue: index must be an ops.LineIndex (ops.line_index), not {type(index).__name__}')
+    if connectivity not in (4, 8):
+        raise ValueError(f'paint_residue: connectivity={connectivity!r} is neither 4 nor 8')
+    grid = residue_grid(index, cell)
+    dev = index.segments.device
+    ks, qs = [torch.empty((0,), device=dev, dtype=torch.int64)], [torch.empty((0,), device=dev, dtype=torch.int64)]
+    for pts in clouds:
+        key, iq = residue_keys(pts, index, z_tol, min_intensity, clear, grid)
+        on = key >= 0
+        ks.append(key[on])
+        qs.append(iq[on].to(torch.int64))
+    keys, iqs = torch.cat(ks), torch.cat(qs)
+    cells, inverse, counts = torch.unique(keys, sorted=True, return_inverse=True, return_counts=True)
+    M = int(cells.shape[0])
+    if M > RESIDUE_MAX_CELLS:
+        raise LanemapHipError(f'paint_residue: {M} occupied cells of {grid["cell"]} m, at most 2^22 are supported: refusing to proceed '
+                              '(raise min_intensity or choose a larger cell)')
+    cell_iq = torch.zeros((M,), device=dev, dtype=torch.int64).index_add_(0, inverse, iqs)      # integer adds: the same bits every run
+    nx, ny = grid['nx'], grid['ny']
+    root, err = cell_components(cells, nx, ny, connectivity)
+    roots, comp = torch.unique(root, sorted=True, return_inverse=True)                           # numbered in ascending root
+    comp, K = comp.to(torch.int32), int(roots.shape[0])
+    stats = residue_stats(comp, cells, nx, ny, counts, cell_iq, K)
+    if int(err):
+        raise LanemapHipError('paint_residue: the union-find of lm_cell_components ran into a loop cap (a bug: please report the input)')
+    cxy = torch.stack([cells % max(nx, 1), cells // max(nx, 1)], dim=1).to(torch.int32)
+    return ResidueBlobs(cxy, comp, stats, grid)
+
+
 def _tilted(p):
     return p.quat[1] != 0.0 or p.quat[2] != 0.0
 

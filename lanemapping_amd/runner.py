@@ -303,6 +303,7 @@ class Runner:
     _las_label = functools.partialmethod(_las_option, 'label', 'las_label', 'MarkingLabels')               # the labelled LAS files
     _las_survey = functools.partialmethod(_las_option, 'survey', 'las_survey', 'MarkingSurvey')            # the marking profile
     _las_colour = functools.partialmethod(_las_option, 'colour', 'las_colour', 'MarkingColour')            # white or yellow, beside the profile
+    _las_residue = functools.partialmethod(_las_option, 'residue', 'las_residue', 'PaintResidue')          # the paint no line explains
 
     @staticmethod
     def _colour_plan(colour, survey, paths):
@@ -387,6 +388,33 @@ class Runner:
         with open(os.path.join(par_dir, 'markings.json'), 'w') as f:
             json.dump({str(k + 1): m for k, m in enumerate(summary)}, f, indent=1)
 
+    def _residue_inputs(self, residue, files, result, out_dir):
+        """The stage after `survey`: the paint that none of the lines the call returns explains (the same lines as _survey_inputs takes),
+        from every input file (files: (path, shift, select) in input order, a file listed several times is used once): one
+        ops.paint_residue call over all files, one read-back (las_io.residue_files).  The raw statistics go to
+        <out_dir>/params/residue.npy ([K,12] int64), the cells to residue_cells.npy ([M,3] int32: cx, cy, component) and what
+        las_io.residue_summary reads off them to residue.json as {blob number from 1: summary}.  Without lines all three are empty."""
+        from . import las_io
+        lines3d, merged = result
+        lines = list(merged) if len(merged) else [l for name in sorted(lines3d) for l in lines3d[name]]
+        seen, once = set(), []
+        for path, shift, select in files:
+            if os.path.realpath(path) not in seen:
+                seen.add(os.path.realpath(path))
+                once.append((path, shift, select))
+        par_dir = self._params_dir(out_dir)
+        if lines and once:
+            blobs = las_io.residue_files(once, lines, residue, device=self.device)
+            stats = blobs.stats
+            cells = np.concatenate([blobs.cells, blobs.comp[:, None]], axis=1).astype(np.int32)
+            summary = las_io.residue_summary(blobs, lines, residue)
+        else:
+            stats, cells, summary = np.zeros((0, 12), np.int64), np.zeros((0, 3), np.int32), []
+        np.save(os.path.join(par_dir, 'residue.npy'), stats)
+        np.save(os.path.join(par_dir, 'residue_cells.npy'), cells)
+        with open(os.path.join(par_dir, 'residue.json'), 'w') as f:
+            json.dump({str(b['blob']): b for b in summary}, f, indent=1)
+
     def _follow_ground(self, gf, names, plist, points, offs, rpar, H, W, out_dir):
         """One batch of tiles through a las_io.GroundFilter: -> (plist, points, offs, rpar) to rasterise and back-project with.  The ground
         model comes from the batch's point ranges (ops.tile_ground); with gf.datum every tile's local_min_ele is replaced in BOTH its
@@ -451,7 +479,7 @@ class Runner:
         return raster_batch(names, plist, points, offs, rpar, scales)
 
     def infer_las_to_map(self, las_and_params, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None, ground=None,
-                         intensity=None, elevation=None, density=None, label=None, survey=None, colour=None):
+                         intensity=None, elevation=None, density=None, label=None, survey=None, colour=None, residue=None):
         """LAS tiles -> map-level 3-D lane lines, every stage of the reference's offline chain on this stack:
 
           LAS file + tile parameter file (utils/io_utils.py:125-150)
@@ -506,12 +534,20 @@ class Runner:
         gets the keys of las_io.marking_colours: coloured, yellow, black, rgb, colour ('white', 'yellow' or 'unknown') and run_colours.
         Refused with a ValueError before anything runs: colour without survey; an input file of a point format without R, G, B (0, 1,
         4, 6, 9).  The return value does not change.
-        Order of the stages: select, (binning,) ground, intensity, rasteriser, density, network, elevation, (merge,) label, survey.
+        residue: a las_io.PaintResidue (default: cfg['las_residue'], a dict of its arguments; absent: nothing changes): last of all, the
+        paint that none of the lines the call returns explains - stop bars, crossing bars, arrows, hatching, a missed line.  Every input
+        file is read once with its `select`; the returns at or above residue.min_intensity that lie within `reach` and `z_tol` of a line
+        but farther than `clear` from it are gridded, their connected blobs found and described on the GPU (ops.paint_residue, one
+        read-back).  The raw statistics are written to <work_dirs>/params/residue.npy ([K,12] int64), the occupied cells to
+        residue_cells.npy ([M,3] int32: cx, cy, blob) and what las_io.residue_summary reads off them - centre, area, length, width, fill,
+        heading and shape against the nearest line - to residue.json as {blob number from 1: summary}.  With no lines found the three
+        files are written empty.  The grid lives in the frame of the first file's las_read_offset.  The return value does not change.
+        Order of the stages: select, (binning,) ground, intensity, rasteriser, density, network, elevation, (merge,) label, survey, residue.
         Single rank (the merge is sequential over the sorted tiles)."""
         from . import las_io
         select, ground, intensity = self._las_select(select), self._las_ground(ground), self._las_intensity(intensity)
         elevation, density, label = self._las_elevation(elevation), self._las_density(density), self._las_label(label)
-        survey, colour = self._las_survey(survey), self._las_colour(colour)
+        survey, colour, residue = self._las_survey(survey), self._las_colour(colour), self._las_residue(residue)
         if label is not None:
             self._label_plan([p for p, _ in las_and_params])              # (a basename collision is refused before anything runs)
         self._colour_plan(colour, survey, [p for p, _ in las_and_params])
@@ -547,6 +583,8 @@ class Runner:
             self._label_inputs(label, inputs, result, out_dir)
         if survey is not None:
             self._survey_inputs(survey, inputs, result, out_dir, colour)
+        if residue is not None:
+            self._residue_inputs(residue, inputs, result, out_dir)
         return result
 
     def _las_chain(self, work_dirs, merge, elevation=None, density=None):
@@ -686,7 +724,7 @@ class Runner:
         return names, plist
 
     def infer_las_strip_to_map(self, las_paths, param_paths, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None,
-                               ground=None, intensity=None, elevation=None, density=None, label=None, survey=None, colour=None):
+                               ground=None, intensity=None, elevation=None, density=None, label=None, survey=None, colour=None, residue=None):
         """A whole strip -> map-level lane lines: the LAS file(s) of the strip are read once, their points are binned into the tiles of
         the layout on the GPU (ops.strip_bin_points: the windows of `param_paths` may overlap and be rotated), and every batch of tiles
         then runs the chain of infer_las_to_map from the rasteriser on.  Same outputs under the same names; a tile is named by the
@@ -701,14 +739,15 @@ class Runner:
         density: as for infer_las_to_map, per batch between the rasteriser and the network.
         label: as for infer_las_to_map, after the merge: every file of `las_paths` is labelled with the layout's las_read_offset and `select`.
         survey: as for infer_las_to_map, last: every file of `las_paths` is surveyed with the layout's las_read_offset and `select`.
-        colour: as for infer_las_to_map, in the survey's pass over the files of `las_paths`."""
+        colour: as for infer_las_to_map, in the survey's pass over the files of `las_paths`.
+        residue: as for infer_las_to_map, last of all: every file of `las_paths` is read with the layout's las_read_offset and `select`."""
         from . import las_io
         if isinstance(las_paths, (str, os.PathLike)):
             las_paths = [las_paths]
         names, plist = self._strip_layout(list(param_paths))
         select, ground, intensity = self._las_select(select), self._las_ground(ground), self._las_intensity(intensity)
         elevation, density, label = self._las_elevation(elevation), self._las_density(density), self._las_label(label)
-        survey, colour = self._las_survey(survey), self._las_colour(colour)
+        survey, colour, residue = self._las_survey(survey), self._las_colour(colour), self._las_residue(residue)
         if label is not None:
             self._label_plan(las_paths)                                    # (a basename collision is refused before anything runs)
         self._colour_plan(colour, survey, las_paths)
@@ -746,6 +785,8 @@ class Runner:
             self._label_inputs(label, [(path, plist[0]['las_read_offset'], select) for path in las_paths], result, out_dir)
         if survey is not None and plist:
             self._survey_inputs(survey, [(path, plist[0]['las_read_offset'], select) for path in las_paths], result, out_dir, colour)
+        if residue is not None and plist:
+            self._residue_inputs(residue, [(path, plist[0]['las_read_offset'], select) for path in las_paths], result, out_dir)
         return result
 
     def infer_lane_geometry_segmentation_segmentor(self, path_ckpt=None, mode_view=False, write_lane_vertex=False,
