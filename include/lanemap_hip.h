@@ -653,6 +653,48 @@ int lm_las_line_colour_records(void* hip_stream, const unsigned char* records, i
                                float half_width, const float* stations, const int* bin_start, const int* bin_start_host, int L, double bin,
                                float z_tol, float min_intensity, int blue_q, int accumulate, long* bins, long* colours, long n_bins);
 
+/* ---- cross-sections along every line (csrc/profile.hip): per station bin of a line a row of lateral cells holding the count, the paint
+ * count, the summed intensity and the summed height of the returns of the band - what tells a double line from a single one, gives a
+ * width and a paint centre that one stray return cannot set, and the road's cross-fall beside the line (las_io.cross_summary,
+ * las_io.snap_lines are the host policy on top of the table).
+ * THE RULE (one definition: cross_row in csrc/profile.hip, which both kernels call, this text, tests/cross_ref.py).  Eligibility, the hit
+ * test and the winner are exactly the labelling rule's (smallest d2, ties to the smaller line, then to the smaller segment index), WITHOUT
+ * a min_intensity: every finite return counts, the table must see asphalt as well as paint.  For a point whose winner is segment s of line
+ * k, with the clamped t, px, py and zl = az + t dz of that rule and st, b, o, q, iq of the marking profile above, unchanged, plain f32, no
+ * contraction:
+ *     hq  = (int)ceil((double)half_width 1024)                 on the host (half_width the f32 the index was built for)
+ *     nl  = 2 hq / lateral_q + 1                               lateral cells per station bin (integer division)
+ *     u   = min(max(q + hq, 0), 2 hq);   c = u / lateral_q
+ *     zq  = (int)rintf((z - zl) 1024.f)
+ *     row = (bin_start[k-1] + b) nl + c
+ *     cells[row] += 1, (iq >= paint_iq), iq, zq
+ * OUTPUT.  cells [n_bins nl][4] int64 = n, n_paint, sum iq, sum zq; an empty cell reads four zeros.  Cell c of a station bin covers the
+ * offsets [(c lateral_q - hq) / 1024, ((c + 1) lateral_q - hq) / 1024) m, left of the line positive.  lateral_q: the cell width in 1/1024 m,
+ * an integer >= 1.  paint_iq: an integer in 0 .. 65536; 65536: nothing is paint; a NaN intensity gives iq = 0.  half_width > 16 and
+ * z_tol > 16 are refused, so |q|, |zq| <= 2^14 + 1 and the sums of 2^31 returns stay inside 64 bits; n_bins nl > 2^27 is refused, which
+ * caps the table at 4 GiB.  Integer sums only: the result does not depend on the order of the points, files or adds, every run writes the
+ * same bits, no float atomic is used.
+ * line_cross_points: the arguments of lm_line_profile_points without min_intensity, then lateral_q, paint_iq, accumulate, cells,
+ *         n_cells = bin_start_host[L] nl.  A kernel of profile_points_kernel's streaming shape, no LDS.
+ * las_line_cross_records: the inputs of lm_las_line_profile_records with the same changes: a further instantiation of las_profile_kernel,
+ *         the records are read once and only read, a record that `select` drops contributes nothing.
+ * Both: accumulate = 0 zeroes cells on the stream first, accumulate = 1 adds to what is there.  Asynchronous, no workspace, nothing read
+ *         back.  N = 0, S = 0 or n_cells = 0 is LM_OK after the initialisation.
+ * Refused with LM_ERR_ARG and a message that names the argument, before anything is launched or written: what the profile entries refuse
+ * of the shared arguments; z_tol > 16; lateral_q < 1; paint_iq outside 0 .. 65536; n_bins nl > 2^27; n_cells != bin_start_host[L] nl; a
+ * null cells with n_cells > 0; "cells is not 8-byte aligned".
+ * NOTE on the name `hip_stream`: as for lm_label_points above; the guarded-buffer cases of these two entries are
+ * tests/test_gpu_cross.py::test_cross_points_guards and ::test_cross_records_guards. */
+int lm_line_cross_points(void* hip_stream, const float* points_xyzi, long N, const float* segments, long S, const LmLineGrid* grid,
+                         const int* cell_start, const int* cell_segs, float half_width, const float* stations, const int* bin_start,
+                         const int* bin_start_host, int L, double bin, float z_tol, int lateral_q, int paint_iq, int accumulate,
+                         long* cells, long n_cells);
+int lm_las_line_cross_records(void* hip_stream, const unsigned char* records, int record_len, int point_format, long n,
+                              const double* scale, const double* offset, const double* shift, const LmLasSelect* select,
+                              const float* segments, long S, const LmLineGrid* grid, const int* cell_start, const int* cell_segs,
+                              float half_width, const float* stations, const int* bin_start, const int* bin_start_host, int L, double bin,
+                              float z_tol, int lateral_q, int paint_iq, int accumulate, long* cells, long n_cells);
+
 /* ---- the paint no lane line explains (csrc/residue.hip): stop bars, crossing bars, arrows, hatching, chevrons and lines the network
  * missed are bright paint in the same returns as the lines, and label, profile and colour above see only paint that lies ON a line.  This
  * stage takes the strip's returns and the lines the call returns, keeps the bright road-level returns that no line explains (the RESIDUE),

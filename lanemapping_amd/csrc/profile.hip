@@ -31,6 +31,13 @@
 // colour words of the lane's staged record before the barrier that frees the stage and runs a second wave merge after profile_merge.  One
 // kernel name, because every kernel with LDS owns a case in the LDS-state tests under its name; a separate colour pass would also read
 // every record twice.
+//
+// Cross-sections along every line (lm_line_cross_points, lm_las_line_cross_records; the rule: include/lanemap_hip.h).  The same pass with a
+// finer target: per station bin a row of nl lateral cells of n, n_paint, sum iq, sum zq over EVERY finite return of the band (no
+// min_intensity).  cross_row is the one device function for the per-point terms; cross_points_kernel has profile_points_kernel's
+// streaming shape and no LDS, las_profile_kernel<false, true> is the record kernel's third instantiation - <false> and <true> compile to
+// the instructions they had before it existed.  Here the lanes of a wave do not share one to three bins: a wave crossing a marking hits
+// about a dozen distinct rows, so cross_add's loop runs about a dozen times; it still beats four atomics per hit lane (cross_add).
 #include "common.h"
 #include "label_rule.h"
 #include "las_record.h"
@@ -54,6 +61,7 @@ constexpr int PER = 4;                   // points per lane of profile_points_ke
 constexpr int CHUNK = 256 * PER;
 constexpr int REC_GROUPS = 4096;         // cap on the workgroups of the record kernel
 constexpr float MAX_HALF_WIDTH = 16.f;   // |q| <= 16 * 1024 + 1: q*q < 2^29, and 2^31 of them stay far inside 64 bits
+constexpr long MAX_CROSS_ROWS = 1L << 27;   // rows of 32 bytes: the cross-section table stays within 4 GiB
 
 struct ProfDev {
     const float4* stations;              // [S]: s0 len rlen 0
@@ -69,8 +77,13 @@ struct ColourDev : ProfDev {             // what las_profile_kernel<true> takes 
     unsigned blue_q;                     // 1 .. 1024
 };
 
-template <bool COLOUR>
-using ProfArg = std::conditional_t<COLOUR, ColourDev, ProfDev>;
+struct CrossDev : ProfDev {              // what las_profile_kernel<false, true> and cross_points_kernel take; bins: the cells [n_bins nl][4]
+    int hq, lateral_q, nl;               // ceil(half_width 1024); the cell width in 1/1024 m; 2 hq / lateral_q + 1 cells per station bin
+    unsigned paint_iq;                   // 0 .. 65536
+};
+
+template <bool COLOUR, bool CROSS = false>
+using ProfArg = std::conditional_t<CROSS, CrossDev, std::conditional_t<COLOUR, ColourDev, ProfDev>>;
 
 // the bin (absolute, -1: none), q and iq of a point whose winner is segment s of line ln at t.  bin_start and stations are device tables
 // the host cannot see: whatever they hold, a bin outside [0, n_bins) is never returned and bin_start is never read outside [0, L].
@@ -173,6 +186,58 @@ __device__ __forceinline__ void colour_merge(long long* __restrict__ colours, in
     }
 }
 
+// The cross-section's per-point terms (one definition: the two kernels and include/lanemap_hip.h) for a point whose winner is segment s of
+// line ln at t: -> the row of its cell in the table (-1: none), iq and zq.  The station bin, q and iq are profile_bin's, unchanged; the
+// lateral cell c <= 2 hq / lateral_q = nl - 1 by the clamp of u, so a row outside [0, n_bins nl) is never returned.
+__device__ __forceinline__ int cross_row(const float4 p, const IndexDev& I, const CrossDev& P, int ln, int s, float t, unsigned& iq, int& zq) {
+    int q;
+    zq = 0;
+    const int B = profile_bin(p, I, P, ln, s, t, q, iq);
+    if (B < 0) return -1;
+    const float4 A = I.seg[2 * s], D = I.seg[2 * s + 1];
+    const float zl = A.z + t * D.y;
+    zq = (int)rintf((p.z - zl) * 1024.f);
+    int u = q + P.hq;
+    u = u > 0 ? u : 0;
+    u = u < 2 * P.hq ? u : 2 * P.hq;
+    return B * P.nl + u / P.lateral_q;
+}
+
+// Wave-uniform like profile_merge: every lane of the wave calls it, row = -1 where the lane has nothing.  Per distinct row of the wave the
+// two counts by ballots and the two sums by cross-lane adds, then lanes 0 .. 3 issue the row's four 64-bit atomics (32 contiguous bytes;
+// an add of 0 is left out).  A row held by one lane alone skips the reduction.  The plain form - every hit lane adding its own four
+// values, zeros left out - was measured beside this one and is slower wherever a wave's lanes share rows (profiles/cross_section.txt).
+__device__ __forceinline__ void cross_add(const CrossDev& P, int row, unsigned iq, int zq) {
+    long long* __restrict__ cells = P.bins;
+    const bool paint = iq >= P.paint_iq;
+    const int lane = (int)__lane_id();
+    unsigned long long todo = __ballot(row >= 0);
+    while (todo) {
+        const int leader = __ffsll(todo) - 1;
+        const int lr = __shfl(row, leader);
+        const bool mine = row == lr;
+        const unsigned long long m = __ballot(mine);
+        const unsigned long long n = (unsigned long long)__popcll(m), np = (unsigned long long)__popcll(__ballot(mine && paint));
+        unsigned siq;
+        int sz;
+        if (n == 1) {
+            siq = (unsigned)__shfl((int)iq, leader), sz = __shfl(zq, leader);
+        } else {
+            siq = mine ? iq : 0u, sz = mine ? zq : 0;                  // 64 * 65535 and 64 * 16385 fit 32 bits
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) {
+                siq += (unsigned)__shfl_xor((int)siq, d);
+                sz += __shfl_xor(sz, d);
+            }
+        }
+        if (lane < 4) {
+            const unsigned long long v = lane == 0 ? n : lane == 1 ? np : lane == 2 ? siq : (unsigned long long)(long long)sz;
+            if (v) atomicAdd(reinterpret_cast<unsigned long long*>(cells) + (long)lr * 4 + lane, v);
+        }
+        todo &= ~m;
+    }
+}
+
 // grid: ceil(n_bins * 6 / 256)
 __global__ __launch_bounds__(256) void profile_init_kernel(long long* __restrict__ bins, long words) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
@@ -215,12 +280,40 @@ __global__ __launch_bounds__(256) void profile_points_kernel(const lab_f32x4* __
     }
 }
 
+// grid: ceil(N / 1024) workgroups.  profile_points_kernel's streaming shape with the cross-section's accumulation; no LDS.
+__global__ __launch_bounds__(256) void cross_points_kernel(const lab_f32x4* __restrict__ pts, long N, IndexDev I, CrossDev P) {
+    const long first = (long)blockIdx.x * CHUNK;
+    const long left = N - first;                               // >= 1
+    float4 p[PER];
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        const long i = (long)j * 256 + threadIdx.x;
+        const lab_f32x4 v = __builtin_nontemporal_load(pts + first + (i < left ? i : left - 1));   // unconditional, tail lanes masked below
+        p[j] = float4{v[0], v[1], v[2], v[3]};
+    }
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        const long i = (long)j * 256 + threadIdx.x;
+        int a = 0, b = 0;
+        if (i < left) label_range(p[j], I, a, b);
+        if (__ballot(b > a) == 0) continue;                    // wave-uniform: a wave beside the lines leaves here
+        float best, t;
+        int s;
+        const int ln = label_search_t<true>(p[j], I, a, b, best, s, t);
+        int row = -1, zq = 0;
+        unsigned iq = 0u;
+        if (ln > 0) row = cross_row(p[j], I, P, ln, s, t, iq, zq);
+        cross_add(P, row, iq, zq);
+    }
+}
+
 // grid: min(blocks of 256 records, the workgroups resident at once) workgroups; dynamic LDS = 256 records.  Per block: stage, decode into
 // registers, barrier (the stage is free again), search and accumulate.  The records are only read.  COLOUR: P is a ColourDev, the lane also
-// takes the R, G, B of its own staged record into registers before the barrier, and the colour row is merged after the profile's.
-template <bool COLOUR>
+// takes the R, G, B of its own staged record into registers before the barrier, and the colour row is merged after the profile's.  CROSS: P
+// is a CrossDev, and after the search the cross-section's cell is accumulated instead of the profile's bin.
+template <bool COLOUR, bool CROSS = false>
 __global__ __launch_bounds__(256) void las_profile_kernel(const unsigned* __restrict__ rec, int record_len, long n, long nblk, LasXf X, LasSel S,
-                                                          int use_sel, IndexDev I, ProfArg<COLOUR> P) {
+                                                          int use_sel, IndexDev I, ProfArg<COLOUR, CROSS> P) {
     extern __shared__ unsigned prof_stage[];
     for (long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
         const int cnt = las_stage_block(rec, record_len, n, blk, prof_stage);
@@ -244,17 +337,24 @@ __global__ __launch_bounds__(256) void las_profile_kernel(const unsigned* __rest
         float best, t;
         int s;
         const int ln = label_search_t<true>(p, I, a, b, best, s, t);
-        int q = 0, B = -1;
-        unsigned iq = 0u;
-        if (ln > 0) B = profile_bin(p, I, P, ln, s, t, q, iq);
-        profile_merge(P.bins, B, q, iq);
-        if constexpr (COLOUR) colour_merge(P.colours, B, cr, cg, cb, P.blue_q);
+        if constexpr (CROSS) {
+            int row = -1, zq = 0;
+            unsigned iq = 0u;
+            if (ln > 0) row = cross_row(p, I, P, ln, s, t, iq, zq);
+            cross_add(P, row, iq, zq);
+        } else {
+            int q = 0, B = -1;
+            unsigned iq = 0u;
+            if (ln > 0) B = profile_bin(p, I, P, ln, s, t, q, iq);
+            profile_merge(P.bins, B, q, iq);
+            if constexpr (COLOUR) colour_merge(P.colours, B, cr, cg, cb, P.blue_q);
+        }
     }
 }
 
-// Workgroups of las_profile_kernel<COLOUR> the current device holds at once for `lds` bytes of dynamic LDS (as label.hip's: asked of the
+// Workgroups of las_profile_kernel<COLOUR, CROSS> the current device holds at once for `lds` bytes of dynamic LDS (as label.hip's: asked of the
 // runtime once per (device, lds) and instantiation, and kept; the number only sizes the grid).
-template <bool COLOUR>
+template <bool COLOUR, bool CROSS>
 int resident_groups(size_t lds, long& groups) {
     static std::mutex mu;
     static std::map<std::pair<int, size_t>, long> known;
@@ -267,7 +367,7 @@ int resident_groups(size_t lds, long& groups) {
         return LM_OK;
     }
     int per_cu = 0, cus = 0;
-    LM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, las_profile_kernel<COLOUR>, 256, lds));
+    LM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, las_profile_kernel<COLOUR, CROSS>, 256, lds));
     LM_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev_id));
     groups = (long)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 256);
     groups = groups < REC_GROUPS ? groups : REC_GROUPS;
@@ -275,10 +375,11 @@ int resident_groups(size_t lds, long& groups) {
     return LM_OK;
 }
 
-// the arguments both entries share, checked before anything is launched or written
+// the arguments the entries share, checked before anything is launched or written.  cross: the table is `cells`, whose size check_cross
+// holds against bin_start_host[L] afterwards; n_bins is then taken from bin_start_host[L]
 int check_profile(const char* who, const LmLineGrid* grid, long S, const void* segments, const void* cell_start, const void* cell_segs,
                   float half_width, const float* stations, const int* bin_start, const int* bin_start_host, int L, double bin, float z_tol,
-                  int accumulate, long* bins, long n_bins, IndexDev& I, ProfDev& P) {
+                  int accumulate, long* bins, long n_bins, IndexDev& I, ProfDev& P, bool cross = false) {
     if (int e = check_index(who, grid, S, segments, cell_start, cell_segs, half_width, z_tol, I)) return e;
     LM_REQUIRE(half_width <= MAX_HALF_WIDTH, "%s: half_width=%g, at most %g m is supported (the offsets are summed in 1/1024 m)", who,
                (double)half_width, (double)MAX_HALF_WIDTH);
@@ -292,12 +393,13 @@ int check_profile(const char* who, const LmLineGrid* grid, long S, const void* s
     for (int k = 0; k < L; ++k)
         LM_REQUIRE(bin_start_host[k + 1] >= bin_start_host[k], "%s: bin_start[%d]=%d is below bin_start[%d]=%d", who, k + 1,
                    bin_start_host[k + 1], k, bin_start_host[k]);
+    if (cross) n_bins = bin_start_host[L];
     LM_REQUIRE(n_bins == (long)bin_start_host[L], "%s: n_bins=%ld, but bin_start[L]=%d", who, n_bins, bin_start_host[L]);
     LM_REQUIRE(S == 0 || (stations && bin_start), "%s: null pointer (stations, bin_start)", who);
-    LM_REQUIRE(n_bins == 0 || bins, "%s: null pointer (bins)", who);
+    LM_REQUIRE(cross || n_bins == 0 || bins, "%s: null pointer (bins)", who);
     LM_REQUIRE(((uintptr_t)stations & 15) == 0, "%s: stations is not 16-byte aligned", who);
     LM_REQUIRE(((uintptr_t)bin_start & 3) == 0, "%s: bin_start is not 4-byte aligned", who);
-    LM_REQUIRE(((uintptr_t)bins & 7) == 0, "%s: bins is not 8-byte aligned", who);
+    LM_REQUIRE(((uintptr_t)bins & 7) == 0, "%s: %s is not 8-byte aligned", who, cross ? "cells" : "bins");
     P = ProfDev{reinterpret_cast<const float4*>(stations), bin_start, reinterpret_cast<long long*>(bins), L, (int)n_bins,
                 (float)(1.0 / bin)};
     return LM_OK;
@@ -315,6 +417,30 @@ int init_colours(const ColourDev& P, hipStream_t s) {
     const long words = (long)P.n_bins * 6;
     if (words == 0) return LM_OK;
     hipLaunchKernelGGL(colour_init_kernel, dim3((unsigned)lm_cdivl(words, 256)), dim3(256), 0, s, P.colours, words);
+    LM_LAUNCH_CHECK();
+    return LM_OK;
+}
+
+// what the two cross-section entries take beside the profile's arguments, checked after them; fills P
+int check_cross(const char* who, float half_width, float z_tol, int lateral_q, int paint_iq, long* cells, long n_cells, CrossDev& P) {
+    LM_REQUIRE(z_tol <= MAX_HALF_WIDTH, "%s: z_tol=%g, at most %g m is supported (the heights are summed in 1/1024 m)", who, (double)z_tol,
+               (double)MAX_HALF_WIDTH);
+    LM_REQUIRE(lateral_q >= 1, "%s: lateral_q=%d must be a cell width >= 1 (in 1/1024 m)", who, lateral_q);
+    LM_REQUIRE(paint_iq >= 0 && paint_iq <= 65536, "%s: paint_iq=%d must lie in 0 .. 65536", who, paint_iq);
+    P.hq = (int)std::ceil((double)half_width * 1024.0);                // <= 16384
+    P.lateral_q = lateral_q, P.nl = 2 * P.hq / lateral_q + 1, P.paint_iq = (unsigned)paint_iq;
+    const long rows = (long)P.n_bins * P.nl;
+    LM_REQUIRE(rows <= MAX_CROSS_ROWS, "%s: %d bins of nl=%d cells are %ld rows, at most 2^27 are supported (choose a larger bin or lateral_q)",
+               who, P.n_bins, P.nl, rows);
+    LM_REQUIRE(n_cells == rows, "%s: n_cells=%ld, but bin_start[L]=%d bins of nl=%d cells are %ld", who, n_cells, P.n_bins, P.nl, rows);
+    LM_REQUIRE(n_cells == 0 || cells, "%s: null pointer (cells)", who);
+    return LM_OK;
+}
+
+int init_cells(const CrossDev& P, hipStream_t s) {
+    const long words = (long)P.n_bins * P.nl * 4;
+    if (words == 0) return LM_OK;
+    hipLaunchKernelGGL(colour_init_kernel, dim3((unsigned)lm_cdivl(words, 256)), dim3(256), 0, s, P.bins, words);
     LM_LAUNCH_CHECK();
     return LM_OK;
 }
@@ -350,12 +476,12 @@ namespace {
 
 // The two record entries.  COLOUR: blue_q and colours are checked after everything the profile entry refuses, both tensors are initialised,
 // and las_profile_kernel<true> fills both in its one pass over the records.
-template <bool COLOUR>
+template <bool COLOUR, bool CROSS = false>
 int las_profile_records(const char* who, void* hip_stream, const unsigned char* records, int record_len, int point_format, long n,
                         const double* scale, const double* offset, const double* shift, const LmLasSelect* select, const float* segments, long S,
                         const LmLineGrid* grid, const int* cell_start, const int* cell_segs, float half_width, const float* stations,
                         const int* bin_start, const int* bin_start_host, int L, double bin, float z_tol, float min_intensity, int blue_q,
-                        int accumulate, long* bins, long* colours, long n_bins) {
+                        int accumulate, long* bins, long* colours, long n_bins, int lateral_q = 0, int paint_iq = 0) {
     static const int min_len[11] = {20, 28, 26, 34, 57, 63, 30, 36, 38, 59, 67};
     static const int rgb_off[11] = {-1, -1, 20, 28, -1, 28, -1, 30, 30, -1, 30};      // rgb_off + 6 <= min_len wherever there is colour
     LM_REQUIRE(point_format >= 0 && point_format <= 10, "%s: unknown point data record format point_format=%d", who, point_format);
@@ -363,10 +489,14 @@ int las_profile_records(const char* who, void* hip_stream, const unsigned char* 
                point_format, min_len[point_format]);
     LM_REQUIRE(n >= 0 && n <= 2147483647L, "%s: n=%ld records, at most 2^31 - 1 are supported", who, n);
     IndexDev I;
-    ProfArg<COLOUR> P;
+    ProfArg<COLOUR, CROSS> P;
     if (int e = check_profile(who, grid, S, segments, cell_start, cell_segs, half_width, stations, bin_start, bin_start_host, L, bin, z_tol,
-                              accumulate, bins, n_bins, I, P))
+                              accumulate, bins, n_bins, I, P, CROSS))
         return e;
+    if constexpr (CROSS) {                                             // (bins: the cells, n_bins: n_cells)
+        if (int e = check_cross(who, half_width, z_tol, lateral_q, paint_iq, bins, n_bins, P)) return e;
+        n_bins = P.n_bins;
+    }
     LM_REQUIRE(scale && offset && (n == 0 || records), "%s: null pointer (scale, offset, records)", who);
     LM_REQUIRE(((uintptr_t)records & 3) == 0, "%s: records is not 4-byte aligned", who);
     LasSel Sel{};
@@ -396,17 +526,21 @@ int las_profile_records(const char* who, void* hip_stream, const unsigned char* 
     const size_t lds = ((size_t)256 * record_len + 3) / 4 * 4;
     long resident = 0;
     if (work)
-        if (int e = resident_groups<COLOUR>(lds, resident)) return e;
+        if (int e = resident_groups<COLOUR, CROSS>(lds, resident)) return e;
     if (!accumulate) {
-        if (int e = init_bins(P, s)) return e;
-        if constexpr (COLOUR)
-            if (int e = init_colours(P, s)) return e;
+        if constexpr (CROSS) {
+            if (int e = init_cells(P, s)) return e;
+        } else {
+            if (int e = init_bins(P, s)) return e;
+            if constexpr (COLOUR)
+                if (int e = init_colours(P, s)) return e;
+        }
     }
     if (!work) return LM_OK;
     const double sh[3] = {shift ? shift[0] : 0.0, shift ? shift[1] : 0.0, shift ? shift[2] : 0.0};
     const LasXf X{scale[0], scale[1], scale[2], offset[0] - sh[0], offset[1] - sh[1], offset[2] - sh[2], 0.f, 1.f, 0};   // raw intensity
     const unsigned groups = (unsigned)(nblk < resident ? nblk : resident);
-    hipLaunchKernelGGL(las_profile_kernel<COLOUR>, dim3(groups), dim3(256), lds, s, reinterpret_cast<const unsigned*>(records), record_len, n, nblk,
+    hipLaunchKernelGGL((las_profile_kernel<COLOUR, CROSS>), dim3(groups), dim3(256), lds, s, reinterpret_cast<const unsigned*>(records), record_len, n, nblk,
                        X, Sel, select ? 1 : 0, I, P);
     LM_LAUNCH_CHECK();
     return LM_OK;
@@ -435,4 +569,41 @@ LM_API int lm_las_line_colour_records(void* hip_stream, const unsigned char* rec
     return las_profile_records<true>("las_line_colour_records", hip_stream, records, record_len, point_format, n, scale, offset, shift, select,
                                      segments, S, grid, cell_start, cell_segs, half_width, stations, bin_start, bin_start_host, L, bin, z_tol,
                                      min_intensity, blue_q, accumulate, bins, colours, n_bins);
+}
+
+// The cross-sections along every line (the rule: include/lanemap_hip.h).  The arguments of lm_line_profile_points without min_intensity -
+// every finite return counts -, then lateral_q, paint_iq; cells DEVICE [n_cells][4] int64, n_cells = bin_start_host[L] nl.
+LM_API int lm_line_cross_points(void* hip_stream, const float* points_xyzi, long N, const float* segments, long S, const LmLineGrid* grid,
+                                const int* cell_start, const int* cell_segs, float half_width, const float* stations, const int* bin_start,
+                                const int* bin_start_host, int L, double bin, float z_tol, int lateral_q, int paint_iq, int accumulate,
+                                long* cells, long n_cells) {
+    IndexDev I;
+    CrossDev P;
+    if (int e = check_profile("line_cross_points", grid, S, segments, cell_start, cell_segs, half_width, stations, bin_start, bin_start_host, L,
+                              bin, z_tol, accumulate, cells, n_cells, I, P, true))
+        return e;
+    if (int e = check_cross("line_cross_points", half_width, z_tol, lateral_q, paint_iq, cells, n_cells, P)) return e;
+    LM_REQUIRE(N >= 0 && N <= 2147483647L, "line_cross_points: N=%ld points, at most 2^31 - 1 are supported", N);
+    LM_REQUIRE(N == 0 || points_xyzi, "line_cross_points: null pointer (points_xyzi)");
+    LM_REQUIRE(((uintptr_t)points_xyzi & 15) == 0, "line_cross_points: points_xyzi is not 16-byte aligned");
+    I.min_inten = NAN;
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (!accumulate)
+        if (int e = init_cells(P, s)) return e;
+    if (N == 0 || S == 0 || n_cells == 0) return LM_OK;
+    hipLaunchKernelGGL(cross_points_kernel, dim3((unsigned)lm_cdivl(N, CHUNK)), dim3(256), 0, s, reinterpret_cast<const lab_f32x4*>(points_xyzi),
+                       N, I, P);
+    LM_LAUNCH_CHECK();
+    return LM_OK;
+}
+
+// as above on the records of a file: the inputs of lm_las_line_profile_records.  las_profile_kernel<false, true>: one pass, records only read.
+LM_API int lm_las_line_cross_records(void* hip_stream, const unsigned char* records, int record_len, int point_format, long n,
+                                     const double* scale, const double* offset, const double* shift, const LmLasSelect* select,
+                                     const float* segments, long S, const LmLineGrid* grid, const int* cell_start, const int* cell_segs,
+                                     float half_width, const float* stations, const int* bin_start, const int* bin_start_host, int L,
+                                     double bin, float z_tol, int lateral_q, int paint_iq, int accumulate, long* cells, long n_cells) {
+    return las_profile_records<false, true>("las_line_cross_records", hip_stream, records, record_len, point_format, n, scale, offset, shift,
+                                            select, segments, S, grid, cell_start, cell_segs, half_width, stations, bin_start, bin_start_host,
+                                            L, bin, z_tol, NAN, 0, accumulate, cells, nullptr, n_cells, lateral_q, paint_iq);
 }

@@ -32,6 +32,11 @@ runs, dash pattern, width and brightness read off the bins.
 triple that point formats 2, 3, 5, 7, 8 and 10 carry per return: the same pass over the records fills a second table per station bin
 (`lm_las_line_colour_records`), and the host reads a colour per line and per paint run off it.
 
+`CrossSection` / `cross_files` / `cross_summary` / `snap_lines` take cross-sections along the lines: per station bin a row of lateral cells
+holding the count, the paint count, the summed intensity and the summed height of every return of the band (`ops.line_cross`,
+`lm_las_line_cross_records`), and on the host the stripes of every station - single or double line, a width and a paint centre read off
+the distribution, the road's cross-fall - and the lines moved onto their paint.
+
 `PaintResidue` / `residue_files` / `residue_summary` inventory the paint that no line explains - stop bars, crossing bars, arrows,
 hatching, a line the network missed: the bright road-level returns away from every line, gridded, labelled into connected blobs and
 described on the GPU (`ops.paint_residue`), and on the host the centre, size, fill and heading of every blob against its nearest line.
@@ -950,6 +955,313 @@ def marking_colours(bins, colours, bin_start, survey, colour):
             run_colours.append(decide(int(c[i0:i1 + 1][sel, 0].sum()), int(c[i0:i1 + 1][sel, 4].sum())))
         out.append({'coloured': n_c, 'yellow': n_y, 'black': n_k, 'rgb': [s / n_c for s in sums] if n_c else None,
                     'colour': decide(n_c, n_y), 'run_colours': run_colours})
+    return out
+
+
+class CrossSection:
+    """How the LAS -> map routes take cross-sections along the lane lines they found (immutable; Runner.infer_las_strip_to_map /
+    infer_las_to_map, `cross=`; cross_files, cross_summary, snap_lines).  EVERY finite return the labelling rule gives a line (within
+    half_width in the plane and z_tol in height, the nearest line winning, no intensity threshold) goes into a table: per station bin
+    along the line a row of lateral cells, each holding the count, the paint count, the summed intensity and the summed height above the
+    line (the rule: include/lanemap_hip.h).  cross_summary reads stripes, double lines, width, the paint's centre and the cross-fall off
+    the table; snap_lines moves the lines onto the paint.
+
+      paint_intensity raw intensity (a number, not NaN; required): a return is paint when its intensity, rounded to a whole number and
+                      clamped into 0 .. 65535, is at least ceil(paint_intensity) - `paint_iq`, clamped into 0 .. 65536 (65536: nothing is)
+      bin             metres (finite, > 0): the length of a station bin along a line
+      half_width      metres (finite, 0 .. 16): half the width of the band around a line
+      lateral         metres (finite, > 0): the width of a lateral cell; the rule takes lateral_q = max(1, round(1024 lateral)) / 1024 m
+      z_tol           metres (0 .. 16): the height band
+      min_points      a cell is KNOWN when it holds at least this many returns (whole number >= 1)
+      paint_share     0 < paint_share <= 1: a known cell is PAINTED when at least this share of its returns is paint (compared exactly)
+      max_hole        up to this many consecutive unknown cells between two painted cells count as painted (whole number >= 0)
+      min_stripe      metres (finite, >= 0): a stripe is a maximal painted run at least this wide
+      smooth          metres (finite, >= 0): snap_lines moves a vertex by the median centre of the stations whose bin midpoint lies within
+                      smooth / 2 of it
+      min_stations    with fewer such stations the vertex stays (whole number >= 1)
+      max_shift       metres (finite, >= 0): a vertex that would move farther stays - an outlier, not a clamp
+    Apart from paint_intensity, which only the data can give, the values are plain defaults, not tuned values."""
+    __slots__ = ('paint_intensity', 'bin', 'half_width', 'lateral', 'z_tol', 'min_points', 'paint_share', 'max_hole', 'min_stripe', 'smooth',
+                 'min_stations', 'max_shift')
+
+    def __init__(self, paint_intensity, bin=0.5, half_width=0.625, lateral=0.03125, z_tol=0.5, min_points=3, paint_share=0.5, max_hole=1,
+                 min_stripe=0.05, smooth=2.0, min_stations=2, max_shift=0.3):
+        num = (int, float, np.integer, np.floating)
+        whole = (int, np.integer)
+
+        def number(v):
+            return not isinstance(v, bool) and isinstance(v, num)
+
+        if not number(paint_intensity) or math.isnan(float(paint_intensity)):
+            raise ValueError(f'CrossSection: paint_intensity={paint_intensity!r} must be a number')
+        if not number(bin) or not (0.0 < float(bin) < math.inf):
+            raise ValueError(f'CrossSection: bin={bin!r} must be a finite length > 0')
+        if not number(half_width) or not (0.0 <= float(half_width) <= 16.0):
+            raise ValueError(f'CrossSection: half_width={half_width!r} must be a number in 0 .. 16 (metres)')
+        if not number(lateral) or not (0.0 < float(lateral) < math.inf):
+            raise ValueError(f'CrossSection: lateral={lateral!r} must be a finite width > 0')
+        if not number(z_tol) or not (0.0 <= float(z_tol) <= 16.0):
+            raise ValueError(f'CrossSection: z_tol={z_tol!r} must be a number in 0 .. 16 (metres)')
+        if isinstance(min_points, bool) or not isinstance(min_points, whole) or int(min_points) < 1:
+            raise ValueError(f'CrossSection: min_points={min_points!r} must be a whole number >= 1')
+        if not number(paint_share) or not (0.0 < float(paint_share) <= 1.0):
+            raise ValueError(f'CrossSection: paint_share={paint_share!r} must be a number with 0 < paint_share <= 1')
+        if isinstance(max_hole, bool) or not isinstance(max_hole, whole) or int(max_hole) < 0:
+            raise ValueError(f'CrossSection: max_hole={max_hole!r} must be a whole number >= 0')
+        if not number(min_stripe) or not (0.0 <= float(min_stripe) < math.inf):
+            raise ValueError(f'CrossSection: min_stripe={min_stripe!r} must be a finite width >= 0')
+        if not number(smooth) or not (0.0 <= float(smooth) < math.inf):
+            raise ValueError(f'CrossSection: smooth={smooth!r} must be a finite length >= 0')
+        if isinstance(min_stations, bool) or not isinstance(min_stations, whole) or int(min_stations) < 1:
+            raise ValueError(f'CrossSection: min_stations={min_stations!r} must be a whole number >= 1')
+        if not number(max_shift) or not (0.0 <= float(max_shift) < math.inf):
+            raise ValueError(f'CrossSection: max_shift={max_shift!r} must be a finite length >= 0')
+        for k, v in (('paint_intensity', float(paint_intensity)), ('bin', float(bin)), ('half_width', float(half_width)),
+                     ('lateral', float(lateral)), ('z_tol', float(z_tol)), ('min_points', int(min_points)), ('paint_share', float(paint_share)),
+                     ('max_hole', int(max_hole)), ('min_stripe', float(min_stripe)), ('smooth', float(smooth)),
+                     ('min_stations', int(min_stations)), ('max_shift', float(max_shift))):
+            object.__setattr__(self, k, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError('CrossSection is immutable')
+
+    def __delattr__(self, name):
+        raise AttributeError('CrossSection is immutable')
+
+    def __repr__(self):
+        return 'CrossSection(' + ', '.join(f'{k}={getattr(self, k)!r}' for k in self.__slots__) + ')'
+
+    def __eq__(self, other):
+        return isinstance(other, CrossSection) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
+
+    def __hash__(self):
+        return hash(tuple(getattr(self, k) for k in self.__slots__))
+
+    @property
+    def lateral_q(self):
+        """The cell width the device entries take, in 1/1024 m: max(1, round(1024 lateral)), halves up."""
+        return max(1, int(math.floor(1024.0 * self.lateral + 0.5)))
+
+    @property
+    def paint_iq(self):
+        """The integer the device entries take: ceil(paint_intensity), clamped into 0 .. 65536."""
+        p = self.paint_intensity
+        return 65536 if p > 65535.0 else 0 if p <= 0.0 else int(math.ceil(p))
+
+    @property
+    def hq(self):
+        """ceil(float32(half_width) 1024): the rule's half width in 1/1024 m."""
+        return int(math.ceil(float(np.float32(self.half_width)) * 1024.0))
+
+    @property
+    def nl(self):
+        """The lateral cells of a station bin: 2 hq // lateral_q + 1."""
+        return 2 * self.hq // self.lateral_q + 1
+
+
+def cross_records(records_u8, header, index, stations, cross, shift=None, select=None, out=None):
+    """One lm_las_line_cross_records call on the DEVICE records of a file (as profile_records takes them) against an ops.LineIndex and the
+    ops.LineStations of the same segments: -> cells [n_bins, nl, 4] int64 device tensor (see ops.line_cross).  The records are only read; a
+    record `select` drops contributes nothing.  out: the cells of an earlier call to add to.  Asynchronous."""
+    from . import ops
+    who = 'las_io.cross_records'
+    if not isinstance(cross, CrossSection):
+        raise TypeError(f'{who}: cross must be a CrossSection, not {type(cross).__name__}')
+    if select is not None and not isinstance(select, PointFilter):
+        raise TypeError(f'{who}: select must be a PointFilter, not {type(select).__name__}')
+    if not records_u8.is_cuda:
+        raise LanemapHipError(f'{who} needs the records on an MI355X (HIP) device; no CPU fallback exists')
+    if not isinstance(index, ops.LineIndex) or not isinstance(stations, ops.LineStations):
+        raise TypeError(f'{who}: index must be an ops.LineIndex and stations an ops.LineStations')
+    fmt, rl, n = header['point_format'], header['record_len'], header['n_points']
+    sel = select.for_format(fmt).as_struct() if select is not None else None
+    if index.half_width != np.float32(cross.half_width):
+        raise ValueError(f'{who}: the index was built for half_width={index.half_width}, the cross-section asks {cross.half_width}')
+    if stations.bin != cross.bin or stations.n_segments != index.n_segments:
+        raise ValueError(f'{who}: the stations were cut for bin={stations.bin} and {stations.n_segments} segments, the cross-section '
+                         f'asks bin={cross.bin}, the index holds {index.n_segments}')
+    dev = records_u8.device
+    nl = cross.nl
+    cells = ops._cross_out(who, stations, nl, out, dev)
+    n_cells = stations.n_bins * nl
+    d3 = lambda v: (C.c_double * 3)(*[float(x) for x in v])
+    check(lib().lm_las_line_cross_records(C.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index)), C.c_void_p(records_u8.data_ptr()),
+                                          int(rl), int(fmt), int(n), d3(header['scale']), d3(header['offset']),
+                                          d3(shift) if shift is not None else None, C.byref(sel) if sel is not None else None,
+                                          *index.args(), *stations.args(), cross.z_tol, cross.lateral_q, cross.paint_iq, int(out is not None),
+                                          C.c_void_p(cells.data_ptr()) if n_cells else None, n_cells))
+    return cells
+
+
+def cross_files(files, lines, cross, device='cuda:0'):
+    """The cross-section table of `lines` (list of [n,3] float64, LAS frame) from the LAS files `files`, a list of (path, shift, select):
+    every file is read once, uploaded and goes through one lm_las_line_cross_records call with its own read offset and PointFilter, all
+    into one table, which is read back once.  The bins each line owns are those of the first file's frame, as in survey_files.
+    -> (cells [n_bins, nl, 4] int64 numpy, bin_start [L + 1] int32 numpy)."""
+    from . import ops
+    if not isinstance(cross, CrossSection):
+        raise TypeError(f'las_io.cross_files: cross must be a CrossSection, not {type(cross).__name__}')
+    device = torch.device(device)
+    lines, files = list(lines), list(files)
+    tables, bin_start, cells = {}, None, None
+    for path, shift, select in files:
+        if select is not None and not isinstance(select, PointFilter):
+            raise TypeError(f'las_io.cross_files: select must be a PointFilter, not {type(select).__name__}')
+        data = np.fromfile(path, dtype=np.uint8)
+        h = parse_header(data)
+        n, rl, off = h['n_points'], h['record_len'], h['offset_to_points']
+        if select is not None:
+            select.for_format(h['point_format'])
+        key = None if shift is None else tuple(float(v) for v in shift)
+        if key not in tables:
+            st, bs = line_stations(lines, shift, cross.bin)
+            bin_start = bs if bin_start is None else bin_start
+            tables[key] = (ops.line_index(line_segments(lines, shift), cross.half_width, device=device),
+                           ops.line_stations(st, bin_start, cross.bin, device=device))
+        index, stations = tables[key]
+        nbytes = n * rl
+        padded = np.zeros(((nbytes + 3) // 4 * 4,), dtype=np.uint8)
+        padded[:nbytes] = data[off:off + nbytes]
+        rec = torch.from_numpy(padded).to(device, non_blocking=True)
+        cells = cross_records(rec, h, index, stations, cross, shift, select, out=cells)
+    if cells is None:                                                       # no file: the empty table of the lines
+        bin_start = line_stations(lines, None, cross.bin)[1]
+        return np.zeros((int(bin_start[-1]), cross.nl, 4), dtype=np.int64), bin_start
+    return cells.cpu().numpy(), bin_start                                   # the one read-back
+
+
+def _median(values):
+    v = sorted(values)
+    return None if not v else float(v[len(v) // 2]) if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
+
+
+def cross_summary(cells, bin_start, cross):
+    """What the cross-section table says about every line (host, integers and float64): cells [n_bins, nl, 4] int64 (n, n_paint, sum iq,
+    sum zq) and bin_start [L + 1] -> one dict per line.  Cell c of a station covers the offsets [(c lateral_q - hq) / 1024,
+    ((c + 1) lateral_q - hq) / 1024) m, left of the line positive.  A cell is KNOWN with n >= min_points, PAINTED when known and n_paint >=
+    paint_share n (exactly: the share's own rational value); up to max_hole consecutive unknown cells between two painted cells count as
+    painted; the STRIPES of a station are its maximal painted runs at least min_stripe wide; a station with a stripe is painted and its
+    centre is the midpoint of its outermost stripe edges.
+
+      stations    the number of painted stations
+      stripes     the most frequent stripe count over the painted stations, ties to the smaller (None without a painted station)
+      double      stripes == 2
+      width       metres: the median stripe width over the stations with that count
+      separation  metres: the median gap between the two stripes of those stations; None unless double
+      extent      metres: the median distance between the outermost stripe edges of those stations
+      offset      metres: the median centre of those stations - where the paint is, left of the given line positive
+      crossfall   m/m, positive rising to the left: the median, over the stations with at least 3 known cells, of the n-weighted least-squares
+                  slope of the cells' mean height (sum zq / n / 1024) against the offset of the cell centres; None without such a station
+      centres     per station the centre, None where the station is not painted
+      counts      per station the number of stripes
+    The first five medians are taken over the stations whose stripe count is the line's, so that a stretch where one stripe of a double
+    line is worn does not pull them."""
+    from fractions import Fraction
+    if not isinstance(cross, CrossSection):
+        raise TypeError(f'cross_summary: cross must be a las_io.CrossSection, not {type(cross).__name__}')
+    cells = np.asarray(cells)
+    bs = np.asarray(bin_start, dtype=np.int64)
+    hq, lq, nl = cross.hq, cross.lateral_q, cross.nl
+    if cells.ndim != 3 or cells.shape[1:] != (nl, 4) or cells.dtype != np.int64 or bs.ndim != 1 or len(bs) < 1 or bs[0] != 0 \
+            or (np.diff(bs) < 0).any() or bs[-1] != len(cells):
+        raise ValueError(f'cross_summary: cells must be [bin_start[L], {nl}, 4] int64 and bin_start a CSR table from 0, not {cells.shape} '
+                         f'{cells.dtype} and {bs.tolist() if len(bs) < 8 else bs.shape}')
+    share = Fraction(cross.paint_share)                                     # the float's exact value
+    out = []
+    for k in range(len(bs) - 1):
+        per_station, falls = [], []
+        for row in cells[bs[k]:bs[k + 1]]:
+            n, npaint, szq = row[:, 0], row[:, 1], row[:, 3]
+            known = n >= cross.min_points
+            state = [0] * nl                                                # 0 unknown, 1 known and not painted, 2 painted
+            for c in np.nonzero(known)[0]:
+                state[c] = 2 if int(npaint[c]) >= share * int(n[c]) else 1
+            last = None                                                     # the holes
+            for c in range(nl):
+                if state[c] == 2:
+                    if last is not None and 0 < c - last - 1 <= cross.max_hole and all(state[j] == 0 for j in range(last + 1, c)):
+                        for j in range(last + 1, c):
+                            state[j] = 2
+                    last = c
+            stripes, c = [], 0
+            while c < nl:
+                if state[c] == 2:
+                    e = c
+                    while e + 1 < nl and state[e + 1] == 2:
+                        e += 1
+                    if (e - c + 1) * lq / 1024.0 >= cross.min_stripe:
+                        stripes.append(((c * lq - hq) / 1024.0, ((e + 1) * lq - hq) / 1024.0))
+                    c = e + 1
+                else:
+                    c += 1
+            per_station.append(stripes)
+            idx = np.nonzero(known)[0]
+            if len(idx) >= 3:                                               # X = 2048 x, the cell centre: exact integers up to one division
+                X = [(2 * int(c) + 1) * lq - 2 * hq for c in idx]
+                w, z = [int(n[c]) for c in idx], [int(szq[c]) for c in idx]
+                N, sx, sz = sum(w), sum(a * b for a, b in zip(w, X)), sum(z)
+                num = N * sum(a * b for a, b in zip(X, z)) - sx * sz
+                den = N * sum(a * b * b for a, b in zip(w, X)) - sx * sx
+                falls.append(2.0 * num / den)
+        counts = [len(s) for s in per_station]
+        painted = [i for i, cnt in enumerate(counts) if cnt]
+        stripes = None
+        if painted:
+            freq = {}
+            for i in painted:
+                freq[counts[i]] = freq.get(counts[i], 0) + 1
+            stripes = min(freq, key=lambda cnt: (-freq[cnt], cnt))
+        typical = [per_station[i] for i in painted if counts[i] == stripes]
+        centre = lambda s: 0.5 * (s[0][0] + s[-1][1])
+        out.append({'stations': len(painted), 'stripes': stripes, 'double': stripes == 2,
+                    'width': _median([b - a for s in typical for a, b in s]),
+                    'separation': _median([s[1][0] - s[0][1] for s in typical]) if stripes == 2 else None,
+                    'extent': _median([s[-1][1] - s[0][0] for s in typical]),
+                    'offset': _median([centre(s) for s in typical]),
+                    'crossfall': _median(falls),
+                    'centres': [centre(s) if s else None for s in per_station],
+                    'counts': counts})
+    return out
+
+
+def snap_lines(lines, summary, bin_start, cross):
+    """Lines (list of [n, >= 2] float64 arrays, as cross_files took them) moved onto their paint: -> a list of arrays of the same shapes.
+    A vertex at station s_v (the arc length in the plane up to it, float64) moves along its left normal by the median centre
+    (cross_summary's `centres`) of the stations that qualify: painted, with the line's stripe count, their bin midpoint (i + 1/2) bin within
+    smooth / 2 of s_v.  The normal is the normalised sum of the unit left normals (-dy, dx) / len of the nearest segment of non-zero
+    length on either side of the vertex.  With fewer than min_stations such stations, a shift beyond max_shift (an outlier, not a clamp)
+    or no normal the vertex stays.  Only x and y change."""
+    if not isinstance(cross, CrossSection):
+        raise TypeError(f'snap_lines: cross must be a las_io.CrossSection, not {type(cross).__name__}')
+    lines, bs = list(lines), np.asarray(bin_start, dtype=np.int64)
+    if len(summary) != len(lines) or len(bs) != len(lines) + 1:
+        raise ValueError(f'snap_lines: {len(lines)} lines, {len(summary)} summaries and a bin_start of {len(bs)} entries do not belong together')
+    out = []
+    for line, m, nb in zip(lines, summary, np.diff(bs)):
+        new = np.array(line, dtype=np.float64, copy=True)
+        if len(m['centres']) != nb:
+            raise ValueError(f"snap_lines: a line of {int(nb)} bins with {len(m['centres'])} centres")
+        if len(new) >= 2 and m['stripes'] is not None:
+            d = np.diff(new[:, :2], axis=0)
+            seg_len = np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1])
+            s_v = np.concatenate([[0.0], np.add.accumulate(seg_len)])
+            good = [((i + 0.5) * cross.bin, c) for i, (c, cnt) in enumerate(zip(m['centres'], m['counts'])) if c is not None and cnt == m['stripes']]
+            for v in range(len(new)):
+                near = [c for mid, c in good if abs(mid - s_v[v]) <= 0.5 * cross.smooth]
+                if len(near) < cross.min_stations:
+                    continue
+                shift = _median(near)
+                if abs(shift) > cross.max_shift:
+                    continue
+                nx = ny = 0.0
+                before = [j for j in range(v - 1, -1, -1) if seg_len[j] > 0][:1]
+                after = [j for j in range(v, len(seg_len)) if seg_len[j] > 0][:1]
+                for j in before + after:
+                    nx, ny = nx - d[j, 1] / seg_len[j], ny + d[j, 0] / seg_len[j]
+                norm = math.sqrt(nx * nx + ny * ny)
+                if norm > 0.0:
+                    new[v, 0], new[v, 1] = line[v][0] + shift * nx / norm, line[v][1] + shift * ny / norm
+        out.append(new)
     return out
 
 

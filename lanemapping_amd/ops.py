@@ -867,6 +867,48 @@ def _profile_out(who, stations, out, device):
     return out
 
 
+def cross_cells(half_width, lateral_q):
+    """-> (hq, nl) of the cross-section rule (include/lanemap_hip.h): hq = ceil(float32(half_width) * 1024) and the nl = 2 hq // lateral_q
+    + 1 lateral cells of a station bin."""
+    import numpy as np
+    if isinstance(lateral_q, bool) or not isinstance(lateral_q, (int, np.integer)) or int(lateral_q) < 1:
+        raise ValueError(f'cross_cells: lateral_q={lateral_q!r} must be a whole number >= 1 (the cell width in 1/1024 m)')
+    hq = int(math.ceil(float(np.float32(half_width)) * 1024.0))
+    return hq, 2 * hq // int(lateral_q) + 1
+
+
+def _cross_out(who, stations, nl, out, device):
+    if out is None:
+        return torch.empty((stations.n_bins, nl, 4), device=device, dtype=torch.int64)
+    if tuple(out.shape) != (stations.n_bins, nl, 4) or out.dtype != torch.int64 or not out.is_contiguous() or out.device != device:
+        raise ValueError(f'{who}: out must be a contiguous [{stations.n_bins},{nl},4] int64 tensor on {device}')
+    return out
+
+
+def line_cross(points, index, stations, z_tol, lateral_q, paint_iq, out=None):
+    """points [N,4] f32 on device -> cells [n_bins, nl, 4] int64 on device: per station bin of every line a row of nl lateral cells, each
+    n, n_paint, sum iq, sum zq over the returns the labelling rule gives that line without a min_intensity (the rule:
+    include/lanemap_hip.h; cell c covers the offsets [(c lateral_q - hq) / 1024, ((c + 1) lateral_q - hq) / 1024) m, left positive; a
+    return is paint when its intensity, rounded into 0..65535, is at least paint_iq; zq its height above the line in 1/1024 m); an empty
+    cell reads four zeros.  index: the ops.LineIndex, stations: the ops.LineStations of the same segments.  out: the cells of an earlier
+    call to add to.  Integer sums only: the same bits whatever the order of the points.  No synchronisation."""
+    if not points.is_cuda:
+        raise LanemapHipError('lanemapping_amd ops need tensors on an MI355X (HIP) device; no CPU fallback exists')
+    assert points.dim() == 2 and points.shape[1] == 4 and points.is_contiguous() and points.dtype == torch.float32
+    if not isinstance(index, LineIndex):
+        raise TypeError(f'line_cross: index must be an ops.LineIndex (ops.line_index), not {type(index).__name__}')
+    if not isinstance(stations, LineStations):
+        raise TypeError(f'line_cross: stations must be an ops.LineStations (ops.line_stations), not {type(stations).__name__}')
+    if stations.n_segments != index.n_segments:
+        raise ValueError(f'line_cross: stations hold {stations.n_segments} rows, the index {index.n_segments} segments')
+    hq, nl = cross_cells(index.half_width, lateral_q)
+    cells = _cross_out('line_cross', stations, nl, out, points.device)
+    N, n_cells = int(points.shape[0]), stations.n_bins * nl
+    check(lib().lm_line_cross_points(_stream(), _ptr(points) if N else None, N, *index.args(), *stations.args(), float(z_tol), int(lateral_q),
+                                     int(paint_iq), int(out is not None), _ptr(cells) if n_cells else None, n_cells))
+    return cells
+
+
 RESIDUE_MAX_SIDE, RESIDUE_MAX_CELLS = 1 << 20, 1 << 22
 STATS_COLUMNS = ('n_cells', 'n_points', 'sum_iq', 'sum_cx', 'sum_cy', 'sum_cx2', 'sum_cxcy', 'sum_cy2', 'min_cx', 'max_cx', 'min_cy', 'max_cy')
 

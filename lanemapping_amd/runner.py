@@ -304,6 +304,7 @@ class Runner:
     _las_survey = functools.partialmethod(_las_option, 'survey', 'las_survey', 'MarkingSurvey')            # the marking profile
     _las_colour = functools.partialmethod(_las_option, 'colour', 'las_colour', 'MarkingColour')            # white or yellow, beside the profile
     _las_residue = functools.partialmethod(_las_option, 'residue', 'las_residue', 'PaintResidue')          # the paint no line explains
+    _las_cross = functools.partialmethod(_las_option, 'cross', 'las_cross', 'CrossSection')                # cross-sections, the snapped lines
 
     @staticmethod
     def _colour_plan(colour, survey, paths):
@@ -388,8 +389,36 @@ class Runner:
         with open(os.path.join(par_dir, 'markings.json'), 'w') as f:
             json.dump({str(k + 1): m for k, m in enumerate(summary)}, f, indent=1)
 
+    def _cross_inputs(self, cross, files, result, out_dir):
+        """The stage after `survey`: the cross-section table of the lines the call returns (the same lines as _survey_inputs takes) from
+        every input file (files: (path, shift, select) in input order, a file listed several times is used once): one
+        lm_las_line_cross_records call per file into one table, one read-back (las_io.cross_files).  The raw table goes to
+        <out_dir>/params/cross_sections.npy ([n_bins, nl, 4] int64), what las_io.cross_summary reads off it to cross_sections.json as
+        {line number: summary}, and the lines moved onto their paint (las_io.snap_lines) to
+        <out_dir>/out_pc_seq_json_dir/merged_snapped.txt and merged_snapped_downsample.txt, in the format of merged.txt.  Without lines
+        all four are empty."""
+        from . import las_io, merge_lines as ml
+        lines3d, merged = result
+        lines = list(merged) if len(merged) else [l for name in sorted(lines3d) for l in lines3d[name]]
+        seen, once = set(), []
+        for path, shift, select in files:
+            if os.path.realpath(path) not in seen:
+                seen.add(os.path.realpath(path))
+                once.append((path, shift, select))
+        cells, bin_start = las_io.cross_files(once, lines, cross, device=self.device)
+        summary = las_io.cross_summary(cells, bin_start, cross)
+        snapped = las_io.snap_lines(lines, summary, bin_start, cross)
+        par_dir = self._params_dir(out_dir)
+        np.save(os.path.join(par_dir, 'cross_sections.npy'), cells)
+        with open(os.path.join(par_dir, 'cross_sections.json'), 'w') as f:
+            json.dump({str(k + 1): m for k, m in enumerate(summary)}, f, indent=1)
+        pc_dir = os.path.join(out_dir, 'out_pc_seq_json_dir')
+        os.makedirs(pc_dir, exist_ok=True)
+        io_utils.save_seqs_list(snapped, os.path.join(pc_dir, 'merged_snapped.txt'))
+        io_utils.save_seqs_list([ml.downsample_seqs(m) for m in snapped if m.shape[0] >= 2], os.path.join(pc_dir, 'merged_snapped_downsample.txt'))
+
     def _residue_inputs(self, residue, files, result, out_dir):
-        """The stage after `survey`: the paint that none of the lines the call returns explains (the same lines as _survey_inputs takes),
+        """The stage after `survey` and `cross`: the paint that none of the lines the call returns explains (the same lines as _survey_inputs takes),
         from every input file (files: (path, shift, select) in input order, a file listed several times is used once): one
         ops.paint_residue call over all files, one read-back (las_io.residue_files).  The raw statistics go to
         <out_dir>/params/residue.npy ([K,12] int64), the cells to residue_cells.npy ([M,3] int32: cx, cy, component) and what
@@ -479,7 +508,7 @@ class Runner:
         return raster_batch(names, plist, points, offs, rpar, scales)
 
     def infer_las_to_map(self, las_and_params, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None, ground=None,
-                         intensity=None, elevation=None, density=None, label=None, survey=None, colour=None, residue=None):
+                         intensity=None, elevation=None, density=None, label=None, survey=None, colour=None, residue=None, cross=None):
         """LAS tiles -> map-level 3-D lane lines, every stage of the reference's offline chain on this stack:
 
           LAS file + tile parameter file (utils/io_utils.py:125-150)
@@ -534,6 +563,15 @@ class Runner:
         gets the keys of las_io.marking_colours: coloured, yellow, black, rgb, colour ('white', 'yellow' or 'unknown') and run_colours.
         Refused with a ValueError before anything runs: colour without survey; an input file of a point format without R, G, B (0, 1,
         4, 6, 9).  The return value does not change.
+        cross: a las_io.CrossSection (default: cfg['las_cross'], a dict of its arguments; absent: nothing changes, file for file and call
+        for call): after `survey` / `colour` and before `residue`, the lines the call returns get a cross-section table from every input
+        file, each read once with its own las_read_offset and `select` (one lm_las_line_cross_records call per file into one table, one
+        read-back): per station bin along every line a row of lateral cells holding the count, the paint count, the summed intensity
+        and the summed height of ALL returns of the band.  The table is written to <work_dirs>/params/cross_sections.npy ([n_bins, nl, 4]
+        int64), what las_io.cross_summary reads off it - stripes, double, width, separation, extent, offset, crossfall, the centre per
+        station - to cross_sections.json as {line number: summary}, and the lines moved onto their paint (las_io.snap_lines) to
+        out_pc_seq_json_dir/merged_snapped.txt and merged_snapped_downsample.txt in the format of merged.txt.  With no lines found the
+        files are written empty.  The return value and every other output do not change.
         residue: a las_io.PaintResidue (default: cfg['las_residue'], a dict of its arguments; absent: nothing changes): last of all, the
         paint that none of the lines the call returns explains - stop bars, crossing bars, arrows, hatching, a missed line.  Every input
         file is read once with its `select`; the returns at or above residue.min_intensity that lie within `reach` and `z_tol` of a line
@@ -542,12 +580,13 @@ class Runner:
         residue_cells.npy ([M,3] int32: cx, cy, blob) and what las_io.residue_summary reads off them - centre, area, length, width, fill,
         heading and shape against the nearest line - to residue.json as {blob number from 1: summary}.  With no lines found the three
         files are written empty.  The grid lives in the frame of the first file's las_read_offset.  The return value does not change.
-        Order of the stages: select, (binning,) ground, intensity, rasteriser, density, network, elevation, (merge,) label, survey, residue.
+        Order of the stages: select, (binning,) ground, intensity, rasteriser, density, network, elevation, (merge,) label, survey, cross, residue.
         Single rank (the merge is sequential over the sorted tiles)."""
         from . import las_io
         select, ground, intensity = self._las_select(select), self._las_ground(ground), self._las_intensity(intensity)
         elevation, density, label = self._las_elevation(elevation), self._las_density(density), self._las_label(label)
         survey, colour, residue = self._las_survey(survey), self._las_colour(colour), self._las_residue(residue)
+        cross = self._las_cross(cross)
         if label is not None:
             self._label_plan([p for p, _ in las_and_params])              # (a basename collision is refused before anything runs)
         self._colour_plan(colour, survey, [p for p, _ in las_and_params])
@@ -583,6 +622,8 @@ class Runner:
             self._label_inputs(label, inputs, result, out_dir)
         if survey is not None:
             self._survey_inputs(survey, inputs, result, out_dir, colour)
+        if cross is not None:
+            self._cross_inputs(cross, inputs, result, out_dir)
         if residue is not None:
             self._residue_inputs(residue, inputs, result, out_dir)
         return result
@@ -724,7 +765,7 @@ class Runner:
         return names, plist
 
     def infer_las_strip_to_map(self, las_paths, param_paths, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None,
-                               ground=None, intensity=None, elevation=None, density=None, label=None, survey=None, colour=None, residue=None):
+                               ground=None, intensity=None, elevation=None, density=None, label=None, survey=None, colour=None, residue=None, cross=None):
         """A whole strip -> map-level lane lines: the LAS file(s) of the strip are read once, their points are binned into the tiles of
         the layout on the GPU (ops.strip_bin_points: the windows of `param_paths` may overlap and be rotated), and every batch of tiles
         then runs the chain of infer_las_to_map from the rasteriser on.  Same outputs under the same names; a tile is named by the
@@ -740,6 +781,7 @@ class Runner:
         label: as for infer_las_to_map, after the merge: every file of `las_paths` is labelled with the layout's las_read_offset and `select`.
         survey: as for infer_las_to_map, last: every file of `las_paths` is surveyed with the layout's las_read_offset and `select`.
         colour: as for infer_las_to_map, in the survey's pass over the files of `las_paths`.
+        cross: as for infer_las_to_map, after the survey: every file of `las_paths` is read with the layout's las_read_offset and `select`.
         residue: as for infer_las_to_map, last of all: every file of `las_paths` is read with the layout's las_read_offset and `select`."""
         from . import las_io
         if isinstance(las_paths, (str, os.PathLike)):
@@ -748,6 +790,7 @@ class Runner:
         select, ground, intensity = self._las_select(select), self._las_ground(ground), self._las_intensity(intensity)
         elevation, density, label = self._las_elevation(elevation), self._las_density(density), self._las_label(label)
         survey, colour, residue = self._las_survey(survey), self._las_colour(colour), self._las_residue(residue)
+        cross = self._las_cross(cross)
         if label is not None:
             self._label_plan(las_paths)                                    # (a basename collision is refused before anything runs)
         self._colour_plan(colour, survey, las_paths)
@@ -785,6 +828,8 @@ class Runner:
             self._label_inputs(label, [(path, plist[0]['las_read_offset'], select) for path in las_paths], result, out_dir)
         if survey is not None and plist:
             self._survey_inputs(survey, [(path, plist[0]['las_read_offset'], select) for path in las_paths], result, out_dir, colour)
+        if cross is not None and plist:
+            self._cross_inputs(cross, [(path, plist[0]['las_read_offset'], select) for path in las_paths], result, out_dir)
         if residue is not None and plist:
             self._residue_inputs(residue, [(path, plist[0]['las_read_offset'], select) for path in las_paths], result, out_dir)
         return result
