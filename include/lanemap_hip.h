@@ -7,6 +7,11 @@
  *   - launches on the hipStream_t passed as `stream` (NULL = default stream) and returns immediately;
  *   - returns 0 on success, non-zero on error (lm_last_error() gives the message; nothing is thrown);
  *   - borrows its inputs (const), never frees or allocates caller-visible memory.
+ * Streams and graphs: an entry enqueues on `stream` and on no other stream.  Every entry may be captured into a HIP graph (after one
+ * eager call of the same shape) except lm_strip_bin_points, lm_tile_ground, lm_ground_select, lm_tile_intensity_window and
+ * lm_drape_vertices, which copy host memory of the call to the device or synchronise the stream: on a capturing stream they return
+ * LM_ERR_ARG with their name and the reason before touching it, and the capture stays valid.  Measured: tests/test_gpu_streams.py
+ * (single-stream captures, three replays each; captures with parallel branches were not measured).
  * Activations are fp32, NHWC ("pixel-major rows", channel stride 1); `ld*` = floats between consecutive pixels.
  * Citations are file:line in the reference (relative to its repo root).
  */

@@ -37,6 +37,31 @@ int lm_ensure_dynamic_lds(const void* kernel, size_t bytes);   // per device and
 
 #define LM_LAUNCH_CHECK() LM_HIP(hipGetLastError())
 
+// Streams and graphs.  An entry enqueues on the stream it is given and on nothing else.  One that only launches kernels and enqueues
+// device-to-device copies may be captured into a HIP graph; it zeroes with lm_zero_async below, never with hipMemsetAsync (captured
+// memset nodes replay wrongly).  One that copies call-local HOST memory to the device
+// (a captured copy node would keep the address of memory that the next call overwrites) or synchronises the stream (which invalidates
+// a capture) must not be: LM_NO_CAPTURE is its FIRST statement, before anything touches the stream.  Anything but "not capturing" - a
+// failed query included - is LM_ERR_ARG with the entry's name and the reason; the capture itself stays valid.
+static inline int lm_refuse_capture(void* stream, const char* who, const char* why) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusActive;
+    const hipError_t e = hipStreamIsCapturing((hipStream_t)stream, &st);
+    if (e == hipSuccess && st == hipStreamCaptureStatusNone) return LM_OK;
+    (void)hipGetLastError();                 // the failed query must not surface at a later launch check
+    if (e != hipSuccess)
+        lm_set_error("%s: must not be called while a stream is being captured (%s); the capture status of its stream could not be queried: %s",
+                     who, why, hipGetErrorString(e));
+    else
+        lm_set_error("%s: must not be called on a stream that is being captured into a graph: %s", who, why);
+    return LM_ERR_ARG;
+}
+#define LM_NO_CAPTURE(stream, who, why)                                  \
+    do {                                                                 \
+        if (int nc_ = lm_refuse_capture((stream), (who), (why))) return nc_; \
+    } while (0)
+#define LM_WHY_HOST_COPY "it copies call-local host memory to the device"
+#define LM_WHY_HOST_COPY_SYNC "it copies call-local host memory to the device and synchronises the stream"
+
 static inline int lm_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 static inline long lm_cdivl(long a, long b) { return (a + b - 1) / b; }
 static inline size_t lm_align256(size_t v) { return (v + 255) / 256 * 256; }   // workspace segments start on 256 bytes
@@ -45,6 +70,30 @@ static inline size_t lm_align256(size_t v) { return (v + 255) / 256 * 256; }   /
 enum { LM_ACT_NONE = 0, LM_ACT_RELU = 1, LM_ACT_GELU = 2 };
 
 #ifdef __HIPCC__
+// Zeroing inside an entry that may be captured: a kernel, never hipMemsetAsync.  Replays of a captured memset node were seen to leave
+// what the previous replay had put there, or to write other bytes than zeros (tests/test_gpu_streams.py: the replays of
+// lm_rowref_decode, lm_tile_gap_hist, lm_sparse_conv_outputs, lm_sparse_to_dense_nhwc and lm_las_label_records over outputs
+// pre-filled with 0xFF); a kernel node replays like every other launch.  Any address, any byte count: 16-byte stores over the
+// aligned middle, single bytes before and behind it.
+namespace {
+__global__ __launch_bounds__(256) __attribute__((unused)) void lm_zero_kernel(unsigned char* __restrict__ p, size_t head, size_t n16,
+                                                                               size_t tail) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n16) reinterpret_cast<uint4*>(p + head)[i] = make_uint4(0u, 0u, 0u, 0u);
+    if (i < head) p[i] = 0;
+    if (i < tail) p[head + 16 * n16 + i] = 0;
+}
+}  // namespace
+static inline __attribute__((unused)) hipError_t lm_zero_async(void* ptr, size_t bytes, hipStream_t s) {
+    if (bytes == 0) return hipSuccess;
+    unsigned char* p = (unsigned char*)ptr;
+    size_t head = (16 - ((uintptr_t)p & 15)) & 15;
+    if (head > bytes) head = bytes;
+    const size_t n16 = (bytes - head) / 16, tail = bytes - head - 16 * n16;         // head + 16 n16 + tail == bytes, head, tail < 16
+    const size_t threads = n16 > 16 ? n16 : 16;
+    hipLaunchKernelGGL(lm_zero_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, p, head, n16, tail);
+    return hipGetLastError();
+}
 // GroupNorm(C,C) + ReLU + bilinear (align_corners=True) building blocks with a FIXED operation order: `#pragma clang fp contract(off)`
 // keeps the compiler from fusing their multiplies and adds differently in different kernels (HIP's __fmul_rn / __fadd_rn are plain
 // operators and do not prevent that), explicit fmaf where a fused multiply-add is wanted.  The same bits in every kernel that uses

@@ -194,11 +194,6 @@ __device__ void pick_bin_block(const unsigned* h, unsigned& need, unsigned& bin,
     __syncthreads();
 }
 
-__global__ __launch_bounds__(256) void zero_u32_kernel(unsigned* __restrict__ p, long n) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) p[i] = 0u;
-}
-
 template <int LEVEL>   // 0,1,2 = histogram passes; 3 = candidate compaction
 __global__ __launch_bounds__(256) void topk_pass_kernel(TopkParams p) {
     __shared__ unsigned lh[NB];
@@ -410,10 +405,8 @@ LM_API int lm_endp_topk(void* stream, const float* endp_logit, void* workspace, 
     LM_REQUIRE(W > 2 * clip && H > 2 * clip && (long)(H - 2 * clip) * (W - 2 * clip) < (1L << 31), "endp_topk: bad crop (H=%d W=%d clip=%d)", H, W, clip);
     p.div_wc = lm_fastdiv_make((unsigned)(W - 2 * clip));
     // (a kernel, not hipMemsetAsync: the call sits inside HIP-graph captures of the tile pipeline, and replays of a captured memset
-    // node were observed to leave the histograms of the previous replay in place)
-    const long zero_words = (long)B * (3 * NB + 4);
-    hipLaunchKernelGGL(zero_u32_kernel, dim3(lm_cdiv(zero_words, 256)), dim3(256), 0, s, (unsigned*)workspace, zero_words);
-    LM_LAUNCH_CHECK();
+    // node were observed to leave the histograms of the previous replay in place - lm_zero_async, common.h)
+    LM_HIP(lm_zero_async(workspace, (size_t)B * (3 * NB + 4) * sizeof(unsigned), s));
     dim3 grid(256, B);
     hipLaunchKernelGGL(topk_pass_kernel<0>, grid, dim3(256), 0, s, p);
     LM_LAUNCH_CHECK();

@@ -129,10 +129,12 @@ LM_API long lm_drape_workspace_bytes(long n_vertices, int B, int radius_px) {
 }
 
 // points: device [sum N][4]; tile_offsets: HOST [B+1]; params: HOST [B]; vertices_rc: HOST [V][2] (row, col); vertex_offsets: HOST [B+1],
-// vertex_offsets[0] = 0, V = vertex_offsets[B]; z [V] f32, npix [V] i32, pixel_min [V][(2R+1)^2] f32 or NULL: device.  Asynchronous.
+// vertex_offsets[0] = 0, V = vertex_offsets[B]; z [V] f32, npix [V] i32, pixel_min [V][(2R+1)^2] f32 or NULL: device.  Asynchronous, but
+// copies host memory of this call to the device: refuses a capturing stream (common.h).
 LM_API int lm_drape_vertices(void* hip_stream, const float* points_xyzi, const long* tile_offsets, const LmRasterParams* params, int B, int H,
                              int W, const int* vertices_rc, const long* vertex_offsets, int radius_px, void* workspace, long workspace_bytes,
                              float* z, int* npix, float* pixel_min) {
+    LM_NO_CAPTURE(hip_stream, "drape_vertices", LM_WHY_HOST_COPY);
     static thread_local std::vector<DrapeTile> h_tiles;
     static thread_local std::vector<DrapeEntry> h_entries;
     static thread_local std::vector<int> h_fill;

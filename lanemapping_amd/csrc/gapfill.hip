@@ -231,7 +231,7 @@ LM_API int lm_tile_gap_hist(void* hip_stream, const unsigned char* tiles_hwc_u8,
     LM_REQUIRE(max_radius_px >= 1 && max_radius_px <= MAX_R, "tile_gap_hist: max_radius_px=%d, 1 to %d are supported", max_radius_px, MAX_R);
     LM_REQUIRE(hist, "tile_gap_hist: null pointer (hist)");
     hipStream_t s = (hipStream_t)hip_stream;
-    LM_HIP(hipMemsetAsync(hist, 0, (size_t)B * (size_t)(max_radius_px + 2) * sizeof(unsigned), s));
+    LM_HIP(lm_zero_async(hist, (size_t)B * (size_t)(max_radius_px + 2) * sizeof(unsigned), s));
     return launch<true>(s, tiles_hwc_u8, B, H, W, nullptr, max_radius_px, hist, max_radius_px + 2, nullptr);
 }
 

@@ -204,9 +204,10 @@ LM_API long lm_tile_ground_workspace_bytes(int B, int H, int W, int cell_px) {
 }
 
 // points: device [sum N][4]; tile_offsets: HOST [B+1]; params: HOST [B]; ground [B][Gy][Gx], ground_min [B], cell_min [B][Gy][Gx] or NULL:
-// device f32.  Asynchronous.
+// device f32.  Asynchronous, but copies host memory of this call to the device: refuses a capturing stream (common.h).
 LM_API int lm_tile_ground(void* hip_stream, const float* points_xyzi, const long* tile_offsets, const LmRasterParams* params, int B, int H,
                           int W, int cell_px, void* workspace, long workspace_bytes, float* ground, float* ground_min, float* cell_min) {
+    LM_NO_CAPTURE(hip_stream, "tile_ground", LM_WHY_HOST_COPY);
     static thread_local std::vector<GroundTile> h_tiles;
     long n_wg, n_blocks, N;
     if (int e = derive_tiles("tile_ground", tile_offsets, params, B, H, W, cell_px, GCHUNK, h_tiles, &n_wg, &n_blocks, &N)) return e;
@@ -245,6 +246,7 @@ LM_API long lm_ground_select_workspace_bytes(long N, int B) {
 LM_API int lm_ground_select(void* hip_stream, const float* points_xyzi, const long* tile_offsets, const LmRasterParams* params, int B, int H,
                             int W, int cell_px, const float* ground, float h_lo, float h_hi, void* workspace, long workspace_bytes,
                             float* points_out, long* out_offsets, long* out_offsets_host) {
+    LM_NO_CAPTURE(hip_stream, "ground_select", LM_WHY_HOST_COPY_SYNC);
     static thread_local std::vector<GroundTile> h_tiles;
     long n_wg, n_blocks, N;
     if (int e = derive_tiles("ground_select", tile_offsets, params, B, H, W, cell_px, SEL_CHUNK, h_tiles, &n_wg, &n_blocks, &N)) return e;

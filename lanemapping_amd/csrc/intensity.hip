@@ -188,10 +188,12 @@ LM_API long lm_tile_intensity_workspace_bytes(int B, int G) {
 }
 
 // points: device [sum N][4]; tile_offsets: HOST [B+1]; params: HOST [B]; group: HOST [B] or NULL; window [G][2] int32, count [G] int64,
-// coarse_hist [G][4096] u32 or NULL: device.  Asynchronous.
+// coarse_hist [G][4096] u32 or NULL: device.  Asynchronous, but copies host memory of this call to the device: refuses a capturing
+// stream (common.h).
 LM_API int lm_tile_intensity_window(void* hip_stream, const float* points_xyzi, const long* tile_offsets, const LmRasterParams* params, int B,
                                     int H, int W, const int* group, int G, int q_lo_ppm, int q_hi_ppm, void* workspace,
                                     long workspace_bytes, int* window, long* count, unsigned* coarse_hist) {
+    LM_NO_CAPTURE(hip_stream, "tile_intensity_window", LM_WHY_HOST_COPY);
     static thread_local std::vector<IntenTile> h_tiles;
     LM_REQUIRE(B >= 1 && B <= LM_MAX_TILES, "tile_intensity_window: B=%d tiles, 1 to %d are supported", B, LM_MAX_TILES);   // G is judged against it
     LM_REQUIRE(G >= 1 && G <= B, "tile_intensity_window: G=%d groups, 1 to B=%d are supported", G, B);

@@ -327,7 +327,7 @@ LM_API int lm_las_label_records(void* hip_stream, const unsigned char* records, 
     long resident = 0;
     if (n > 0)
         if (int e = resident_groups(lds, resident)) return e;
-    if (counts) LM_HIP(hipMemsetAsync(counts, 0, ((size_t)L + 1) * sizeof(unsigned long), s));
+    if (counts) LM_HIP(lm_zero_async(counts, ((size_t)L + 1) * sizeof(unsigned long), s));
     if (n == 0) return LM_OK;
     const double sh[3] = {shift ? shift[0] : 0.0, shift ? shift[1] : 0.0, shift ? shift[2] : 0.0};
     const LasXf X{scale[0], scale[1], scale[2], offset[0] - sh[0], offset[1] - sh[1], offset[2] - sh[2], 0.f, 1.f, 0};   // raw intensity

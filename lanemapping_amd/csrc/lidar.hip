@@ -299,7 +299,7 @@ LM_API int lm_voxelize_hard(void* stream, const float* points, long n, const flo
     hipStream_t s = (hipStream_t)stream;
     if (n == 0) {   // no points: the sample contributes no rows
         if (row_base) LM_HIP(hipMemcpyAsync(row_end, row_base, sizeof(int), hipMemcpyDeviceToDevice, s));
-        else LM_HIP(hipMemsetAsync(row_end, 0, sizeof(int), s));
+        else LM_HIP(lm_zero_async(row_end, sizeof(int), s));
         return LM_OK;
     }
     VoxGeom G;
@@ -392,7 +392,7 @@ LM_API int lm_sparse_conv_outputs(void* stream, const int* in_coords, long n_in,
     size_t tb = scan_temp_bytes(cells);
     hipStream_t s = (hipStream_t)stream;
     const Grid3 go{B, Do, Ho, Wo};
-    LM_HIP(hipMemsetAsync(flags, 0, (size_t)cells * 4, s));
+    LM_HIP(lm_zero_async(flags, (size_t)cells * 4, s));
     hipLaunchKernelGGL(conv_mark_kernel, dim3(lm_cdiv(n_in, 256)), dim3(256), 0, s, in_coords, n_in, cv, go, flags);
     LM_LAUNCH_CHECK();
     {
@@ -428,7 +428,7 @@ LM_API int lm_sparse_to_dense_nhwc(void* stream, const float* feats, int ldf, co
                                    int H, int W, int C, int flip_h) {
     LM_REQUIRE(out && (n == 0 || (feats && coords)) && ldf >= C && C > 0, "sparse_to_dense: bad args");
     hipStream_t s = (hipStream_t)stream;
-    LM_HIP(hipMemsetAsync(out, 0, (size_t)B * D * H * W * C * sizeof(float), s));
+    LM_HIP(lm_zero_async(out, (size_t)B * D * H * W * C * sizeof(float), s));
     if (n > 0) {
         hipLaunchKernelGGL(densify_kernel, dim3(lm_cdiv(n, 4)), dim3(256), 0, s, feats, ldf, coords, n, Grid3{B, D, H, W}, C, flip_h, out);
         LM_LAUNCH_CHECK();
@@ -667,8 +667,8 @@ LM_API int lm_las_decode_select(void* hip_stream, const unsigned char* records, 
                lm_las_select_workspace_bytes(n));
     hipStream_t s = (hipStream_t)hip_stream;
     if (n == 0) {
-        LM_HIP(hipMemsetAsync(kept, 0, sizeof(long), s));
-        if (class_hist) LM_HIP(hipMemsetAsync(class_hist, 0, 256 * sizeof(unsigned long), s));
+        LM_HIP(lm_zero_async(kept, sizeof(long), s));
+        if (class_hist) LM_HIP(lm_zero_async(class_hist, 256 * sizeof(unsigned long), s));
         return LM_OK;
     }
     const double sh[3] = {shift ? shift[0] : 0.0, shift ? shift[1] : 0.0, shift ? shift[2] : 0.0};

@@ -293,7 +293,7 @@ LM_API int lm_cell_components(void* hip_stream, const long* keys, long M, int nx
     LM_REQUIRE(((uintptr_t)root & 3) == 0, "cell_components: root is not 4-byte aligned");
     LM_REQUIRE(((uintptr_t)err & 3) == 0, "cell_components: err is not 4-byte aligned");
     hipStream_t s = (hipStream_t)hip_stream;
-    LM_HIP(hipMemsetAsync(err, 0, sizeof(int), s));
+    LM_HIP(lm_zero_async(err, sizeof(int), s));
     if (M == 0) return LM_OK;
     const dim3 groups((unsigned)lm_cdivl(M, 256));
     hipLaunchKernelGGL(components_init_kernel, groups, dim3(256), 0, s, root, (int)M);

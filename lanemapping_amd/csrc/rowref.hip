@@ -257,8 +257,8 @@ LM_API int lm_rowref_decode(void* stream, const float* ext2, const float* cls2, 
     // conf / cls_map (the reference's dense one-hot maps, :334-363) are optional: the tile pipeline only needs col_idx
     LM_REQUIRE(ext2 && cls2 && col_idx, "rowref_decode: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    if (conf) LM_HIP(hipMemsetAsync(conf, 0, (size_t)B * H * W, s));
-    if (cls_map) LM_HIP(hipMemsetAsync(cls_map, 0, (size_t)B * (L + 1) * H * W, s));
+    if (conf) LM_HIP(lm_zero_async(conf, (size_t)B * H * W, s));
+    if (cls_map) LM_HIP(lm_zero_async(cls_map, (size_t)B * (L + 1) * H * W, s));
     const long total = (long)B * L * H;
     hipLaunchKernelGGL(rowref_decode_kernel, dim3(lm_cdiv(total, 256)), dim3(256), 0, s, ext2, cls2, conf, cls_map, col_idx, H, W, L, total);
     LM_LAUNCH_CHECK();

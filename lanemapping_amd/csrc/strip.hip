@@ -328,10 +328,11 @@ LM_API long lm_strip_bin_workspace_bytes(long N, int T) {
 }
 
 // points: device [N][4]; params: HOST [T]; counts [T], offsets [T+1]: device int64; offsets_host: HOST [T+1] (may be NULL);
-// binned: device [capacity][4].  Synchronises the stream once (the total decides whether the scatter may run).
+// binned: device [capacity][4].  Synchronises the stream once (the total decides whether the scatter may run): refuses a capturing stream.
 LM_API int lm_strip_bin_points(void* hip_stream, const float* points_xyzi, long N, const LmRasterParams* params, int T, int H, int W,
                                double z_lo, double z_hi, void* workspace, long workspace_bytes, long* counts, long* offsets,
                                long* offsets_host, float* binned, long capacity) {
+    LM_NO_CAPTURE(hip_stream, "strip_bin", LM_WHY_HOST_COPY_SYNC);
     LM_REQUIRE(params && workspace && counts && offsets, "strip_bin: null pointer");
     LM_REQUIRE(T >= 1 && T <= MAX_T, "strip_bin: T=%d tiles, 1 to %d are supported", T, MAX_T);
     LM_REQUIRE(N >= 0 && N <= 2147483647L && capacity >= 0, "strip_bin: N=%ld points, at most 2^31 - 1 are supported", N);

@@ -1046,7 +1046,8 @@ def strip_bin_points(points, params, H=1152, W=1152, z_range=None, capacity=None
     ints): the points of tile 0, then tile 1, ... in cloud order, exactly those the rasteriser keeps for each tile - the
     (points, tile_offsets) pair bev_raster_batch takes.  z_range = (lo, hi) of the cloud (the LAS header's) bounds the lookup grid of
     tilted tiles; None: taken from the points when a tile is tilted (one more pass and sync).  One device-to-host read of the offsets;
-    if the first guess of the output size was short, one second call."""
+    if the first guess of the output size was short, one second call.  Not inside a graph capture (the entry refuses a capturing
+    stream by name)."""
     if not points.is_cuda:
         _ptr(points)
     assert points.dim() == 2 and points.shape[1] == 4 and points.is_contiguous() and points.dtype == torch.float32
@@ -1087,7 +1088,8 @@ def tile_ground(points, tile_offsets, params, H=1152, W=1152, cell_px=32, want_c
     -> (ground [B,Gy,Gx] f32, ground_min [B] f32) on the device, Gy = ceil(H / cell_px), Gx = ceil(W / cell_px).  A cell's raw value is
     the smallest tile-frame height vz of the points the rasteriser keeps for the tile in that cell; ground is the lower median of the
     non-empty cells of its 3 x 3 neighbourhood (NaN where all nine are empty), ground_min the tile's smallest finite ground (+inf: none).
-    want_cell_min: -> (ground, ground_min, cell_min [B,Gy,Gx]), the raw minima, NaN = empty.  No synchronisation."""
+    want_cell_min: -> (ground, ground_min, cell_min [B,Gy,Gx]), the raw minima, NaN = empty.  No synchronisation, but the tile table is
+    copied from host memory of the call: not inside a graph capture (the entry refuses a capturing stream by name)."""
     B, offs, par = _tile_range_args('tile_ground', points, tile_offsets, params)
     H, W, cell_px = int(H), int(W), int(cell_px)
     need = lib().lm_tile_ground_workspace_bytes(B, H, W, cell_px)
@@ -1106,7 +1108,8 @@ def ground_select(points, tile_offsets, params, ground, H=1152, W=1152, cell_px=
     """The points of every tile whose height above the tile's ground model lies in h_range = (lo, hi): kept <=> the rasteriser keeps the
     point for the tile, vz is finite and lo <= vz - ground[b, cell] <= hi (infinite bounds switch a side off).  -> (points_out
     [sum kept, 4], offsets: B+1 host ints) as strip_bin_points returns them: each tile's kept points in their input order, the pair
-    bev_raster_batch takes.  `ground` is tile_ground's for the same tiles, H, W and cell_px.  One device-to-host read of the offsets."""
+    bev_raster_batch takes.  `ground` is tile_ground's for the same tiles, H, W and cell_px.  One device-to-host read of the offsets: not
+    inside a graph capture (the entry refuses a capturing stream by name)."""
     B, offs, par = _tile_range_args('ground_select', points, tile_offsets, params)
     H, W, cell_px = int(H), int(W), int(cell_px)
     Gy, Gx = (-(-H // cell_px), -(-W // cell_px)) if cell_px > 0 else (0, 0)
@@ -1130,7 +1133,8 @@ def tile_intensity_window(points, tile_offsets, params, H=1152, W=1152, percenti
     hist [G,4096] int32 (the counted points per coarse bin key >> 4).  A point counts for a tile when the rasteriser keeps it for the
     tile and its intensity is not NaN; its key is floor(clamp(intensity, 0, 65535)).  With n counted points in a group, window[g] holds the
     keys of 0-based ranks (n - 1) * ppm // 10**6 in ascending order for ppm = round(p * 10**4) of the two percentiles; n = 0: (-1, -1).
-    group: B ints in 0..G-1 with G = max + 1 (None: every tile its own group).  Exact and reproducible.  No synchronisation."""
+    group: B ints in 0..G-1 with G = max + 1 (None: every tile its own group).  Exact and reproducible.  No synchronisation, but the
+    tile table is copied from host memory of the call: not inside a graph capture (the entry refuses a capturing stream by name)."""
     B, offs, par = _tile_range_args('tile_intensity_window', points, tile_offsets, params)
     H, W = int(H), int(W)
     if group is None:
@@ -1161,7 +1165,8 @@ def drape_vertices(points, tile_offsets, params, vertices, vertex_offsets, H=115
     takes: vertices [V,2] int32 host array of (row, col) pixels, tile 0's first; vertex_offsets: B+1 ints, vertex_offsets[0] = 0.
     -> (z [V] f32, npix [V] int32) on the device, with want_pixel_min also pixel_min [V, 2R+1, 2R+1] f32 (NaN = empty).  pixel_min[v, i, j]
     is the smallest tile-frame height vz of the points the rasteriser keeps for the vertex's tile in pixel (row + i - R, col + j - R), z[v]
-    the lower median of the npix[v] non-empty ones (NaN for none).  Exact and reproducible.  No synchronisation."""
+    the lower median of the npix[v] non-empty ones (NaN for none).  Exact and reproducible.  No synchronisation, but the tile and vertex
+    tables are copied from host memory of the call: not inside a graph capture (the entry refuses a capturing stream by name)."""
     import numpy as np
     B, offs, par = _tile_range_args('drape_vertices', points, tile_offsets, params)
     H, W, R = int(H), int(W), int(radius_px)

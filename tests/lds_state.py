@@ -114,6 +114,27 @@ _ACTIVE = None
 
 
 @contextlib.contextmanager
+def interposed(wrap):
+    """The one way the test harnesses get in front of the library: every stream-taking `lm_*` attribute of the library object that
+    lanemapping_amd._lib.lib() returns is replaced by wrap(fn, name) - on the object itself, so a handle taken before the context is
+    interposed like one taken inside it; only an ENTRY bound outside escapes - and put back on exit.  Users: poisoned() below (a fill
+    before each entry) and stream_state.watching() (which stream each entry was given)."""
+    from lanemapping_amd import _lib
+    real = _lib.lib()
+    saved = {name: (name in vars(real), getattr(real, name)) for name in stream_entries()}
+    for name, (_, fn) in saved.items():
+        setattr(real, name, wrap(fn, name))
+    try:
+        yield real
+    finally:
+        for name, (had, fn) in saved.items():
+            if had:
+                setattr(real, name, fn)
+            else:
+                delattr(real, name)
+
+
+@contextlib.contextmanager
 def poisoned(word):
     """Inside the context every stream-taking `lm_*` attribute of the library object that lanemapping_amd._lib.lib() returns enqueues the
     fill first.  The attributes are replaced on the object itself, so a library handle taken before the context (`L = lib()` at the top
@@ -121,30 +142,20 @@ def poisoned(word):
     no stream-taking entry at all, is an AssertionError on exit: a poisoned run that enqueued no fill proves nothing.  Yields the state
     (`.fills`).  Nested contexts give one fill per call, with the inner word."""
     global _ACTIVE
-    from lanemapping_amd import _lib
-    real = _lib.lib()
     outer = _ACTIVE
     state = _Poisoning(diag().lmd_lds_fill, word)
-    saved = None
-    if outer is None:
-        saved = {name: (name in vars(real), getattr(real, name)) for name in stream_entries()}
-        for name, (_, fn) in saved.items():
-            setattr(real, name, state.wrap(fn, name))
-    _ACTIVE = state
-    try:
-        yield state
-        assert state.fills > 0, ('no stream-taking lm_* entry was called through the library object inside poisoned(): nothing ran after '
-                                 'poisoned LDS (an entry bound outside the context bypasses it)')
-    finally:
-        _ACTIVE = outer
-        if outer is not None:
-            outer.fills += state.fills
-        else:
-            for name, (had, fn) in saved.items():
-                if had:
-                    setattr(real, name, fn)
-                else:
-                    delattr(real, name)
+    with contextlib.ExitStack() as stack:
+        if outer is None:
+            stack.enter_context(interposed(state.wrap))
+        _ACTIVE = state
+        try:
+            yield state
+            assert state.fills > 0, ('no stream-taking lm_* entry was called through the library object inside poisoned(): nothing ran after '
+                                     'poisoned LDS (an entry bound outside the context bypasses it)')
+        finally:
+            _ACTIVE = outer
+            if outer is not None:
+                outer.fills += state.fills
 
 
 def _bits(v):

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import lds_state
+import stream_state
 from lanemapping_amd import io_utils, ops, synth
 from lanemapping_amd._lib import LanemapHipError, LmRasterParams, lib
 
@@ -206,17 +207,14 @@ def test_bin_is_deterministic_also_beside_a_call_on_another_stream(dev):
     b2, o2 = ops.strip_bin_points(cloud, params, H, W, z_range=zr)
     assert o1 == o2 and torch.equal(b1.view(torch.int32), b2.view(torch.int32))
     other = torch.from_numpy(_cloud(62, 3_000_000, -5.0, 44.0 * 9 + 62.0, -15.0, 70.0)).to(dev)
-    side = torch.cuda.Stream(device=dev)
-    torch.cuda.synchronize(dev)
-    # the main stream is kept busy with rasterisations of another cloud while the side stream bins
     ob, oo = ops.strip_bin_points(other, params, H, W, z_range=zr)
-    for _ in range(4):
-        ops.bev_raster_batch(ob, oo, params, H, W)
-    with torch.cuda.stream(side):
-        b3, o3 = ops.strip_bin_points(cloud, params, H, W, z_range=zr)
-    side.synchronize()
-    torch.cuda.synchronize(dev)
-    assert o1 == o3 and torch.equal(b1.view(torch.int32), b3.view(torch.int32))
+    # off the default stream, which a blocker keeps busy meanwhile (tests/stream_state.py): the entry is given the side stream, its
+    # result has the same bits, and the call waits neither for the default stream nor for the device
+    def run(state):
+        b, o = ops.strip_bin_points(cloud, params, H, W, z_range=zr)
+        return {'binned': b.view(torch.int32), 'offsets': torch.tensor(o, dtype=torch.int64)}
+    got = stream_state.stream_runs(stream_state.Case('strip_bin 2M points', ['lm_strip_bin_points'], lambda d: {}, run, lambda state, k: None), dev)
+    assert got['offsets'].tolist() == o1 and torch.equal(got['binned'], b1.view(torch.int32).cpu())
     ob2, oo2 = ops.strip_bin_points(other, params, H, W, z_range=zr)
     assert oo == oo2 and torch.equal(ob.view(torch.int32), ob2.view(torch.int32))
 
