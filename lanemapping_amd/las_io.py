@@ -55,7 +55,42 @@ DROP_SYNTHETIC, DROP_KEYPOINT, DROP_WITHHELD, DROP_OVERLAP = 1, 2, 4, 8         
 RETURNS = {'all': 0, 'first': 1, 'last': 2, 'single': 3}                         # LM_LAS_RETURNS_*
 
 
-class PointFilter:
+def _number(v):
+    """A Python or numpy number, no bool: what an option that is a length, a ratio or an intensity takes."""
+    return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating))
+
+
+def _whole(v):
+    """A Python or numpy integer, no bool: what an option that is a count takes."""
+    return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+
+
+class _Options:
+    """What the option classes of this module share: a value that cannot be changed, compared, hashed and printed by the __slots__ of its
+    class, in their order.  A class validates its arguments in __init__ and stores them with _set."""
+    __slots__ = ()
+
+    def _set(self, **values):
+        for k, v in values.items():
+            object.__setattr__(self, k, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError(f'{type(self).__name__} is immutable')
+
+    def __delattr__(self, name):
+        raise AttributeError(f'{type(self).__name__} is immutable')
+
+    def __repr__(self):
+        return type(self).__name__ + '(' + ', '.join(f'{k}={getattr(self, k)!r}' for k in self.__slots__) + ')'
+
+    def __eq__(self, other):
+        return type(other) is type(self) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
+
+    def __hash__(self):
+        return hash(tuple(getattr(self, k) for k in self.__slots__))
+
+
+class PointFilter(_Options):
     """Which point records a reader keeps (immutable).  A record is kept when all of these hold:
 
       classes        its classification is one of `classes` (values 0..255; None: every class)
@@ -83,25 +118,8 @@ class PointFilter:
             if lo > hi:
                 raise ValueError(f'PointFilter: z_range={z_range!r} is empty (lo > hi)')
             z_range = (lo, hi)
-        for k, v in (('classes', classes), ('drop_withheld', bool(drop_withheld)), ('drop_synthetic', bool(drop_synthetic)),
-                     ('drop_keypoint', bool(drop_keypoint)), ('drop_overlap', bool(drop_overlap)), ('returns', returns),
-                     ('z_range', z_range)):
-            object.__setattr__(self, k, v)
-
-    def __setattr__(self, name, value):
-        raise AttributeError('PointFilter is immutable')
-
-    def __delattr__(self, name):
-        raise AttributeError('PointFilter is immutable')
-
-    def __repr__(self):
-        return 'PointFilter(' + ', '.join(f'{k}={getattr(self, k)!r}' for k in self.__slots__) + ')'
-
-    def __eq__(self, other):
-        return isinstance(other, PointFilter) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
-
-    def __hash__(self):
-        return hash(tuple(getattr(self, k) for k in self.__slots__))
+        self._set(classes=classes, drop_withheld=bool(drop_withheld), drop_synthetic=bool(drop_synthetic), drop_keypoint=bool(drop_keypoint),
+                  drop_overlap=bool(drop_overlap), returns=returns, z_range=z_range)
 
     def for_format(self, point_format):
         """-> self, after checking the filter against a file's point data record format: formats 0-5 store the classification in five
@@ -126,7 +144,7 @@ class PointFilter:
         return s
 
 
-class GroundFilter:
+class GroundFilter(_Options):
     """How the LAS -> map routes follow the terrain (immutable; Runner.infer_las_strip_to_map / infer_las_to_map, `ground=`).  Both parts
     rest on the per-tile ground model of ops.tile_ground: cells of cell_px x cell_px pixels, each the lower median over its 3 x 3
     neighbourhood of the cells' smallest tile-frame heights.
@@ -156,23 +174,7 @@ class GroundFilter:
         margin = float(datum_margin)
         if not (margin >= 0.0 and math.isfinite(margin)):
             raise ValueError(f'GroundFilter: datum_margin={datum_margin!r} must be a finite number >= 0')
-        for k, v in (('height_range', height_range), ('cell_px', int(cell_px)), ('datum', bool(datum)), ('datum_margin', margin)):
-            object.__setattr__(self, k, v)
-
-    def __setattr__(self, name, value):
-        raise AttributeError('GroundFilter is immutable')
-
-    def __delattr__(self, name):
-        raise AttributeError('GroundFilter is immutable')
-
-    def __repr__(self):
-        return 'GroundFilter(' + ', '.join(f'{k}={getattr(self, k)!r}' for k in self.__slots__) + ')'
-
-    def __eq__(self, other):
-        return isinstance(other, GroundFilter) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
-
-    def __hash__(self):
-        return hash(tuple(getattr(self, k) for k in self.__slots__))
+        self._set(height_range=height_range, cell_px=int(cell_px), datum=bool(datum), datum_margin=margin)
 
 
 def ground_datum(ground_min, ele_reso, margin, fallback):
@@ -186,7 +188,7 @@ def ground_datum(ground_min, ele_reso, margin, fallback):
     return math.floor((g - float(margin)) / float(ele_reso)) * float(ele_reso)
 
 
-class IntensityStretch:
+class IntensityStretch(_Options):
     """How the LAS -> map routes choose the rasteriser's intensity window (immutable; Runner.infer_las_strip_to_map / infer_las_to_map,
     `intensity=`).  The window is read off the data: two percentiles of the intensities of the points a tile keeps
     (ops.tile_intensity_window), stretched so that the upper one lands on `white` (intensity_window below).
@@ -223,24 +225,8 @@ class IntensityStretch:
             raise ValueError(f'IntensityStretch: fallback={fallback!r} must be a pair of numbers') from None
         if not (f_lo < f_hi < math.inf and f_hi > 0.0 and f_lo > -math.inf):
             raise ValueError(f'IntensityStretch: fallback={fallback!r} must be a finite window lo < hi with hi > 0')
-        for k, v in (('percentiles', (lo, hi)), ('scope', scope), ('white', float(white)), ('min_span', float(min_span)),
-                     ('min_points', int(min_points)), ('fallback', (f_lo, f_hi))):
-            object.__setattr__(self, k, v)
-
-    def __setattr__(self, name, value):
-        raise AttributeError('IntensityStretch is immutable')
-
-    def __delattr__(self, name):
-        raise AttributeError('IntensityStretch is immutable')
-
-    def __repr__(self):
-        return 'IntensityStretch(' + ', '.join(f'{k}={getattr(self, k)!r}' for k in self.__slots__) + ')'
-
-    def __eq__(self, other):
-        return isinstance(other, IntensityStretch) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
-
-    def __hash__(self):
-        return hash(tuple(getattr(self, k) for k in self.__slots__))
+        self._set(percentiles=(lo, hi), scope=scope, white=float(white), min_span=float(min_span), min_points=int(min_points),
+                  fallback=(f_lo, f_hi))
 
 
 def intensity_window(lo_key, hi_key, count, stretch):
@@ -260,7 +246,7 @@ def intensity_window(lo_key, hi_key, count, stretch):
     return lo, hi, stretch.white / (hi - lo)
 
 
-class ElevationDrape:
+class ElevationDrape(_Options):
     """How the LAS -> map routes give their 3-D lane vertices a height (immutable; Runner.infer_las_strip_to_map / infer_las_to_map,
     `elevation=`).  The height of a vertex is read off the points the rasteriser saw (ops.drape_vertices): the lower median, over the
     (2 radius_px + 1)^2 pixels around the vertex pixel, of each pixel's smallest tile-frame height - instead of the 8-bit elevation of the
@@ -281,26 +267,10 @@ class ElevationDrape:
             raise ValueError(f'ElevationDrape: min_pixels={min_pixels!r} must be a whole number >= 1')
         if fit not in ('line', 'none'):
             raise ValueError(f"ElevationDrape: fit={fit!r} must be 'line' or 'none'")
-        for k, v in (('radius_px', int(radius_px)), ('min_pixels', int(min_pixels)), ('fit', fit)):
-            object.__setattr__(self, k, v)
-
-    def __setattr__(self, name, value):
-        raise AttributeError('ElevationDrape is immutable')
-
-    def __delattr__(self, name):
-        raise AttributeError('ElevationDrape is immutable')
-
-    def __repr__(self):
-        return 'ElevationDrape(' + ', '.join(f'{k}={getattr(self, k)!r}' for k in self.__slots__) + ')'
-
-    def __eq__(self, other):
-        return isinstance(other, ElevationDrape) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
-
-    def __hash__(self):
-        return hash(tuple(getattr(self, k) for k in self.__slots__))
+        self._set(radius_px=int(radius_px), min_pixels=int(min_pixels), fit=fit)
 
 
-class GapFill:
+class GapFill(_Options):
     """How the LAS -> map routes close the holes between the returns of a scanner that delivers fewer returns than pixels (immutable;
     Runner.infer_las_strip_to_map / infer_las_to_map, `density=`).  Between the rasteriser and the network every empty pixel of a tile
     takes the three bytes of the nearest non-empty pixel of the same tile within a disc of `radius` pixels, ties in distance going to the
@@ -315,32 +285,16 @@ class GapFill:
     __slots__ = ('radius_px', 'max_radius_px', 'coverage')
 
     def __init__(self, radius_px='auto', max_radius_px=4, coverage=0.9):
-        if isinstance(max_radius_px, bool) or not isinstance(max_radius_px, (int, np.integer)) or not 1 <= int(max_radius_px) <= 8:
+        if not _whole(max_radius_px) or not 1 <= int(max_radius_px) <= 8:
             raise ValueError(f'GapFill: max_radius_px={max_radius_px!r} must be a whole number of pixels in 1..8')
         if not (isinstance(radius_px, str) and radius_px == 'auto'):
-            if isinstance(radius_px, bool) or not isinstance(radius_px, (int, np.integer)) or not 0 <= int(radius_px) <= int(max_radius_px):
+            if not _whole(radius_px) or not 0 <= int(radius_px) <= int(max_radius_px):
                 raise ValueError(f"GapFill: radius_px={radius_px!r} must be 'auto' or a whole number of pixels in 0..max_radius_px="
                                  f'{int(max_radius_px)}')
             radius_px = int(radius_px)
-        if isinstance(coverage, bool) or not isinstance(coverage, (int, float, np.integer, np.floating)) or not 0 < float(coverage) <= 1:
+        if not _number(coverage) or not 0 < float(coverage) <= 1:
             raise ValueError(f'GapFill: coverage={coverage!r} must be a number with 0 < coverage <= 1')
-        for k, v in (('radius_px', radius_px), ('max_radius_px', int(max_radius_px)), ('coverage', float(coverage))):
-            object.__setattr__(self, k, v)
-
-    def __setattr__(self, name, value):
-        raise AttributeError('GapFill is immutable')
-
-    def __delattr__(self, name):
-        raise AttributeError('GapFill is immutable')
-
-    def __repr__(self):
-        return 'GapFill(' + ', '.join(f'{k}={getattr(self, k)!r}' for k in self.__slots__) + ')'
-
-    def __eq__(self, other):
-        return isinstance(other, GapFill) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
-
-    def __hash__(self):
-        return hash(tuple(getattr(self, k) for k in self.__slots__))
+        self._set(radius_px=radius_px, max_radius_px=int(max_radius_px), coverage=float(coverage))
 
 
 def gap_radius(hist_row, fill):
@@ -365,7 +319,7 @@ def gap_radius(hist_row, fill):
     return R
 
 
-class MarkingLabels:
+class MarkingLabels(_Options):
     """How the LAS -> map routes label the returns of their input by the lines they found (immutable; Runner.infer_las_strip_to_map /
     infer_las_to_map, `label=`; label_las).  A return is labelled with line k (counted from 1 in the order of the lines) when it lies within
     half_width of the line in the plane and within z_tol of it in height, the nearest line winning (the rule: include/lanemap_hip.h).
@@ -380,37 +334,20 @@ class MarkingLabels:
     __slots__ = ('half_width', 'z_tol', 'min_intensity', 'marking_class', 'line_ids')
 
     def __init__(self, half_width=0.15, z_tol=0.5, min_intensity=None, marking_class=None, line_ids=True):
-        num = (int, float, np.integer, np.floating)
-        if isinstance(half_width, bool) or not isinstance(half_width, num) or not (0.0 <= float(half_width) < math.inf):
+        if not _number(half_width) or not (0.0 <= float(half_width) < math.inf):
             raise ValueError(f'MarkingLabels: half_width={half_width!r} must be a finite number >= 0')
-        if isinstance(z_tol, bool) or not isinstance(z_tol, num) or not float(z_tol) >= 0.0:
+        if not _number(z_tol) or not float(z_tol) >= 0.0:
             raise ValueError(f'MarkingLabels: z_tol={z_tol!r} must be a number >= 0')
         if min_intensity is not None:
-            if isinstance(min_intensity, bool) or not isinstance(min_intensity, num) or math.isnan(float(min_intensity)):
+            if not _number(min_intensity) or math.isnan(float(min_intensity)):
                 raise ValueError(f'MarkingLabels: min_intensity={min_intensity!r} must be None or a number')
             min_intensity = float(min_intensity)
         if marking_class is not None:
-            if isinstance(marking_class, bool) or not isinstance(marking_class, (int, np.integer)) or not 0 <= int(marking_class) <= 255:
+            if not _whole(marking_class) or not 0 <= int(marking_class) <= 255:
                 raise ValueError(f'MarkingLabels: marking_class={marking_class!r} must be None or a class in 0..255')
             marking_class = int(marking_class)
-        for k, v in (('half_width', float(half_width)), ('z_tol', float(z_tol)), ('min_intensity', min_intensity),
-                     ('marking_class', marking_class), ('line_ids', bool(line_ids))):
-            object.__setattr__(self, k, v)
-
-    def __setattr__(self, name, value):
-        raise AttributeError('MarkingLabels is immutable')
-
-    def __delattr__(self, name):
-        raise AttributeError('MarkingLabels is immutable')
-
-    def __repr__(self):
-        return 'MarkingLabels(' + ', '.join(f'{k}={getattr(self, k)!r}' for k in self.__slots__) + ')'
-
-    def __eq__(self, other):
-        return isinstance(other, MarkingLabels) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
-
-    def __hash__(self):
-        return hash(tuple(getattr(self, k) for k in self.__slots__))
+        self._set(half_width=float(half_width), z_tol=float(z_tol), min_intensity=min_intensity, marking_class=marking_class,
+                  line_ids=bool(line_ids))
 
     def for_format(self, point_format):
         """-> the classification labelled records of a file of this point data record format get: marking_class, or its default for the
@@ -452,33 +389,60 @@ def line_segments(lines, shift=None):
     return np.concatenate(rows) if rows else np.zeros((0, 8), dtype=np.float32)
 
 
+def _d3(v):
+    """Three numbers -> the double[3] the C entries take."""
+    return (C.c_double * 3)(*[float(x) for x in v])
+
+
+def _upload_records(data, header, device):
+    """The point records of a parsed file (data: its bytes as a uint8 array, header: parse_header's dict) -> a uint8 tensor on `device`,
+    zero-padded to a multiple of four bytes as the record entries take them.  The copy is asynchronous."""
+    off, nbytes = header['offset_to_points'], header['n_points'] * header['record_len']
+    padded = np.zeros(((nbytes + 3) // 4 * 4,), dtype=np.uint8)
+    padded[:nbytes] = data[off:off + nbytes]
+    return torch.from_numpy(padded).to(device, non_blocking=True)
+
+
+def _records_args(who, records_u8, header, shift, select, index, stations, asker, half_width, bin=None):
+    """What the record entries (label_records, profile_records, profile_colour_records, cross_records) share: the checks of select, of
+    the records' device and of the tables against what the caller's options ask (`asker`: the words of the message, 'the survey asks';
+    bin None: the entry takes no stations), and -> (the leading arguments of the C entry, the records' device).  The arguments: the
+    current stream of the RECORDS' device, the records, record_len, point_format, n, scale, offset, shift or None, the select or None,
+    index.args() and, with stations, stations.args()."""
+    from . import ops
+    if select is not None and not isinstance(select, PointFilter):
+        raise TypeError(f'{who}: select must be a PointFilter, not {type(select).__name__}')
+    if not records_u8.is_cuda:
+        raise LanemapHipError(f'{who} needs the records on an MI355X (HIP) device; no CPU fallback exists')
+    if bin is not None and (not isinstance(index, ops.LineIndex) or not isinstance(stations, ops.LineStations)):
+        raise TypeError(f'{who}: index must be an ops.LineIndex and stations an ops.LineStations')
+    fmt, rl, n = header['point_format'], header['record_len'], header['n_points']
+    sel = select.for_format(fmt).as_struct() if select is not None else None
+    if index.half_width != np.float32(half_width):
+        raise ValueError(f'{who}: the index was built for half_width={index.half_width}, {asker} {half_width}')
+    if bin is not None and (stations.bin != bin or stations.n_segments != index.n_segments):
+        raise ValueError(f'{who}: the stations were cut for bin={stations.bin} and {stations.n_segments} segments, {asker} bin={bin}, '
+                         f'the index holds {index.n_segments}')
+    dev = records_u8.device
+    return (C.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index)), C.c_void_p(records_u8.data_ptr()), int(rl), int(fmt), int(n),
+            _d3(header['scale']), _d3(header['offset']), _d3(shift) if shift is not None else None,
+            C.byref(sel) if sel is not None else None, *index.args(), *(stations.args() if bin is not None else ())), dev
+
+
 def label_records(records_u8, header, index, labels, shift=None, select=None, n_lines=None, want_line=False):
     """One lm_las_label_records call on the DEVICE records of a file (padded to a multiple of 4 bytes; `header`: parse_header's dict)
     against an ops.line_index: -> (patched records, counts [n_lines + 1] int64 device tensor[, line [n] int32]).  Asynchronous."""
-    from . import ops
     if not isinstance(labels, MarkingLabels):
         raise TypeError(f'las_io.label_records: labels must be a MarkingLabels, not {type(labels).__name__}')
-    if select is not None and not isinstance(select, PointFilter):
-        raise TypeError(f'las_io.label_records: select must be a PointFilter, not {type(select).__name__}')
-    if not records_u8.is_cuda:
-        raise LanemapHipError('las_io.label_records needs the records on an MI355X (HIP) device; no CPU fallback exists')
-    fmt, rl, n = header['point_format'], header['record_len'], header['n_points']
-    cls = labels.for_format(fmt)
-    sel = select.for_format(fmt).as_struct() if select is not None else None
+    args, dev = _records_args('las_io.label_records', records_u8, header, shift, select, index, None, 'labels ask', labels.half_width)
+    cls = labels.for_format(header['point_format'])
     L = index.n_lines if n_lines is None else int(n_lines)
-    if index.half_width != np.float32(labels.half_width):
-        raise ValueError(f'las_io.label_records: the index was built for half_width={index.half_width}, labels ask {labels.half_width}')
-    dev = records_u8.device
     out = torch.empty_like(records_u8)
     counts = torch.empty((L + 1,), device=dev, dtype=torch.int64)
-    line = torch.empty((n,), device=dev, dtype=torch.int32) if want_line else None
-    d3 = lambda v: (C.c_double * 3)(*[float(x) for x in v])
+    line = torch.empty((header['n_points'],), device=dev, dtype=torch.int32) if want_line else None
     mi = math.nan if labels.min_intensity is None else labels.min_intensity
-    check(lib().lm_las_label_records(C.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index)), C.c_void_p(records_u8.data_ptr()), int(rl),
-                                     int(fmt), int(n), d3(header['scale']), d3(header['offset']), d3(shift) if shift is not None else None,
-                                     C.byref(sel) if sel is not None else None, *index.args(), labels.z_tol, mi, cls,
-                                     int(labels.line_ids), C.c_void_p(out.data_ptr()), C.c_void_p(line.data_ptr()) if want_line else None,
-                                     C.c_void_p(counts.data_ptr()), L))
+    check(lib().lm_las_label_records(*args, labels.z_tol, mi, cls, int(labels.line_ids), C.c_void_p(out.data_ptr()),
+                                     C.c_void_p(line.data_ptr()) if want_line else None, C.c_void_p(counts.data_ptr()), L))
     return (out, counts, line) if want_line else (out, counts)
 
 
@@ -504,12 +468,10 @@ def label_las(path, out_path, lines, labels, shift, select=None, device='cuda:0'
     lines = list(lines)
     index = ops.line_index(line_segments(lines, shift), labels.half_width, device=device)
     nbytes = n * rl
-    padded = np.zeros(((nbytes + 3) // 4 * 4,), dtype=np.uint8)
-    padded[:nbytes] = data[off:off + nbytes]
-    rec = torch.from_numpy(padded).to(device, non_blocking=True)
+    rec = _upload_records(data, h, device)
     out, counts = label_records(rec, h, index, labels, shift, select, n_lines=len(lines))
     both = torch.cat([out, counts.view(torch.uint8)]).cpu().numpy()        # the one read-back
-    counts = both[len(padded):].view(np.int64)
+    counts = both[len(rec):].view(np.int64)
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
     with open(out_path, 'wb') as f:
         f.write(data[:off].tobytes())
@@ -519,7 +481,7 @@ def label_las(path, out_path, lines, labels, shift, select=None, device='cuda:0'
     return {'records': int(n), 'labelled': int(sum(per_line)), 'per_line': per_line}
 
 
-class MarkingSurvey:
+class MarkingSurvey(_Options):
     """How the LAS -> map routes profile the lane lines they found from the returns of their input (immutable;
     Runner.infer_las_strip_to_map / infer_las_to_map, `survey=`; survey_las, marking_summary).  The returns the labelling rule gives a line
     (within half_width in the plane and z_tol in height, the nearest line winning) are accumulated per station bin along the line (the
@@ -538,41 +500,24 @@ class MarkingSurvey:
     __slots__ = ('bin', 'half_width', 'z_tol', 'min_intensity', 'min_points', 'max_gap', 'solid_cover')
 
     def __init__(self, bin=0.25, half_width=0.3, z_tol=0.5, min_intensity=None, min_points=3, max_gap=0.5, solid_cover=0.8):
-        num = (int, float, np.integer, np.floating)
-        if isinstance(bin, bool) or not isinstance(bin, num) or not (0.0 < float(bin) < math.inf):
+        if not _number(bin) or not (0.0 < float(bin) < math.inf):
             raise ValueError(f'MarkingSurvey: bin={bin!r} must be a finite length > 0')
-        if isinstance(half_width, bool) or not isinstance(half_width, num) or not (0.0 <= float(half_width) <= 16.0):
+        if not _number(half_width) or not (0.0 <= float(half_width) <= 16.0):
             raise ValueError(f'MarkingSurvey: half_width={half_width!r} must be a number in 0 .. 16 (metres)')
-        if isinstance(z_tol, bool) or not isinstance(z_tol, num) or not float(z_tol) >= 0.0:
+        if not _number(z_tol) or not float(z_tol) >= 0.0:
             raise ValueError(f'MarkingSurvey: z_tol={z_tol!r} must be a number >= 0')
         if min_intensity is not None:
-            if isinstance(min_intensity, bool) or not isinstance(min_intensity, num) or math.isnan(float(min_intensity)):
+            if not _number(min_intensity) or math.isnan(float(min_intensity)):
                 raise ValueError(f'MarkingSurvey: min_intensity={min_intensity!r} must be None or a number')
             min_intensity = float(min_intensity)
-        if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)) or int(min_points) < 1:
+        if not _whole(min_points) or int(min_points) < 1:
             raise ValueError(f'MarkingSurvey: min_points={min_points!r} must be a whole number >= 1')
-        if isinstance(max_gap, bool) or not isinstance(max_gap, num) or not (0.0 <= float(max_gap) < math.inf):
+        if not _number(max_gap) or not (0.0 <= float(max_gap) < math.inf):
             raise ValueError(f'MarkingSurvey: max_gap={max_gap!r} must be a finite length >= 0')
-        if isinstance(solid_cover, bool) or not isinstance(solid_cover, num) or not (0.0 < float(solid_cover) <= 1.0):
+        if not _number(solid_cover) or not (0.0 < float(solid_cover) <= 1.0):
             raise ValueError(f'MarkingSurvey: solid_cover={solid_cover!r} must be a number with 0 < solid_cover <= 1')
-        for k, v in (('bin', float(bin)), ('half_width', float(half_width)), ('z_tol', float(z_tol)), ('min_intensity', min_intensity),
-                     ('min_points', int(min_points)), ('max_gap', float(max_gap)), ('solid_cover', float(solid_cover))):
-            object.__setattr__(self, k, v)
-
-    def __setattr__(self, name, value):
-        raise AttributeError('MarkingSurvey is immutable')
-
-    def __delattr__(self, name):
-        raise AttributeError('MarkingSurvey is immutable')
-
-    def __repr__(self):
-        return 'MarkingSurvey(' + ', '.join(f'{k}={getattr(self, k)!r}' for k in self.__slots__) + ')'
-
-    def __eq__(self, other):
-        return isinstance(other, MarkingSurvey) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
-
-    def __hash__(self):
-        return hash(tuple(getattr(self, k) for k in self.__slots__))
+        self._set(bin=float(bin), half_width=float(half_width), z_tol=float(z_tol), min_intensity=min_intensity, min_points=int(min_points),
+                  max_gap=float(max_gap), solid_cover=float(solid_cover))
 
 
 def line_stations(lines, shift=None, bin=0.25):
@@ -582,7 +527,7 @@ def line_stations(lines, shift=None, bin=0.25):
     of the len64 of the earlier segments of the same line, rounded to float32; len = float32(len64); rlen = float32(1 / len64), 0 where
     len64 == 0.  Line k (from 1) owns the bins bin_start[k-1] .. bin_start[k] - 1: max(1, ceil(total len64 / bin)) of them for a line with
     segments, none for a line with fewer than two vertices."""
-    if isinstance(bin, bool) or not isinstance(bin, (int, float, np.integer, np.floating)) or not (0.0 < float(bin) < math.inf):
+    if not _number(bin) or not (0.0 < float(bin) < math.inf):
         raise ValueError(f'line_stations: bin={bin!r} must be a finite length > 0')
     bin = float(bin)
     lines = list(lines)
@@ -615,31 +560,55 @@ def profile_records(records_u8, header, index, stations, survey, shift=None, sel
     ops.line_profile).  The records are only read; a record `select` drops contributes nothing.  out: the bins of an earlier call to add to
     - the files of a strip go into one profile this way.  Asynchronous."""
     from . import ops
+    who = 'las_io.profile_records'
     if not isinstance(survey, MarkingSurvey):
-        raise TypeError(f'las_io.profile_records: survey must be a MarkingSurvey, not {type(survey).__name__}')
-    if select is not None and not isinstance(select, PointFilter):
-        raise TypeError(f'las_io.profile_records: select must be a PointFilter, not {type(select).__name__}')
-    if not records_u8.is_cuda:
-        raise LanemapHipError('las_io.profile_records needs the records on an MI355X (HIP) device; no CPU fallback exists')
-    if not isinstance(index, ops.LineIndex) or not isinstance(stations, ops.LineStations):
-        raise TypeError('las_io.profile_records: index must be an ops.LineIndex and stations an ops.LineStations')
-    fmt, rl, n = header['point_format'], header['record_len'], header['n_points']
-    sel = select.for_format(fmt).as_struct() if select is not None else None
-    if index.half_width != np.float32(survey.half_width):
-        raise ValueError(f'las_io.profile_records: the index was built for half_width={index.half_width}, the survey asks {survey.half_width}')
-    if stations.bin != survey.bin or stations.n_segments != index.n_segments:
-        raise ValueError(f'las_io.profile_records: the stations were cut for bin={stations.bin} and {stations.n_segments} segments, the survey '
-                         f'asks bin={survey.bin}, the index holds {index.n_segments}')
-    dev = records_u8.device
-    bins = ops._profile_out('las_io.profile_records', stations, out, dev)
-    d3 = lambda v: (C.c_double * 3)(*[float(x) for x in v])
+        raise TypeError(f'{who}: survey must be a MarkingSurvey, not {type(survey).__name__}')
+    args, dev = _records_args(who, records_u8, header, shift, select, index, stations, 'the survey asks', survey.half_width, survey.bin)
+    nb = stations.n_bins
+    bins = ops._table_out(who, (nb, 6), out, dev)
     mi = math.nan if survey.min_intensity is None else survey.min_intensity
-    check(lib().lm_las_line_profile_records(C.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index)), C.c_void_p(records_u8.data_ptr()),
-                                            int(rl), int(fmt), int(n), d3(header['scale']), d3(header['offset']),
-                                            d3(shift) if shift is not None else None, C.byref(sel) if sel is not None else None,
-                                            *index.args(), *stations.args(), survey.z_tol, mi, int(out is not None),
-                                            C.c_void_p(bins.data_ptr()) if stations.n_bins else None, stations.n_bins))
+    check(lib().lm_las_line_profile_records(*args, survey.z_tol, mi, int(out is not None), C.c_void_p(bins.data_ptr()) if nb else None, nb))
     return bins
+
+
+def _each_file(who, files, lines, bin, half_width, device, per_file, require=None):
+    """The loop of survey_files, survey_colour_files and cross_files over `files`, a list of (path, shift, select).  Every select is
+    checked and `require`, if given, is called with every path before a file is read.  Then every file is read once and uploaded once
+    (_upload_records) and goes through one call per_file(records, header, tables, shift, select, out) with tables = the ops.LineIndex
+    (of `half_width`) and the ops.LineStations (of `bin`) of the lines in the frame of its own shift - built once per distinct shift -
+    and the result of the call before it as `out`.  The bins each line owns, bin_start, are those of the FIRST file's frame, in every table.
+    -> (what the last call returned, bin_start); without a file (None, the bin_start of the unshifted lines).  Nothing is read back."""
+    from . import ops
+    device = torch.device(device)
+    lines, files = list(lines), list(files)
+    for _, _, select in files:
+        if select is not None and not isinstance(select, PointFilter):
+            raise TypeError(f'{who}: select must be a PointFilter, not {type(select).__name__}')
+    for path, _, _ in files if require is not None else ():
+        require(path)
+    tables, bin_start, out = {}, None, None
+    for path, shift, select in files:
+        data = np.fromfile(path, dtype=np.uint8)
+        h = parse_header(data)
+        if select is not None:
+            select.for_format(h['point_format'])
+        key = None if shift is None else tuple(float(v) for v in shift)
+        if key not in tables:
+            st, bs = line_stations(lines, shift, bin)
+            bin_start = bs if bin_start is None else bin_start
+            tables[key] = (ops.line_index(line_segments(lines, shift), half_width, device=device),
+                           ops.line_stations(st, bin_start, bin, device=device))
+        out = per_file(_upload_records(data, h, device), h, tables[key], shift, select, out)
+    if out is None:
+        bin_start = line_stations(lines, None, bin)[1]
+    return out, bin_start
+
+
+def _empty_bins(bin_start):
+    """-> the [n_bins, 6] int64 numpy profile no return went into: four zeros, then the empty minimum and maximum of q."""
+    host = np.zeros((int(bin_start[-1]), 6), dtype=np.int64)
+    host[:, 4], host[:, 5] = 2 ** 31 - 1, -2 ** 31
+    return host
 
 
 def survey_files(files, lines, survey, device='cuda:0'):
@@ -648,37 +617,12 @@ def survey_files(files, lines, survey, device='cuda:0'):
     tensor, which is read back once.  The bins each line owns (bin_start) are those of the first file's frame; where another file's shift
     rounds a line's length into one bin more, the rule's clamp to the line's last bin holds.
     -> (bins [n_bins, 6] int64 numpy, bin_start [L + 1] int32 numpy)."""
-    from . import ops
     if not isinstance(survey, MarkingSurvey):
         raise TypeError(f'las_io.survey_files: survey must be a MarkingSurvey, not {type(survey).__name__}')
-    device = torch.device(device)
-    lines, files = list(lines), list(files)
-    tables, bin_start, bins = {}, None, None
-    for path, shift, select in files:
-        if select is not None and not isinstance(select, PointFilter):
-            raise TypeError(f'las_io.survey_files: select must be a PointFilter, not {type(select).__name__}')
-        data = np.fromfile(path, dtype=np.uint8)
-        h = parse_header(data)
-        n, rl, off = h['n_points'], h['record_len'], h['offset_to_points']
-        if select is not None:
-            select.for_format(h['point_format'])
-        key = None if shift is None else tuple(float(v) for v in shift)
-        if key not in tables:
-            st, bs = line_stations(lines, shift, survey.bin)
-            bin_start = bs if bin_start is None else bin_start
-            tables[key] = (ops.line_index(line_segments(lines, shift), survey.half_width, device=device),
-                           ops.line_stations(st, bin_start, survey.bin, device=device))
-        index, stations = tables[key]
-        nbytes = n * rl
-        padded = np.zeros(((nbytes + 3) // 4 * 4,), dtype=np.uint8)
-        padded[:nbytes] = data[off:off + nbytes]
-        rec = torch.from_numpy(padded).to(device, non_blocking=True)
-        bins = profile_records(rec, h, index, stations, survey, shift, select, out=bins)
+    bins, bin_start = _each_file('las_io.survey_files', files, lines, survey.bin, survey.half_width, device,
+                                 lambda rec, h, tables, shift, select, out: profile_records(rec, h, *tables, survey, shift, select, out=out))
     if bins is None:                                                        # no file: the empty profile of the lines
-        bin_start = line_stations(lines, None, survey.bin)[1]
-        host = np.zeros((int(bin_start[-1]), 6), dtype=np.int64)
-        host[:, 4], host[:, 5] = 2 ** 31 - 1, -2 ** 31
-        return host, bin_start
+        return _empty_bins(bin_start), bin_start
     return bins.cpu().numpy(), bin_start                                    # the one read-back
 
 
@@ -748,12 +692,12 @@ RGB_OFFSET = {2: 20, 3: 28, 5: 28, 7: 30, 8: 30, 10: 30}      # byte offset of t
 def rgb_offset(point_format):
     """-> the byte offset of the 16-bit R, G, B triple in a record of this point data record format (2: 20; 3, 5: 28; 7, 8, 10: 30), or
     None for a format without colour (0, 1, 4, 6, 9)."""
-    if isinstance(point_format, bool) or not isinstance(point_format, (int, np.integer)) or not 0 <= int(point_format) <= 10:
+    if not _whole(point_format) or not 0 <= int(point_format) <= 10:
         raise ValueError(f'rgb_offset: unknown point data record format {point_format!r}')
     return RGB_OFFSET.get(int(point_format))
 
 
-class MarkingColour:
+class MarkingColour(_Options):
     """How the LAS -> map routes tell white markings from yellow ones (immutable; Runner.infer_las_strip_to_map / infer_las_to_map,
     `colour=` beside `survey=`; survey_colour_las, marking_colours).  The returns of a line's station bins (MarkingSurvey's rule) that
     carry a colour - any R, G, B triple but three zeros, which colourisation leaves where no camera saw the point - are counted and
@@ -769,30 +713,13 @@ class MarkingColour:
     __slots__ = ('yellow_ratio', 'yellow_share', 'min_coloured')
 
     def __init__(self, yellow_ratio=0.75, yellow_share=0.5, min_coloured=10):
-        num = (int, float, np.integer, np.floating)
-        if isinstance(yellow_ratio, bool) or not isinstance(yellow_ratio, num) or not (0.0 < float(yellow_ratio) <= 1.0):
+        if not _number(yellow_ratio) or not (0.0 < float(yellow_ratio) <= 1.0):
             raise ValueError(f'MarkingColour: yellow_ratio={yellow_ratio!r} must be a number with 0 < yellow_ratio <= 1')
-        if isinstance(yellow_share, bool) or not isinstance(yellow_share, num) or not (0.0 < float(yellow_share) <= 1.0):
+        if not _number(yellow_share) or not (0.0 < float(yellow_share) <= 1.0):
             raise ValueError(f'MarkingColour: yellow_share={yellow_share!r} must be a number with 0 < yellow_share <= 1')
-        if isinstance(min_coloured, bool) or not isinstance(min_coloured, (int, np.integer)) or int(min_coloured) < 1:
+        if not _whole(min_coloured) or int(min_coloured) < 1:
             raise ValueError(f'MarkingColour: min_coloured={min_coloured!r} must be a whole number >= 1')
-        for k, v in (('yellow_ratio', float(yellow_ratio)), ('yellow_share', float(yellow_share)), ('min_coloured', int(min_coloured))):
-            object.__setattr__(self, k, v)
-
-    def __setattr__(self, name, value):
-        raise AttributeError('MarkingColour is immutable')
-
-    def __delattr__(self, name):
-        raise AttributeError('MarkingColour is immutable')
-
-    def __repr__(self):
-        return 'MarkingColour(' + ', '.join(f'{k}={getattr(self, k)!r}' for k in self.__slots__) + ')'
-
-    def __eq__(self, other):
-        return isinstance(other, MarkingColour) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
-
-    def __hash__(self):
-        return hash(tuple(getattr(self, k) for k in self.__slots__))
+        self._set(yellow_ratio=float(yellow_ratio), yellow_share=float(yellow_share), min_coloured=int(min_coloured))
 
     @property
     def blue_q(self):
@@ -811,33 +738,17 @@ def profile_colour_records(records_u8, header, index, stations, survey, colour, 
         raise TypeError(f'{who}: survey must be a MarkingSurvey, not {type(survey).__name__}')
     if not isinstance(colour, MarkingColour):
         raise TypeError(f'{who}: colour must be a MarkingColour, not {type(colour).__name__}')
-    if select is not None and not isinstance(select, PointFilter):
-        raise TypeError(f'{who}: select must be a PointFilter, not {type(select).__name__}')
-    if not records_u8.is_cuda:
-        raise LanemapHipError(f'{who} needs the records on an MI355X (HIP) device; no CPU fallback exists')
-    if not isinstance(index, ops.LineIndex) or not isinstance(stations, ops.LineStations):
-        raise TypeError(f'{who}: index must be an ops.LineIndex and stations an ops.LineStations')
-    fmt, rl, n = header['point_format'], header['record_len'], header['n_points']
+    args, dev = _records_args(who, records_u8, header, shift, select, index, stations, 'the survey asks', survey.half_width, survey.bin)
+    fmt = header['point_format']
     if rgb_offset(fmt) is None:
         raise ValueError(f'{who}: point format {fmt} carries no RGB (formats {sorted(RGB_OFFSET)} do)')
-    sel = select.for_format(fmt).as_struct() if select is not None else None
-    if index.half_width != np.float32(survey.half_width):
-        raise ValueError(f'{who}: the index was built for half_width={index.half_width}, the survey asks {survey.half_width}')
-    if stations.bin != survey.bin or stations.n_segments != index.n_segments:
-        raise ValueError(f'{who}: the stations were cut for bin={stations.bin} and {stations.n_segments} segments, the survey '
-                         f'asks bin={survey.bin}, the index holds {index.n_segments}')
-    dev = records_u8.device
     if out is not None and not (isinstance(out, (tuple, list)) and len(out) == 2):
         raise ValueError(f'{who}: out must be the (bins, colours) pair of an earlier call')
-    bins = ops._profile_out(who, stations, None if out is None else out[0], dev)
-    colours = ops._profile_out(who, stations, None if out is None else out[1], dev)
-    d3 = lambda v: (C.c_double * 3)(*[float(x) for x in v])
-    mi = math.nan if survey.min_intensity is None else survey.min_intensity
     nb = stations.n_bins
-    check(lib().lm_las_line_colour_records(C.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index)), C.c_void_p(records_u8.data_ptr()),
-                                           int(rl), int(fmt), int(n), d3(header['scale']), d3(header['offset']),
-                                           d3(shift) if shift is not None else None, C.byref(sel) if sel is not None else None,
-                                           *index.args(), *stations.args(), survey.z_tol, mi, colour.blue_q, int(out is not None),
+    bins = ops._table_out(who, (nb, 6), None if out is None else out[0], dev)
+    colours = ops._table_out(who, (nb, 6), None if out is None else out[1], dev)
+    mi = math.nan if survey.min_intensity is None else survey.min_intensity
+    check(lib().lm_las_line_colour_records(*args, survey.z_tol, mi, colour.blue_q, int(out is not None),
                                            C.c_void_p(bins.data_ptr()) if nb else None, C.c_void_p(colours.data_ptr()) if nb else None, nb))
     return bins, colours
 
@@ -847,40 +758,15 @@ def survey_colour_files(files, lines, survey, colour, device='cuda:0'):
     lm_las_line_colour_records call into one (bins, colours) pair, which is read back once.  All headers are read before anything is
     uploaded: a file whose point format has no colour is refused with a ValueError that names the file and its format.
     -> (bins [n_bins, 6] int64 numpy, colours [n_bins, 6] int64 numpy, bin_start [L + 1] int32 numpy)."""
-    from . import ops
     if not isinstance(survey, MarkingSurvey):
         raise TypeError(f'las_io.survey_colour_files: survey must be a MarkingSurvey, not {type(survey).__name__}')
     if not isinstance(colour, MarkingColour):
         raise TypeError(f'las_io.survey_colour_files: colour must be a MarkingColour, not {type(colour).__name__}')
-    device = torch.device(device)
-    lines, files = list(lines), list(files)
-    for path, shift, select in files:
-        if select is not None and not isinstance(select, PointFilter):
-            raise TypeError(f'las_io.survey_colour_files: select must be a PointFilter, not {type(select).__name__}')
-        require_colour(path)
-    tables, bin_start, pair = {}, None, None
-    for path, shift, select in files:
-        data = np.fromfile(path, dtype=np.uint8)
-        h = parse_header(data)
-        n, rl, off = h['n_points'], h['record_len'], h['offset_to_points']
-        if select is not None:
-            select.for_format(h['point_format'])
-        key = None if shift is None else tuple(float(v) for v in shift)
-        if key not in tables:
-            st, bs = line_stations(lines, shift, survey.bin)
-            bin_start = bs if bin_start is None else bin_start
-            tables[key] = (ops.line_index(line_segments(lines, shift), survey.half_width, device=device),
-                           ops.line_stations(st, bin_start, survey.bin, device=device))
-        index, stations = tables[key]
-        nbytes = n * rl
-        padded = np.zeros(((nbytes + 3) // 4 * 4,), dtype=np.uint8)
-        padded[:nbytes] = data[off:off + nbytes]
-        rec = torch.from_numpy(padded).to(device, non_blocking=True)
-        pair = profile_colour_records(rec, h, index, stations, survey, colour, shift, select, out=pair)
+    pair, bin_start = _each_file('las_io.survey_colour_files', files, lines, survey.bin, survey.half_width, device,
+                                 lambda rec, h, tables, shift, select, out:
+                                 profile_colour_records(rec, h, *tables, survey, colour, shift, select, out=out), require=require_colour)
     if pair is None:                                                        # no file: the empty tables of the lines
-        bin_start = line_stations(lines, None, survey.bin)[1]
-        host = np.zeros((int(bin_start[-1]), 6), dtype=np.int64)
-        host[:, 4], host[:, 5] = 2 ** 31 - 1, -2 ** 31
+        host = _empty_bins(bin_start)
         return host, np.zeros_like(host), bin_start
     both = torch.stack(pair).cpu().numpy()                                  # the one read-back
     return both[0], both[1], bin_start
@@ -958,7 +844,7 @@ def marking_colours(bins, colours, bin_start, survey, colour):
     return out
 
 
-class CrossSection:
+class CrossSection(_Options):
     """How the LAS -> map routes take cross-sections along the lane lines they found (immutable; Runner.infer_las_strip_to_map /
     infer_las_to_map, `cross=`; cross_files, cross_summary, snap_lines).  EVERY finite return the labelling rule gives a line (within
     half_width in the plane and z_tol in height, the nearest line winning, no intensity threshold) goes into a table: per station bin
@@ -986,56 +872,33 @@ class CrossSection:
 
     def __init__(self, paint_intensity, bin=0.5, half_width=0.625, lateral=0.03125, z_tol=0.5, min_points=3, paint_share=0.5, max_hole=1,
                  min_stripe=0.05, smooth=2.0, min_stations=2, max_shift=0.3):
-        num = (int, float, np.integer, np.floating)
-        whole = (int, np.integer)
-
-        def number(v):
-            return not isinstance(v, bool) and isinstance(v, num)
-
-        if not number(paint_intensity) or math.isnan(float(paint_intensity)):
+        if not _number(paint_intensity) or math.isnan(float(paint_intensity)):
             raise ValueError(f'CrossSection: paint_intensity={paint_intensity!r} must be a number')
-        if not number(bin) or not (0.0 < float(bin) < math.inf):
+        if not _number(bin) or not (0.0 < float(bin) < math.inf):
             raise ValueError(f'CrossSection: bin={bin!r} must be a finite length > 0')
-        if not number(half_width) or not (0.0 <= float(half_width) <= 16.0):
+        if not _number(half_width) or not (0.0 <= float(half_width) <= 16.0):
             raise ValueError(f'CrossSection: half_width={half_width!r} must be a number in 0 .. 16 (metres)')
-        if not number(lateral) or not (0.0 < float(lateral) < math.inf):
+        if not _number(lateral) or not (0.0 < float(lateral) < math.inf):
             raise ValueError(f'CrossSection: lateral={lateral!r} must be a finite width > 0')
-        if not number(z_tol) or not (0.0 <= float(z_tol) <= 16.0):
+        if not _number(z_tol) or not (0.0 <= float(z_tol) <= 16.0):
             raise ValueError(f'CrossSection: z_tol={z_tol!r} must be a number in 0 .. 16 (metres)')
-        if isinstance(min_points, bool) or not isinstance(min_points, whole) or int(min_points) < 1:
+        if not _whole(min_points) or int(min_points) < 1:
             raise ValueError(f'CrossSection: min_points={min_points!r} must be a whole number >= 1')
-        if not number(paint_share) or not (0.0 < float(paint_share) <= 1.0):
+        if not _number(paint_share) or not (0.0 < float(paint_share) <= 1.0):
             raise ValueError(f'CrossSection: paint_share={paint_share!r} must be a number with 0 < paint_share <= 1')
-        if isinstance(max_hole, bool) or not isinstance(max_hole, whole) or int(max_hole) < 0:
+        if not _whole(max_hole) or int(max_hole) < 0:
             raise ValueError(f'CrossSection: max_hole={max_hole!r} must be a whole number >= 0')
-        if not number(min_stripe) or not (0.0 <= float(min_stripe) < math.inf):
+        if not _number(min_stripe) or not (0.0 <= float(min_stripe) < math.inf):
             raise ValueError(f'CrossSection: min_stripe={min_stripe!r} must be a finite width >= 0')
-        if not number(smooth) or not (0.0 <= float(smooth) < math.inf):
+        if not _number(smooth) or not (0.0 <= float(smooth) < math.inf):
             raise ValueError(f'CrossSection: smooth={smooth!r} must be a finite length >= 0')
-        if isinstance(min_stations, bool) or not isinstance(min_stations, whole) or int(min_stations) < 1:
+        if not _whole(min_stations) or int(min_stations) < 1:
             raise ValueError(f'CrossSection: min_stations={min_stations!r} must be a whole number >= 1')
-        if not number(max_shift) or not (0.0 <= float(max_shift) < math.inf):
+        if not _number(max_shift) or not (0.0 <= float(max_shift) < math.inf):
             raise ValueError(f'CrossSection: max_shift={max_shift!r} must be a finite length >= 0')
-        for k, v in (('paint_intensity', float(paint_intensity)), ('bin', float(bin)), ('half_width', float(half_width)),
-                     ('lateral', float(lateral)), ('z_tol', float(z_tol)), ('min_points', int(min_points)), ('paint_share', float(paint_share)),
-                     ('max_hole', int(max_hole)), ('min_stripe', float(min_stripe)), ('smooth', float(smooth)),
-                     ('min_stations', int(min_stations)), ('max_shift', float(max_shift))):
-            object.__setattr__(self, k, v)
-
-    def __setattr__(self, name, value):
-        raise AttributeError('CrossSection is immutable')
-
-    def __delattr__(self, name):
-        raise AttributeError('CrossSection is immutable')
-
-    def __repr__(self):
-        return 'CrossSection(' + ', '.join(f'{k}={getattr(self, k)!r}' for k in self.__slots__) + ')'
-
-    def __eq__(self, other):
-        return isinstance(other, CrossSection) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
-
-    def __hash__(self):
-        return hash(tuple(getattr(self, k) for k in self.__slots__))
+        self._set(paint_intensity=float(paint_intensity), bin=float(bin), half_width=float(half_width), lateral=float(lateral),
+                  z_tol=float(z_tol), min_points=int(min_points), paint_share=float(paint_share), max_hole=int(max_hole),
+                  min_stripe=float(min_stripe), smooth=float(smooth), min_stations=int(min_stations), max_shift=float(max_shift))
 
     @property
     def lateral_q(self):
@@ -1067,28 +930,11 @@ def cross_records(records_u8, header, index, stations, cross, shift=None, select
     who = 'las_io.cross_records'
     if not isinstance(cross, CrossSection):
         raise TypeError(f'{who}: cross must be a CrossSection, not {type(cross).__name__}')
-    if select is not None and not isinstance(select, PointFilter):
-        raise TypeError(f'{who}: select must be a PointFilter, not {type(select).__name__}')
-    if not records_u8.is_cuda:
-        raise LanemapHipError(f'{who} needs the records on an MI355X (HIP) device; no CPU fallback exists')
-    if not isinstance(index, ops.LineIndex) or not isinstance(stations, ops.LineStations):
-        raise TypeError(f'{who}: index must be an ops.LineIndex and stations an ops.LineStations')
-    fmt, rl, n = header['point_format'], header['record_len'], header['n_points']
-    sel = select.for_format(fmt).as_struct() if select is not None else None
-    if index.half_width != np.float32(cross.half_width):
-        raise ValueError(f'{who}: the index was built for half_width={index.half_width}, the cross-section asks {cross.half_width}')
-    if stations.bin != cross.bin or stations.n_segments != index.n_segments:
-        raise ValueError(f'{who}: the stations were cut for bin={stations.bin} and {stations.n_segments} segments, the cross-section '
-                         f'asks bin={cross.bin}, the index holds {index.n_segments}')
-    dev = records_u8.device
+    args, dev = _records_args(who, records_u8, header, shift, select, index, stations, 'the cross-section asks', cross.half_width, cross.bin)
     nl = cross.nl
-    cells = ops._cross_out(who, stations, nl, out, dev)
+    cells = ops._table_out(who, (stations.n_bins, nl, 4), out, dev)
     n_cells = stations.n_bins * nl
-    d3 = lambda v: (C.c_double * 3)(*[float(x) for x in v])
-    check(lib().lm_las_line_cross_records(C.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index)), C.c_void_p(records_u8.data_ptr()),
-                                          int(rl), int(fmt), int(n), d3(header['scale']), d3(header['offset']),
-                                          d3(shift) if shift is not None else None, C.byref(sel) if sel is not None else None,
-                                          *index.args(), *stations.args(), cross.z_tol, cross.lateral_q, cross.paint_iq, int(out is not None),
+    check(lib().lm_las_line_cross_records(*args, cross.z_tol, cross.lateral_q, cross.paint_iq, int(out is not None),
                                           C.c_void_p(cells.data_ptr()) if n_cells else None, n_cells))
     return cells
 
@@ -1098,34 +944,11 @@ def cross_files(files, lines, cross, device='cuda:0'):
     every file is read once, uploaded and goes through one lm_las_line_cross_records call with its own read offset and PointFilter, all
     into one table, which is read back once.  The bins each line owns are those of the first file's frame, as in survey_files.
     -> (cells [n_bins, nl, 4] int64 numpy, bin_start [L + 1] int32 numpy)."""
-    from . import ops
     if not isinstance(cross, CrossSection):
         raise TypeError(f'las_io.cross_files: cross must be a CrossSection, not {type(cross).__name__}')
-    device = torch.device(device)
-    lines, files = list(lines), list(files)
-    tables, bin_start, cells = {}, None, None
-    for path, shift, select in files:
-        if select is not None and not isinstance(select, PointFilter):
-            raise TypeError(f'las_io.cross_files: select must be a PointFilter, not {type(select).__name__}')
-        data = np.fromfile(path, dtype=np.uint8)
-        h = parse_header(data)
-        n, rl, off = h['n_points'], h['record_len'], h['offset_to_points']
-        if select is not None:
-            select.for_format(h['point_format'])
-        key = None if shift is None else tuple(float(v) for v in shift)
-        if key not in tables:
-            st, bs = line_stations(lines, shift, cross.bin)
-            bin_start = bs if bin_start is None else bin_start
-            tables[key] = (ops.line_index(line_segments(lines, shift), cross.half_width, device=device),
-                           ops.line_stations(st, bin_start, cross.bin, device=device))
-        index, stations = tables[key]
-        nbytes = n * rl
-        padded = np.zeros(((nbytes + 3) // 4 * 4,), dtype=np.uint8)
-        padded[:nbytes] = data[off:off + nbytes]
-        rec = torch.from_numpy(padded).to(device, non_blocking=True)
-        cells = cross_records(rec, h, index, stations, cross, shift, select, out=cells)
+    cells, bin_start = _each_file('las_io.cross_files', files, lines, cross.bin, cross.half_width, device,
+                                  lambda rec, h, tables, shift, select, out: cross_records(rec, h, *tables, cross, shift, select, out=out))
     if cells is None:                                                       # no file: the empty table of the lines
-        bin_start = line_stations(lines, None, cross.bin)[1]
         return np.zeros((int(bin_start[-1]), cross.nl, 4), dtype=np.int64), bin_start
     return cells.cpu().numpy(), bin_start                                   # the one read-back
 
@@ -1265,7 +1088,7 @@ def snap_lines(lines, summary, bin_start, cross):
     return out
 
 
-class PaintResidue:
+class PaintResidue(_Options):
     """How the LAS -> map routes inventory the paint that no lane line explains (immutable; Runner.infer_las_strip_to_map /
     infer_las_to_map, `residue=`; residue_files, residue_summary).  A return is RESIDUE when it is bright, lies within `reach` in the plane
     and z_tol in height of some line the call found - so signs, vehicles and bridges stay out - and farther than `clear` from the nearest
@@ -1289,46 +1112,28 @@ class PaintResidue:
 
     def __init__(self, min_intensity, clear=0.3, reach=6.0, z_tol=0.5, cell=0.1, connectivity=8, min_cells=20, min_points=20, elongated=2.0,
                  angle_tol_deg=30.0):
-        num = (int, float, np.integer, np.floating)
-        isnum = lambda v: not isinstance(v, bool) and isinstance(v, num)
-        if not isnum(min_intensity) or not math.isfinite(float(min_intensity)):
+        if not _number(min_intensity) or not math.isfinite(float(min_intensity)):
             raise ValueError(f'PaintResidue: min_intensity={min_intensity!r} must be a finite number (without one the whole road is one blob)')
-        if not isnum(reach) or not (0.0 < float(reach) <= 16.0):
+        if not _number(reach) or not (0.0 < float(reach) <= 16.0):
             raise ValueError(f'PaintResidue: reach={reach!r} must be a number with 0 < reach <= 16 (metres)')
-        if not isnum(clear) or not (0.0 <= float(clear) < float(reach)):
+        if not _number(clear) or not (0.0 <= float(clear) < float(reach)):
             raise ValueError(f'PaintResidue: clear={clear!r} must be a number with 0 <= clear < reach={reach!r}')
-        if not isnum(z_tol) or not float(z_tol) >= 0.0:
+        if not _number(z_tol) or not float(z_tol) >= 0.0:
             raise ValueError(f'PaintResidue: z_tol={z_tol!r} must be a number >= 0')
-        if not isnum(cell) or not (0.0 < float(cell) < math.inf):
+        if not _number(cell) or not (0.0 < float(cell) < math.inf):
             raise ValueError(f'PaintResidue: cell={cell!r} must be a finite size > 0')
         if isinstance(connectivity, bool) or connectivity not in (4, 8):
             raise ValueError(f'PaintResidue: connectivity={connectivity!r} is neither 4 nor 8')
         for name, v in (('min_cells', min_cells), ('min_points', min_points)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
+            if not _whole(v) or int(v) < 1:
                 raise ValueError(f'PaintResidue: {name}={v!r} must be a whole number >= 1')
-        if not isnum(elongated) or not (1.0 <= float(elongated) < math.inf):
+        if not _number(elongated) or not (1.0 <= float(elongated) < math.inf):
             raise ValueError(f'PaintResidue: elongated={elongated!r} must be a finite ratio >= 1')
-        if not isnum(angle_tol_deg) or not (0.0 <= float(angle_tol_deg) <= 45.0):
+        if not _number(angle_tol_deg) or not (0.0 <= float(angle_tol_deg) <= 45.0):
             raise ValueError(f'PaintResidue: angle_tol_deg={angle_tol_deg!r} must be a number in 0 .. 45 (degrees)')
-        for k, v in (('min_intensity', float(min_intensity)), ('clear', float(clear)), ('reach', float(reach)), ('z_tol', float(z_tol)),
-                     ('cell', float(cell)), ('connectivity', int(connectivity)), ('min_cells', int(min_cells)), ('min_points', int(min_points)),
-                     ('elongated', float(elongated)), ('angle_tol_deg', float(angle_tol_deg))):
-            object.__setattr__(self, k, v)
-
-    def __setattr__(self, name, value):
-        raise AttributeError('PaintResidue is immutable')
-
-    def __delattr__(self, name):
-        raise AttributeError('PaintResidue is immutable')
-
-    def __repr__(self):
-        return 'PaintResidue(' + ', '.join(f'{k}={getattr(self, k)!r}' for k in self.__slots__) + ')'
-
-    def __eq__(self, other):
-        return isinstance(other, PaintResidue) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
-
-    def __hash__(self):
-        return hash(tuple(getattr(self, k) for k in self.__slots__))
+        self._set(min_intensity=float(min_intensity), clear=float(clear), reach=float(reach), z_tol=float(z_tol), cell=float(cell),
+                  connectivity=int(connectivity), min_cells=int(min_cells), min_points=int(min_points), elongated=float(elongated),
+                  angle_tol_deg=float(angle_tol_deg))
 
 
 def residue_index_cell(residue):
@@ -1460,14 +1265,19 @@ def decode_points(records_u8, record_len, n, scale, offset, shift=None, normalis
         return _decode_select(records_u8, record_len, n, scale, offset, shift, normalise, out, point_format, select, return_hist)
     if return_hist:
         raise ValueError('las_io.decode_points: return_hist needs select= (PointFilter(drop_withheld=False) keeps every record)')
-    if out is None:
-        out = torch.empty((n, 4), device=records_u8.device, dtype=torch.float32)
-    elif tuple(out.shape) != (n, 4) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != records_u8.device:
-        raise ValueError(f'las_io.decode_points: out must be a contiguous [{n},4] float32 tensor on {records_u8.device}')
-    d3 = lambda v: (C.c_double * 3)(*[float(x) for x in v])
+    out = _decode_out(out, n, records_u8.device)
     check(lib().lm_las_decode_points(C.c_void_p(torch._C._cuda_getCurrentRawStream(records_u8.device.index)), C.c_void_p(records_u8.data_ptr()),
-                                     int(record_len), int(n), d3(scale), d3(offset), d3(shift) if shift is not None else None,
+                                     int(record_len), int(n), _d3(scale), _d3(offset), _d3(shift) if shift is not None else None,
                                      INTEN_MIN, INTEN_MAX, int(normalise), C.c_void_p(out.data_ptr())))
+    return out
+
+
+def _decode_out(out, n, device):
+    """-> `out` after its check, or a new [n,4] float32 tensor on `device`: where decode_points writes its rows."""
+    if out is None:
+        return torch.empty((n, 4), device=device, dtype=torch.float32)
+    if tuple(out.shape) != (n, 4) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != device:
+        raise ValueError(f'las_io.decode_points: out must be a contiguous [{n},4] float32 tensor on {device}')
     return out
 
 
@@ -1478,17 +1288,13 @@ def _decode_select(records_u8, record_len, n, scale, offset, shift, normalise, o
         raise ValueError('las_io.decode_points: select= needs point_format (classification and flags sit in other bits from format 6 on)')
     sel = select.for_format(point_format).as_struct()
     dev = records_u8.device
-    if out is None:
-        out = torch.empty((n, 4), device=dev, dtype=torch.float32)
-    elif tuple(out.shape) != (n, 4) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
-        raise ValueError(f'las_io.decode_points: out must be a contiguous [{n},4] float32 tensor on {dev}')
+    out = _decode_out(out, n, dev)
     L = lib()
     need = int(L.lm_las_select_workspace_bytes(int(n)))
     ws = torch.empty((max(need, 4),), device=dev, dtype=torch.uint8)
     meta = torch.empty((257,), device=dev, dtype=torch.int64)          # kept, then the class histogram
-    d3 = lambda v: (C.c_double * 3)(*[float(x) for x in v])
     check(L.lm_las_decode_select(C.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index)), C.c_void_p(records_u8.data_ptr()),
-                                 int(record_len), int(point_format), int(n), d3(scale), d3(offset), d3(shift) if shift is not None else None,
+                                 int(record_len), int(point_format), int(n), _d3(scale), _d3(offset), _d3(shift) if shift is not None else None,
                                  INTEN_MIN, INTEN_MAX, int(normalise), C.byref(sel), C.c_void_p(ws.data_ptr()), need,
                                  C.c_void_p(out.data_ptr()), C.c_void_p(meta.data_ptr()),
                                  C.c_void_p(meta.data_ptr() + 8) if return_hist else None))
@@ -1501,15 +1307,12 @@ def _decode_select(records_u8, record_len, n, scale, offset, shift, normalise, o
 def _read(path, device, shift, normalise, select=None, class_hist=False):
     data = np.fromfile(path, dtype=np.uint8)
     h = parse_header(data)
-    n, rl, off = h['n_points'], h['record_len'], h['offset_to_points']
+    n, rl = h['n_points'], h['record_len']
     if select is not None:
         select.for_format(h['point_format'])                          # refused before anything is uploaded
     elif class_hist:
         raise ValueError('las_io: class_hist needs select= (PointFilter(drop_withheld=False) keeps every record)')
-    nbytes = n * rl
-    padded = np.zeros(((nbytes + 3) // 4 * 4,), dtype=np.uint8)
-    padded[:nbytes] = data[off:off + nbytes]
-    rec = torch.from_numpy(padded).to(device, non_blocking=True)
+    rec = _upload_records(data, h, device)
     if select is None:
         return decode_points(rec, rl, n, h['scale'], h['offset'], shift, normalise), h
     res = decode_points(rec, rl, n, h['scale'], h['offset'], shift, normalise, point_format=h['point_format'], select=select,

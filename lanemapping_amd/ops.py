@@ -783,15 +783,35 @@ def line_index(segments, half_width, cell=None, device='cuda:0'):
     return LineIndex(up(seg), up(cell_start), up(cell_segs), g, np.float32(half_width))
 
 
-def label_points(points, index, z_tol, min_intensity=None, want_dist2=False):
-    """points [N,4] f32 on device (x, y, z, intensity in the frame of the index' segments) -> line [N] int32: 0, or the number (from 1) of
-    the line whose band the point lies in, the nearest winning (the rule: include/lanemap_hip.h).  want_dist2: -> (line, dist2 [N] f32),
-    the squared horizontal distance to the winner, +inf without one.  No synchronisation."""
+def _line_args(who, points, index, *stations):
+    """The argument checks of label_points, line_profile and line_cross: points [N,4] float32, contiguous, on the device; index an
+    ops.LineIndex; stations (passed where the entry takes them) the ops.LineStations of the same segments."""
     if not points.is_cuda:
         raise LanemapHipError('lanemapping_amd ops need tensors on an MI355X (HIP) device; no CPU fallback exists')
     assert points.dim() == 2 and points.shape[1] == 4 and points.is_contiguous() and points.dtype == torch.float32
     if not isinstance(index, LineIndex):
-        raise TypeError(f'label_points: index must be an ops.LineIndex (ops.line_index), not {type(index).__name__}')
+        raise TypeError(f'{who}: index must be an ops.LineIndex (ops.line_index), not {type(index).__name__}')
+    for st in stations:
+        if not isinstance(st, LineStations):
+            raise TypeError(f'{who}: stations must be an ops.LineStations (ops.line_stations), not {type(st).__name__}')
+        if st.n_segments != index.n_segments:
+            raise ValueError(f'{who}: stations hold {st.n_segments} rows, the index {index.n_segments} segments')
+
+
+def _table_out(who, shape, out, device):
+    """-> `out` after its check, or a new int64 tensor of `shape` on `device`: the table an accumulating entry writes."""
+    if out is None:
+        return torch.empty(shape, device=device, dtype=torch.int64)
+    if tuple(out.shape) != tuple(shape) or out.dtype != torch.int64 or not out.is_contiguous() or out.device != device:
+        raise ValueError(f'{who}: out must be a contiguous [{",".join(str(v) for v in shape)}] int64 tensor on {device}')
+    return out
+
+
+def label_points(points, index, z_tol, min_intensity=None, want_dist2=False):
+    """points [N,4] f32 on device (x, y, z, intensity in the frame of the index' segments) -> line [N] int32: 0, or the number (from 1) of
+    the line whose band the point lies in, the nearest winning (the rule: include/lanemap_hip.h).  want_dist2: -> (line, dist2 [N] f32),
+    the squared horizontal distance to the winner, +inf without one.  No synchronisation."""
+    _line_args('label_points', points, index)
     N = int(points.shape[0])
     line = torch.empty((N,), device=points.device, dtype=torch.int32)
     dist2 = torch.empty((N,), device=points.device, dtype=torch.float32) if want_dist2 else None
@@ -842,29 +862,13 @@ def line_profile(points, index, stations, z_tol, min_intensity=None, out=None):
     1/1024 m, left positive; iq the intensity rounded into 0..65535); an empty bin reads 0, 0, 0, 0, 2^31 - 1, -2^31.  index: the
     ops.LineIndex, stations: the ops.LineStations of the same segments.  out: a bins tensor of an earlier call to add to.  Integer sums,
     minima and maxima only: the same bits whatever the order of the points.  No synchronisation."""
-    if not points.is_cuda:
-        raise LanemapHipError('lanemapping_amd ops need tensors on an MI355X (HIP) device; no CPU fallback exists')
-    assert points.dim() == 2 and points.shape[1] == 4 and points.is_contiguous() and points.dtype == torch.float32
-    if not isinstance(index, LineIndex):
-        raise TypeError(f'line_profile: index must be an ops.LineIndex (ops.line_index), not {type(index).__name__}')
-    if not isinstance(stations, LineStations):
-        raise TypeError(f'line_profile: stations must be an ops.LineStations (ops.line_stations), not {type(stations).__name__}')
-    if stations.n_segments != index.n_segments:
-        raise ValueError(f'line_profile: stations hold {stations.n_segments} rows, the index {index.n_segments} segments')
-    bins = _profile_out('line_profile', stations, out, points.device)
+    _line_args('line_profile', points, index, stations)
+    bins = _table_out('line_profile', (stations.n_bins, 6), out, points.device)
     N = int(points.shape[0])
     mi = math.nan if min_intensity is None else float(min_intensity)
     check(lib().lm_line_profile_points(_stream(), _ptr(points) if N else None, N, *index.args(), *stations.args(), float(z_tol), mi,
                                        int(out is not None), _ptr(bins) if stations.n_bins else None, stations.n_bins))
     return bins
-
-
-def _profile_out(who, stations, out, device):
-    if out is None:
-        return stations.new_bins()
-    if tuple(out.shape) != (stations.n_bins, 6) or out.dtype != torch.int64 or not out.is_contiguous() or out.device != device:
-        raise ValueError(f'{who}: out must be a contiguous [{stations.n_bins},6] int64 tensor on {device}')
-    return out
 
 
 def cross_cells(half_width, lateral_q):
@@ -877,14 +881,6 @@ def cross_cells(half_width, lateral_q):
     return hq, 2 * hq // int(lateral_q) + 1
 
 
-def _cross_out(who, stations, nl, out, device):
-    if out is None:
-        return torch.empty((stations.n_bins, nl, 4), device=device, dtype=torch.int64)
-    if tuple(out.shape) != (stations.n_bins, nl, 4) or out.dtype != torch.int64 or not out.is_contiguous() or out.device != device:
-        raise ValueError(f'{who}: out must be a contiguous [{stations.n_bins},{nl},4] int64 tensor on {device}')
-    return out
-
-
 def line_cross(points, index, stations, z_tol, lateral_q, paint_iq, out=None):
     """points [N,4] f32 on device -> cells [n_bins, nl, 4] int64 on device: per station bin of every line a row of nl lateral cells, each
     n, n_paint, sum iq, sum zq over the returns the labelling rule gives that line without a min_intensity (the rule:
@@ -892,17 +888,9 @@ def line_cross(points, index, stations, z_tol, lateral_q, paint_iq, out=None):
     return is paint when its intensity, rounded into 0..65535, is at least paint_iq; zq its height above the line in 1/1024 m); an empty
     cell reads four zeros.  index: the ops.LineIndex, stations: the ops.LineStations of the same segments.  out: the cells of an earlier
     call to add to.  Integer sums only: the same bits whatever the order of the points.  No synchronisation."""
-    if not points.is_cuda:
-        raise LanemapHipError('lanemapping_amd ops need tensors on an MI355X (HIP) device; no CPU fallback exists')
-    assert points.dim() == 2 and points.shape[1] == 4 and points.is_contiguous() and points.dtype == torch.float32
-    if not isinstance(index, LineIndex):
-        raise TypeError(f'line_cross: index must be an ops.LineIndex (ops.line_index), not {type(index).__name__}')
-    if not isinstance(stations, LineStations):
-        raise TypeError(f'line_cross: stations must be an ops.LineStations (ops.line_stations), not {type(stations).__name__}')
-    if stations.n_segments != index.n_segments:
-        raise ValueError(f'line_cross: stations hold {stations.n_segments} rows, the index {index.n_segments} segments')
+    _line_args('line_cross', points, index, stations)
     hq, nl = cross_cells(index.half_width, lateral_q)
-    cells = _cross_out('line_cross', stations, nl, out, points.device)
+    cells = _table_out('line_cross', (stations.n_bins, nl, 4), out, points.device)
     N, n_cells = int(points.shape[0]), stations.n_bins * nl
     check(lib().lm_line_cross_points(_stream(), _ptr(points) if N else None, N, *index.args(), *stations.args(), float(z_tol), int(lateral_q),
                                      int(paint_iq), int(out is not None), _ptr(cells) if n_cells else None, n_cells))

@@ -340,18 +340,33 @@ class Runner:
                 plan.append(real)
         return plan
 
+    @staticmethod
+    def _result_lines(result):
+        """The lines a LAS route returns, as the stages after the map take them: result = (lines3d, merged) -> `merged`, or the tiles' 3-D
+        lines in tile-name order when nothing was merged."""
+        lines3d, merged = result
+        return list(merged) if len(merged) else [l for name in sorted(lines3d) for l in lines3d[name]]
+
+    @staticmethod
+    def _each_once(files):
+        """files: (path, shift, select) in input order -> the same list with every real file once: a file listed several times (under
+        another name too) keeps the read offset and filter of its first listing."""
+        seen, once = set(), []
+        for path, shift, select in files:
+            if os.path.realpath(path) not in seen:
+                seen.add(os.path.realpath(path))
+                once.append((path, shift, select))
+        return once
+
     def _label_inputs(self, labels, files, result, out_dir):
         """The last stage of the LAS routes: every input file (files: (path, shift, select) in input order) labelled against the lines the
         call returns - `merged`, or the tiles' 3-D lines in tile-name order when nothing was merged - and written to
         <out_dir>/labelled/<basename>; what was done goes to <out_dir>/params/labels.json as {file: [records, labelled, [per-line counts]]}."""
         from . import las_io
-        lines3d, merged = result
-        lines = list(merged) if len(merged) else [l for name in sorted(lines3d) for l in lines3d[name]]
-        done, todo = {}, self._label_plan([f[0] for f in files])
-        for path, shift, select in files:
-            if os.path.realpath(path) not in todo:
-                continue                                                   # (listed before: labelled once)
-            todo.remove(os.path.realpath(path))
+        lines = self._result_lines(result)
+        self._label_plan([f[0] for f in files])                            # (a basename collision is refused before anything is read)
+        done = {}
+        for path, shift, select in self._each_once(files):
             base = os.path.basename(path)
             r = las_io.label_las(path, os.path.join(out_dir, 'labelled', base), lines, labels, shift, select=select, device=self.device)
             done[base] = [r['records'], r['labelled'], r['per_line']]
@@ -368,13 +383,8 @@ class Runner:
         and one read-back -, the colour table goes to <out_dir>/params/marking_colours.npy, and every line's summary in markings.json also
         carries the keys of las_io.marking_colours.  markings.npy holds the same bytes either way."""
         from . import las_io
-        lines3d, merged = result
-        lines = list(merged) if len(merged) else [l for name in sorted(lines3d) for l in lines3d[name]]
-        seen, once = set(), []
-        for path, shift, select in files:
-            if os.path.realpath(path) not in seen:
-                seen.add(os.path.realpath(path))
-                once.append((path, shift, select))
+        lines = self._result_lines(result)
+        once = self._each_once(files)
         if colour is None:
             bins, bin_start = las_io.survey_files(once, lines, survey, device=self.device)
             summary = las_io.marking_summary(bins, bin_start, survey)
@@ -398,13 +408,8 @@ class Runner:
         <out_dir>/out_pc_seq_json_dir/merged_snapped.txt and merged_snapped_downsample.txt, in the format of merged.txt.  Without lines
         all four are empty."""
         from . import las_io, merge_lines as ml
-        lines3d, merged = result
-        lines = list(merged) if len(merged) else [l for name in sorted(lines3d) for l in lines3d[name]]
-        seen, once = set(), []
-        for path, shift, select in files:
-            if os.path.realpath(path) not in seen:
-                seen.add(os.path.realpath(path))
-                once.append((path, shift, select))
+        lines = self._result_lines(result)
+        once = self._each_once(files)
         cells, bin_start = las_io.cross_files(once, lines, cross, device=self.device)
         summary = las_io.cross_summary(cells, bin_start, cross)
         snapped = las_io.snap_lines(lines, summary, bin_start, cross)
@@ -424,13 +429,8 @@ class Runner:
         <out_dir>/params/residue.npy ([K,12] int64), the cells to residue_cells.npy ([M,3] int32: cx, cy, component) and what
         las_io.residue_summary reads off them to residue.json as {blob number from 1: summary}.  Without lines all three are empty."""
         from . import las_io
-        lines3d, merged = result
-        lines = list(merged) if len(merged) else [l for name in sorted(lines3d) for l in lines3d[name]]
-        seen, once = set(), []
-        for path, shift, select in files:
-            if os.path.realpath(path) not in seen:
-                seen.add(os.path.realpath(path))
-                once.append((path, shift, select))
+        lines = self._result_lines(result)
+        once = self._each_once(files)
         par_dir = self._params_dir(out_dir)
         if lines and once:
             blobs = las_io.residue_files(once, lines, residue, device=self.device)

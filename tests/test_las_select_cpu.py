@@ -250,3 +250,122 @@ def test_header_declares_the_entry_with_hip_stream_and_the_inventories_hold():
     # the guarded-buffer case the header's NOTE points to exists
     gpu = open(os.path.join(ROOT, 'tests', 'test_gpu_las_select.py')).read()
     assert re.search(r'^def test_select_guards\(', gpu, flags=re.M) and 'lm_las_decode_select(' in gpu
+
+
+# ------------------------------------------------------------------------------------------------ the ten option classes
+OPTION_CASES = [
+    (las_io.PointFilter, dict(classes=[11, 2], drop_keypoint=True, returns='last', z_range=(-1, 2.5))),
+    (las_io.GroundFilter, dict(height_range=(-0.5, 1), cell_px=16, datum=False, datum_margin=0.5)),
+    (las_io.IntensityStretch, dict(percentiles=(2, 99), scope='strip', white=240, min_span=8, min_points=10, fallback=(100, 2000))),
+    (las_io.ElevationDrape, dict(radius_px=2, min_pixels=3, fit='none')),
+    (las_io.GapFill, dict(radius_px=2, max_radius_px=3, coverage=0.5)),
+    (las_io.MarkingLabels, dict(half_width=0.25, z_tol=1, min_intensity=700, marking_class=70, line_ids=False)),
+    (las_io.MarkingSurvey, dict(bin=0.5, half_width=0.25, z_tol=1, min_intensity=900, min_points=2, max_gap=1, solid_cover=0.75)),
+    (las_io.MarkingColour, dict(yellow_ratio=0.5, yellow_share=0.25, min_coloured=3)),
+    (las_io.CrossSection, dict(paint_intensity=9000)),
+    (las_io.PaintResidue, dict(min_intensity=9000)),
+]
+
+
+def test_the_option_case_list_names_every_option_class():
+    """Every class of las_io that declares __slots__ of its own is in OPTION_CASES: a new stage's options get the same checks."""
+    slotted = {c for c in vars(las_io).values() if isinstance(c, type) and c.__module__ == las_io.__name__ and c.__dict__.get('__slots__')}
+    assert slotted == {c for c, _ in OPTION_CASES} and len(OPTION_CASES) == 10
+
+
+@pytest.mark.parametrize('cls, kwargs', OPTION_CASES, ids=[c.__name__ for c, _ in OPTION_CASES])
+def test_option_classes_are_values(cls, kwargs):
+    """What the ten option classes share: repr round-trips, equality and hash by value within the class only, no assignment, no deletion,
+    no instance dictionary, the arguments in __slots__ order."""
+    name = cls.__name__
+    x = cls(**kwargs)
+    values = tuple(getattr(x, k) for k in cls.__slots__)
+    y = eval(repr(x), {name: cls})
+    assert y == x and y is not x and hash(y) == hash(x) and not (y != x)
+    assert cls(**kwargs) == x and hash(cls(**kwargs)) == hash(x)
+    other = next(c(**kw) for c, kw in OPTION_CASES if c is not cls)
+    assert x != other and not (x == other) and x != values and not (x == values) and x != None    # noqa: E711
+    for k in cls.__slots__:
+        with pytest.raises(AttributeError, match=f'{name} is immutable'):
+            setattr(x, k, getattr(x, k))
+        with pytest.raises(AttributeError, match=f'{name} is immutable'):
+            delattr(x, k)
+    with pytest.raises(AttributeError):
+        x.no_such_option = 1
+    assert not hasattr(x, '__dict__')
+    assert repr(x) == name + '(' + ', '.join(f'{k}={v!r}' for k, v in zip(cls.__slots__, values)) + ')'
+    assert tuple(getattr(x, k) for k in cls.__slots__) == values, 'a refused assignment changed nothing'
+
+
+# ------------------------------------------------------------------------------------------------ the Runner's stages after the map
+def _stage_runner():
+    from lanemapping_amd.runner import Runner
+    rn = Runner.__new__(Runner)
+    rn.device = 'cuda:0'
+    return rn
+
+
+def test_runner_stages_take_each_real_file_once_and_the_lines_the_call_returns(tmp_path, monkeypatch):
+    """The four stages after the map (label, survey with and without colour, cross, residue) hand las_io each real file once, in input
+    order, with the (path, shift, select) of its first listing - a symbolic link to a listed file is that file -, and the lines the call
+    returns: `merged` when there are any, else the tiles' 3-D lines in the order of the sorted tile names.  las_io's file functions are
+    replaced by recorders, so nothing here needs a GPU."""
+    from lanemapping_amd import ops
+    a, b, link = str(tmp_path / 'a.las'), str(tmp_path / 'b.las'), str(tmp_path / 'again.las')
+    for p in (a, b):
+        open(p, 'wb').close()
+    os.symlink(a, link)
+    sel = PointFilter(classes=[2])
+    files = [(b, [5.0, 0.0, 0.0], None), (a, [1.0, 2.0, 3.0], sel), (b, [6.0, 0.0, 0.0], sel), (link, [7.0, 0.0, 0.0], None), (a, [8.0, 0.0, 0.0], None)]
+    once = [(b, [5.0, 0.0, 0.0], None), (a, [1.0, 2.0, 3.0], sel)]
+    line = lambda x: np.array([[x, 0.0, 0.0], [x, 4.0, 0.0]])
+    lines3d = {'t2': [line(3.0)], 't10': [line(1.0), line(2.0)]}                  # 't10' sorts before 't2'
+    merged = [line(9.0), line(8.0)]
+    got = {}
+    real = {k: getattr(las_io, k) for k in ('survey_files', 'survey_colour_files', 'cross_files')}
+
+    def label_las(path, out_path, lines, labels, shift, select=None, device='cuda:0'):
+        got.setdefault('label', []).append(((path, shift, select), lines, out_path))
+        return {'records': 0, 'labelled': 0, 'per_line': [0] * len(lines)}
+
+    def table(kind):
+        def fake(files_, lines, *options, device='cuda:0'):
+            got[kind] = (list(files_), lines)
+            return real[kind]([], lines, *options, device=device)              # the tables of no file: host only
+        return fake
+
+    def residue_files(files_, lines, residue, device='cuda:0'):
+        got['residue'] = (list(files_), lines)
+        return ops.ResidueBlobs(np.zeros((0, 2), np.int32), np.zeros(0, np.int32), np.zeros((0, 12), np.int64),
+                                {'x0': 0.0, 'y0': 0.0, 'cell': residue.cell, 'nx': 1, 'ny': 1, 'shift': [0.0, 0.0, 0.0]})
+
+    monkeypatch.setattr(las_io, 'label_las', label_las)
+    monkeypatch.setattr(las_io, 'residue_files', residue_files)
+    for kind in real:
+        monkeypatch.setattr(las_io, kind, table(kind))
+    rn = _stage_runner()
+    survey, colour = las_io.MarkingSurvey(), las_io.MarkingColour()
+    for tag, result, want in (('merged', (lines3d, merged), merged), ('tiles', (lines3d, []), [line(1.0), line(2.0), line(3.0)])):
+        got.clear()
+        out = str(tmp_path / tag)
+        rn._label_inputs(las_io.MarkingLabels(), files, result, out)
+        rn._survey_inputs(survey, files, result, out)
+        rn._survey_inputs(survey, files, result, out, colour)
+        rn._cross_inputs(las_io.CrossSection(9000.0), files, result, out)
+        rn._residue_inputs(las_io.PaintResidue(9000.0), files, result, out)
+        assert [g[0] for g in got['label']] == once, tag
+        assert [g[2] for g in got['label']] == [os.path.join(out, 'labelled', 'b.las'), os.path.join(out, 'labelled', 'a.las')]
+        for kind in ('survey_files', 'survey_colour_files', 'cross_files', 'residue'):
+            assert got[kind][0] == once, (tag, kind)
+        for lines in [g[1] for g in got['label']] + [got[k][1] for k in ('survey_files', 'survey_colour_files', 'cross_files', 'residue')]:
+            assert len(lines) == len(want) and all(np.array_equal(l, w) for l, w in zip(lines, want)), tag
+        assert sorted(os.listdir(os.path.join(out, 'params'))) == ['cross_sections.json', 'cross_sections.npy', 'labels.json', 'marking_colours.npy',
+                                                                   'markings.json', 'markings.npy', 'residue.json', 'residue.npy', 'residue_cells.npy']
+    # two different files under one basename: refused by the label stage before anything is labelled
+    os.makedirs(str(tmp_path / 'd'))
+    twin = str(tmp_path / 'd' / 'a.las')
+    open(twin, 'wb').close()
+    got.clear()
+    with pytest.raises(ValueError, match="share the basename 'a.las'"):
+        rn._label_inputs(las_io.MarkingLabels(), [(a, None, None), (twin, None, None)], (lines3d, merged), str(tmp_path / 'twin'))
+    assert 'label' not in got and not os.path.exists(str(tmp_path / 'twin'))
