@@ -7,6 +7,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'liblanemap_hip.so')
+HEADER = os.path.join(os.path.dirname(HERE), 'include', 'lanemap_hip.h')   # csrc/common.h includes it: every source depends on it
 DIAG_SRC = os.path.join(os.path.dirname(HERE), 'tests', 'hip')
 DIAG_LIB = os.path.join(HERE, 'liblanemap_diag.so')
 DIAG_SOURCES = ['lds_state.hip']        # same compiler and flags as SOURCES; linked with errors.cpp's helpers into a library of their own
@@ -32,7 +33,7 @@ def _stale():
     if not os.path.exists(LIB) or (diag and not os.path.exists(DIAG_LIB)):
         return True
     t = min([os.path.getmtime(LIB)] + ([os.path.getmtime(DIAG_LIB)] if diag else []))
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(DIAG_SRC, f) for f in diag] + [os.path.abspath(__file__)]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(DIAG_SRC, f) for f in diag] + [os.path.abspath(__file__), HEADER]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

@@ -5,15 +5,11 @@
 #include <cstdint>
 #include <cstdio>
 
-#define LM_API extern "C" __attribute__((visibility("default")))
+// The C ABI - every entry's prototype, the structs that cross it, the LM_OK .. and LM_ACT_.. codes - has one definition, the public
+// header.  A definition below that disagrees with its prototype does not compile.
+#include "../../include/lanemap_hip.h"
 
-enum {
-    LM_OK = 0,
-    LM_ERR_ARG = 1,      // unsupported shape / null pointer
-    LM_ERR_HIP = 2,      // HIP runtime error (see lm_last_error)
-    LM_ERR_NO_DEVICE = 3,
-    LM_ERR_CAPACITY = 4  // an output buffer is too small; the needed size has been reported
-};
+#define LM_API extern "C" __attribute__((visibility("default")))   // on the definition: exported; the prototype is the header's
 
 void lm_set_error(const char* fmt, ...);
 int lm_ensure_dynamic_lds(const void* kernel, size_t bytes);   // per device and kernel, thread-safe (errors.cpp)
@@ -65,9 +61,6 @@ static inline int lm_refuse_capture(void* stream, const char* who, const char* w
 static inline int lm_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 static inline long lm_cdivl(long a, long b) { return (a + b - 1) / b; }
 static inline size_t lm_align256(size_t v) { return (v + 255) / 256 * 256; }   // workspace segments start on 256 bytes
-
-// activation codes shared by the GEMM/conv epilogues
-enum { LM_ACT_NONE = 0, LM_ACT_RELU = 1, LM_ACT_GELU = 2 };
 
 #ifdef __HIPCC__
 // Zeroing inside an entry that may be captured: a kernel, never hipMemsetAsync.  Replays of a captured memset node were seen to leave

@@ -24,23 +24,12 @@
 #include "las_record.h"
 
 #include <cmath>
-#include <map>
-#include <mutex>
-#include <utility>
 #include <vector>
-
-struct LmLasSelect {          // include/lanemap_hip.h
-    unsigned class_mask[8];
-    unsigned drop_flags;
-    int returns;
-    float z_lo, z_hi;
-};
 
 namespace {
 
 constexpr int PER = 4;                   // points per lane of label_points_kernel: four 16-byte loads in flight
 constexpr int CHUNK = 256 * PER;         // points per workgroup
-constexpr int REC_GROUPS = 4096;         // cap on the workgroups of the record kernel (it launches as many as are resident at once)
 constexpr int HIST = 1024;               // labels counted in LDS; a larger label adds to HBM directly
 
 // IndexDev, label_range and label_search: label_rule.h
@@ -125,29 +114,6 @@ __global__ __launch_bounds__(256) void las_label_kernel(const unsigned* rec, int
     if (counts)                                                            // integer adds: exact whatever the order
         for (int k = threadIdx.x; k < HIST && k <= L; k += 256)
             if (hist[k]) atomicAdd(&counts[k], (unsigned long long)hist[k]);
-}
-
-// Workgroups of las_label_kernel the current device holds at once for `lds` bytes of dynamic LDS, asked of the runtime once per
-// (device, lds) and kept.  The current device: like every entry of this library the call launches on it, so it must be the stream's.  The
-// number only sizes the grid; the kernel's block loop is right for any.
-int resident_groups(size_t lds, long& groups) {
-    static std::mutex mu;
-    static std::map<std::pair<int, size_t>, long> known;
-    int dev_id = 0;
-    LM_HIP(hipGetDevice(&dev_id));
-    std::lock_guard<std::mutex> lock(mu);
-    const auto it = known.find({dev_id, lds});
-    if (it != known.end()) {
-        groups = it->second;
-        return LM_OK;
-    }
-    int per_cu = 0, cus = 0;
-    LM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, las_label_kernel, 256, lds));
-    LM_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev_id));
-    groups = (long)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 256);
-    groups = groups < REC_GROUPS ? groups : REC_GROUPS;
-    known[{dev_id, lds}] = groups;
-    return LM_OK;
 }
 
 // distance in the plane from the point c to the segment a + t d, t in [0, 1] (double)
@@ -289,11 +255,7 @@ LM_API int lm_las_label_records(void* hip_stream, const unsigned char* records, 
                                 const float* segments, long S, const LmLineGrid* grid, const int* cell_start, const int* cell_segs,
                                 float half_width, float z_tol, float min_intensity, int marking_class, int write_line_id,
                                 unsigned char* records_out, int* line, unsigned long* counts, int L) {
-    static const int min_len[11] = {20, 28, 26, 34, 57, 63, 30, 36, 38, 59, 67};
-    LM_REQUIRE(point_format >= 0 && point_format <= 10, "las_label_records: unknown point data record format point_format=%d", point_format);
-    LM_REQUIRE(record_len >= min_len[point_format] && record_len <= 160, "las_label_records: bad record_len=%d for format %d (%d .. 160)",
-               record_len, point_format, min_len[point_format]);
-    LM_REQUIRE(n >= 0 && n <= 2147483647L, "las_label_records: n=%ld records, at most 2^31 - 1 are supported", n);
+    if (int e = las_check_records("las_label_records", point_format, record_len, n)) return e;
     LM_REQUIRE(marking_class >= 0 && marking_class <= (point_format >= 6 ? 255 : 31),
                "las_label_records: marking_class=%d does not fit format %d (0 .. %d)", marking_class, point_format, point_format >= 6 ? 255 : 31);
     LM_REQUIRE(L >= 0, "las_label_records: L=%d lines", L);
@@ -307,30 +269,20 @@ LM_API int lm_las_label_records(void* hip_stream, const unsigned char* records, 
     LM_REQUIRE(((uintptr_t)records_out & 3) == 0, "las_label_records: records_out is not 4-byte aligned");
     LM_REQUIRE(((uintptr_t)line & 3) == 0, "las_label_records: line is not 4-byte aligned");
     LM_REQUIRE(((uintptr_t)counts & 7) == 0, "las_label_records: counts is not 8-byte aligned");
-    LasSel Sel{};
-    if (select) {
-        LM_REQUIRE(select->returns >= 0 && select->returns <= 3, "las_label_records: select returns=%d is none of all (0), first (1), last (2), single (3)",
-                   select->returns);
-        LM_REQUIRE(select->drop_flags < 16u, "las_label_records: select drop_flags=%u has bits beyond synthetic | key-point | withheld | overlap",
-                   select->drop_flags);
-        LM_REQUIRE(select->z_lo == select->z_lo && select->z_hi == select->z_hi, "las_label_records: select z_lo / z_hi must not be NaN");
-        for (int k = 0; k < 8; ++k) Sel.cls[k] = select->class_mask[k];
-        Sel.drop = select->drop_flags, Sel.returns = select->returns, Sel.z_lo = select->z_lo, Sel.z_hi = select->z_hi;
-    }
-    Sel.fmt6 = point_format >= 6;
+    LasSel Sel;
+    if (int e = las_check_select("las_label_records", "select ", select, point_format, Sel)) return e;
     I.min_inten = min_intensity;
     hipStream_t s = (hipStream_t)hip_stream;
     const long nblk = (n + 255) / 256;
-    const size_t lds = ((size_t)256 * record_len + 3) / 4 * 4;
+    const size_t lds = las_stage_bytes(record_len);
     // every workgroup walks its share of the blocks: as many workgroups as the device holds at once, so that none waits for a slot while
     // the others are half way through (registers and LDS decide how many that is)
     long resident = 0;
     if (n > 0)
-        if (int e = resident_groups(lds, resident)) return e;
+        if (int e = resident_groups(las_label_kernel, lds, resident)) return e;
     if (counts) LM_HIP(lm_zero_async(counts, ((size_t)L + 1) * sizeof(unsigned long), s));
     if (n == 0) return LM_OK;
-    const double sh[3] = {shift ? shift[0] : 0.0, shift ? shift[1] : 0.0, shift ? shift[2] : 0.0};
-    const LasXf X{scale[0], scale[1], scale[2], offset[0] - sh[0], offset[1] - sh[1], offset[2] - sh[2], 0.f, 1.f, 0};   // raw intensity
+    const LasXf X = las_xf(scale, offset, shift, 0.f, 1.f, 0);         // raw intensity
     const unsigned groups = (unsigned)(nblk < resident ? nblk : resident);
     hipLaunchKernelGGL(las_label_kernel, dim3(groups), dim3(256), lds, s, reinterpret_cast<const unsigned*>(records), record_len, n, nblk, X,
                        Sel, select ? 1 : 0, I, point_format >= 6 ? 1 : 0, (unsigned)marking_class, write_line_id ? 1 : 0,

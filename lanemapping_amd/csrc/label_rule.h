@@ -9,14 +9,6 @@
 
 typedef float lab_f32x4 __attribute__((ext_vector_type(4)));
 
-struct LmLineGrid {           // include/lanemap_hip.h
-    double x0, y0, cell;
-    int nx, ny;
-    int min_line, max_line;
-    long n_segments, n_entries;
-    float half_width;
-};
-
 namespace {
 
 constexpr long MAX_CELLS = 1L << 24;
@@ -99,6 +91,15 @@ inline int check_index(const char* who, const LmLineGrid* grid, long S, const vo
     I.cell_segs = reinterpret_cast<const int*>(cell_segs);
     I.x0 = (float)grid->x0, I.y0 = (float)grid->y0, I.inv = (float)(1.0 / grid->cell);
     I.nx = grid->nx, I.ny = grid->ny;
+    return LM_OK;
+}
+
+// the cloud of an entry whose only per-point buffer is points_xyzi (lm_label_points and lm_residue_keys name a second one in the same
+// refusal: their checks stay with them)
+inline int check_points(const char* who, const float* points_xyzi, long N) {
+    LM_REQUIRE(N >= 0 && N <= 2147483647L, "%s: N=%ld points, at most 2^31 - 1 are supported", who, N);
+    LM_REQUIRE(N == 0 || points_xyzi, "%s: null pointer (points_xyzi)", who);
+    LM_REQUIRE(((uintptr_t)points_xyzi & 15) == 0, "%s: points_xyzi is not 16-byte aligned", who);
     return LM_OK;
 }
 

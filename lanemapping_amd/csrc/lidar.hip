@@ -486,12 +486,6 @@ double rdf64(const unsigned char* p) {
 
 }  // namespace
 
-struct LmLasHeader {          // the fields of the public header block the ingest needs
-    int version_major, version_minor, point_format, record_len;
-    long n_points, offset_to_points;
-    double scale[3], offset[3], min_xyz[3], max_xyz[3];
-};
-
 // Parse the LAS public header block (HOST bytes).  Errors: not a LAS file, truncated, compressed (LAZ) or unknown format.
 LM_API int lm_las_parse_header(const unsigned char* bytes, long len, LmLasHeader* h) {
     LM_REQUIRE(bytes && h, "las_parse_header: null pointer");
@@ -517,8 +511,7 @@ LM_API int lm_las_parse_header(const unsigned char* bytes, long len, LmLasHeader
         const long n64 = (long)rd64(bytes + 247);
         if (n64 > 0) h->n_points = n64;
     }
-    static const int min_len[11] = {20, 28, 26, 34, 57, 63, 30, 36, 38, 59, 67};
-    LM_REQUIRE(h->record_len >= min_len[h->point_format], "las_parse_header: record length %d too short for format %d", h->record_len,
+    LM_REQUIRE(h->record_len >= las_min_len[h->point_format], "las_parse_header: record length %d too short for format %d", h->record_len,
                h->point_format);
     LM_REQUIRE(h->offset_to_points >= header_size && h->offset_to_points + h->n_points * h->record_len <= len,
                "las_parse_header: point data (%ld records of %d B at %ld) exceeds the file (%ld B)", h->n_points, h->record_len,
@@ -532,14 +525,14 @@ LM_API int lm_las_decode_points(void* stream, const unsigned char* records, int 
                                 const double* offset, const double* shift, float inten_lo, float inten_hi, int normalise,
                                 float* out_xyzi) {
     LM_REQUIRE(scale && offset && out_xyzi && (records || n == 0), "las_decode_points: null pointer");
+    // (not las_check_records: no format is given, any record_len in 20 .. 160 is taken, and the refusal has its own words)
     LM_REQUIRE(record_len >= 20 && record_len <= 160 && n >= 0, "las_decode_points: bad record length %d", record_len);
     LM_REQUIRE(((uintptr_t)records & 3) == 0 && ((uintptr_t)out_xyzi & 15) == 0, "las_decode_points: buffers must be 4 / 16-byte aligned");
     if (n == 0) return LM_OK;
-    const double sh[3] = {shift ? shift[0] : 0.0, shift ? shift[1] : 0.0, shift ? shift[2] : 0.0};
-    const size_t lds = ((size_t)256 * record_len + 3) / 4 * 4;
-    hipLaunchKernelGGL(las_decode_kernel, dim3(lm_cdiv(n, 256)), dim3(256), lds, (hipStream_t)stream,
-                       reinterpret_cast<const unsigned*>(records), record_len, n, scale[0], scale[1], scale[2], offset[0] - sh[0],
-                       offset[1] - sh[1], offset[2] - sh[2], inten_lo, inten_hi, normalise, reinterpret_cast<float4*>(out_xyzi));
+    const LasXf X = las_xf(scale, offset, shift, inten_lo, inten_hi, normalise);
+    hipLaunchKernelGGL(las_decode_kernel, dim3(lm_cdiv(n, 256)), dim3(256), las_stage_bytes(record_len), (hipStream_t)stream,
+                       reinterpret_cast<const unsigned*>(records), record_len, n, X.sx, X.sy, X.sz, X.ox, X.oy, X.oz, X.lo, X.hi, X.normalise,
+                       reinterpret_cast<float4*>(out_xyzi));
     LM_LAUNCH_CHECK();
     return LM_OK;
 }
@@ -558,7 +551,7 @@ namespace {
 
 constexpr int SEL_HIST_GROUPS = 2048;   // most workgroups of the count pass (8 resident per CU) = columns of the partial class histogram
 
-// (LasXf, LasSel, las_record_xyzi, las_record_keep and las_stage_block: las_record.h, shared with label.hip)
+// (LasXf, LasSel, las_record_xyzi, las_record_keep and las_stage_block: las_record.h, shared with label.hip and profile.hip)
 // counts[b] = kept records of block b, counts[nblk] = 0 (the scan turns it into the total); hist_part (may be NULL) [256][gridDim.x]:
 // the classes of ALL records this workgroup walked, counted in LDS and written once
 __global__ __launch_bounds__(256) void las_select_count_kernel(const unsigned* __restrict__ rec, int record_len, long n, long nblk, LasXf X,
@@ -631,13 +624,6 @@ long sel_groups(long n) { return sel_blocks(n) < SEL_HIST_GROUPS ? sel_blocks(n)
 
 }  // namespace
 
-struct LmLasSelect {          // include/lanemap_hip.h
-    unsigned class_mask[8];
-    unsigned drop_flags;
-    int returns;
-    float z_lo, z_hi;
-};
-
 LM_API long lm_las_select_workspace_bytes(long n) {
     if (n < 0 || n > 2147483647L) return 0;
     const long L = sel_blocks(n) + 1;
@@ -651,15 +637,13 @@ LM_API int lm_las_decode_select(void* hip_stream, const unsigned char* records, 
                                 const double* scale, const double* offset, const double* shift, float inten_lo, float inten_hi,
                                 int normalise, const LmLasSelect* select, void* workspace, long workspace_bytes, float* out_xyzi,
                                 long* kept, unsigned long* class_hist) {
+    // (not las_check_records: any record_len in 20 .. 160 is taken whatever the format, and the refusals have their own words)
     LM_REQUIRE(record_len >= 20 && record_len <= 160, "las_decode_select: bad record length %d", record_len);
     LM_REQUIRE(n >= 0 && n <= 2147483647L, "las_decode_select: n=%ld records, at most 2^31 - 1 are supported", n);
     LM_REQUIRE(point_format >= 0 && point_format <= 10, "las_decode_select: unknown point data record format %d", point_format);
     LM_REQUIRE(scale && offset && select && kept && (n == 0 || (records && out_xyzi && workspace)), "las_decode_select: null pointer");
-    LM_REQUIRE(select->returns >= 0 && select->returns <= 3, "las_decode_select: returns=%d is none of all (0), first (1), last (2), single (3)",
-               select->returns);
-    LM_REQUIRE(select->drop_flags < 16u, "las_decode_select: drop_flags=%u has bits beyond synthetic | key-point | withheld | overlap",
-               select->drop_flags);
-    LM_REQUIRE(select->z_lo == select->z_lo && select->z_hi == select->z_hi, "las_decode_select: z_lo / z_hi must not be NaN");
+    LasSel S;
+    if (int e = las_check_select("las_decode_select", "", select, point_format, S)) return e;
     LM_REQUIRE(((uintptr_t)records & 3) == 0 && ((uintptr_t)out_xyzi & 15) == 0 && ((uintptr_t)workspace & 3) == 0 &&
                    ((uintptr_t)kept & 7) == 0 && ((uintptr_t)class_hist & 7) == 0,
                "las_decode_select: buffers must be 4 / 16 / 4 / 8 / 8-byte aligned");
@@ -671,11 +655,7 @@ LM_API int lm_las_decode_select(void* hip_stream, const unsigned char* records, 
         if (class_hist) LM_HIP(lm_zero_async(class_hist, 256 * sizeof(unsigned long), s));
         return LM_OK;
     }
-    const double sh[3] = {shift ? shift[0] : 0.0, shift ? shift[1] : 0.0, shift ? shift[2] : 0.0};
-    const LasXf X{scale[0], scale[1], scale[2], offset[0] - sh[0], offset[1] - sh[1], offset[2] - sh[2], inten_lo, inten_hi, normalise};
-    LasSel S;
-    for (int k = 0; k < 8; ++k) S.cls[k] = select->class_mask[k];
-    S.drop = select->drop_flags, S.returns = select->returns, S.z_lo = select->z_lo, S.z_hi = select->z_hi, S.fmt6 = point_format >= 6;
+    const LasXf X = las_xf(scale, offset, shift, inten_lo, inten_hi, normalise);
     const long nblk = sel_blocks(n), L = nblk + 1;
     const int groups = (int)sel_groups(n);
     char* w = (char*)workspace;
@@ -685,7 +665,7 @@ LM_API int lm_las_decode_select(void* hip_stream, const unsigned char* records, 
     const size_t scan_bytes = lm_align256(scan_temp_bytes(L));
     w += scan_bytes;
     unsigned* hist_part = class_hist ? (unsigned*)w : nullptr;
-    const size_t lds = ((size_t)256 * record_len + 3) / 4 * 4;
+    const size_t lds = las_stage_bytes(record_len);
     const unsigned* rec = reinterpret_cast<const unsigned*>(records);
     hipLaunchKernelGGL(las_select_count_kernel, dim3((unsigned)groups), dim3(256), lds, s, rec, record_len, n, nblk, X, S, counts, hist_part);
     LM_LAUNCH_CHECK();

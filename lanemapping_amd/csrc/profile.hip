@@ -43,23 +43,12 @@
 #include "las_record.h"
 
 #include <cmath>
-#include <map>
-#include <mutex>
 #include <type_traits>
-#include <utility>
-
-struct LmLasSelect {          // include/lanemap_hip.h
-    unsigned class_mask[8];
-    unsigned drop_flags;
-    int returns;
-    float z_lo, z_hi;
-};
 
 namespace {
 
 constexpr int PER = 4;                   // points per lane of profile_points_kernel, as label_points_kernel
 constexpr int CHUNK = 256 * PER;
-constexpr int REC_GROUPS = 4096;         // cap on the workgroups of the record kernel
 constexpr float MAX_HALF_WIDTH = 16.f;   // |q| <= 16 * 1024 + 1: q*q < 2^29, and 2^31 of them stay far inside 64 bits
 constexpr long MAX_CROSS_ROWS = 1L << 27;   // rows of 32 bytes: the cross-section table stays within 4 GiB
 
@@ -352,56 +341,99 @@ __global__ __launch_bounds__(256) void las_profile_kernel(const unsigned* __rest
     }
 }
 
-// Workgroups of las_profile_kernel<COLOUR, CROSS> the current device holds at once for `lds` bytes of dynamic LDS (as label.hip's: asked of the
-// runtime once per (device, lds) and instantiation, and kept; the number only sizes the grid).
-template <bool COLOUR, bool CROSS>
-int resident_groups(size_t lds, long& groups) {
-    static std::mutex mu;
-    static std::map<std::pair<int, size_t>, long> known;
-    int dev_id = 0;
-    LM_HIP(hipGetDevice(&dev_id));
-    std::lock_guard<std::mutex> lock(mu);
-    const auto it = known.find({dev_id, lds});
-    if (it != known.end()) {
-        groups = it->second;
-        return LM_OK;
-    }
-    int per_cu = 0, cus = 0;
-    LM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, las_profile_kernel<COLOUR, CROSS>, 256, lds));
-    LM_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev_id));
-    groups = (long)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 256);
-    groups = groups < REC_GROUPS ? groups : REC_GROUPS;
-    known[{dev_id, lds}] = groups;
+// What the entries take, grouped by what it describes; an LM_API entry fills these from its parameters.
+struct LineArgs {                        // the lines: the index of lm_label_points and the station and bin tables on top of it
+    const float* segments;
+    long S;
+    const LmLineGrid* grid;
+    const int *cell_start, *cell_segs;
+    float half_width, z_tol;
+    const float* stations;
+    const int *bin_start, *bin_start_host;
+    int L;
+    double bin;
+    int accumulate;
+};
+
+struct RecordArgs {                      // the records of a file, and what decodes and selects them
+    const unsigned char* records;
+    int record_len, point_format;
+    long n;
+    const double *scale, *offset, *shift;
+    const LmLasSelect* select;
+};
+
+struct TableArgs {                       // where the result goes: an entry sets the members of its kind, the others stay zero
+    float min_intensity;                 // profile, colour (the cross-sections count every finite return: NaN)
+    long* bins;                          // profile, colour
+    long n_bins;
+    long* colours;                       // colour
+    int blue_q;
+    long* cells;                         // cross-sections
+    long n_cells;
+    int lateral_q, paint_iq;
+};
+
+// the lines, up to the host copy of the bin table -> I, and P but for its table
+int check_lines(const char* who, const LineArgs& A, IndexDev& I, ProfDev& P) {
+    if (int e = check_index(who, A.grid, A.S, A.segments, A.cell_start, A.cell_segs, A.half_width, A.z_tol, I)) return e;
+    LM_REQUIRE(A.half_width <= MAX_HALF_WIDTH, "%s: half_width=%g, at most %g m is supported (the offsets are summed in 1/1024 m)", who,
+               (double)A.half_width, (double)MAX_HALF_WIDTH);
+    LM_REQUIRE(A.bin > 0 && A.bin < HUGE_VAL, "%s: bin=%g must be a finite length > 0", who, A.bin);
+    LM_REQUIRE(A.accumulate == 0 || A.accumulate == 1, "%s: accumulate=%d is neither 0 nor 1", who, A.accumulate);
+    LM_REQUIRE(A.L >= 0, "%s: L=%d lines", who, A.L);
+    LM_REQUIRE(A.S == 0 || (A.grid->min_line >= 1 && A.grid->max_line <= A.L), "%s: segments carry lines %d .. %d, outside 1 .. L=%d", who,
+               A.S ? A.grid->min_line : 0, A.S ? A.grid->max_line : 0, A.L);
+    LM_REQUIRE(A.bin_start_host, "%s: null pointer (bin_start_host)", who);
+    LM_REQUIRE(A.bin_start_host[0] == 0, "%s: bin_start[0]=%d must be 0", who, A.bin_start_host[0]);
+    for (int k = 0; k < A.L; ++k)
+        LM_REQUIRE(A.bin_start_host[k + 1] >= A.bin_start_host[k], "%s: bin_start[%d]=%d is below bin_start[%d]=%d", who, k + 1,
+                   A.bin_start_host[k + 1], k, A.bin_start_host[k]);
+    P = ProfDev{reinterpret_cast<const float4*>(A.stations), A.bin_start, nullptr, A.L, A.bin_start_host[A.L], (float)(1.0 / A.bin)};
     return LM_OK;
 }
 
-// the arguments the entries share, checked before anything is launched or written.  cross: the table is `cells`, whose size check_cross
-// holds against bin_start_host[L] afterwards; n_bins is then taken from bin_start_host[L]
-int check_profile(const char* who, const LmLineGrid* grid, long S, const void* segments, const void* cell_start, const void* cell_segs,
-                  float half_width, const float* stations, const int* bin_start, const int* bin_start_host, int L, double bin, float z_tol,
-                  int accumulate, long* bins, long n_bins, IndexDev& I, ProfDev& P, bool cross = false) {
-    if (int e = check_index(who, grid, S, segments, cell_start, cell_segs, half_width, z_tol, I)) return e;
-    LM_REQUIRE(half_width <= MAX_HALF_WIDTH, "%s: half_width=%g, at most %g m is supported (the offsets are summed in 1/1024 m)", who,
-               (double)half_width, (double)MAX_HALF_WIDTH);
-    LM_REQUIRE(bin > 0 && bin < HUGE_VAL, "%s: bin=%g must be a finite length > 0", who, bin);
-    LM_REQUIRE(accumulate == 0 || accumulate == 1, "%s: accumulate=%d is neither 0 nor 1", who, accumulate);
-    LM_REQUIRE(L >= 0, "%s: L=%d lines", who, L);
-    LM_REQUIRE(S == 0 || (grid->min_line >= 1 && grid->max_line <= L), "%s: segments carry lines %d .. %d, outside 1 .. L=%d", who,
-               S ? grid->min_line : 0, S ? grid->max_line : 0, L);
-    LM_REQUIRE(bin_start_host, "%s: null pointer (bin_start_host)", who);
-    LM_REQUIRE(bin_start_host[0] == 0, "%s: bin_start[0]=%d must be 0", who, bin_start_host[0]);
-    for (int k = 0; k < L; ++k)
-        LM_REQUIRE(bin_start_host[k + 1] >= bin_start_host[k], "%s: bin_start[%d]=%d is below bin_start[%d]=%d", who, k + 1,
-                   bin_start_host[k + 1], k, bin_start_host[k]);
-    if (cross) n_bins = bin_start_host[L];
-    LM_REQUIRE(n_bins == (long)bin_start_host[L], "%s: n_bins=%ld, but bin_start[L]=%d", who, n_bins, bin_start_host[L]);
-    LM_REQUIRE(S == 0 || (stations && bin_start), "%s: null pointer (stations, bin_start)", who);
-    LM_REQUIRE(cross || n_bins == 0 || bins, "%s: null pointer (bins)", who);
-    LM_REQUIRE(((uintptr_t)stations & 15) == 0, "%s: stations is not 16-byte aligned", who);
-    LM_REQUIRE(((uintptr_t)bin_start & 3) == 0, "%s: bin_start is not 4-byte aligned", who);
-    LM_REQUIRE(((uintptr_t)bins & 7) == 0, "%s: %s is not 8-byte aligned", who, cross ? "cells" : "bins");
-    P = ProfDev{reinterpret_cast<const float4*>(stations), bin_start, reinterpret_cast<long long*>(bins), L, (int)n_bins,
-                (float)(1.0 / bin)};
+// the two device tables of the lines: there, and aligned (two steps: the profile refuses a null `bins` between them)
+int check_line_tables(const char* who, const LineArgs& A) {
+    LM_REQUIRE(A.S == 0 || (A.stations && A.bin_start), "%s: null pointer (stations, bin_start)", who);
+    return LM_OK;
+}
+int check_line_tables_aligned(const char* who, const LineArgs& A) {
+    LM_REQUIRE(((uintptr_t)A.stations & 15) == 0, "%s: stations is not 16-byte aligned", who);
+    LM_REQUIRE(((uintptr_t)A.bin_start & 3) == 0, "%s: bin_start is not 4-byte aligned", who);
+    return LM_OK;
+}
+
+// the arguments of the profile and colour entries, checked before anything is launched or written; fills I and P
+int check_profile(const char* who, const LineArgs& A, long* bins, long n_bins, IndexDev& I, ProfDev& P) {
+    if (int e = check_lines(who, A, I, P)) return e;
+    LM_REQUIRE(n_bins == (long)P.n_bins, "%s: n_bins=%ld, but bin_start[L]=%d", who, n_bins, P.n_bins);
+    if (int e = check_line_tables(who, A)) return e;
+    LM_REQUIRE(n_bins == 0 || bins, "%s: null pointer (bins)", who);
+    if (int e = check_line_tables_aligned(who, A)) return e;
+    LM_REQUIRE(((uintptr_t)bins & 7) == 0, "%s: bins is not 8-byte aligned", who);
+    P.bins = reinterpret_cast<long long*>(bins);
+    return LM_OK;
+}
+
+// the arguments of the two cross-section entries, checked likewise; fills I and P
+int check_cross(const char* who, const LineArgs& A, int lateral_q, int paint_iq, long* cells, long n_cells, IndexDev& I, CrossDev& P) {
+    if (int e = check_lines(who, A, I, P)) return e;
+    if (int e = check_line_tables(who, A)) return e;
+    if (int e = check_line_tables_aligned(who, A)) return e;
+    LM_REQUIRE(((uintptr_t)cells & 7) == 0, "%s: cells is not 8-byte aligned", who);
+    LM_REQUIRE(A.z_tol <= MAX_HALF_WIDTH, "%s: z_tol=%g, at most %g m is supported (the heights are summed in 1/1024 m)", who, (double)A.z_tol,
+               (double)MAX_HALF_WIDTH);
+    LM_REQUIRE(lateral_q >= 1, "%s: lateral_q=%d must be a cell width >= 1 (in 1/1024 m)", who, lateral_q);
+    LM_REQUIRE(paint_iq >= 0 && paint_iq <= 65536, "%s: paint_iq=%d must lie in 0 .. 65536", who, paint_iq);
+    P.hq = (int)std::ceil((double)A.half_width * 1024.0);              // <= 16384
+    P.lateral_q = lateral_q, P.nl = 2 * P.hq / lateral_q + 1, P.paint_iq = (unsigned)paint_iq;
+    const long rows = (long)P.n_bins * P.nl;
+    LM_REQUIRE(rows <= MAX_CROSS_ROWS, "%s: %d bins of nl=%d cells are %ld rows, at most 2^27 are supported (choose a larger bin or lateral_q)",
+               who, P.n_bins, P.nl, rows);
+    LM_REQUIRE(n_cells == rows, "%s: n_cells=%ld, but bin_start[L]=%d bins of nl=%d cells are %ld", who, n_cells, P.n_bins, P.nl, rows);
+    LM_REQUIRE(n_cells == 0 || cells, "%s: null pointer (cells)", who);
+    P.bins = reinterpret_cast<long long*>(cells);
     return LM_OK;
 }
 
@@ -413,37 +445,14 @@ int init_bins(const ProfDev& P, hipStream_t s) {
     return LM_OK;
 }
 
-int init_colours(const ColourDev& P, hipStream_t s) {
-    const long words = (long)P.n_bins * 6;
+// zeroes a table of `words` int64: the colours [n_bins][6], the cells [n_bins nl][4]
+int zero_table(long long* table, long words, hipStream_t s) {
     if (words == 0) return LM_OK;
-    hipLaunchKernelGGL(colour_init_kernel, dim3((unsigned)lm_cdivl(words, 256)), dim3(256), 0, s, P.colours, words);
+    hipLaunchKernelGGL(colour_init_kernel, dim3((unsigned)lm_cdivl(words, 256)), dim3(256), 0, s, table, words);
     LM_LAUNCH_CHECK();
     return LM_OK;
 }
-
-// what the two cross-section entries take beside the profile's arguments, checked after them; fills P
-int check_cross(const char* who, float half_width, float z_tol, int lateral_q, int paint_iq, long* cells, long n_cells, CrossDev& P) {
-    LM_REQUIRE(z_tol <= MAX_HALF_WIDTH, "%s: z_tol=%g, at most %g m is supported (the heights are summed in 1/1024 m)", who, (double)z_tol,
-               (double)MAX_HALF_WIDTH);
-    LM_REQUIRE(lateral_q >= 1, "%s: lateral_q=%d must be a cell width >= 1 (in 1/1024 m)", who, lateral_q);
-    LM_REQUIRE(paint_iq >= 0 && paint_iq <= 65536, "%s: paint_iq=%d must lie in 0 .. 65536", who, paint_iq);
-    P.hq = (int)std::ceil((double)half_width * 1024.0);                // <= 16384
-    P.lateral_q = lateral_q, P.nl = 2 * P.hq / lateral_q + 1, P.paint_iq = (unsigned)paint_iq;
-    const long rows = (long)P.n_bins * P.nl;
-    LM_REQUIRE(rows <= MAX_CROSS_ROWS, "%s: %d bins of nl=%d cells are %ld rows, at most 2^27 are supported (choose a larger bin or lateral_q)",
-               who, P.n_bins, P.nl, rows);
-    LM_REQUIRE(n_cells == rows, "%s: n_cells=%ld, but bin_start[L]=%d bins of nl=%d cells are %ld", who, n_cells, P.n_bins, P.nl, rows);
-    LM_REQUIRE(n_cells == 0 || cells, "%s: null pointer (cells)", who);
-    return LM_OK;
-}
-
-int init_cells(const CrossDev& P, hipStream_t s) {
-    const long words = (long)P.n_bins * P.nl * 4;
-    if (words == 0) return LM_OK;
-    hipLaunchKernelGGL(colour_init_kernel, dim3((unsigned)lm_cdivl(words, 256)), dim3(256), 0, s, P.bins, words);
-    LM_LAUNCH_CHECK();
-    return LM_OK;
-}
+int zero_cells(const CrossDev& P, hipStream_t s) { return zero_table(P.bins, (long)P.n_bins * P.nl * 4, s); }
 
 }  // namespace
 
@@ -455,12 +464,9 @@ LM_API int lm_line_profile_points(void* hip_stream, const float* points_xyzi, lo
                                   int accumulate, long* bins, long n_bins) {
     IndexDev I;
     ProfDev P;
-    if (int e = check_profile("line_profile_points", grid, S, segments, cell_start, cell_segs, half_width, stations, bin_start, bin_start_host,
-                              L, bin, z_tol, accumulate, bins, n_bins, I, P))
-        return e;
-    LM_REQUIRE(N >= 0 && N <= 2147483647L, "line_profile_points: N=%ld points, at most 2^31 - 1 are supported", N);
-    LM_REQUIRE(N == 0 || points_xyzi, "line_profile_points: null pointer (points_xyzi)");
-    LM_REQUIRE(((uintptr_t)points_xyzi & 15) == 0, "line_profile_points: points_xyzi is not 16-byte aligned");
+    const LineArgs A{segments, S, grid, cell_start, cell_segs, half_width, z_tol, stations, bin_start, bin_start_host, L, bin, accumulate};
+    if (int e = check_profile("line_profile_points", A, bins, n_bins, I, P)) return e;
+    if (int e = check_points("line_profile_points", points_xyzi, N)) return e;
     I.min_inten = min_intensity;
     hipStream_t s = (hipStream_t)hip_stream;
     if (!accumulate)
@@ -474,74 +480,54 @@ LM_API int lm_line_profile_points(void* hip_stream, const float* points_xyzi, lo
 
 namespace {
 
-// The two record entries.  COLOUR: blue_q and colours are checked after everything the profile entry refuses, both tensors are initialised,
-// and las_profile_kernel<true> fills both in its one pass over the records.
-template <bool COLOUR, bool CROSS = false>
-int las_profile_records(const char* who, void* hip_stream, const unsigned char* records, int record_len, int point_format, long n,
-                        const double* scale, const double* offset, const double* shift, const LmLasSelect* select, const float* segments, long S,
-                        const LmLineGrid* grid, const int* cell_start, const int* cell_segs, float half_width, const float* stations,
-                        const int* bin_start, const int* bin_start_host, int L, double bin, float z_tol, float min_intensity, int blue_q,
-                        int accumulate, long* bins, long* colours, long n_bins, int lateral_q = 0, int paint_iq = 0) {
-    static const int min_len[11] = {20, 28, 26, 34, 57, 63, 30, 36, 38, 59, 67};
-    static const int rgb_off[11] = {-1, -1, 20, 28, -1, 28, -1, 30, 30, -1, 30};      // rgb_off + 6 <= min_len wherever there is colour
-    LM_REQUIRE(point_format >= 0 && point_format <= 10, "%s: unknown point data record format point_format=%d", who, point_format);
-    LM_REQUIRE(record_len >= min_len[point_format] && record_len <= 160, "%s: bad record_len=%d for format %d (%d .. 160)", who, record_len,
-               point_format, min_len[point_format]);
-    LM_REQUIRE(n >= 0 && n <= 2147483647L, "%s: n=%ld records, at most 2^31 - 1 are supported", who, n);
+// The three record entries.  COLOUR: blue_q and colours are checked after everything the profile entry refuses, both tensors are initialised,
+// and las_profile_kernel<true> fills both in its one pass over the records.  CROSS: the cells take the place of the bins.
+template <bool COLOUR, bool CROSS>
+int las_profile_records(const char* who, void* hip_stream, const RecordArgs& R, const LineArgs& A, const TableArgs& T) {
+    static const int rgb_off[11] = {-1, -1, 20, 28, -1, 28, -1, 30, 30, -1, 30};      // rgb_off + 6 <= las_min_len wherever there is colour
+    if (int e = las_check_records(who, R.point_format, R.record_len, R.n)) return e;
     IndexDev I;
     ProfArg<COLOUR, CROSS> P;
-    if (int e = check_profile(who, grid, S, segments, cell_start, cell_segs, half_width, stations, bin_start, bin_start_host, L, bin, z_tol,
-                              accumulate, bins, n_bins, I, P, CROSS))
-        return e;
-    if constexpr (CROSS) {                                             // (bins: the cells, n_bins: n_cells)
-        if (int e = check_cross(who, half_width, z_tol, lateral_q, paint_iq, bins, n_bins, P)) return e;
-        n_bins = P.n_bins;
+    if constexpr (CROSS) {
+        if (int e = check_cross(who, A, T.lateral_q, T.paint_iq, T.cells, T.n_cells, I, P)) return e;
+    } else {
+        if (int e = check_profile(who, A, T.bins, T.n_bins, I, P)) return e;
     }
-    LM_REQUIRE(scale && offset && (n == 0 || records), "%s: null pointer (scale, offset, records)", who);
-    LM_REQUIRE(((uintptr_t)records & 3) == 0, "%s: records is not 4-byte aligned", who);
-    LasSel Sel{};
-    if (select) {
-        LM_REQUIRE(select->returns >= 0 && select->returns <= 3, "%s: select returns=%d is none of all (0), first (1), last (2), single (3)", who,
-                   select->returns);
-        LM_REQUIRE(select->drop_flags < 16u, "%s: select drop_flags=%u has bits beyond synthetic | key-point | withheld | overlap", who,
-                   select->drop_flags);
-        LM_REQUIRE(select->z_lo == select->z_lo && select->z_hi == select->z_hi, "%s: select z_lo / z_hi must not be NaN", who);
-        for (int k = 0; k < 8; ++k) Sel.cls[k] = select->class_mask[k];
-        Sel.drop = select->drop_flags, Sel.returns = select->returns, Sel.z_lo = select->z_lo, Sel.z_hi = select->z_hi;
-    }
+    LM_REQUIRE(R.scale && R.offset && (R.n == 0 || R.records), "%s: null pointer (scale, offset, records)", who);
+    LM_REQUIRE(((uintptr_t)R.records & 3) == 0, "%s: records is not 4-byte aligned", who);
+    LasSel Sel;
+    if (int e = las_check_select(who, "select ", R.select, R.point_format, Sel)) return e;
     if constexpr (COLOUR) {
-        LM_REQUIRE(rgb_off[point_format] >= 0, "%s: point_format=%d carries no RGB (formats 2, 3, 5, 7, 8 and 10 do)", who, point_format);
-        LM_REQUIRE(blue_q >= 1 && blue_q <= 1024, "%s: blue_q=%d must lie in 1 .. 1024", who, blue_q);
-        LM_REQUIRE(n_bins == 0 || colours, "%s: null pointer (colours)", who);
-        LM_REQUIRE(((uintptr_t)colours & 7) == 0, "%s: colours is not 8-byte aligned", who);
-        const uintptr_t b0 = (uintptr_t)bins, c0 = (uintptr_t)colours, bytes = (uintptr_t)n_bins * 48;
-        LM_REQUIRE(n_bins == 0 || b0 + bytes <= c0 || c0 + bytes <= b0, "%s: colours overlaps bins", who);
-        P.colours = reinterpret_cast<long long*>(colours), P.rgb_off = rgb_off[point_format], P.blue_q = (unsigned)blue_q;
+        LM_REQUIRE(rgb_off[R.point_format] >= 0, "%s: point_format=%d carries no RGB (formats 2, 3, 5, 7, 8 and 10 do)", who, R.point_format);
+        LM_REQUIRE(T.blue_q >= 1 && T.blue_q <= 1024, "%s: blue_q=%d must lie in 1 .. 1024", who, T.blue_q);
+        LM_REQUIRE(T.n_bins == 0 || T.colours, "%s: null pointer (colours)", who);
+        LM_REQUIRE(((uintptr_t)T.colours & 7) == 0, "%s: colours is not 8-byte aligned", who);
+        const uintptr_t b0 = (uintptr_t)T.bins, c0 = (uintptr_t)T.colours, bytes = (uintptr_t)T.n_bins * 48;
+        LM_REQUIRE(T.n_bins == 0 || b0 + bytes <= c0 || c0 + bytes <= b0, "%s: colours overlaps bins", who);
+        P.colours = reinterpret_cast<long long*>(T.colours), P.rgb_off = rgb_off[R.point_format], P.blue_q = (unsigned)T.blue_q;
     }
-    Sel.fmt6 = point_format >= 6;
-    I.min_inten = min_intensity;
+    I.min_inten = T.min_intensity;
     hipStream_t s = (hipStream_t)hip_stream;
-    const bool work = n > 0 && S > 0 && n_bins > 0;
-    const long nblk = (n + 255) / 256;
-    const size_t lds = ((size_t)256 * record_len + 3) / 4 * 4;
+    const bool work = R.n > 0 && A.S > 0 && P.n_bins > 0;
+    const long nblk = (R.n + 255) / 256;
+    const size_t lds = las_stage_bytes(R.record_len);
     long resident = 0;
     if (work)
-        if (int e = resident_groups<COLOUR, CROSS>(lds, resident)) return e;
-    if (!accumulate) {
+        if (int e = resident_groups(las_profile_kernel<COLOUR, CROSS>, lds, resident)) return e;
+    if (!A.accumulate) {
         if constexpr (CROSS) {
-            if (int e = init_cells(P, s)) return e;
+            if (int e = zero_cells(P, s)) return e;
         } else {
             if (int e = init_bins(P, s)) return e;
             if constexpr (COLOUR)
-                if (int e = init_colours(P, s)) return e;
+                if (int e = zero_table(P.colours, (long)P.n_bins * 6, s)) return e;
         }
     }
     if (!work) return LM_OK;
-    const double sh[3] = {shift ? shift[0] : 0.0, shift ? shift[1] : 0.0, shift ? shift[2] : 0.0};
-    const LasXf X{scale[0], scale[1], scale[2], offset[0] - sh[0], offset[1] - sh[1], offset[2] - sh[2], 0.f, 1.f, 0};   // raw intensity
+    const LasXf X = las_xf(R.scale, R.offset, R.shift, 0.f, 1.f, 0);  // raw intensity
     const unsigned groups = (unsigned)(nblk < resident ? nblk : resident);
-    hipLaunchKernelGGL((las_profile_kernel<COLOUR, CROSS>), dim3(groups), dim3(256), lds, s, reinterpret_cast<const unsigned*>(records), record_len, n, nblk,
-                       X, Sel, select ? 1 : 0, I, P);
+    hipLaunchKernelGGL((las_profile_kernel<COLOUR, CROSS>), dim3(groups), dim3(256), lds, s, reinterpret_cast<const unsigned*>(R.records),
+                       R.record_len, R.n, nblk, X, Sel, R.select ? 1 : 0, I, P);
     LM_LAUNCH_CHECK();
     return LM_OK;
 }
@@ -554,9 +540,11 @@ LM_API int lm_las_line_profile_records(void* hip_stream, const unsigned char* re
                                        const float* segments, long S, const LmLineGrid* grid, const int* cell_start, const int* cell_segs,
                                        float half_width, const float* stations, const int* bin_start, const int* bin_start_host, int L,
                                        double bin, float z_tol, float min_intensity, int accumulate, long* bins, long n_bins) {
-    return las_profile_records<false>("las_line_profile_records", hip_stream, records, record_len, point_format, n, scale, offset, shift, select,
-                                      segments, S, grid, cell_start, cell_segs, half_width, stations, bin_start, bin_start_host, L, bin, z_tol,
-                                      min_intensity, 0, accumulate, bins, nullptr, n_bins);
+    const RecordArgs R{records, record_len, point_format, n, scale, offset, shift, select};
+    const LineArgs A{segments, S, grid, cell_start, cell_segs, half_width, z_tol, stations, bin_start, bin_start_host, L, bin, accumulate};
+    TableArgs T{};
+    T.min_intensity = min_intensity, T.bins = bins, T.n_bins = n_bins;
+    return las_profile_records<false, false>("las_line_profile_records", hip_stream, R, A, T);
 }
 
 // as above, point formats 2, 3, 5, 7, 8, 10; colours DEVICE [n_bins][6] int64, disjoint from bins.  One pass over the records fills both.
@@ -566,9 +554,11 @@ LM_API int lm_las_line_colour_records(void* hip_stream, const unsigned char* rec
                                       float half_width, const float* stations, const int* bin_start, const int* bin_start_host, int L,
                                       double bin, float z_tol, float min_intensity, int blue_q, int accumulate, long* bins, long* colours,
                                       long n_bins) {
-    return las_profile_records<true>("las_line_colour_records", hip_stream, records, record_len, point_format, n, scale, offset, shift, select,
-                                     segments, S, grid, cell_start, cell_segs, half_width, stations, bin_start, bin_start_host, L, bin, z_tol,
-                                     min_intensity, blue_q, accumulate, bins, colours, n_bins);
+    const RecordArgs R{records, record_len, point_format, n, scale, offset, shift, select};
+    const LineArgs A{segments, S, grid, cell_start, cell_segs, half_width, z_tol, stations, bin_start, bin_start_host, L, bin, accumulate};
+    TableArgs T{};
+    T.min_intensity = min_intensity, T.bins = bins, T.n_bins = n_bins, T.colours = colours, T.blue_q = blue_q;
+    return las_profile_records<true, false>("las_line_colour_records", hip_stream, R, A, T);
 }
 
 // The cross-sections along every line (the rule: include/lanemap_hip.h).  The arguments of lm_line_profile_points without min_intensity -
@@ -579,17 +569,13 @@ LM_API int lm_line_cross_points(void* hip_stream, const float* points_xyzi, long
                                 long* cells, long n_cells) {
     IndexDev I;
     CrossDev P;
-    if (int e = check_profile("line_cross_points", grid, S, segments, cell_start, cell_segs, half_width, stations, bin_start, bin_start_host, L,
-                              bin, z_tol, accumulate, cells, n_cells, I, P, true))
-        return e;
-    if (int e = check_cross("line_cross_points", half_width, z_tol, lateral_q, paint_iq, cells, n_cells, P)) return e;
-    LM_REQUIRE(N >= 0 && N <= 2147483647L, "line_cross_points: N=%ld points, at most 2^31 - 1 are supported", N);
-    LM_REQUIRE(N == 0 || points_xyzi, "line_cross_points: null pointer (points_xyzi)");
-    LM_REQUIRE(((uintptr_t)points_xyzi & 15) == 0, "line_cross_points: points_xyzi is not 16-byte aligned");
+    const LineArgs A{segments, S, grid, cell_start, cell_segs, half_width, z_tol, stations, bin_start, bin_start_host, L, bin, accumulate};
+    if (int e = check_cross("line_cross_points", A, lateral_q, paint_iq, cells, n_cells, I, P)) return e;
+    if (int e = check_points("line_cross_points", points_xyzi, N)) return e;
     I.min_inten = NAN;
     hipStream_t s = (hipStream_t)hip_stream;
     if (!accumulate)
-        if (int e = init_cells(P, s)) return e;
+        if (int e = zero_cells(P, s)) return e;
     if (N == 0 || S == 0 || n_cells == 0) return LM_OK;
     hipLaunchKernelGGL(cross_points_kernel, dim3((unsigned)lm_cdivl(N, CHUNK)), dim3(256), 0, s, reinterpret_cast<const lab_f32x4*>(points_xyzi),
                        N, I, P);
@@ -603,7 +589,9 @@ LM_API int lm_las_line_cross_records(void* hip_stream, const unsigned char* reco
                                      const float* segments, long S, const LmLineGrid* grid, const int* cell_start, const int* cell_segs,
                                      float half_width, const float* stations, const int* bin_start, const int* bin_start_host, int L,
                                      double bin, float z_tol, int lateral_q, int paint_iq, int accumulate, long* cells, long n_cells) {
-    return las_profile_records<false, true>("las_line_cross_records", hip_stream, records, record_len, point_format, n, scale, offset, shift,
-                                            select, segments, S, grid, cell_start, cell_segs, half_width, stations, bin_start, bin_start_host,
-                                            L, bin, z_tol, NAN, 0, accumulate, cells, nullptr, n_cells, lateral_q, paint_iq);
+    const RecordArgs R{records, record_len, point_format, n, scale, offset, shift, select};
+    const LineArgs A{segments, S, grid, cell_start, cell_segs, half_width, z_tol, stations, bin_start, bin_start_host, L, bin, accumulate};
+    TableArgs T{};
+    T.min_intensity = NAN, T.cells = cells, T.n_cells = n_cells, T.lateral_q = lateral_q, T.paint_iq = paint_iq;
+    return las_profile_records<false, true>("las_line_cross_records", hip_stream, R, A, T);
 }

@@ -8,16 +8,7 @@
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-struct LmRasterParams {      // mirrors the reference's per-tile parameter file (utils/io_utils.py:125-150)
-    float quat[4];           // las_rotation_trans_quan[3:7] = [w,x,y,z]
-    float trans[3];          // las_rotation_trans_quan[0:3]
-    float bev_img_offset[2];
-    float img_reso[2];
-    float local_min_ele;
-    float ele_reso;
-    float inten_lo, inten_hi;   // 800, 33000
-};
-
+// (LmRasterParams, the reference's per-tile parameter file, utils/io_utils.py:125-150: include/lanemap_hip.h)
 struct TileXf {                        // derived per-tile constants (host, double -> float)
     float m[9], t[3], off[2], irow, icol, min_ele, iele, lo, hi, iscale;
     long start, count;                 // point range of the tile in the concatenated buffer

@@ -28,11 +28,6 @@
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-struct LmStripGrid {          // include/lanemap_hip.h
-    double x0, y0, cell;
-    int nx, ny;
-};
-
 namespace {
 
 constexpr int SW = 256;                  // threads per workgroup = 4 independent waves (no workgroup barrier anywhere)
