@@ -19,6 +19,7 @@ namespace {
 
 constexpr int NCH = 16;     // header_fea_dim
 
+// NOT common.h's lm_bilin_axis: no `fp contract(off)` and no out > 1 guard, so other bits - keep it as it is
 __device__ __forceinline__ void bilin_axis(int o, int in, int out, int& i0, int& i1, float& w0, float& w1) {
     const float scale = (float)(in - 1) / (float)(out - 1);
     const float src = scale * (float)o;

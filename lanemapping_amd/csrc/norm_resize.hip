@@ -19,8 +19,44 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
-__device__ __forceinline__ void bilin_axis(int o, int in, int out, int& i0, int& i1, float& w0, float& w1) {
-    lm_bilin_axis(o, in, out, i0, i1, w0, w1);
+// ----------------------------------------------------------------------------- shared steps of the GN + ReLU + bilinear kernels
+// (the four kernels that normalise and blend agree bit for bit because they run these, not copies of them)
+// Per-channel affine of the normalisation, v * a + g, of a channel quad: s0, s1 = its four (mean, rstd) pairs as two 16-byte loads,
+// gm / bt = gamma / beta of the same channels.  Loading is the caller's: gn_relu_upsample_sum_kernel loads first and computes later.
+__device__ __forceinline__ void gn_affine4(f32x4 s0, f32x4 s1, f32x4 gm, f32x4 bt, f32x4& a, f32x4& g) {
+    const float mean[4] = {s0[0], s0[2], s1[0], s1[2]}, rstd[4] = {s0[1], s0[3], s1[1], s1[3]};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float ae, ge;
+        lm_gn_affine(mean[e], rstd[e], gm[e], bt[e], ae, ge);
+        a[e] = ae;
+        g[e] = ge;
+    }
+}
+// the same from the statistics of (b, c): st = stats + (b * C + c) * 2
+__device__ __forceinline__ void gn_affine4_at(const float* st, f32x4 gm, f32x4 bt, f32x4& a, f32x4& g) {
+    gn_affine4(reinterpret_cast<const f32x4*>(st)[0], reinterpret_cast<const f32x4*>(st)[1], gm, bt, a, g);
+}
+__device__ __forceinline__ f32x4 gn_relu4(f32x4 v, f32x4 a, f32x4 g) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = lm_gn_relu(v[e], a[e], g[e]);
+    return v;
+}
+__device__ __forceinline__ f32x4 bilerp4(f32x4 v00, f32x4 v01, f32x4 v10, f32x4 v11, float wy0, float wy1, float wx0, float wx1) {
+    f32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = lm_bilerp(v00[e], v01[e], v10[e], v11[e], wy0, wy1, wx0, wx1);
+    return o;
+}
+// flat index of an output channel quad of [B][Ho][Wo][C / 4] -> first channel, column, row, image
+__device__ __forceinline__ void decode_quad(long i, int C, int Ho, int Wo, int& c, int& ox, int& oy, int& b) {
+    const int c4n = C / 4;
+    c = (int)(i % c4n) * 4;
+    long t = i / c4n;
+    ox = (int)(t % Wo);
+    t /= Wo;
+    oy = (int)(t % Ho);
+    b = (int)(t / Ho);
 }
 
 // ----------------------------------------------------------------------------- GroupNorm stats
@@ -96,47 +132,19 @@ __global__ __launch_bounds__(256) void gn_relu_upsample_kernel(const float* __re
                                                                int accumulate, long total4) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= total4) return;
-    const int c4n = C / 4;
-    const int c = (int)(i % c4n) * 4;
-    long t = i / c4n;
-    const int ox = (int)(t % Wo);
-    t /= Wo;
-    const int oy = (int)(t % Ho);
-    const int b = (int)(t / Ho);
+    int c, ox, oy, b;
+    decode_quad(i, C, Ho, Wo, c, ox, oy, b);
     int y0, y1, x0, x1;
     float wy0, wy1, wx0, wx1;
-    bilin_axis(oy, Hi, Ho, y0, y1, wy0, wy1);
-    bilin_axis(ox, Wi, Wo, x0, x1, wx0, wx1);
-    f32x4 a, g;   // per-channel affine of the normalisation: v*a + g  (statistics / gamma / beta as 16-byte loads)
-    {
-        const f32x4* st = reinterpret_cast<const f32x4*>(stats + ((long)b * C + c) * 2);
-        const f32x4 s0 = st[0], s1 = st[1], gm = *reinterpret_cast<const f32x4*>(gamma + c), bt = *reinterpret_cast<const f32x4*>(beta + c);
-        const float mean[4] = {s0[0], s0[2], s1[0], s1[2]}, rstd[4] = {s0[1], s0[3], s1[1], s1[3]};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float ae, ge;
-            lm_gn_affine(mean[e], rstd[e], gm[e], bt[e], ae, ge);
-            a[e] = ae;
-            g[e] = ge;
-        }
-    }
+    lm_bilin_axis(oy, Hi, Ho, y0, y1, wy0, wy1);
+    lm_bilin_axis(ox, Wi, Wo, x0, x1, wx0, wx1);
+    f32x4 a, g;
+    gn_affine4_at(stats + ((long)b * C + c) * 2, *reinterpret_cast<const f32x4*>(gamma + c), *reinterpret_cast<const f32x4*>(beta + c), a, g);
     const float* xb = x + (long)b * Hi * Wi * C + c;
-    auto tap = [&](int yy, int xx) {
-        f32x4 v = *reinterpret_cast<const f32x4*>(xb + ((long)yy * Wi + xx) * C);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = lm_gn_relu(v[e], a[e], g[e]);
-        return v;
-    };
-    const f32x4 v00 = tap(y0, x0), v01 = tap(y0, x1), v10 = tap(y1, x0), v11 = tap(y1, x1);
-    f32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = lm_bilerp(v00[e], v01[e], v10[e], v11[e], wy0, wy1, wx0, wx1);
+    auto tap = [&](int yy, int xx) { return gn_relu4(*reinterpret_cast<const f32x4*>(xb + ((long)yy * Wi + xx) * C), a, g); };
+    f32x4 o = bilerp4(tap(y0, x0), tap(y0, x1), tap(y1, x0), tap(y1, x1), wy0, wy1, wx0, wx1);
     f32x4* yp = reinterpret_cast<f32x4*>(y + i * 4);
-    if (accumulate) {
-        const f32x4 prev = *yp;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = prev[e] + o[e];
-    }
+    if (accumulate) o = *yp + o;
     *yp = o;
 }
 
@@ -165,13 +173,41 @@ struct Proj1x1 {
     int cout, ldy1;
 };
 
+// The projection of one pixel in gn_relu_upsample_sum_kernel and gn_sum3_lds_kernel.  Each kernel forms the partial sums itself -
+// part[n] = fmaf(acc[e], w[e][n], part[n]) from 0 over its channels e = 0, 1, 2, 3 IN THIS ORDER, n = the 8 (padded) outputs - because
+// the weights come from LDS in one and from registers in the other.  The rest is shared:
+// transpose-reduce over the c4n = C/4 lanes of the pixel: each of the first three steps halves the outputs a lane keeps while doubling
+// the lanes summed (4 + 2 + 1 shuffles), then plain butterflies: 9-10 shuffles instead of 8 x log2(C/4).  Leaves the sum of output
+// proj_lane_output(li) in part[0]; `lane` = lane of the wave.  (It returns nothing: with a return value the callers' fmaf chains came
+// out as 16 scalar FMAs instead of 8 packed ones.)
+__device__ __forceinline__ void proj_reduce(float (&part)[8], int lane, unsigned c4n) {
+#pragma unroll
+    for (int half = 4, mask = 1; half >= 1; half >>= 1, mask <<= 1) {
+        const bool upper = (lane & mask) != 0;
+#pragma unroll
+        for (int jj = 0; jj < half; ++jj) {
+            // (two plain selects: left to itself the compiler turns them into `part[upper ? jj : jj + half]`, a run-time index it
+            // resolves with a compare + select per array element - ~200 of the kernel's 500 VALU instructions, profiles/README.md)
+            float lo = part[jj], hi = part[jj + half];
+            asm volatile("" : "+v"(lo), "+v"(hi));
+            const float send = upper ? lo : hi, keep = upper ? hi : lo;
+            part[jj] = keep + __shfl_xor(send, mask);
+        }
+    }
+    for (unsigned o = 8; o < c4n; o <<= 1) part[0] += __shfl_xor(part[0], (int)o);
+}
+// the output n that lane li = c / 4 of the pixel holds after proj_reduce, and whether the lane stores it (+ bias[n]) to y1[pixel][n]:
+// lanes >= 8 hold copies
+__device__ __forceinline__ int proj_lane_output(unsigned li) { return 4 * (int)(li & 1) + 2 * (int)((li >> 1) & 1) + (int)((li >> 2) & 1); }
+__device__ __forceinline__ bool proj_lane_stores(const Proj1x1& Q, unsigned li, int n) { return li < 8 && n < Q.cout; }
+
 // grid (ceil(Wo * C/4 / 256), Ho, B): the output row and the image come from the block index, the column with one division by C/4 (a
 // shift for the power-of-two channel counts of the FPN).
 // N terms, SAME = bit k set when term k has the output's size (one tap, returned as it is).  Both are TEMPLATE parameters: with run-time
 // term counts / sizes every term sat behind a branch, its loads could not be hoisted above the previous term's arithmetic, and a thread
 // paid up to three serial memory round trips - the counters showed 73 % of the wave cycles parked at s_waitcnt with 8 waves per SIMD
 // (tools/prof_gn_pmc.sh).  Now the statistics and every tap of every term are loaded first (up to 6 + 6 16-byte loads in flight per
-// lane), then the arithmetic runs in the old order: same bits.
+// lane), then the arithmetic runs term by term in the order of three gn_relu_upsample_kernel calls.
 // 16 bytes at element `elem` of a wave-uniform base: byte offset kept in 32 bits so that the access becomes scalar base + vector offset
 __device__ __forceinline__ f32x4 ld_quad(const float* base, unsigned elem) {
     return *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(base) + (elem << 2));
@@ -214,8 +250,8 @@ __global__ __launch_bounds__(256) void gn_relu_upsample_sum_kernel(GnSum P, cons
             tap[k][3] = ld_quad(xb, (unsigned)((y1 * T.Wi + x1) * T.ld + c));
         }
     }
-    // the projection weights are staged BEHIND the taps' loads: in front of them (rounds 2-3) every workgroup paid two memory round
-    // trips in a row - weights, barrier, taps
+    // the projection weights are staged BEHIND the taps' loads: in front of them every workgroup paid two memory round trips in a
+    // row - weights, barrier, taps
     if (Q.w) {
         for (int k = threadIdx.x; k < C * 8; k += 256) wl[k] = (k & 7) < Q.cout ? Q.w[(k >> 3) * 16 + (k & 7)] : 0.f;
         __syncthreads();
@@ -226,27 +262,13 @@ __global__ __launch_bounds__(256) void gn_relu_upsample_sum_kernel(GnSum P, cons
 #pragma unroll
     for (int k = 0; k < N; ++k) {
         f32x4 a, g;
-        const float mean[4] = {st0[k][0], st0[k][2], st1[k][0], st1[k][2]}, rstd[4] = {st0[k][1], st0[k][3], st1[k][1], st1[k][3]};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float ae, ge;
-            lm_gn_affine(mean[e], rstd[e], gm[e], bt[e], ae, ge);
-            a[e] = ae;
-            g[e] = ge;
-        }
+        gn_affine4(st0[k], st1[k], gm, bt, a, g);
         f32x4 o;
-        if ((SAME >> k) & 1) {              // same size: the blend has weights (1, 0) and returns the tap itself, bit for bit
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = lm_gn_relu(tap[k][0][e], a[e], g[e]);
-        } else {
-            f32x4 v[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[q][e] = lm_gn_relu(tap[k][q][e], a[e], g[e]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = lm_bilerp(v[0][e], v[1][e], v[2][e], v[3][e], wy0[k], wy1[k], wx0[k], wx1[k]);
-        }
+        if ((SAME >> k) & 1)                // same size: the blend has weights (1, 0) and returns the tap itself, bit for bit
+            o = gn_relu4(tap[k][0], a, g);
+        else
+            o = bilerp4(gn_relu4(tap[k][0], a, g), gn_relu4(tap[k][1], a, g), gn_relu4(tap[k][2], a, g), gn_relu4(tap[k][3], a, g),
+                        wy0[k], wy1[k], wx0[k], wx1[k]);
         if (k == 0) {
             acc = o;
         } else {
@@ -269,26 +291,10 @@ __global__ __launch_bounds__(256) void gn_relu_upsample_sum_kernel(GnSum P, cons
                 part[4 + n] = fmaf(acc[e], w1[n], part[4 + n]);
             }
         }
-        // transpose-reduce over the C/4 lanes of the pixel: each of the first three steps halves the outputs a lane keeps while doubling
-        // the lanes summed (4 + 2 + 1 shuffles), then plain butterflies: 9-10 shuffles instead of 8 x log2(C/4)
-        const int lane = threadIdx.x & 63;
-#pragma unroll
-        for (int half = 4, mask = 1; half >= 1; half >>= 1, mask <<= 1) {
-            const bool upper = (lane & mask) != 0;
-#pragma unroll
-            for (int jj = 0; jj < half; ++jj) {
-                // (two plain selects: left to itself the compiler turns them into `part[upper ? jj : jj + half]`, a run-time index it
-                // resolves with a compare + select per array element - ~200 of the kernel's 500 VALU instructions, profiles/README.md)
-                float lo = part[jj], hi = part[jj + half];
-                asm volatile("" : "+v"(lo), "+v"(hi));
-                const float send = upper ? lo : hi, keep = upper ? hi : lo;
-                part[jj] = keep + __shfl_xor(send, mask);
-            }
-        }
-        for (unsigned o = 8; o < c4n; o <<= 1) part[0] += __shfl_xor(part[0], (int)o);
+        proj_reduce(part, threadIdx.x & 63, c4n);
         const unsigned li = (unsigned)c >> 2;
-        const int n = 4 * (int)(li & 1) + 2 * (int)((li >> 1) & 1) + (int)((li >> 2) & 1);
-        if (li < 8 && n < Q.cout) Q.y1[(long)((b * Ho + oy) * Wo + ox) * Q.ldy1 + n] = part[0] + (Q.bias ? Q.bias[n] : 0.f);
+        const int n = proj_lane_output(li);
+        if (proj_lane_stores(Q, li, n)) Q.y1[(long)((b * Ho + oy) * Wo + ox) * Q.ldy1 + n] = part[0] + (Q.bias ? Q.bias[n] : 0.f);
     }
 }
 
@@ -298,49 +304,31 @@ __global__ __launch_bounds__(256) void gn_relu_upsample_sum_kernel(GnSum P, cons
 // again by every output that touches it.  Here a workgroup owns UT_R x UT_C output pixels x all channels: the source block it needs
 // (<= UT_SR x UT_SC pixels for scales <= 1/2 + eps, checked by the launcher) is read ONCE, normalised + ReLU'd once per element and kept
 // in LDS; the outputs then blend four ds_read_b128 taps.  Same per-element arithmetic (lm_gn_relu, then lm_bilerp with lm_bilin_axis
-// weights) => same bits as gn_relu_upsample_kernel / gn_relu_upsample_sum_kernel<1, 0>.
+// weights, through the helpers at the top of this file) as gn_relu_upsample_kernel / gn_relu_upsample_sum_kernel<1, 0>.
 constexpr int UT_R = 8, UT_C = 16;
 
-__global__ __launch_bounds__(256) void gn_relu_up_lds_kernel(GnTerm T, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                             float* __restrict__ y, int Ho, int Wo, int C, int SR, int SC) {
-    extern __shared__ __attribute__((aligned(16))) float ups[];       // [SR * SC][C] normalised source block
-    __shared__ int ty0[UT_R], ty1[UT_R], tx0[UT_C], tx1[UT_C];        // taps (relative to the block origin) and weights of the tile's rows / columns
-    __shared__ float twy0[UT_R], twy1[UT_R], twx0[UT_C], twx1[UT_C];
-    const int tid = threadIdx.x, c4n = C / 4;
-    const int oy0 = blockIdx.y * UT_R, ox0 = blockIdx.x * UT_C, b = blockIdx.z;
-    const int ny = min(UT_R, Ho - oy0), nx = min(UT_C, Wo - ox0);
-    int sy0, sx0, i1;
+// The LDS up-sampling tile of gn_relu_up_lds_kernel and gn_sum3_lds_kernel.  The kernels declare the LDS - the normalised + ReLU'd
+// source block ups[SR * SC][C] (dynamic) and the eight tap tables - and the helpers get pointers to it.
+// first tap of output row / column o0: the origin of the tile's source block
+__device__ __forceinline__ int up_tile_origin(int o0, int in, float scale) {
+    int i0, i1;
     float w0, w1;
-    lm_bilin_axis_scaled(oy0, T.Hi, T.sy, sy0, i1, w0, w1);           // block origin = first tap of the first row / column
-    lm_bilin_axis_scaled(ox0, T.Wi, T.sx, sx0, i1, w0, w1);
-    if (tid < UT_R) {
-        int a0, a1;
-        lm_bilin_axis_scaled(min(oy0 + tid, Ho - 1), T.Hi, T.sy, a0, a1, w0, w1);
-        ty0[tid] = a0 - sy0; ty1[tid] = a1 - sy0; twy0[tid] = w0; twy1[tid] = w1;
-    } else if (tid >= 64 && tid < 64 + UT_C) {
-        const int t = tid - 64;
-        int a0, a1;
-        lm_bilin_axis_scaled(min(ox0 + t, Wo - 1), T.Wi, T.sx, a0, a1, w0, w1);
-        tx0[t] = a0 - sx0; tx1[t] = a1 - sx0; twx0[t] = w0; twx1[t] = w1;
-    }
-    // ---- phase 1: source block -> LDS.  256 % (C/4) == 0: a thread keeps one channel quad and walks the pixels
-    const int cq = tid % c4n, pstep = 256 / c4n, p0 = tid / c4n;
-    const int c = cq * 4;
-    f32x4 a, g;
-    {
-        const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + c), bt = *reinterpret_cast<const f32x4*>(beta + c);
-        const f32x4* st = reinterpret_cast<const f32x4*>(T.stats + ((long)b * C + c) * 2);      // (mean, rstd) x 4 channels
-        const f32x4 st0 = st[0], st1 = st[1];
-        const float mean[4] = {st0[0], st0[2], st1[0], st1[2]}, rstd[4] = {st0[1], st0[3], st1[1], st1[3]};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float ae, ge;
-            lm_gn_affine(mean[e], rstd[e], gm[e], bt[e], ae, ge);
-            a[e] = ae;
-            g[e] = ge;
-        }
-    }
-    const int nsrc = SR * SC;
+    lm_bilin_axis_scaled(o0, in, scale, i0, i1, w0, w1);
+    return i0;
+}
+// entry t of one axis' tap tables: the taps (relative to the origin) and weights of output row / column o0 + t, clamped to the image.
+// Threads 0..UT_R-1 write the rows and 64..64+UT_C-1 the columns; the kernel's barrier comes before the tables are read.  (That
+// two-armed `if` stays in the kernels: inside a helper the compiler merges the arms' stores behind selected addresses, +15 instructions.)
+__device__ __forceinline__ void up_axis_taps(int t, int o0, int out, int in, float scale, int origin, int* t0, int* t1, float* w0, float* w1) {
+    int a0, a1;
+    lm_bilin_axis_scaled(min(o0 + t, out - 1), in, scale, a0, a1, w0[t], w1[t]);
+    t0[t] = a0 - origin;
+    t1[t] = a1 - origin;
+}
+// source block (SC columns from (sy0, sx0), nsrc pixels) of image b -> ups, normalised with (a, g).  256 % (C/4) == 0: a thread keeps
+// one channel quad c and walks the pixels p0, p0 + pstep, ...
+__device__ __forceinline__ void up_tile_stage(float* ups, const GnTerm& T, int b, int C, int c, int p0, int pstep, int sy0, int sx0, int SC,
+                                              int nsrc, f32x4 a, f32x4 g) {
     const float* xb = T.x + (long)b * T.Hi * T.Wi * T.ld + c;
     constexpr int UNR = 4;                                             // loads in flight per thread and round
     for (int pb = p0; pb < nsrc; pb += pstep * UNR) {
@@ -355,86 +343,84 @@ __global__ __launch_bounds__(256) void gn_relu_up_lds_kernel(GnTerm T, const flo
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
             const int pp = pb + u * pstep;
-            if (pp < nsrc) {
-                f32x4 o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = lm_gn_relu(v[u][e], a[e], g[e]);
-                *reinterpret_cast<f32x4*>(ups + (long)pp * C + c) = o;
-            }
+            if (pp < nsrc) *reinterpret_cast<f32x4*>(ups + (long)pp * C + c) = gn_relu4(v[u], a, g);
         }
     }
+}
+// channel quad c of the tile's output (r, q): four ds_read_b128 taps, blended
+struct UpTile {
+    const float* ups;
+    const int *ty0, *ty1, *tx0, *tx1;              // taps (relative to the block origin) of the tile's rows / columns
+    const float *twy0, *twy1, *twx0, *twx1;        // and their weights
+    int SC, C;
+};
+__device__ __forceinline__ f32x4 up_tile_blend(const UpTile& U, int r, int q, int c) {
+    const float* s0 = U.ups + (long)(U.ty0[r] * U.SC) * U.C + c;
+    const float* s1 = U.ups + (long)(U.ty1[r] * U.SC) * U.C + c;
+    const f32x4 v00 = *reinterpret_cast<const f32x4*>(s0 + U.tx0[q] * U.C), v01 = *reinterpret_cast<const f32x4*>(s0 + U.tx1[q] * U.C);
+    const f32x4 v10 = *reinterpret_cast<const f32x4*>(s1 + U.tx0[q] * U.C), v11 = *reinterpret_cast<const f32x4*>(s1 + U.tx1[q] * U.C);
+    return bilerp4(v00, v01, v10, v11, U.twy0[r], U.twy1[r], U.twx0[q], U.twx1[q]);
+}
+
+__global__ __launch_bounds__(256) void gn_relu_up_lds_kernel(GnTerm T, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                             float* __restrict__ y, int Ho, int Wo, int C, int SR, int SC) {
+    extern __shared__ __attribute__((aligned(16))) float ups[];
+    __shared__ int ty0[UT_R], ty1[UT_R], tx0[UT_C], tx1[UT_C];
+    __shared__ float twy0[UT_R], twy1[UT_R], twx0[UT_C], twx1[UT_C];
+    const UpTile U{ups, ty0, ty1, tx0, tx1, twy0, twy1, twx0, twx1, SC, C};
+    const int tid = threadIdx.x, c4n = C / 4;
+    const int oy0 = blockIdx.y * UT_R, ox0 = blockIdx.x * UT_C, b = blockIdx.z;
+    const int ny = min(UT_R, Ho - oy0), nx = min(UT_C, Wo - ox0);
+    const int sy0 = up_tile_origin(oy0, T.Hi, T.sy), sx0 = up_tile_origin(ox0, T.Wi, T.sx);
+    if (tid < UT_R) up_axis_taps(tid, oy0, Ho, T.Hi, T.sy, sy0, ty0, ty1, twy0, twy1);
+    else if (tid >= 64 && tid < 64 + UT_C) up_axis_taps(tid - 64, ox0, Wo, T.Wi, T.sx, sx0, tx0, tx1, twx0, twx1);
+    // ---- phase 1: source block -> LDS
+    const int cq = tid % c4n, pstep = 256 / c4n, p0 = tid / c4n;
+    const int c = cq * 4;
+    f32x4 a, g;
+    gn_affine4_at(T.stats + ((long)b * C + c) * 2, *reinterpret_cast<const f32x4*>(gamma + c), *reinterpret_cast<const f32x4*>(beta + c), a, g);
+    up_tile_stage(ups, T, b, C, c, p0, pstep, sy0, sx0, SC, SR * SC, a, g);
     __syncthreads();
     // ---- phase 2: outputs
     const long obase = ((long)b * Ho + oy0) * Wo + ox0;
     for (int pp = p0; pp < UT_R * UT_C; pp += pstep) {
         const int r = pp / UT_C, q = pp % UT_C;
         if (r >= ny || q >= nx) continue;
-        const float* s0 = ups + (long)(ty0[r] * SC) * C + c;
-        const float* s1 = ups + (long)(ty1[r] * SC) * C + c;
-        const f32x4 v00 = *reinterpret_cast<const f32x4*>(s0 + tx0[q] * C), v01 = *reinterpret_cast<const f32x4*>(s0 + tx1[q] * C);
-        const f32x4 v10 = *reinterpret_cast<const f32x4*>(s1 + tx0[q] * C), v11 = *reinterpret_cast<const f32x4*>(s1 + tx1[q] * C);
-        const float wy0 = twy0[r], wy1 = twy1[r], wx0 = twx0[q], wx1 = twx1[q];
-        f32x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = lm_bilerp(v00[e], v01[e], v10[e], v11[e], wy0, wy1, wx0, wx1);
-        __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(y + (obase + (long)r * Wo + q) * C + c));
+        __builtin_nontemporal_store(up_tile_blend(U, r, q, c), reinterpret_cast<f32x4*>(y + (obase + (long)r * Wo + q) * C + c));
     }
 }
 
-// ----------------------------------------------------------------------------- s2 + s3 + s4 with the up-sampled term staged in LDS (round 5)
+// ----------------------------------------------------------------------------- s2 + s3 + s4 with the up-sampled term staged in LDS
 // The three-term call of the semantic branches - two same-size terms (s2, s4) and ONE up-sampled term (s3: 144^2 -> 288^2) followed by the
 // branch's 1x1 output layer - ran at 2.9 TB/s in gn_relu_upsample_sum_kernel<3, 5>: per output quad six 16-byte loads, three
 // (mean, rstd) pairs, three GroupNorm affines, the blend and the projection weights from LDS.  Here a workgroup owns UT_R x UT_C output
 // pixels x all channels, a thread keeps ONE channel quad for all its pixels: the affines of the three terms and its 4 x 8 projection
 // weights are made once per thread, the up-sampled term's source block is normalised once per element and staged in LDS (as in
-// gn_relu_up_lds_kernel), and an output quad costs two 16-byte global loads + four ds_read_b128.  Same per-element arithmetic in the
-// same order (lm_gn_relu per tap, lm_bilerp, (t0 + t1) + t2, the fmaf chain and the shuffle tree of the projection): SAME BITS as
-// gn_relu_upsample_sum_kernel<3, 5> (test_gn_sum_three_terms_lds_bit_identical).  C/4 lanes of a pixel sit in one wave (C/4 | 64).
+// gn_relu_up_lds_kernel), and an output quad costs two 16-byte global loads + four ds_read_b128.  The arithmetic and its order are
+// gn_relu_upsample_sum_kernel<3, 5>'s through the shared helpers (gn_affine4, gn_relu4, bilerp4, (t0 + t1) + t2, the fmaf chain,
+// proj_reduce): the same bits (test_gn_sum_three_terms_lds_bit_identical).  C/4 lanes of a pixel sit in one wave (C/4 | 64).
 __global__ __launch_bounds__(256) void gn_sum3_lds_kernel(GnSum P, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                           float* __restrict__ y, int Ho, int Wo, int C, int SR, int SC, Proj1x1 Q) {
-    extern __shared__ __attribute__((aligned(16))) float ups[];       // [SR * SC][C] normalised + ReLU'd source block of term 1
+    extern __shared__ __attribute__((aligned(16))) float ups[];       // source block of term 1
     __shared__ int ty0[UT_R], ty1[UT_R], tx0[UT_C], tx1[UT_C];
     __shared__ float twy0[UT_R], twy1[UT_R], twx0[UT_C], twx1[UT_C];
+    const UpTile U{ups, ty0, ty1, tx0, tx1, twy0, twy1, twx0, twx1, SC, C};
     const int tid = threadIdx.x, c4n = C / 4;
     const int oy0 = blockIdx.y * UT_R, ox0 = blockIdx.x * UT_C, b = blockIdx.z;
     const int ny = min(UT_R, Ho - oy0), nx = min(UT_C, Wo - ox0);
     const GnTerm& T0 = P.t[0];
     const GnTerm& T1 = P.t[1];
     const GnTerm& T2 = P.t[2];
-    int sy0, sx0, i1;
-    float w0, w1;
-    lm_bilin_axis_scaled(oy0, T1.Hi, T1.sy, sy0, i1, w0, w1);
-    lm_bilin_axis_scaled(ox0, T1.Wi, T1.sx, sx0, i1, w0, w1);
-    if (tid < UT_R) {
-        int a0, a1;
-        lm_bilin_axis_scaled(min(oy0 + tid, Ho - 1), T1.Hi, T1.sy, a0, a1, w0, w1);
-        ty0[tid] = a0 - sy0; ty1[tid] = a1 - sy0; twy0[tid] = w0; twy1[tid] = w1;
-    } else if (tid >= 64 && tid < 64 + UT_C) {
-        const int t = tid - 64;
-        int a0, a1;
-        lm_bilin_axis_scaled(min(ox0 + t, Wo - 1), T1.Wi, T1.sx, a0, a1, w0, w1);
-        tx0[t] = a0 - sx0; tx1[t] = a1 - sx0; twx0[t] = w0; twx1[t] = w1;
-    }
+    const int sy0 = up_tile_origin(oy0, T1.Hi, T1.sy), sx0 = up_tile_origin(ox0, T1.Wi, T1.sx);
+    if (tid < UT_R) up_axis_taps(tid, oy0, Ho, T1.Hi, T1.sy, sy0, ty0, ty1, twy0, twy1);
+    else if (tid >= 64 && tid < 64 + UT_C) up_axis_taps(tid - 64, ox0, Wo, T1.Wi, T1.sx, sx0, tx0, tx1, twx0, twx1);
     const int cq = tid % c4n, pstep = 256 / c4n, p0 = tid / c4n;
     const int c = cq * 4;
     // the three affines of this thread's channel quad
     f32x4 a[3], g[3];
-    {
-        const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + c), bt = *reinterpret_cast<const f32x4*>(beta + c);
+    const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + c), bt = *reinterpret_cast<const f32x4*>(beta + c);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const f32x4* st = reinterpret_cast<const f32x4*>(P.t[k].stats + ((long)b * C + c) * 2);      // (mean, rstd) x 4 channels
-            const f32x4 st0 = st[0], st1 = st[1];
-            const float mean[4] = {st0[0], st0[2], st1[0], st1[2]}, rstd[4] = {st0[1], st0[3], st1[1], st1[3]};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float ae, ge;
-                lm_gn_affine(mean[e], rstd[e], gm[e], bt[e], ae, ge);
-                a[k][e] = ae;
-                g[k][e] = ge;
-            }
-        }
-    }
+    for (int k = 0; k < 3; ++k) gn_affine4_at(P.t[k].stats + ((long)b * C + c) * 2, gm, bt, a[k], g[k]);
     // projection weights of this thread's four channels, [e][8] (cout padded with zeros, like the LDS copy of the per-output kernel)
     float pw[4][8];
 #pragma unroll
@@ -442,39 +428,14 @@ __global__ __launch_bounds__(256) void gn_sum3_lds_kernel(GnSum P, const float* 
 #pragma unroll
         for (int n = 0; n < 8; ++n) pw[e][n] = n < Q.cout ? Q.w[(c + e) * 16 + n] : 0.f;
     // ---- phase 1: source block of the up-sampled term -> LDS
-    const int nsrc = SR * SC;
-    {
-        const float* xb = T1.x + (long)b * T1.Hi * T1.Wi * T1.ld + c;
-        constexpr int UNR = 4;
-        for (int pb = p0; pb < nsrc; pb += pstep * UNR) {
-            f32x4 v[UNR];
-#pragma unroll
-            for (int u = 0; u < UNR; ++u) {
-                const int pp = pb + u * pstep;
-                const int r = pp / SC, q = pp - r * SC;
-                const int yy = min(sy0 + r, T1.Hi - 1), xx = min(sx0 + q, T1.Wi - 1);
-                if (pp < nsrc) v[u] = *reinterpret_cast<const f32x4*>(xb + ((long)yy * T1.Wi + xx) * T1.ld);
-            }
-#pragma unroll
-            for (int u = 0; u < UNR; ++u) {
-                const int pp = pb + u * pstep;
-                if (pp < nsrc) {
-                    f32x4 o;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = lm_gn_relu(v[u][e], a[1][e], g[1][e]);
-                    *reinterpret_cast<f32x4*>(ups + (long)pp * C + c) = o;
-                }
-            }
-        }
-    }
+    up_tile_stage(ups, T1, b, C, c, p0, pstep, sy0, sx0, SC, SR * SC, a[1], g[1]);
     __syncthreads();
     // ---- phase 2: outputs, UNR2 pixels of this thread in flight
     const float* x0b = T0.x + (long)b * T0.Hi * T0.Wi * T0.ld + c;
     const float* x2b = T2.x + (long)b * T2.Hi * T2.Wi * T2.ld + c;
-    const int lane = tid & 63;
     const unsigned li = (unsigned)cq;
-    const int nsel = 4 * (int)(li & 1) + 2 * (int)((li >> 1) & 1) + (int)((li >> 2) & 1);
-    const float pbias = (li < 8 && nsel < Q.cout && Q.bias) ? Q.bias[nsel] : 0.f;
+    const int nsel = proj_lane_output(li);
+    const float pbias = (proj_lane_stores(Q, li, nsel) && Q.bias) ? Q.bias[nsel] : 0.f;
     constexpr int UNR2 = 4;
     for (int pb = p0; pb < UT_R * UT_C; pb += pstep * UNR2) {
         f32x4 t0[UNR2], t2[UNR2];
@@ -491,24 +452,12 @@ __global__ __launch_bounds__(256) void gn_sum3_lds_kernel(GnSum P, const float* 
         }
 #pragma unroll
         for (int u = 0; u < UNR2; ++u) {
-            const int r = min(rr[u], UT_R - 1), q = qq[u];
-            const float* s0 = ups + (long)(ty0[r] * SC) * C + c;
-            const float* s1 = ups + (long)(ty1[r] * SC) * C + c;
-            const f32x4 v00 = *reinterpret_cast<const f32x4*>(s0 + tx0[q] * C), v01 = *reinterpret_cast<const f32x4*>(s0 + tx1[q] * C);
-            const f32x4 v10 = *reinterpret_cast<const f32x4*>(s1 + tx0[q] * C), v11 = *reinterpret_cast<const f32x4*>(s1 + tx1[q] * C);
-            const float wy0 = twy0[r], wy1 = twy1[r], wx0 = twx0[q], wx1 = twx1[q];
+            const f32x4 o0 = gn_relu4(t0[u], a[0], g[0]), o1 = up_tile_blend(U, min(rr[u], UT_R - 1), qq[u], c), o2 = gn_relu4(t2[u], a[2], g[2]);
             f32x4 acc;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-#pragma clang fp contract(off)
-                const float o0 = lm_gn_relu(t0[u][e], a[0][e], g[0][e]);
-                const float o1 = lm_bilerp(v00[e], v01[e], v10[e], v11[e], wy0, wy1, wx0, wx1);
-                const float o2 = lm_gn_relu(t2[u][e], a[2][e], g[2][e]);
-                acc[e] = (o0 + o1) + o2;
-            }
+            for (int e = 0; e < 4; ++e) acc[e] = (o0[e] + o1[e]) + o2[e];
             const long opix = ((long)b * Ho + oy0 + rr[u]) * Wo + ox0 + qq[u];
             if (y && live[u]) *reinterpret_cast<f32x4*>(y + opix * C + c) = acc;
-            // the 1x1 projection: the per-output kernel's fmaf chain and transpose-reduce, lane for lane
             float part[8];
 #pragma unroll
             for (int n = 0; n < 8; ++n) part[n] = 0.f;
@@ -516,19 +465,8 @@ __global__ __launch_bounds__(256) void gn_sum3_lds_kernel(GnSum P, const float* 
             for (int e = 0; e < 4; ++e)
 #pragma unroll
                 for (int n = 0; n < 8; ++n) part[n] = fmaf(acc[e], pw[e][n], part[n]);
-#pragma unroll
-            for (int half = 4, mask = 1; half >= 1; half >>= 1, mask <<= 1) {
-                const bool upper = (lane & mask) != 0;
-#pragma unroll
-                for (int jj = 0; jj < half; ++jj) {
-                    float lo = part[jj], hi = part[jj + half];
-                    asm volatile("" : "+v"(lo), "+v"(hi));
-                    const float send = upper ? lo : hi, keep = upper ? hi : lo;
-                    part[jj] = keep + __shfl_xor(send, mask);
-                }
-            }
-            for (unsigned o = 8; o < (unsigned)c4n; o <<= 1) part[0] += __shfl_xor(part[0], (int)o);
-            if (live[u] && li < 8 && nsel < Q.cout) Q.y1[opix * Q.ldy1 + nsel] = part[0] + pbias;
+            proj_reduce(part, tid & 63, (unsigned)c4n);
+            if (live[u] && proj_lane_stores(Q, li, nsel)) Q.y1[opix * Q.ldy1 + nsel] = part[0] + pbias;
         }
     }
 }
@@ -539,39 +477,24 @@ __global__ __launch_bounds__(256) void upsample_nhwc_kernel(const float* __restr
                                                             int C, long total4) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= total4) return;
-    const int c4n = C / 4;
-    const int c = (int)(i % c4n) * 4;
-    long t = i / c4n;
-    const int ox = (int)(t % Wo);
-    t /= Wo;
-    const int oy = (int)(t % Ho);
-    const int b = (int)(t / Ho);
+    int c, ox, oy, b;
+    decode_quad(i, C, Ho, Wo, c, ox, oy, b);
     int y0, y1, x0, x1;
     float wy0, wy1, wx0, wx1;
-    bilin_axis(oy, Hi, Ho, y0, y1, wy0, wy1);
-    bilin_axis(ox, Wi, Wo, x0, x1, wx0, wx1);
+    lm_bilin_axis(oy, Hi, Ho, y0, y1, wy0, wy1);
+    lm_bilin_axis(ox, Wi, Wo, x0, x1, wx0, wx1);
     const float* xb = x + (long)b * Hi * Wi * ldx + c;
     const f32x4 v00 = *reinterpret_cast<const f32x4*>(xb + ((long)y0 * Wi + x0) * ldx);
     const f32x4 v01 = *reinterpret_cast<const f32x4*>(xb + ((long)y0 * Wi + x1) * ldx);
     const f32x4 v10 = *reinterpret_cast<const f32x4*>(xb + ((long)y1 * Wi + x0) * ldx);
     const f32x4 v11 = *reinterpret_cast<const f32x4*>(xb + ((long)y1 * Wi + x1) * ldx);
     const long opix = ((long)b * Ho + oy) * Wo + ox;
-    f32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = lm_bilerp(v00[e], v01[e], v10[e], v11[e], wy0, wy1, wx0, wx1);
-    if (add) {
-        const f32x4 r = *reinterpret_cast<const f32x4*>(add + opix * lda + c);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = o[e] + r[e];
-    }
+    f32x4 o = bilerp4(v00, v01, v10, v11, wy0, wy1, wx0, wx1);
+    if (add) o = o + *reinterpret_cast<const f32x4*>(add + opix * lda + c);
     *reinterpret_cast<f32x4*>(y + opix * ldy + c) = o;
 }
 
 // NHWC (few channels) -> planar [B,C,Ho,Wo]
-__device__ __forceinline__ float upsample_blend(float v00, float v01, float v10, float v11, float wy0, float wy1, float wx0, float wx1) {
-    return lm_bilerp(v00, v01, v10, v11, wy0, wy1, wx0, wx1);      // fixed-order blend (common.h): scalar and vector kernels agree bit for bit
-}
-
 __global__ __launch_bounds__(256) void upsample_to_chw_kernel(const float* __restrict__ x, int ldx, float* __restrict__ y,
                                                               int Hi, int Wi, int Ho, int Wo, int C, long total) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
@@ -584,16 +507,16 @@ __global__ __launch_bounds__(256) void upsample_to_chw_kernel(const float* __res
     const int b = (int)(t / C);
     int y0, y1, x0, x1;
     float wy0, wy1, wx0, wx1;
-    bilin_axis(oy, Hi, Ho, y0, y1, wy0, wy1);
-    bilin_axis(ox, Wi, Wo, x0, x1, wx0, wx1);
+    lm_bilin_axis(oy, Hi, Ho, y0, y1, wy0, wy1);
+    lm_bilin_axis(ox, Wi, Wo, x0, x1, wx0, wx1);
     const float* xb = x + (long)b * Hi * Wi * ldx + c;
     const float v00 = xb[((long)y0 * Wi + x0) * ldx], v01 = xb[((long)y0 * Wi + x1) * ldx];
     const float v10 = xb[((long)y1 * Wi + x0) * ldx], v11 = xb[((long)y1 * Wi + x1) * ldx];
-    y[i] = upsample_blend(v00, v01, v10, v11, wy0, wy1, wx0, wx1);
+    y[i] = lm_bilerp(v00, v01, v10, v11, wy0, wy1, wx0, wx1);
 }
 
 // four horizontally adjacent outputs per thread (Wo % 4 == 0): one row decode and one y-axis interpolation per 16-byte store, 32-bit
-// index math.  Same blend as the scalar kernel (both written as the plain expression in this file).
+// index math.  Same blend as the scalar kernel: lm_bilerp's fixed order (common.h), so the two agree bit for bit.
 __global__ __launch_bounds__(256) void upsample_to_chw4_kernel(const float* __restrict__ x, int ldx, float* __restrict__ y,
                                                                int Hi, int Wi, int Ho, int Wo, int C, unsigned total4) {
     const unsigned i = blockIdx.x * 256u + threadIdx.x;
@@ -607,7 +530,7 @@ __global__ __launch_bounds__(256) void upsample_to_chw4_kernel(const float* __re
     const int b = (int)(t / (unsigned)C);
     int y0, y1;
     float wy0, wy1;
-    bilin_axis(oy, Hi, Ho, y0, y1, wy0, wy1);
+    lm_bilin_axis(oy, Hi, Ho, y0, y1, wy0, wy1);
     const float* xb = x + (long)b * Hi * Wi * ldx + c;
     const float* r0 = xb + (long)y0 * Wi * ldx;
     const float* r1 = xb + (long)y1 * Wi * ldx;
@@ -616,83 +539,63 @@ __global__ __launch_bounds__(256) void upsample_to_chw4_kernel(const float* __re
     for (int k = 0; k < 4; ++k) {
         int x0, x1;
         float wx0, wx1;
-        bilin_axis(ox0 + k, Wi, Wo, x0, x1, wx0, wx1);
+        lm_bilin_axis(ox0 + k, Wi, Wo, x0, x1, wx0, wx1);
         const float v00 = r0[(long)x0 * ldx], v01 = r0[(long)x1 * ldx], v10 = r1[(long)x0 * ldx], v11 = r1[(long)x1 * ldx];
-        o[k] = upsample_blend(v00, v01, v10, v11, wy0, wy1, wx0, wx1);
+        o[k] = lm_bilerp(v00, v01, v10, v11, wy0, wy1, wx0, wx1);
     }
     *reinterpret_cast<f32x4*>(y + (long)i * 4) = o;
 }
 
 // ----------------------------------------------------------------------------- LayerNorm: one wave per row
+// Two-pass arithmetic, PER * 64 >= D columns per lane slot.  MASKED: the columns >= D are masked out - a masked column holds 0 and adds
+// 0 to the lane's sum, so each lane's sums and the butterfly run in the same order as without the mask.
+template <int PER, bool MASKED>
+__device__ __forceinline__ void layernorm_row(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                              float* __restrict__ y, long rows, int D, float eps) {
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const float* xr = x + row * D;
+    float v[PER];
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const int c = k * 64 + lane;
+        v[k] = (!MASKED || c < D) ? xr[c] : 0.f;
+        s += v[k];
+    }
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    const float mean = s / (float)D;
+    float q = 0.f;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const float d = (!MASKED || k * 64 + lane < D) ? v[k] - mean : 0.f;
+        q += d * d;
+    }
+    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
+    const float rstd = 1.0f / sqrtf(q / (float)D + eps);
+    float* yr = y + row * D;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const int c = k * 64 + lane;
+        if (!MASKED || c < D) yr[c] = (v[k] - mean) * rstd * gamma[c] + beta[c];
+    }
+}
+
+// D = PER * 64 (512 and 1024)
 template <int PER>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, float* __restrict__ y, long rows,
                                                         float eps) {
-    constexpr int D = PER * 64;
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int lane = threadIdx.x & 63;
-    const float* xr = x + row * D;
-    float v[PER];
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-        v[k] = xr[k * 64 + lane];
-        s += v[k];
-    }
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    const float mean = s / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-        const float d = v[k] - mean;
-        q += d * d;
-    }
-    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
-    const float rstd = 1.0f / sqrtf(q / (float)D + eps);
-    float* yr = y + row * D;
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-        const int c = k * 64 + lane;
-        yr[c] = (v[k] - mean) * rstd * gamma[c] + beta[c];
-    }
+    layernorm_row<PER, false>(x, gamma, beta, y, rows, PER * 64, eps);
 }
 
-// The other widths (D % 32 == 0, 32 <= D <= 4096, not 768; the ViT at patch sizes 4 / 6 / 12 / 16 has D = 128 / 288 / 1152 / 2048): the same
-// one-wave-per-row, two-pass arithmetic with PER * 64 >= D columns per lane slot and the columns >= D masked out.  A masked column
-// holds 0 and adds 0 to the lane's sum, so each lane's sums and the butterfly run in the same order as in layernorm_kernel.
+// The other widths (D % 32 == 0, 32 <= D <= 4096, not 768; the ViT at patch sizes 4 / 6 / 12 / 16 has D = 128 / 288 / 1152 / 2048)
 template <int PER>
 __global__ __launch_bounds__(256) void layernorm_masked_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, float* __restrict__ y, long rows, int D,
                                                                float eps) {
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int lane = threadIdx.x & 63;
-    const float* xr = x + row * D;
-    float v[PER];
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-        const int c = k * 64 + lane;
-        v[k] = c < D ? xr[c] : 0.f;
-        s += v[k];
-    }
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    const float mean = s / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-        const float d = k * 64 + lane < D ? v[k] - mean : 0.f;
-        q += d * d;
-    }
-    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
-    const float rstd = 1.0f / sqrtf(q / (float)D + eps);
-    float* yr = y + row * D;
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-        const int c = k * 64 + lane;
-        if (c < D) yr[c] = (v[k] - mean) * rstd * gamma[c] + beta[c];
-    }
+    layernorm_row<PER, true>(x, gamma, beta, y, rows, D, eps);
 }
 
 __global__ __launch_bounds__(256) void unpatchify_kernel(const float* __restrict__ t, float* __restrict__ y, int G, int P,
@@ -709,6 +612,12 @@ __global__ __launch_bounds__(256) void unpatchify_kernel(const float* __restrict
     y[i] = t[((long)b * G * G + gh * G + gw) * (P * P * C) + (p1 * P + p2) * C + c];
 }
 
+int launch_gn_final(void* stream, const double* part, float* stats, int B, int HW, int C, int nchunk, float eps, int split) {
+    hipLaunchKernelGGL(gn_final_kernel, dim3(lm_cdiv(C, 32), B), dim3(256), 0, (hipStream_t)stream, part, stats, HW, C, nchunk, eps, split);
+    LM_LAUNCH_CHECK();
+    return LM_OK;
+}
+
 }  // namespace
 
 LM_API int lm_gn_stats(void* stream, const float* x, double* workspace, float* stats, int B, int HW, int C, float eps) {
@@ -717,25 +626,19 @@ LM_API int lm_gn_stats(void* stream, const float* x, double* workspace, float* s
     const int nchunk = lm_cdiv(HW, GN_CHUNK);
     hipLaunchKernelGGL(gn_partial_kernel, dim3(nchunk, B), dim3(256), 0, (hipStream_t)stream, x, workspace, HW, C, nchunk);
     LM_LAUNCH_CHECK();
-    hipLaunchKernelGGL(gn_final_kernel, dim3(lm_cdiv(C, 32), B), dim3(256), 0, (hipStream_t)stream, workspace, stats, HW, C, nchunk, eps, 1);
-    LM_LAUNCH_CHECK();
-    return LM_OK;
+    return launch_gn_final(stream, workspace, stats, B, HW, C, nchunk, eps, 1);
 }
 
 // second pass for partials produced by lm_conv2d_nhwc_mfma_f32_gnstats ([B][nchunk][C][2] doubles)
 LM_API int lm_gn_finalize(void* stream, const double* partial, float* stats, int B, int HW, int C, int nchunk, float eps) {
     LM_REQUIRE(partial && stats && nchunk >= 1, "gn_finalize: bad args");
-    hipLaunchKernelGGL(gn_final_kernel, dim3(lm_cdiv(C, 32), B), dim3(256), 0, (hipStream_t)stream, partial, stats, HW, C, nchunk, eps, 1);
-    LM_LAUNCH_CHECK();
-    return LM_OK;
+    return launch_gn_final(stream, partial, stats, B, HW, C, nchunk, eps, 1);
 }
 
 // the same with the statistics laid out per channel group: stats [split][B][C / split][2] (C % split == 0) - same values
 LM_API int lm_gn_finalize_split(void* stream, const double* partial, float* stats, int B, int HW, int C, int nchunk, float eps, int split) {
     LM_REQUIRE(partial && stats && nchunk >= 1 && split >= 1 && C % split == 0, "gn_finalize_split: bad args (C=%d split=%d)", C, split);
-    hipLaunchKernelGGL(gn_final_kernel, dim3(lm_cdiv(C, 32), B), dim3(256), 0, (hipStream_t)stream, partial, stats, HW, C, nchunk, eps, split);
-    LM_LAUNCH_CHECK();
-    return LM_OK;
+    return launch_gn_final(stream, partial, stats, B, HW, C, nchunk, eps, split);
 }
 
 LM_API long lm_gn_stats_workspace_bytes(int B, int HW, int C) {
@@ -772,6 +675,28 @@ int up_block_extent(int in, int out, int tile) {
     return ext;
 }
 
+// Whether the up-sampled term T takes an LDS kernel: its test-only switch is on, the scale is <= 1/2 on both axes, and the source block
+// of a UT_R x UT_C output tile (SR x SC pixels x C floats) fits `cap` bytes.
+struct UpLdsRoute {
+    int SR, SC;
+    size_t bytes;
+};
+bool up_lds_route(const GnTerm& T, int Ho, int Wo, int C, size_t cap, bool on, UpLdsRoute& R) {
+    if (!on || T.Hi <= 1 || T.Wi <= 1 || Ho < 2 * T.Hi - 1 || Wo < 2 * T.Wi - 1) return false;
+    R.SR = up_block_extent(T.Hi, Ho, UT_R);
+    R.SC = up_block_extent(T.Wi, Wo, UT_C);
+    R.bytes = (size_t)R.SR * R.SC * C * sizeof(float);
+    return R.bytes <= cap;
+}
+// grid (ceil(Wo / UT_C), ceil(Ho / UT_R), B), `lds` bytes of dynamic LDS
+template <class Kernel, class... Args>
+int launch_up_tile(Kernel kernel, size_t lds, void* stream, int B, int Ho, int Wo, Args... args) {
+    if (int e = lm_ensure_dynamic_lds((const void*)kernel, lds)) return e;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)lm_cdiv(Wo, UT_C), (unsigned)lm_cdiv(Ho, UT_R), (unsigned)B), dim3(256), lds, (hipStream_t)stream, args...);
+    LM_LAUNCH_CHECK();
+    return LM_OK;
+}
+
 int launch_gn_sum(void* stream, int n, const float* const* x, const float* const* stats, const int* Hi, const int* Wi, const int* ldx,
                   const float* gamma, const float* beta, float* y, int B, int Ho, int Wo, int C, Proj1x1 Q) {
     LM_REQUIRE(n >= 1 && n <= 3 && x && stats && Hi && Wi && gamma && beta && C > 0 && C % 4 == 0, "gn_relu_upsample_sum: bad args");
@@ -798,32 +723,18 @@ int launch_gn_sum(void* stream, int n, const float* const* x, const float* const
     int same = 0;
     for (int k = 0; k < n; ++k)
         if (Hi[k] == Ho && Wi[k] == Wo) same |= 1 << k;
-    if (n == 1 && same == 0 && !Q.w && y && 256 % c4n == 0 && Hi[0] > 1 && Wi[0] > 1 && Ho >= 2 * Hi[0] - 1 && Wo >= 2 * Wi[0] - 1) {
-        // one up-sampling term (scale <= 1/2): source block staged in LDS
+    UpLdsRoute R;
+    if (n == 1 && same == 0 && !Q.w && y && 256 % c4n == 0) {
+        // one up-sampling term: source block staged in LDS
         static const bool lds_up = [] { const char* e = getenv("LM_GN_UP_LDS"); return !e || atoi(e) != 0; }();
-        const int SR = up_block_extent(Hi[0], Ho, UT_R), SC = up_block_extent(Wi[0], Wo, UT_C);
-        const size_t lds = (size_t)SR * SC * C * sizeof(float);
-        if (lds_up && lds <= 72 * 1024) {
-            if (int e = lm_ensure_dynamic_lds((const void*)gn_relu_up_lds_kernel, lds)) return e;
-            hipLaunchKernelGGL(gn_relu_up_lds_kernel, dim3((unsigned)lm_cdiv(Wo, UT_C), (unsigned)lm_cdiv(Ho, UT_R), (unsigned)B), dim3(256), lds,
-                               (hipStream_t)stream, P.t[0], gamma, beta, y, Ho, Wo, C, SR, SC);
-            LM_LAUNCH_CHECK();
-            return LM_OK;
-        }
+        if (up_lds_route(P.t[0], Ho, Wo, C, 72 * 1024, lds_up, R))
+            return launch_up_tile(gn_relu_up_lds_kernel, R.bytes, stream, B, Ho, Wo, P.t[0], gamma, beta, y, Ho, Wo, C, R.SR, R.SC);
     }
-    if (n == 3 && same == 5 && Q.w && c4n >= 8 && c4n <= 64 && (c4n & (c4n - 1)) == 0 && Hi[1] > 1 && Wi[1] > 1 && Ho >= 2 * Hi[1] - 1 &&
-        Wo >= 2 * Wi[1] - 1) {
+    if (n == 3 && same == 5 && Q.w && c4n >= 8 && c4n <= 64 && (c4n & (c4n - 1)) == 0) {
         // s2 + s3 + s4 (+ the branch's 1x1 output layer): the up-sampled middle term through LDS, affines and weights once per thread
         static const bool lds_sum = [] { const char* e = getenv("LM_GN_SUM_LDS"); return !e || atoi(e) != 0; }();
-        const int SR = up_block_extent(Hi[1], Ho, UT_R), SC = up_block_extent(Wi[1], Wo, UT_C);
-        const size_t lds = (size_t)SR * SC * C * sizeof(float);
-        if (lds_sum && lds <= 64 * 1024) {
-            if (int e = lm_ensure_dynamic_lds((const void*)gn_sum3_lds_kernel, lds)) return e;
-            hipLaunchKernelGGL(gn_sum3_lds_kernel, dim3((unsigned)lm_cdiv(Wo, UT_C), (unsigned)lm_cdiv(Ho, UT_R), (unsigned)B), dim3(256), lds,
-                               (hipStream_t)stream, P, gamma, beta, y, Ho, Wo, C, SR, SC, Q);
-            LM_LAUNCH_CHECK();
-            return LM_OK;
-        }
+        if (up_lds_route(P.t[1], Ho, Wo, C, 64 * 1024, lds_sum, R))
+            return launch_up_tile(gn_sum3_lds_kernel, R.bytes, stream, B, Ho, Wo, P, gamma, beta, y, Ho, Wo, C, R.SR, R.SC, Q);
     }
     const dim3 grid((unsigned)lm_cdiv((long)Wo * c4n, 256), (unsigned)Ho, (unsigned)B);
 #define LM_GNS(NN, SS)                                                                                                           \

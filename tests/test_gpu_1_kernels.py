@@ -161,6 +161,54 @@ def test_gn_relu_upsample_one_term_lds_block(dev, B, C, hi, wi, ho, wo, ld):
     _close(got, ref, 1e-5, 'one term, LDS block')
 
 
+def test_gn_relu_upsample_sum_every_instantiation(dev):
+    """All 14 gn_relu_upsample_sum_kernel<N, SAME> (n = 1..3 terms, every mask of same-size terms) against the chain of accumulating
+    lm_gn_relu_upsample calls, bit for bit, without and with the fused 1x1 projection (cout 5; with and without writing the sum; against
+    F.conv2d on the fp64 reference).  Output 9 x 37 from 6 x 20: a scale above 1/2, so neither LDS kernel takes the call; a row of
+    37 * C/4 = 296 quads spans two workgroups, the second ragged; term 1 is a channel slice (ld 48).  C = 24 (C/4 no power of two: the
+    column comes from a division, not a shift) runs without projection, which needs a power of two."""
+    from lanemapping_amd import ops
+    B, size, coarse = 2, (9, 37), (6, 20)
+    for C in (32, 24):
+        g = torch.Generator().manual_seed(300 + C)
+        gamma, beta = torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g)
+        gd, bd = gamma.to(dev), beta.to(dev)
+        terms, dense, ref = {}, {}, {}          # per (term, same size?): the operand (term 1 a slice), its dense copy, the fp64 term
+        for k in range(3):
+            for same in (0, 1):
+                h, w = size if same else coarse
+                ld = 48 if k == 1 else C
+                wide = (torch.randn(B, h, w, ld, generator=g) * (k + 1) + 0.5 * k)
+                x = wide.to(dev)[..., ld - C:].permute(0, 3, 1, 2)
+                dense[k, same] = x.contiguous(memory_format=torch.channels_last)
+                x64 = wide[..., ld - C:].permute(0, 3, 1, 2).double()
+                # (mean, rstd) from torch: lm_gn_stats takes only channel counts that divide 256
+                stats = torch.stack((x64.mean((2, 3)), 1.0 / torch.sqrt(x64.var((2, 3), unbiased=False) + 1e-5)), -1)
+                terms[k, same] = (x, stats.float().to(dev))
+                ref[k, same] = F.interpolate(F.relu(F.group_norm(x64, C, gamma.double(), beta.double(), 1e-5)), size=size, mode='bilinear',
+                                             align_corners=True)
+        if C == 32:
+            w = torch.randn(5, C, 1, 1, generator=g) / 8
+            bias = torch.randn(5, generator=g)
+            w16, biasd = ops.pack_small(w.to(dev)), bias.to(dev)
+        for n in (1, 2, 3):
+            for mask in range(1 << n):
+                name = f'C={C} n={n} same={mask}'
+                pick = [(k, (mask >> k) & 1) for k in range(n)]
+                y = ops.gn_relu_upsample_sum([terms[p] for p in pick], gd, bd, size)
+                z = None
+                for p in pick:
+                    z = ops.gn_relu_upsample(dense[p], terms[p][1], gd, bd, size, out=z, accumulate=z is not None)
+                assert torch.equal(y, z), (name, float((y - z).abs().max()))
+                if C != 32:
+                    continue
+                ysum, y1 = ops.gn_relu_upsample_sum([terms[p] for p in pick], gd, bd, size, proj=(w16, biasd, 5))
+                only = ops.gn_relu_upsample_sum([terms[p] for p in pick], gd, bd, size, proj=(w16, biasd, 5), keep_sum=False)
+                assert torch.equal(only, y1), name
+                assert torch.equal(ysum, y), name
+                _close(y1, F.conv2d(sum(ref[p] for p in pick), w.double(), bias.double()), 1e-5, f'fused 1x1, {name}')
+
+
 @pytest.mark.parametrize('cin,cout,B,h,w,mode', [(64, 256, 2, 72, 72, 'up'), (128, 256, 1, 36, 40, 'up'), (64, 128, 2, 40, 24, 'res'),
                                                  (64, 200, 1, 33, 17, 'up'), (256, 256, 1, 36, 36, 'up'), (64, 256, 1, 24, 24, 'rows')])
 def test_conv1x1_lateral_residuals(dev, cin, cout, B, h, w, mode):
