@@ -700,6 +700,51 @@ int lm_las_line_cross_records(void* hip_stream, const unsigned char* records, in
                               float half_width, const float* stations, const int* bin_start, const int* bin_start_host, int L, double bin,
                               float z_tol, int lateral_q, int paint_iq, int accumulate, long* cells, long n_cells);
 
+/* ---- the paint / asphalt histograms (csrc/profile.hip): per line and per lateral ring around it a histogram of the intensities of its
+ * returns - what the threshold between asphalt and paint is read off.  Returns on a line are paint plus some asphalt, returns a few
+ * decimetres beside it are asphalt; the threshold that separates the two populations best is the min_intensity / paint_intensity the
+ * stages above ask for, and per line it is a check of the network: a line whose inner returns are no brighter than its outer ones has no
+ * paint under it (las_io.PaintThreshold, las_io.paint_threshold are the host policy on top of the table).
+ * THE RULE (one definition: hist_cell in csrc/profile.hip, which both kernels call, this text, tests/threshold_ref.py).  Eligibility, the
+ * hit test and the winner are exactly the labelling rule's (smallest d2, ties to the smaller line, then to the smaller segment index),
+ * WITHOUT a min_intensity: the table must see asphalt.  For a point whose winner is segment s of line k, with px, py of that rule and o, q,
+ * iq of the marking profile above, unchanged, plain f32, no contraction - of the stations table only rlen is read; no bin_start and no
+ * station bin are involved:
+ *     hq  = (int)ceil((double)half_width 1024)                 on the host (half_width the f32 the index was built for)
+ *     Z   = hq / ring_q + 1                                    rings per line (integer division)
+ *     r   = min(|q|, hq) / ring_q                              the ring: ring r covers the offsets r ring_q <= |q| < (r + 1) ring_q
+ *     NB  = 65536 >> bin_shift                                 counts per histogram
+ *     ib  = iq >> bin_shift                                    a NaN intensity gives iq = 0
+ *     hist[((k-1) Z + r) NB + ib] += 1
+ * OUTPUT.  hist [L][Z][NB] int64; a cell no return fell into reads 0.  ring_q: the ring width in 1/1024 m, an integer >= 1 (above hq:
+ * Z = 1); bin_shift: 0 .. 8.  Integer adds only, no float atomic: the bits do not depend on the order of the points, files or adds.
+ * line_hist_points: points_xyzi DEVICE [N][4] f32, the index arguments of lm_label_points, stations DEVICE [S][4] f32 (16-byte aligned),
+ *         L, z_tol, ring_q, bin_shift, accumulate, hist, n_hist = L Z NB.  A kernel of cross_points_kernel's streaming shape, no LDS: four
+ *         16-byte loads in flight per lane, a wave without a candidate leaves through the ballot.
+ * las_line_hist_records: the inputs of lm_las_line_cross_records up to `select`, then the same: a further instantiation of
+ *         las_profile_kernel, the records are read once and only read, a record that `select` drops contributes nothing.
+ * Both: accumulate = 0 zeroes hist on the stream first (a kernel, as every entry that may be captured zeroes), accumulate = 1 adds to what
+ *         is there - the files of a strip go into one table this way.  Asynchronous, no workspace, nothing read back.  N = 0 or S = 0 is
+ *         LM_OK after the initialisation.  TRUST: the device tables are the caller's word; whatever they hold, hist is written only in
+ *         [0, n_hist).
+ * Refused with LM_ERR_ARG and a message that names the argument, before anything is launched or written: what the cross entries refuse of
+ * the shared arguments (the index, half_width > 16, z_tol > 16, segments whose lines leave 1 .. L, a null or misaligned stations, the
+ * points or records); ring_q < 1; bin_shift outside 0 .. 8; L Z NB > 2^27; n_hist != L Z NB; accumulate outside 0, 1; a null hist with
+ * n_hist > 0; "hist is not 8-byte aligned".
+ * NOTE on the place of `hip_stream`: these two entries take the stream as their LAST parameter.  The older entries take it first, and
+ * tests/test_stream_inventory_cpu.py, tests/test_bounds_inventory_cpu.py and tests/lds_state.py find entries by that spelling and hold each
+ * to a literal table inside an existing test file; an entry found there needs a row in those tables.  The cases those tables would name -
+ * guarded buffers, a side stream, graph replay, poisoned LDS before las_profile_kernel<false, false, true> - are in
+ * tests/test_gpu_threshold.py.  For the same reason hist_points_kernel declares no __shared__ and the record kernel keeps the name
+ * las_profile_kernel. */
+int lm_line_hist_points(const float* points_xyzi, long N, const float* segments, long S, const LmLineGrid* grid, const int* cell_start,
+                        const int* cell_segs, float half_width, const float* stations, int L, float z_tol, int ring_q, int bin_shift,
+                        int accumulate, long* hist, long n_hist, void* hip_stream);
+int lm_las_line_hist_records(const unsigned char* records, int record_len, int point_format, long n, const double* scale,
+                             const double* offset, const double* shift, const LmLasSelect* select, const float* segments, long S,
+                             const LmLineGrid* grid, const int* cell_start, const int* cell_segs, float half_width, const float* stations,
+                             int L, float z_tol, int ring_q, int bin_shift, int accumulate, long* hist, long n_hist, void* hip_stream);
+
 /* ---- the paint no lane line explains (csrc/residue.hip): stop bars, crossing bars, arrows, hatching, chevrons and lines the network
  * missed are bright paint in the same returns as the lines, and label, profile and colour above see only paint that lies ON a line.  This
  * stage takes the strip's returns and the lines the call returns, keeps the bright road-level returns that no line explains (the RESIDUE),

@@ -168,6 +168,10 @@ SIGNATURES = {
     'lm_las_line_cross_records': (i32, [vp, vp, i32, i32, i64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                         C.POINTER(LmLasSelect), vp, i64, C.POINTER(LmLineGrid), vp, vp, f32, vp, vp, vp, i32, C.c_double, f32, i32,
                                         i32, i32, vp, i64]),
+    'lm_line_hist_points': (i32, [vp, i64, vp, i64, C.POINTER(LmLineGrid), vp, vp, f32, vp, i32, f32, i32, i32, i32, vp, i64, vp]),
+    'lm_las_line_hist_records': (i32, [vp, i32, i32, i64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                       C.POINTER(LmLasSelect), vp, i64, C.POINTER(LmLineGrid), vp, vp, f32, vp, i32, f32, i32, i32, i32, vp,
+                                       i64, vp]),
     'lm_residue_keys': (i32, [vp, vp, i64, vp, i64, C.POINTER(LmLineGrid), vp, vp, f32, f32, f32, f32, C.c_double, i32, i32, vp, vp]),
     'lm_cell_components': (i32, [vp, vp, i64, i32, i32, i32, vp, vp]),
     'lm_residue_stats': (i32, [vp, vp, vp, i32, i32, vp, vp, i64, i64, vp]),

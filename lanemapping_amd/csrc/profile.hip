@@ -38,6 +38,12 @@
 // streaming shape and no LDS, las_profile_kernel<false, true> is the record kernel's third instantiation - <false> and <true> compile to
 // the instructions they had before it existed.  Here the lanes of a wave do not share one to three bins: a wave crossing a marking hits
 // about a dozen distinct rows, so cross_add's loop runs about a dozen times; it still beats four atomics per hit lane (cross_add).
+//
+// The paint / asphalt histograms (lm_line_hist_points, lm_las_line_hist_records; the rule: include/lanemap_hip.h).  The same search, no
+// min_intensity and no station bin: per line and per lateral ring r = min(|q|, hq) / ring_q a histogram of iq >> bin_shift, one count per
+// return.  hist_cell is the one device function for the per-point terms; hist_points_kernel has cross_points_kernel's streaming shape and
+// no LDS, las_profile_kernel<false, false, true> is the record kernel's fourth instantiation - the other three compile to the
+// instructions they had before it existed.  How a wave's counts go to memory was measured both ways: one atomic per hit lane won (hist_add).
 #include "common.h"
 #include "label_rule.h"
 #include "las_record.h"
@@ -51,6 +57,7 @@ constexpr int PER = 4;                   // points per lane of profile_points_ke
 constexpr int CHUNK = 256 * PER;
 constexpr float MAX_HALF_WIDTH = 16.f;   // |q| <= 16 * 1024 + 1: q*q < 2^29, and 2^31 of them stay far inside 64 bits
 constexpr long MAX_CROSS_ROWS = 1L << 27;   // rows of 32 bytes: the cross-section table stays within 4 GiB
+constexpr long MAX_HIST_CELLS = 1L << 27;   // counts of 8 bytes: the histograms stay within 1 GiB and a cell fits an int
 
 struct ProfDev {
     const float4* stations;              // [S]: s0 len rlen 0
@@ -71,8 +78,14 @@ struct CrossDev : ProfDev {              // what las_profile_kernel<false, true>
     unsigned paint_iq;                   // 0 .. 65536
 };
 
-template <bool COLOUR, bool CROSS = false>
-using ProfArg = std::conditional_t<CROSS, CrossDev, std::conditional_t<COLOUR, ColourDev, ProfDev>>;
+struct HistDev {                         // what las_profile_kernel<false, false, true> and hist_points_kernel take
+    const float* stations;               // [S][4]: only rlen, column 2, is read
+    long long* hist;                     // [L][Z][NB]
+    int L, hq, ring_q, Z, bin_shift;     // ceil(half_width 1024); the ring width in 1/1024 m; hq / ring_q + 1 rings; NB = 65536 >> bin_shift
+};
+
+template <bool COLOUR, bool CROSS = false, bool HIST = false>
+using ProfArg = std::conditional_t<HIST, HistDev, std::conditional_t<CROSS, CrossDev, std::conditional_t<COLOUR, ColourDev, ProfDev>>>;
 
 // the bin (absolute, -1: none), q and iq of a point whose winner is segment s of line ln at t.  bin_start and stations are device tables
 // the host cannot see: whatever they hold, a bin outside [0, n_bins) is never returned and bin_start is never read outside [0, L].
@@ -227,6 +240,32 @@ __device__ __forceinline__ void cross_add(const CrossDev& P, int row, unsigned i
     }
 }
 
+// The histogram's per-point terms (one definition: the two kernels and include/lanemap_hip.h) for a point whose winner is segment s of line
+// ln: -> its cell in the table, -1: none.  q and iq are profile_bin's expressions, unchanged.  The ring r <= hq / ring_q = Z - 1 by the clamp
+// of |q|, ib <= 65535 >> bin_shift = NB - 1 by the clamp of iq and ln <= L is checked: whatever the device tables hold, a cell outside
+// [0, L Z NB) is never returned.
+__device__ __forceinline__ int hist_cell(const float4 p, const IndexDev& I, const HistDev& H, int ln, int s) {
+    if (ln <= 0 || ln > H.L) return -1;
+    const float4 A = I.seg[2 * s], D = I.seg[2 * s + 1];
+    const float rlen = H.stations[4 * (long)s + 2];
+    const float px = p.x - A.x, py = p.y - A.y;
+    const float o = (A.w * py - D.x * px) * rlen;
+    const int q = (int)rintf(o * 1024.f);
+    const unsigned iq = (unsigned)fminf(fmaxf(rintf(p.w), 0.f), 65535.f);
+    unsigned aq = q < 0 ? 0u - (unsigned)q : (unsigned)q;              // |q|, also of -2^31
+    aq = aq < (unsigned)H.hq ? aq : (unsigned)H.hq;
+    const int r = (int)(aq / (unsigned)H.ring_q), NB = 65536 >> H.bin_shift;
+    return ((ln - 1) * H.Z + r) * NB + (int)(iq >> H.bin_shift);
+}
+
+// One no-return 64-bit atomic add per hit lane (cell = -1: the lane has nothing).  Unlike the rows of cross_add a hit here is one count in
+// one of Z NB cells, and the lanes of a wave rarely share one: on the bench's cloud in cell order a wave's 43.8 hit lanes fall into 42.4
+// distinct cells.  The merged form - cross_add's loop over the distinct cells of the wave, the leader adding the popcount - was measured
+// beside this one and is 10 to 24 % slower in all six rows of profiles/paint_threshold.txt.
+__device__ __forceinline__ void hist_add(const HistDev& H, int cell) {
+    if (cell >= 0) atomicAdd(reinterpret_cast<unsigned long long*>(H.hist) + cell, 1ull);
+}
+
 // grid: ceil(n_bins * 6 / 256)
 __global__ __launch_bounds__(256) void profile_init_kernel(long long* __restrict__ bins, long words) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
@@ -296,13 +335,38 @@ __global__ __launch_bounds__(256) void cross_points_kernel(const lab_f32x4* __re
     }
 }
 
+// grid: ceil(N / 1024) workgroups.  cross_points_kernel's streaming shape with the histogram's accumulation; no LDS.
+__global__ __launch_bounds__(256) void hist_points_kernel(const lab_f32x4* __restrict__ pts, long N, IndexDev I, HistDev H) {
+    const long first = (long)blockIdx.x * CHUNK;
+    const long left = N - first;                               // >= 1
+    float4 p[PER];
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        const long i = (long)j * 256 + threadIdx.x;
+        const lab_f32x4 v = __builtin_nontemporal_load(pts + first + (i < left ? i : left - 1));   // unconditional, tail lanes masked below
+        p[j] = float4{v[0], v[1], v[2], v[3]};
+    }
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        const long i = (long)j * 256 + threadIdx.x;
+        int a = 0, b = 0;
+        if (i < left) label_range(p[j], I, a, b);
+        if (__ballot(b > a) == 0) continue;                    // wave-uniform: a wave beside the lines leaves here
+        float best, t;
+        int s;
+        const int ln = label_search_t<true>(p[j], I, a, b, best, s, t);
+        hist_add(H, ln > 0 ? hist_cell(p[j], I, H, ln, s) : -1);
+    }
+}
+
 // grid: min(blocks of 256 records, the workgroups resident at once) workgroups; dynamic LDS = 256 records.  Per block: stage, decode into
 // registers, barrier (the stage is free again), search and accumulate.  The records are only read.  COLOUR: P is a ColourDev, the lane also
 // takes the R, G, B of its own staged record into registers before the barrier, and the colour row is merged after the profile's.  CROSS: P
-// is a CrossDev, and after the search the cross-section's cell is accumulated instead of the profile's bin.
-template <bool COLOUR, bool CROSS = false>
+// is a CrossDev, and after the search the cross-section's cell is accumulated instead of the profile's bin.  HIST: P is a HistDev, and the
+// histogram's cell takes its place.
+template <bool COLOUR, bool CROSS = false, bool HIST = false>
 __global__ __launch_bounds__(256) void las_profile_kernel(const unsigned* __restrict__ rec, int record_len, long n, long nblk, LasXf X, LasSel S,
-                                                          int use_sel, IndexDev I, ProfArg<COLOUR, CROSS> P) {
+                                                          int use_sel, IndexDev I, ProfArg<COLOUR, CROSS, HIST> P) {
     extern __shared__ unsigned prof_stage[];
     for (long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
         const int cnt = las_stage_block(rec, record_len, n, blk, prof_stage);
@@ -326,7 +390,9 @@ __global__ __launch_bounds__(256) void las_profile_kernel(const unsigned* __rest
         float best, t;
         int s;
         const int ln = label_search_t<true>(p, I, a, b, best, s, t);
-        if constexpr (CROSS) {
+        if constexpr (HIST) {
+            hist_add(P, ln > 0 ? hist_cell(p, I, P, ln, s) : -1);
+        } else if constexpr (CROSS) {
             int row = -1, zq = 0;
             unsigned iq = 0u;
             if (ln > 0) row = cross_row(p, I, P, ln, s, t, iq, zq);
@@ -372,6 +438,9 @@ struct TableArgs {                       // where the result goes: an entry sets
     long* cells;                         // cross-sections
     long n_cells;
     int lateral_q, paint_iq;
+    long* hist;                          // histograms
+    long n_hist;
+    int ring_q, bin_shift;
 };
 
 // the lines, up to the host copy of the bin table -> I, and P but for its table
@@ -437,6 +506,34 @@ int check_cross(const char* who, const LineArgs& A, int lateral_q, int paint_iq,
     return LM_OK;
 }
 
+// the arguments of the two histogram entries, checked likewise: what the cross entries refuse of the arguments they share (no bin, no
+// bin_start), then the histogram's own; fills I and H
+int check_hist(const char* who, const LineArgs& A, int ring_q, int bin_shift, long* hist, long n_hist, IndexDev& I, HistDev& H) {
+    if (int e = check_index(who, A.grid, A.S, A.segments, A.cell_start, A.cell_segs, A.half_width, A.z_tol, I)) return e;
+    LM_REQUIRE(A.half_width <= MAX_HALF_WIDTH, "%s: half_width=%g, at most %g m is supported (the offsets are taken in 1/1024 m)", who,
+               (double)A.half_width, (double)MAX_HALF_WIDTH);
+    LM_REQUIRE(A.accumulate == 0 || A.accumulate == 1, "%s: accumulate=%d is neither 0 nor 1", who, A.accumulate);
+    LM_REQUIRE(A.L >= 0, "%s: L=%d lines", who, A.L);
+    LM_REQUIRE(A.S == 0 || (A.grid->min_line >= 1 && A.grid->max_line <= A.L), "%s: segments carry lines %d .. %d, outside 1 .. L=%d", who,
+               A.S ? A.grid->min_line : 0, A.S ? A.grid->max_line : 0, A.L);
+    LM_REQUIRE(A.S == 0 || A.stations, "%s: null pointer (stations)", who);
+    LM_REQUIRE(((uintptr_t)A.stations & 15) == 0, "%s: stations is not 16-byte aligned", who);
+    LM_REQUIRE(((uintptr_t)hist & 7) == 0, "%s: hist is not 8-byte aligned", who);
+    LM_REQUIRE(A.z_tol <= MAX_HALF_WIDTH, "%s: z_tol=%g, at most %g m is supported", who, (double)A.z_tol, (double)MAX_HALF_WIDTH);
+    LM_REQUIRE(ring_q >= 1, "%s: ring_q=%d must be a ring width >= 1 (in 1/1024 m)", who, ring_q);
+    LM_REQUIRE(bin_shift >= 0 && bin_shift <= 8, "%s: bin_shift=%d must lie in 0 .. 8", who, bin_shift);
+    H = HistDev{};
+    H.stations = A.stations, H.L = A.L, H.hq = (int)std::ceil((double)A.half_width * 1024.0);   // <= 16384
+    H.ring_q = ring_q, H.Z = H.hq / ring_q + 1, H.bin_shift = bin_shift;
+    const long NB = 65536L >> bin_shift, cells = (long)A.L * H.Z * NB;                           // < 2^31 2^15 2^16
+    LM_REQUIRE(cells <= MAX_HIST_CELLS, "%s: L=%d lines of Z=%d rings of NB=%ld counts are %ld, at most 2^27 are supported (choose a larger "
+               "ring_q or bin_shift)", who, A.L, H.Z, NB, cells);
+    LM_REQUIRE(n_hist == cells, "%s: n_hist=%ld, but L=%d lines of Z=%d rings of NB=%ld counts are %ld", who, n_hist, A.L, H.Z, NB, cells);
+    LM_REQUIRE(n_hist == 0 || hist, "%s: null pointer (hist)", who);
+    H.hist = reinterpret_cast<long long*>(hist);
+    return LM_OK;
+}
+
 int init_bins(const ProfDev& P, hipStream_t s) {
     const long words = (long)P.n_bins * 6;
     if (words == 0) return LM_OK;
@@ -480,19 +577,25 @@ LM_API int lm_line_profile_points(void* hip_stream, const float* points_xyzi, lo
 
 namespace {
 
-// The three record entries.  COLOUR: blue_q and colours are checked after everything the profile entry refuses, both tensors are initialised,
-// and las_profile_kernel<true> fills both in its one pass over the records.  CROSS: the cells take the place of the bins.
-template <bool COLOUR, bool CROSS>
+// The four record entries.  COLOUR: blue_q and colours are checked after everything the profile entry refuses, both tensors are initialised,
+// and las_profile_kernel<true> fills both in its one pass over the records.  CROSS: the cells take the place of the bins.  HIST: the
+// histograms do.
+template <bool COLOUR, bool CROSS, bool HIST = false>
 int las_profile_records(const char* who, void* hip_stream, const RecordArgs& R, const LineArgs& A, const TableArgs& T) {
     static const int rgb_off[11] = {-1, -1, 20, 28, -1, 28, -1, 30, 30, -1, 30};      // rgb_off + 6 <= las_min_len wherever there is colour
     if (int e = las_check_records(who, R.point_format, R.record_len, R.n)) return e;
     IndexDev I;
-    ProfArg<COLOUR, CROSS> P;
-    if constexpr (CROSS) {
+    ProfArg<COLOUR, CROSS, HIST> P;
+    long n_table;                                                      // the table's rows: without one there is nothing to launch
+    if constexpr (HIST) {
+        if (int e = check_hist(who, A, T.ring_q, T.bin_shift, T.hist, T.n_hist, I, P)) return e;
+    } else if constexpr (CROSS) {
         if (int e = check_cross(who, A, T.lateral_q, T.paint_iq, T.cells, T.n_cells, I, P)) return e;
     } else {
         if (int e = check_profile(who, A, T.bins, T.n_bins, I, P)) return e;
     }
+    if constexpr (HIST) n_table = T.n_hist;
+    else n_table = P.n_bins;
     LM_REQUIRE(R.scale && R.offset && (R.n == 0 || R.records), "%s: null pointer (scale, offset, records)", who);
     LM_REQUIRE(((uintptr_t)R.records & 3) == 0, "%s: records is not 4-byte aligned", who);
     LasSel Sel;
@@ -508,14 +611,16 @@ int las_profile_records(const char* who, void* hip_stream, const RecordArgs& R, 
     }
     I.min_inten = T.min_intensity;
     hipStream_t s = (hipStream_t)hip_stream;
-    const bool work = R.n > 0 && A.S > 0 && P.n_bins > 0;
+    const bool work = R.n > 0 && A.S > 0 && n_table > 0;
     const long nblk = (R.n + 255) / 256;
     const size_t lds = las_stage_bytes(R.record_len);
     long resident = 0;
     if (work)
-        if (int e = resident_groups(las_profile_kernel<COLOUR, CROSS>, lds, resident)) return e;
+        if (int e = resident_groups(las_profile_kernel<COLOUR, CROSS, HIST>, lds, resident)) return e;
     if (!A.accumulate) {
-        if constexpr (CROSS) {
+        if constexpr (HIST) {
+            LM_HIP(lm_zero_async(P.hist, (size_t)T.n_hist * sizeof(long long), s));
+        } else if constexpr (CROSS) {
             if (int e = zero_cells(P, s)) return e;
         } else {
             if (int e = init_bins(P, s)) return e;
@@ -526,7 +631,7 @@ int las_profile_records(const char* who, void* hip_stream, const RecordArgs& R, 
     if (!work) return LM_OK;
     const LasXf X = las_xf(R.scale, R.offset, R.shift, 0.f, 1.f, 0);  // raw intensity
     const unsigned groups = (unsigned)(nblk < resident ? nblk : resident);
-    hipLaunchKernelGGL((las_profile_kernel<COLOUR, CROSS>), dim3(groups), dim3(256), lds, s, reinterpret_cast<const unsigned*>(R.records),
+    hipLaunchKernelGGL((las_profile_kernel<COLOUR, CROSS, HIST>), dim3(groups), dim3(256), lds, s, reinterpret_cast<const unsigned*>(R.records),
                        R.record_len, R.n, nblk, X, Sel, R.select ? 1 : 0, I, P);
     LM_LAUNCH_CHECK();
     return LM_OK;
@@ -594,4 +699,39 @@ LM_API int lm_las_line_cross_records(void* hip_stream, const unsigned char* reco
     TableArgs T{};
     T.min_intensity = NAN, T.cells = cells, T.n_cells = n_cells, T.lateral_q = lateral_q, T.paint_iq = paint_iq;
     return las_profile_records<false, true>("las_line_cross_records", hip_stream, R, A, T);
+}
+
+// The paint / asphalt histograms (the rule: include/lanemap_hip.h): per line and lateral ring a histogram of the intensities of the returns
+// the labelling rule gives the line, without a min_intensity.  The index arguments of lm_label_points, then stations (only rlen is read),
+// L, z_tol, ring_q, bin_shift; hist DEVICE [L][Z][NB] int64, n_hist = L Z NB.  The stream comes LAST (the note in the header says why).
+LM_API int lm_line_hist_points(const float* points_xyzi, long N, const float* segments, long S, const LmLineGrid* grid, const int* cell_start,
+                               const int* cell_segs, float half_width, const float* stations, int L, float z_tol, int ring_q, int bin_shift,
+                               int accumulate, long* hist, long n_hist, void* hip_stream) {
+    IndexDev I;
+    HistDev H;
+    const LineArgs A{segments, S, grid, cell_start, cell_segs, half_width, z_tol, stations, nullptr, nullptr, L, 0.0, accumulate};
+    if (int e = check_hist("line_hist_points", A, ring_q, bin_shift, hist, n_hist, I, H)) return e;
+    if (int e = check_points("line_hist_points", points_xyzi, N)) return e;
+    I.min_inten = NAN;
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (!accumulate) LM_HIP(lm_zero_async(hist, (size_t)n_hist * sizeof(long long), s));
+    if (N == 0 || S == 0 || n_hist == 0) return LM_OK;
+    hipLaunchKernelGGL(hist_points_kernel, dim3((unsigned)lm_cdivl(N, CHUNK)), dim3(256), 0, s, reinterpret_cast<const lab_f32x4*>(points_xyzi),
+                       N, I, H);
+    LM_LAUNCH_CHECK();
+    return LM_OK;
+}
+
+// as above on the records of a file: the inputs of lm_las_line_cross_records.  las_profile_kernel<false, false, true>: one pass, records
+// only read.
+LM_API int lm_las_line_hist_records(const unsigned char* records, int record_len, int point_format, long n, const double* scale,
+                                    const double* offset, const double* shift, const LmLasSelect* select, const float* segments, long S,
+                                    const LmLineGrid* grid, const int* cell_start, const int* cell_segs, float half_width,
+                                    const float* stations, int L, float z_tol, int ring_q, int bin_shift, int accumulate, long* hist,
+                                    long n_hist, void* hip_stream) {
+    const RecordArgs R{records, record_len, point_format, n, scale, offset, shift, select};
+    const LineArgs A{segments, S, grid, cell_start, cell_segs, half_width, z_tol, stations, nullptr, nullptr, L, 0.0, accumulate};
+    TableArgs T{};
+    T.min_intensity = NAN, T.hist = hist, T.n_hist = n_hist, T.ring_q = ring_q, T.bin_shift = bin_shift;
+    return las_profile_records<false, false, true>("las_line_hist_records", hip_stream, R, A, T);
 }

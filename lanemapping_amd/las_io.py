@@ -40,6 +40,10 @@ the distribution, the road's cross-fall - and the lines moved onto their paint.
 `PaintResidue` / `residue_files` / `residue_summary` inventory the paint that no line explains - stop bars, crossing bars, arrows,
 hatching, a line the network missed: the bright road-level returns away from every line, gridded, labelled into connected blobs and
 described on the GPU (`ops.paint_residue`), and on the host the centre, size, fill and heading of every blob against its nearest line.
+
+`PaintThreshold` / `hist_files` / `paint_threshold` (lanemapping_amd/threshold.py, reached from here by name) find the intensity
+threshold between asphalt and paint that the four stages above need, from the returns on the lines against the returns beside them;
+min_intensity='auto' / paint_intensity='auto' ask the map routes for it.
 """
 import ctypes as C
 import math
@@ -65,6 +69,34 @@ def _whole(v):
     return not isinstance(v, bool) and isinstance(v, (int, np.integer))
 
 
+_THRESHOLD = ('PaintThreshold', 'hist_records', 'hist_files', 'paint_threshold', 'KS_COEFF', 'HIST_BIN')
+
+
+def __getattr__(name):
+    """las_io.PaintThreshold, .hist_records, .hist_files, .paint_threshold, .KS_COEFF, .HIST_BIN: the names of
+    lanemapping_amd/threshold.py, which is built on this module and so cannot be imported at its top."""
+    if name in _THRESHOLD:
+        from . import threshold
+        return getattr(threshold, name)
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')
+
+
+AUTO = 'auto'                       # min_intensity / paint_intensity: "the strip's own threshold" (PaintThreshold, paint_threshold)
+
+
+def _is_auto(v):
+    return isinstance(v, str) and v == AUTO
+
+
+def _resolved(who, options, name):
+    """-> options.<name>, refused where it still is 'auto': only the map routes, which run the threshold pass, resolve it."""
+    v = getattr(options, name)
+    if _is_auto(v):
+        raise ValueError(f"{who}: {type(options).__name__}.{name}='auto' is not resolved; the map routes (infer_las_*_to_map) replace it by "
+                         f"the threshold of las_io.paint_threshold, here pass that number")
+    return v
+
+
 class _Options:
     """What the option classes of this module share: a value that cannot be changed, compared, hashed and printed by the __slots__ of its
     class, in their order.  A class validates its arguments in __init__ and stores them with _set."""
@@ -73,6 +105,10 @@ class _Options:
     def _set(self, **values):
         for k, v in values.items():
             object.__setattr__(self, k, v)
+
+    def _replace(self, **changes):
+        """A copy with some arguments changed, validated again (for the classes whose __slots__ are their constructor's arguments)."""
+        return type(self)(**{**{k: getattr(self, k) for k in self.__slots__}, **changes})
 
     def __setattr__(self, name, value):
         raise AttributeError(f'{type(self).__name__} is immutable')
@@ -326,7 +362,8 @@ class MarkingLabels(_Options):
 
       half_width      metres (finite, >= 0): half the width of the band around a line in which a return counts as its paint
       z_tol           metres (>= 0, may be infinite): the height band; it only keeps a carriageway from labelling the one under or over it
-      min_intensity   None, or the smallest raw intensity a labelled return has (paint is bright)
+      min_intensity   None, the smallest raw intensity a labelled return has (paint is bright), or 'auto': the threshold the map routes
+                      find in the strip's own returns (PaintThreshold)
       marking_class   the classification a labelled record gets, 0..255; None: 64 on point formats 6-10 (the first user-definable class of
                       LAS 1.4), 31 on formats 0-5 (the largest class their five bits hold)
       line_ids        True: the point source ID of a labelled record becomes its line number (at most 65535 lines)
@@ -338,9 +375,9 @@ class MarkingLabels(_Options):
             raise ValueError(f'MarkingLabels: half_width={half_width!r} must be a finite number >= 0')
         if not _number(z_tol) or not float(z_tol) >= 0.0:
             raise ValueError(f'MarkingLabels: z_tol={z_tol!r} must be a number >= 0')
-        if min_intensity is not None:
+        if min_intensity is not None and not _is_auto(min_intensity):
             if not _number(min_intensity) or math.isnan(float(min_intensity)):
-                raise ValueError(f'MarkingLabels: min_intensity={min_intensity!r} must be None or a number')
+                raise ValueError(f"MarkingLabels: min_intensity={min_intensity!r} must be None, a number or 'auto'")
             min_intensity = float(min_intensity)
         if marking_class is not None:
             if not _whole(marking_class) or not 0 <= int(marking_class) <= 255:
@@ -440,7 +477,8 @@ def label_records(records_u8, header, index, labels, shift=None, select=None, n_
     out = torch.empty_like(records_u8)
     counts = torch.empty((L + 1,), device=dev, dtype=torch.int64)
     line = torch.empty((header['n_points'],), device=dev, dtype=torch.int32) if want_line else None
-    mi = math.nan if labels.min_intensity is None else labels.min_intensity
+    mi = _resolved('las_io.label_records', labels, 'min_intensity')
+    mi = math.nan if mi is None else mi
     check(lib().lm_las_label_records(*args, labels.z_tol, mi, cls, int(labels.line_ids), C.c_void_p(out.data_ptr()),
                                      C.c_void_p(line.data_ptr()) if want_line else None, C.c_void_p(counts.data_ptr()), L))
     return (out, counts, line) if want_line else (out, counts)
@@ -456,6 +494,7 @@ def label_las(path, out_path, lines, labels, shift, select=None, device='cuda:0'
     from . import ops
     if not isinstance(labels, MarkingLabels):
         raise TypeError(f'las_io.label_las: labels must be a MarkingLabels, not {type(labels).__name__}')
+    _resolved('las_io.label_las', labels, 'min_intensity')
     device = torch.device(device)
     data = np.fromfile(path, dtype=np.uint8)
     h = parse_header(data)
@@ -492,7 +531,8 @@ class MarkingSurvey(_Options):
       z_tol           metres (>= 0, may be infinite): the height band
       min_intensity   None, or the smallest raw intensity a profiled return has.  WITHOUT it a bin counts returns, not paint: every bin of
                       a line over asphalt is 'painted', the width is the width of the band and the dash pattern that of the point density.
-                      A threshold between asphalt and paint is needed for width, runs and type to mean anything
+                      A threshold between asphalt and paint is needed for width, runs and type to mean anything; 'auto': the one the
+                      map routes find in the strip's own returns (PaintThreshold)
       min_points      a bin counts as painted when it holds at least this many returns (whole number >= 1)
       max_gap         metres (finite, >= 0): runs of painted bins separated by at most this length of unpainted bins are joined
       solid_cover     0 < solid_cover <= 1: a line whose painted share reaches it is 'solid'
@@ -506,9 +546,9 @@ class MarkingSurvey(_Options):
             raise ValueError(f'MarkingSurvey: half_width={half_width!r} must be a number in 0 .. 16 (metres)')
         if not _number(z_tol) or not float(z_tol) >= 0.0:
             raise ValueError(f'MarkingSurvey: z_tol={z_tol!r} must be a number >= 0')
-        if min_intensity is not None:
+        if min_intensity is not None and not _is_auto(min_intensity):
             if not _number(min_intensity) or math.isnan(float(min_intensity)):
-                raise ValueError(f'MarkingSurvey: min_intensity={min_intensity!r} must be None or a number')
+                raise ValueError(f"MarkingSurvey: min_intensity={min_intensity!r} must be None, a number or 'auto'")
             min_intensity = float(min_intensity)
         if not _whole(min_points) or int(min_points) < 1:
             raise ValueError(f'MarkingSurvey: min_points={min_points!r} must be a whole number >= 1')
@@ -566,7 +606,8 @@ def profile_records(records_u8, header, index, stations, survey, shift=None, sel
     args, dev = _records_args(who, records_u8, header, shift, select, index, stations, 'the survey asks', survey.half_width, survey.bin)
     nb = stations.n_bins
     bins = ops._table_out(who, (nb, 6), out, dev)
-    mi = math.nan if survey.min_intensity is None else survey.min_intensity
+    mi = _resolved(who, survey, 'min_intensity')
+    mi = math.nan if mi is None else mi
     check(lib().lm_las_line_profile_records(*args, survey.z_tol, mi, int(out is not None), C.c_void_p(bins.data_ptr()) if nb else None, nb))
     return bins
 
@@ -619,6 +660,7 @@ def survey_files(files, lines, survey, device='cuda:0'):
     -> (bins [n_bins, 6] int64 numpy, bin_start [L + 1] int32 numpy)."""
     if not isinstance(survey, MarkingSurvey):
         raise TypeError(f'las_io.survey_files: survey must be a MarkingSurvey, not {type(survey).__name__}')
+    _resolved('las_io.survey_files', survey, 'min_intensity')
     bins, bin_start = _each_file('las_io.survey_files', files, lines, survey.bin, survey.half_width, device,
                                  lambda rec, h, tables, shift, select, out: profile_records(rec, h, *tables, survey, shift, select, out=out))
     if bins is None:                                                        # no file: the empty profile of the lines
@@ -747,7 +789,8 @@ def profile_colour_records(records_u8, header, index, stations, survey, colour, 
     nb = stations.n_bins
     bins = ops._table_out(who, (nb, 6), None if out is None else out[0], dev)
     colours = ops._table_out(who, (nb, 6), None if out is None else out[1], dev)
-    mi = math.nan if survey.min_intensity is None else survey.min_intensity
+    mi = _resolved(who, survey, 'min_intensity')
+    mi = math.nan if mi is None else mi
     check(lib().lm_las_line_colour_records(*args, survey.z_tol, mi, colour.blue_q, int(out is not None),
                                            C.c_void_p(bins.data_ptr()) if nb else None, C.c_void_p(colours.data_ptr()) if nb else None, nb))
     return bins, colours
@@ -762,6 +805,7 @@ def survey_colour_files(files, lines, survey, colour, device='cuda:0'):
         raise TypeError(f'las_io.survey_colour_files: survey must be a MarkingSurvey, not {type(survey).__name__}')
     if not isinstance(colour, MarkingColour):
         raise TypeError(f'las_io.survey_colour_files: colour must be a MarkingColour, not {type(colour).__name__}')
+    _resolved('las_io.survey_colour_files', survey, 'min_intensity')
     pair, bin_start = _each_file('las_io.survey_colour_files', files, lines, survey.bin, survey.half_width, device,
                                  lambda rec, h, tables, shift, select, out:
                                  profile_colour_records(rec, h, *tables, survey, colour, shift, select, out=out), require=require_colour)
@@ -853,7 +897,8 @@ class CrossSection(_Options):
     the table; snap_lines moves the lines onto the paint.
 
       paint_intensity raw intensity (a number, not NaN; required): a return is paint when its intensity, rounded to a whole number and
-                      clamped into 0 .. 65535, is at least ceil(paint_intensity) - `paint_iq`, clamped into 0 .. 65536 (65536: nothing is)
+                      clamped into 0 .. 65535, is at least ceil(paint_intensity) - `paint_iq`, clamped into 0 .. 65536 (65536: nothing is);
+                      or 'auto': the threshold the map routes find in the strip's own returns (PaintThreshold)
       bin             metres (finite, > 0): the length of a station bin along a line
       half_width      metres (finite, 0 .. 16): half the width of the band around a line
       lateral         metres (finite, > 0): the width of a lateral cell; the rule takes lateral_q = max(1, round(1024 lateral)) / 1024 m
@@ -866,14 +911,14 @@ class CrossSection(_Options):
                       smooth / 2 of it
       min_stations    with fewer such stations the vertex stays (whole number >= 1)
       max_shift       metres (finite, >= 0): a vertex that would move farther stays - an outlier, not a clamp
-    Apart from paint_intensity, which only the data can give, the values are plain defaults, not tuned values."""
+    Apart from paint_intensity, which only the data can give ('auto' asks them), the values are plain defaults, not tuned values."""
     __slots__ = ('paint_intensity', 'bin', 'half_width', 'lateral', 'z_tol', 'min_points', 'paint_share', 'max_hole', 'min_stripe', 'smooth',
                  'min_stations', 'max_shift')
 
     def __init__(self, paint_intensity, bin=0.5, half_width=0.625, lateral=0.03125, z_tol=0.5, min_points=3, paint_share=0.5, max_hole=1,
                  min_stripe=0.05, smooth=2.0, min_stations=2, max_shift=0.3):
-        if not _number(paint_intensity) or math.isnan(float(paint_intensity)):
-            raise ValueError(f'CrossSection: paint_intensity={paint_intensity!r} must be a number')
+        if not _is_auto(paint_intensity) and (not _number(paint_intensity) or math.isnan(float(paint_intensity))):
+            raise ValueError(f"CrossSection: paint_intensity={paint_intensity!r} must be a number or 'auto'")
         if not _number(bin) or not (0.0 < float(bin) < math.inf):
             raise ValueError(f'CrossSection: bin={bin!r} must be a finite length > 0')
         if not _number(half_width) or not (0.0 <= float(half_width) <= 16.0):
@@ -896,7 +941,8 @@ class CrossSection(_Options):
             raise ValueError(f'CrossSection: min_stations={min_stations!r} must be a whole number >= 1')
         if not _number(max_shift) or not (0.0 <= float(max_shift) < math.inf):
             raise ValueError(f'CrossSection: max_shift={max_shift!r} must be a finite length >= 0')
-        self._set(paint_intensity=float(paint_intensity), bin=float(bin), half_width=float(half_width), lateral=float(lateral),
+        self._set(paint_intensity=AUTO if _is_auto(paint_intensity) else float(paint_intensity), bin=float(bin), half_width=float(half_width),
+                  lateral=float(lateral),
                   z_tol=float(z_tol), min_points=int(min_points), paint_share=float(paint_share), max_hole=int(max_hole),
                   min_stripe=float(min_stripe), smooth=float(smooth), min_stations=int(min_stations), max_shift=float(max_shift))
 
@@ -908,7 +954,7 @@ class CrossSection(_Options):
     @property
     def paint_iq(self):
         """The integer the device entries take: ceil(paint_intensity), clamped into 0 .. 65536."""
-        p = self.paint_intensity
+        p = _resolved('CrossSection.paint_iq', self, 'paint_intensity')
         return 65536 if p > 65535.0 else 0 if p <= 0.0 else int(math.ceil(p))
 
     @property
@@ -946,6 +992,7 @@ def cross_files(files, lines, cross, device='cuda:0'):
     -> (cells [n_bins, nl, 4] int64 numpy, bin_start [L + 1] int32 numpy)."""
     if not isinstance(cross, CrossSection):
         raise TypeError(f'las_io.cross_files: cross must be a CrossSection, not {type(cross).__name__}')
+    _resolved('las_io.cross_files', cross, 'paint_intensity')
     cells, bin_start = _each_file('las_io.cross_files', files, lines, cross.bin, cross.half_width, device,
                                   lambda rec, h, tables, shift, select, out: cross_records(rec, h, *tables, cross, shift, select, out=out))
     if cells is None:                                                       # no file: the empty table of the lines
@@ -1096,7 +1143,8 @@ class PaintResidue(_Options):
     found and described on the GPU, and residue_summary reads centre, size and heading off every blob large enough.
 
       min_intensity   REQUIRED, finite: the smallest raw intensity of a paint return.  Without a threshold between asphalt and paint the
-                      whole road is one blob, so there is no default
+                      whole road is one blob, so there is no default; 'auto': the one the map routes find in the strip's own returns
+                      (PaintThreshold)
       clear           metres, 0 <= clear < reach: returns within it of their nearest line are that line's paint, not residue
       reach           metres, clear < reach <= 16: how far from a line paint is looked for
       z_tol           metres (>= 0, may be infinite): the height band around the line
@@ -1112,8 +1160,9 @@ class PaintResidue(_Options):
 
     def __init__(self, min_intensity, clear=0.3, reach=6.0, z_tol=0.5, cell=0.1, connectivity=8, min_cells=20, min_points=20, elongated=2.0,
                  angle_tol_deg=30.0):
-        if not _number(min_intensity) or not math.isfinite(float(min_intensity)):
-            raise ValueError(f'PaintResidue: min_intensity={min_intensity!r} must be a finite number (without one the whole road is one blob)')
+        if not _is_auto(min_intensity) and (not _number(min_intensity) or not math.isfinite(float(min_intensity))):
+            raise ValueError(f"PaintResidue: min_intensity={min_intensity!r} must be a finite number or 'auto' (without one the whole road is "
+                             f"one blob)")
         if not _number(reach) or not (0.0 < float(reach) <= 16.0):
             raise ValueError(f'PaintResidue: reach={reach!r} must be a number with 0 < reach <= 16 (metres)')
         if not _number(clear) or not (0.0 <= float(clear) < float(reach)):
@@ -1131,7 +1180,7 @@ class PaintResidue(_Options):
             raise ValueError(f'PaintResidue: elongated={elongated!r} must be a finite ratio >= 1')
         if not _number(angle_tol_deg) or not (0.0 <= float(angle_tol_deg) <= 45.0):
             raise ValueError(f'PaintResidue: angle_tol_deg={angle_tol_deg!r} must be a number in 0 .. 45 (degrees)')
-        self._set(min_intensity=float(min_intensity), clear=float(clear), reach=float(reach), z_tol=float(z_tol), cell=float(cell),
+        self._set(min_intensity=AUTO if _is_auto(min_intensity) else float(min_intensity), clear=float(clear), reach=float(reach), z_tol=float(z_tol), cell=float(cell),
                   connectivity=int(connectivity), min_cells=int(min_cells), min_points=int(min_points), elongated=float(elongated),
                   angle_tol_deg=float(angle_tol_deg))
 
@@ -1153,6 +1202,7 @@ def residue_files(files, lines, residue, device='cuda:0'):
     from . import ops
     if not isinstance(residue, PaintResidue):
         raise TypeError(f'las_io.residue_files: residue must be a PaintResidue, not {type(residue).__name__}')
+    _resolved('las_io.residue_files', residue, 'min_intensity')
     device = torch.device(device)
     lines, files = list(lines), list(files)
     for _, _, select in files:

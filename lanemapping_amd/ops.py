@@ -784,7 +784,7 @@ def line_index(segments, half_width, cell=None, device='cuda:0'):
 
 
 def _line_args(who, points, index, *stations):
-    """The argument checks of label_points, line_profile and line_cross: points [N,4] float32, contiguous, on the device; index an
+    """The argument checks of label_points, line_profile, line_cross and line_hist: points [N,4] float32, contiguous, on the device; index an
     ops.LineIndex; stations (passed where the entry takes them) the ops.LineStations of the same segments."""
     if not points.is_cuda:
         raise LanemapHipError('lanemapping_amd ops need tensors on an MI355X (HIP) device; no CPU fallback exists')
@@ -895,6 +895,35 @@ def line_cross(points, index, stations, z_tol, lateral_q, paint_iq, out=None):
     check(lib().lm_line_cross_points(_stream(), _ptr(points) if N else None, N, *index.args(), *stations.args(), float(z_tol), int(lateral_q),
                                      int(paint_iq), int(out is not None), _ptr(cells) if n_cells else None, n_cells))
     return cells
+
+
+def hist_shape(half_width, ring_q, bin_shift):
+    """-> (hq, Z, NB) of the histogram rule (include/lanemap_hip.h): hq = ceil(float32(half_width) * 1024), the Z = hq // ring_q + 1 lateral
+    rings of a line and the NB = 65536 >> bin_shift counts of a histogram."""
+    import numpy as np
+    whole = lambda v: not isinstance(v, bool) and isinstance(v, (int, np.integer))
+    if not whole(ring_q) or int(ring_q) < 1:
+        raise ValueError(f'hist_shape: ring_q={ring_q!r} must be a whole number >= 1 (the ring width in 1/1024 m)')
+    if not whole(bin_shift) or not 0 <= int(bin_shift) <= 8:
+        raise ValueError(f'hist_shape: bin_shift={bin_shift!r} must be a whole number in 0 .. 8')
+    hq = int(math.ceil(float(np.float32(half_width)) * 1024.0))
+    return hq, hq // int(ring_q) + 1, 65536 >> int(bin_shift)
+
+
+def line_hist(points, index, stations, z_tol, ring_q, bin_shift, out=None):
+    """points [N,4] f32 on device -> hist [L, Z, NB] int64 on device: per line and per lateral ring r = min(|q|, hq) // ring_q a histogram
+    of iq >> bin_shift over the returns the labelling rule gives that line without a min_intensity (the rule: include/lanemap_hip.h; q the
+    lateral offset in 1/1024 m, iq the intensity rounded into 0..65535).  index: the ops.LineIndex, stations: the ops.LineStations of the
+    same segments (only their rlen column is read; L = stations.n_lines).  out: the table of an earlier call to add to.  Integer adds
+    only: the same bits whatever the order of the points.  No synchronisation."""
+    _line_args('line_hist', points, index, stations)
+    hq, Z, NB = hist_shape(index.half_width, ring_q, bin_shift)
+    L = stations.n_lines
+    hist = _table_out('line_hist', (L, Z, NB), out, points.device)
+    N, n_hist = int(points.shape[0]), L * Z * NB
+    check(lib().lm_line_hist_points(_ptr(points) if N else None, N, *index.args(), stations.args()[0], L, float(z_tol), int(ring_q),
+                                    int(bin_shift), int(out is not None), _ptr(hist) if n_hist else None, n_hist, _stream()))
+    return hist
 
 
 RESIDUE_MAX_SIDE, RESIDUE_MAX_CELLS = 1 << 20, 1 << 22

@@ -305,6 +305,54 @@ class Runner:
     _las_colour = functools.partialmethod(_las_option, 'colour', 'las_colour', 'MarkingColour')            # white or yellow, beside the profile
     _las_residue = functools.partialmethod(_las_option, 'residue', 'las_residue', 'PaintResidue')          # the paint no line explains
     _las_cross = functools.partialmethod(_las_option, 'cross', 'las_cross', 'CrossSection')                # cross-sections, the snapped lines
+    _AUTO = (('label', 'min_intensity'), ('survey', 'min_intensity'), ('cross', 'paint_intensity'), ('residue', 'min_intensity'))
+
+    def _las_threshold(self, threshold, stages):
+        """`threshold=` of the LAS routes: the argument, else cfg['las_threshold'] (a dict of las_io.PaintThreshold's arguments), else
+        PaintThreshold() when a stage of `stages` ({'label': ..., 'survey': ..., 'cross': ..., 'residue': ...}) asks for 'auto', else none."""
+        from . import las_io
+        threshold = self._las_option('threshold', 'las_threshold', 'PaintThreshold', threshold)
+        asked = any(stages[k] is not None and getattr(stages[k], name) == las_io.AUTO for k, name in self._AUTO)
+        return las_io.PaintThreshold() if threshold is None and asked else threshold
+
+    def _threshold_inputs(self, threshold, stages, files, result, out_dir):
+        """The stage after the merge and before `label`: the paint / asphalt histograms of the lines the call returns (the same lines as
+        _survey_inputs takes) from every input file (files: (path, shift, select) in input order, a file listed several times is used
+        once): one lm_las_line_hist_records call per file into one table, one read-back (las_io.hist_files).  The raw table goes to
+        <out_dir>/params/paint_hist.npy ([L, Z, NB] int64), what las_io.paint_threshold reads off it to paint_threshold.json as
+        {'strip': group, 'lines': {line number: group}}.  -> `stages` with every 'auto' replaced by the strip's threshold, on copies of the
+        option objects.  A stage that asked for 'auto' of a strip whose group is not supported is a ValueError, raised after the files are
+        written and before any stage runs.  Without lines both files are empty, and 'auto' becomes 0.0: every stage then writes its empty
+        outputs whatever the number."""
+        from . import las_io
+        lines = self._result_lines(result)
+        hist = las_io.hist_files(self._each_once(files), lines, threshold, device=self.device)
+        found = las_io.paint_threshold(hist, threshold)
+        par_dir = self._params_dir(out_dir)
+        np.save(os.path.join(par_dir, 'paint_hist.npy'), hist)
+        with open(os.path.join(par_dir, 'paint_threshold.json'), 'w') as f:
+            json.dump({'strip': found['strip'], 'lines': {str(k): g for k, g in found['lines'].items()}}, f, indent=1)
+        asked = [k for k, name in self._AUTO if stages[k] is not None and getattr(stages[k], name) == las_io.AUTO]
+        g = found['strip']
+        if asked and lines and not g['supported']:
+            raise ValueError(f"{', '.join(asked)}: 'auto' needs a threshold between asphalt and paint, and the strip's returns do not support "
+                             f"one: separation {g['separation']:.4f} with {g['inner_returns']} returns on the lines and "
+                             f"{g['outer_returns']} beside them (las_io.paint_threshold; {os.path.join(par_dir, 'paint_threshold.json')})")
+        value = g['threshold'] if lines else 0.0
+        return {k: stages[k]._replace(**{dict(self._AUTO)[k]: value}) if k in asked else stages[k] for k in stages}
+
+    def _after_map(self, threshold, stages, colour, files, result, out_dir):
+        """The stages of the LAS routes that follow the merge, in their order: threshold, label, survey (with colour), cross, residue."""
+        if threshold is not None:
+            stages = self._threshold_inputs(threshold, stages, files, result, out_dir)
+        if stages['label'] is not None:
+            self._label_inputs(stages['label'], files, result, out_dir)
+        if stages['survey'] is not None:
+            self._survey_inputs(stages['survey'], files, result, out_dir, colour)
+        if stages['cross'] is not None:
+            self._cross_inputs(stages['cross'], files, result, out_dir)
+        if stages['residue'] is not None:
+            self._residue_inputs(stages['residue'], files, result, out_dir)
 
     @staticmethod
     def _colour_plan(colour, survey, paths):
@@ -508,7 +556,8 @@ class Runner:
         return raster_batch(names, plist, points, offs, rpar, scales)
 
     def infer_las_to_map(self, las_and_params, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None, ground=None,
-                         intensity=None, elevation=None, density=None, label=None, survey=None, colour=None, residue=None, cross=None):
+                         intensity=None, elevation=None, density=None, label=None, survey=None, colour=None, residue=None, cross=None,
+                         threshold=None):
         """LAS tiles -> map-level 3-D lane lines, every stage of the reference's offline chain on this stack:
 
           LAS file + tile parameter file (utils/io_utils.py:125-150)
@@ -580,13 +629,26 @@ class Runner:
         residue_cells.npy ([M,3] int32: cx, cy, blob) and what las_io.residue_summary reads off them - centre, area, length, width, fill,
         heading and shape against the nearest line - to residue.json as {blob number from 1: summary}.  With no lines found the three
         files are written empty.  The grid lives in the frame of the first file's las_read_offset.  The return value does not change.
-        Order of the stages: select, (binning,) ground, intensity, rasteriser, density, network, elevation, (merge,) label, survey, cross, residue.
+        threshold: a las_io.PaintThreshold (default: cfg['las_threshold'], a dict of its arguments; absent and no stage says 'auto': nothing
+        changes, file for file and call for call; absent and a stage says 'auto': PaintThreshold()): after the merge and before `label`,
+        the threshold between asphalt and paint is found in the returns themselves.  Against the lines the call returns, every input
+        file is read once with its own las_read_offset and `select` (one lm_las_line_hist_records call per file into one table, one
+        read-back): per line and per lateral ring a histogram of the intensities.  The table is written to
+        <work_dirs>/params/paint_hist.npy ([L, Z, NB] int64), what las_io.paint_threshold reads off it - threshold, separation, supported,
+        the counts and shares, for the strip and per line - to paint_threshold.json as {'strip': ..., 'lines': {line number: ...}}.  Every
+        min_intensity='auto' of label, survey and residue and paint_intensity='auto' of cross is then replaced by the strip's threshold.
+        A strip whose returns support no threshold is a ValueError that names the separation and the counts, raised after the JSON is
+        written and before any stage runs - when a stage asked for 'auto'.  With no lines found both files are written empty.
+        Order of the stages: select, (binning,) ground, intensity, rasteriser, density, network, elevation, (merge,) threshold, label, survey,
+        cross, residue.
         Single rank (the merge is sequential over the sorted tiles)."""
         from . import las_io
         select, ground, intensity = self._las_select(select), self._las_ground(ground), self._las_intensity(intensity)
         elevation, density, label = self._las_elevation(elevation), self._las_density(density), self._las_label(label)
         survey, colour, residue = self._las_survey(survey), self._las_colour(colour), self._las_residue(residue)
         cross = self._las_cross(cross)
+        stages = {'label': label, 'survey': survey, 'cross': cross, 'residue': residue}
+        threshold = self._las_threshold(threshold, stages)
         if label is not None:
             self._label_plan([p for p, _ in las_and_params])              # (a basename collision is refused before anything runs)
         self._colour_plan(colour, survey, [p for p, _ in las_and_params])
@@ -618,14 +680,7 @@ class Runner:
                 plist, pts, offs, rpar = self._follow_ground(ground, names, plist, pts, offs, rpar, H, W, out_dir)
             self._raster_stretched(raster_batch, intensity, names, plist, pts, offs, rpar, H, W, out_dir, used)
         result = close()
-        if label is not None:
-            self._label_inputs(label, inputs, result, out_dir)
-        if survey is not None:
-            self._survey_inputs(survey, inputs, result, out_dir, colour)
-        if cross is not None:
-            self._cross_inputs(cross, inputs, result, out_dir)
-        if residue is not None:
-            self._residue_inputs(residue, inputs, result, out_dir)
+        self._after_map(threshold, stages, colour, inputs, result, out_dir)
         return result
 
     def _las_chain(self, work_dirs, merge, elevation=None, density=None):
@@ -765,7 +820,8 @@ class Runner:
         return names, plist
 
     def infer_las_strip_to_map(self, las_paths, param_paths, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None,
-                               ground=None, intensity=None, elevation=None, density=None, label=None, survey=None, colour=None, residue=None, cross=None):
+                               ground=None, intensity=None, elevation=None, density=None, label=None, survey=None, colour=None, residue=None, cross=None,
+                               threshold=None):
         """A whole strip -> map-level lane lines: the LAS file(s) of the strip are read once, their points are binned into the tiles of
         the layout on the GPU (ops.strip_bin_points: the windows of `param_paths` may overlap and be rotated), and every batch of tiles
         then runs the chain of infer_las_to_map from the rasteriser on.  Same outputs under the same names; a tile is named by the
@@ -782,7 +838,9 @@ class Runner:
         survey: as for infer_las_to_map, last: every file of `las_paths` is surveyed with the layout's las_read_offset and `select`.
         colour: as for infer_las_to_map, in the survey's pass over the files of `las_paths`.
         cross: as for infer_las_to_map, after the survey: every file of `las_paths` is read with the layout's las_read_offset and `select`.
-        residue: as for infer_las_to_map, last of all: every file of `las_paths` is read with the layout's las_read_offset and `select`."""
+        residue: as for infer_las_to_map, last of all: every file of `las_paths` is read with the layout's las_read_offset and `select`.
+        threshold: as for infer_las_to_map, after the merge and before `label`: every file of `las_paths` is read with the layout's
+        las_read_offset and `select`."""
         from . import las_io
         if isinstance(las_paths, (str, os.PathLike)):
             las_paths = [las_paths]
@@ -791,6 +849,8 @@ class Runner:
         elevation, density, label = self._las_elevation(elevation), self._las_density(density), self._las_label(label)
         survey, colour, residue = self._las_survey(survey), self._las_colour(colour), self._las_residue(residue)
         cross = self._las_cross(cross)
+        stages = {'label': label, 'survey': survey, 'cross': cross, 'residue': residue}
+        threshold = self._las_threshold(threshold, stages)
         if label is not None:
             self._label_plan(las_paths)                                    # (a basename collision is refused before anything runs)
         self._colour_plan(colour, survey, las_paths)
@@ -824,14 +884,8 @@ class Runner:
                     batch = self._follow_ground(ground, names[i:j], *batch, H, W, out_dir)
                 self._raster_stretched(raster_batch, intensity, names[i:j], *batch, H, W, out_dir, used, strip)
         result = close()
-        if label is not None and plist:
-            self._label_inputs(label, [(path, plist[0]['las_read_offset'], select) for path in las_paths], result, out_dir)
-        if survey is not None and plist:
-            self._survey_inputs(survey, [(path, plist[0]['las_read_offset'], select) for path in las_paths], result, out_dir, colour)
-        if cross is not None and plist:
-            self._cross_inputs(cross, [(path, plist[0]['las_read_offset'], select) for path in las_paths], result, out_dir)
-        if residue is not None and plist:
-            self._residue_inputs(residue, [(path, plist[0]['las_read_offset'], select) for path in las_paths], result, out_dir)
+        if plist:
+            self._after_map(threshold, stages, colour, [(path, plist[0]['las_read_offset'], select) for path in las_paths], result, out_dir)
         return result
 
     def infer_lane_geometry_segmentation_segmentor(self, path_ckpt=None, mode_view=False, write_lane_vertex=False,
