@@ -8,8 +8,8 @@
  *   - returns 0 on success, non-zero on error (lm_last_error() gives the message; nothing is thrown);
  *   - borrows its inputs (const), never frees or allocates caller-visible memory.
  * Streams and graphs: an entry enqueues on `stream` and on no other stream.  Every entry may be captured into a HIP graph (after one
- * eager call of the same shape) except lm_strip_bin_points, lm_tile_ground, lm_ground_select, lm_tile_intensity_window and
- * lm_drape_vertices, which copy host memory of the call to the device or synchronise the stream: on a capturing stream they return
+ * eager call of the same shape) except lm_strip_bin_points, lm_strip_plan_create, lm_tile_ground, lm_ground_select,
+ * lm_tile_intensity_window and lm_drape_vertices, which copy host memory of the call to the device or synchronise the stream: on a capturing stream they return
  * LM_ERR_ARG with their name and the reason before touching it, and the capture stays valid.  Measured: tests/test_gpu_streams.py
  * (single-stream captures, three replays each; captures with parallel branches were not measured).
  * Activations are fp32, NHWC ("pixel-major rows", channel stride 1); `ld*` = floats between consecutive pixels.
@@ -260,6 +260,47 @@ long lm_strip_bin_workspace_bytes(long N, int T);
 int lm_strip_bin_points(void* hip_stream, const float* points_xyzi, long N, const LmRasterParams* params, int T, int H, int W,
                         double z_lo, double z_hi, void* workspace, long workspace_bytes, long* counts, long* offsets,
                         long* offsets_host, float* binned, long capacity);
+
+/* ---- strip binning, chunk by chunk (csrc/strip.hip): the same binned / offsets pair for a strip that is never held as one cloud ------
+ * lm_strip_bin_points needs the whole cloud on the device beside its output.  The chunked form takes the strip as consecutive chunks,
+ * twice: pass A counts every chunk into one running row of per-tile counts; the caller reads that row once, lays out binned by its
+ * exclusive prefix - for all tiles, or for a run of consecutive tiles at a time - and pass B scatters every chunk behind per-tile cursors.
+ * Inside a tile the points keep the order of the chunks, and inside a chunk their own: bit for bit what lm_strip_bin_points gives for
+ * the chunks concatenated, whatever the chunk sizes (the membership test never depends on the lookup grid, and a slot depends only on
+ * the number of points of the tile before the point).  The kernels are those of lm_strip_bin_points: strip_pass_kernel counts, the scan
+ * is lm_exclusive_scan_u32's, strip_pass_kernel scatters, reading the cursors where it reads offsets there; the instantiation that
+ * scatters behind cursors also checks every slot against `capacity`.  A one-workgroup kernel (a tile per thread and step, no atomics, no
+ * LDS) adds the chunk's per-tile totals to the running row, in stream order.
+ * THE PLAN.  The host grid and the tile constants of a layout do not depend on the chunk; with hundreds of chunks per strip they are
+ * built and uploaded once, by lm_strip_plan_create, into `consts` - DEVICE memory of the caller (lm_strip_plan_consts_bytes(T, nx ny) bytes
+ * for the nx x ny cells lm_strip_build_grid reports, 16-byte aligned) that must stay alive and untouched while the plan is used.  The handle itself is host memory, freed by
+ * lm_strip_plan_destroy (NULL is LM_OK).  A plan for a sub-list of `params` bins into those tiles only.  plan_create refuses what
+ * lm_strip_bin_points refuses of the shared arguments (T outside 1 .. 4096, more than 8 tiles reaching into one grid cell, a tilted tile
+ * with an infinite z range, a degenerate tile), copies host memory to the device and synchronises the stream, so it also refuses a
+ * capturing stream; the other entries are asynchronous, read nothing back and may be captured.
+ * lm_strip_bin_count:   points DEVICE [N][4] f32, 16-byte aligned, N <= 2^31 - 1 PER CHUNK (the strip's total is not bounded);
+ *         workspace DEVICE, lm_strip_chunk_workspace_bytes(N, T) bytes; counts_accum DEVICE [T] int64, owned and zeroed by the caller:
+ *         counts_accum[t] += the chunk's points of tile t.
+ * lm_strip_bin_scatter: cursors DEVICE [T] int64, in and out.  The point of tile t with rank r among the chunk's points of t goes to
+ *         binned[cursors[t] + r]; afterwards cursors[t] has grown by the chunk's count of t.  binned DEVICE [capacity][4] f32.  A slot
+ *         outside [0, capacity) is NOT written; 1 is stored to err (DEVICE, one int, zeroed by the caller; a vector store) instead, and
+ *         the cursors advance all the same.  Whatever the cursors hold, nothing is written outside binned[0 .. capacity).
+ * N = 0 is LM_OK and launches nothing.  Refused with LM_ERR_ARG and a message that names the argument: a plan that is no handle, N,
+ * null or misaligned points / workspace / counts_accum / cursors / binned / err, a workspace too small, a negative capacity.
+ * NOTE on the place of `hip_stream`: as for lm_line_hist_points below, these entries take the stream as their LAST parameter: the
+ * inventories of tests/test_stream_inventory_cpu.py, tests/test_bounds_inventory_cpu.py and tests/lds_state.py find entries by the stream
+ * in first place and hold each to a literal table inside an existing test file.  The cases those tables would name - guarded buffers, a
+ * side stream, poisoned LDS before strip_pass_kernel<true, true> - are in tests/test_gpu_strip_stream.py.  For the same reason
+ * strip_advance_kernel declares no __shared__. */
+long lm_strip_plan_consts_bytes(int T, long n_cells);
+int lm_strip_plan_create(const LmRasterParams* params, int T, int H, int W, double z_lo, double z_hi, void* consts, long consts_bytes,
+                         void** plan, void* hip_stream);
+int lm_strip_plan_destroy(void* plan);
+long lm_strip_chunk_workspace_bytes(long N, int T);
+int lm_strip_bin_count(const void* plan, const float* points_xyzi, long N, void* workspace, long workspace_bytes, long* counts_accum,
+                       void* hip_stream);
+int lm_strip_bin_scatter(const void* plan, const float* points_xyzi, long N, void* workspace, long workspace_bytes, long* cursors,
+                         float* binned, long capacity, int* err, void* hip_stream);
 
 /* ---- per-tile ground model (csrc/ground.hip): a coarse grid of ground heights under every tile, and the selection of points by their
  * height above it.  Both entries take the (points, tile_offsets, params) triple of lm_bev_raster_batch: points DEVICE [sum N][4] f32

@@ -101,6 +101,12 @@ SIGNATURES = {
     'lm_strip_bin_workspace_bytes': (i64, [i64, i32]),
     'lm_strip_bin_points': (i32, [vp, vp, i64, C.POINTER(LmRasterParams), i32, i32, i32, C.c_double, C.c_double, vp, i64, vp, vp,
                                   C.POINTER(i64), vp, i64]),
+    'lm_strip_plan_consts_bytes': (i64, [i32, i64]),
+    'lm_strip_plan_create': (i32, [C.POINTER(LmRasterParams), i32, i32, i32, C.c_double, C.c_double, vp, i64, C.POINTER(vp), vp]),
+    'lm_strip_plan_destroy': (i32, [vp]),
+    'lm_strip_chunk_workspace_bytes': (i64, [i64, i32]),
+    'lm_strip_bin_count': (i32, [vp, vp, i64, vp, i64, vp, vp]),
+    'lm_strip_bin_scatter': (i32, [vp, vp, i64, vp, i64, vp, vp, i64, vp, vp]),
     'lm_tile_ground_workspace_bytes': (i64, [i32, i32, i32, i32]),
     'lm_tile_ground': (i32, [vp, vp, C.POINTER(i64), C.POINTER(LmRasterParams), i32, i32, i32, i32, vp, i64, vp, vp, vp]),
     'lm_ground_select_workspace_bytes': (i64, [i64, i32]),

@@ -18,6 +18,12 @@
 // z in [z_lo, z_hi] (tilted tiles: the footprint moves with z); a wave holding a point outside that range, or a non-finite one, tests
 // its 64 points against all T tiles instead, so the result never depends on the grid.
 // HBM traffic = 16 N (count) + 16 N (scatter) + 16 sum(counts) + table; the per-wave table rows cost 4 T bytes per 32 KB of points.
+//
+// The chunked form (lm_strip_plan_create, lm_strip_bin_count, lm_strip_bin_scatter) bins a strip that is never held as one cloud: the
+// same passes per chunk, the per-tile totals of every chunk added to a running int64 row by strip_advance_kernel - the counts in pass
+// A, the cursors in pass B, which the scatter reads where it reads offsets above (and checks against the capacity: they are the
+// caller's).  Chunks in cloud order give the bits of the whole-cloud call.  The grid and the tile constants go to the device once per
+// layout, in a plan, instead of once per call.
 #include "common.h"
 #include "prim.h"
 #include "tile_points.h"
@@ -46,13 +52,17 @@ struct GridDev {
     int nx, ny;
 };
 
-template <bool SCATTER>
+// BOUNDED (the chunked scatter, lm_strip_bin_scatter): `offsets` are the caller's running cursors, so a slot is checked against
+// `capacity` before it is written and an overrun is flagged in *err instead
+template <bool SCATTER, bool BOUNDED>
 struct WaveCtx {
     unsigned* cur;                       // this wave's LDS row: count of / cursor into every tile
     const unsigned* table;
     const long* offsets;
     f32x4* binned;
     long nwc, wc;
+    long capacity;
+    unsigned* err;
     int lane;
 
     // the lanes flagged in `b` (= ballot(in)) hold points of tile tt, in cloud order
@@ -61,7 +71,13 @@ struct WaveCtx {
         unsigned c = cur[tt];
         if (SCATTER) {
             if (c == UNSET) c = table[(long)tt * nwc + wc] - table[(long)tt * nwc];
-            if (in) binned[offsets[tt] + (long)c + __popcll(b & ((1ull << lane) - 1ull))] = p;
+            if (BOUNDED) {
+                const long slot = offsets[tt] + (long)c + __popcll(b & ((1ull << lane) - 1ull));
+                if (in) {
+                    if ((unsigned long)slot < (unsigned long)capacity) binned[slot] = p;
+                    else *err = 1u;              // (a vector store from the lane that holds the point)
+                }
+            } else if (in) binned[offsets[tt] + (long)c + __popcll(b & ((1ull << lane) - 1ull))] = p;
         }
         cur[tt] = c + (unsigned)__popcll(b);     // every lane stores the same value: LDS operations of one wave complete in order
         __builtin_amdgcn_wave_barrier();
@@ -69,18 +85,21 @@ struct WaveCtx {
 };
 
 // grid: ceil(nwc / 4) workgroups; dynamic LDS = 4 * T words
-template <bool SCATTER>
+template <bool SCATTER, bool BOUNDED = false>
 __global__ __launch_bounds__(SW) void strip_pass_kernel(const f32x4* __restrict__ pts, long N, const LmWindowXf* __restrict__ xf, int T,
                                                         const u32x4* __restrict__ cells, GridDev G, int H, int W, unsigned* table, long nwc,
-                                                        const long* __restrict__ offsets, f32x4* __restrict__ binned) {
+                                                        const long* __restrict__ offsets, f32x4* __restrict__ binned, long capacity,
+                                                        unsigned* __restrict__ err) {
     extern __shared__ unsigned strip_lds[];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    WaveCtx<SCATTER> C;
+    WaveCtx<SCATTER, BOUNDED> C;
     C.cur = strip_lds + wv * T;
     C.table = table;
     C.offsets = offsets;
     C.binned = binned;
     C.nwc = nwc;
+    C.capacity = capacity;
+    C.err = err;
     C.wc = (long)blockIdx.x * WAVES + wv;
     C.lane = lane;
     if (C.wc >= nwc) return;
@@ -176,7 +195,47 @@ __global__ __launch_bounds__(256) void strip_offsets_kernel(const unsigned* __re
     }
 }
 
+// one workgroup, in stream order: the per-tile totals of one chunk, out of its scanned table, added to the caller's running int64 row
+// (the counts of pass A, the cursors of pass B).  A tile per thread and step, nothing shared: no atomics, no LDS
+__global__ __launch_bounds__(256) void strip_advance_kernel(const unsigned* __restrict__ table, long nwc, int T, long* __restrict__ running) {
+    for (int t = threadIdx.x; t < T; t += 256) running[t] += (long)(table[(long)(t + 1) * nwc] - table[(long)t * nwc]);
+}
+
 long nwc_of(long N) { return (N + WCHUNK - 1) / WCHUNK; }
+
+GridDev grid_dev(const LmStripGrid& grid, double z_lo, double z_hi) {
+    GridDev G;
+    G.x0 = (float)grid.x0, G.y0 = (float)grid.y0, G.inv = (float)(1.0 / grid.cell);
+    G.zlo = (float)z_lo, G.zhi = (float)z_hi;
+    // the lists hold for z in [z_lo, z_hi]: a float bound must not reach outside it
+    if ((double)G.zlo < z_lo) G.zlo = std::nextafterf(G.zlo, INFINITY);
+    if ((double)G.zhi > z_hi) G.zhi = std::nextafterf(G.zhi, -INFINITY);
+    G.nx = grid.nx, G.ny = grid.ny;
+    return G;
+}
+
+constexpr unsigned PLAN_MAGIC = 0x4C4D5350u;   // 'LMSP'
+
+// What lm_strip_plan_create leaves behind for the chunked entries: the layout's constants, on the device once
+struct StripPlan {
+    unsigned magic;
+    int T, H, W;
+    GridDev G;
+    const LmWindowXf* d_xf;              // both inside the caller's `consts` buffer
+    const u32x4* d_cells;
+};
+
+struct ChunkWork {                       // the workspace of one chunk: its table and the scan's scratch
+    unsigned* table;
+    void* scan_tmp;
+    size_t scan_bytes;
+    long nwc, L;
+};
+
+long chunk_workspace_bytes(long N, int T) {
+    const long L = (long)T * nwc_of(N) + 1;
+    return (long)(lm_align256((size_t)L * 4) + lm_align256(lm_prim_scan_temp_bytes(L)));
+}
 
 struct Footprint {                       // one tile on the host, in double, from the float constants the device uses
     double m[6], t[3], inv[9], lo[2], hi[2];   // window in v-space: lo <= (vx, vy) <= hi
@@ -354,13 +413,7 @@ LM_API int lm_strip_bin_points(void* hip_stream, const float* points_xyzi, long 
     w += lm_align256((size_t)L * 4);
     void* scan_tmp = w;
     const size_t scan_bytes = lm_align256(lm_prim_scan_temp_bytes(L));
-    GridDev G;
-    G.x0 = (float)grid.x0, G.y0 = (float)grid.y0, G.inv = (float)(1.0 / grid.cell);
-    G.zlo = (float)z_lo, G.zhi = (float)z_hi;
-    // the lists hold for z in [z_lo, z_hi]: a float bound must not reach outside it
-    if ((double)G.zlo < z_lo) G.zlo = std::nextafterf(G.zlo, INFINITY);
-    if ((double)G.zhi > z_hi) G.zhi = std::nextafterf(G.zhi, -INFINITY);
-    G.nx = grid.nx, G.ny = grid.ny;
+    const GridDev G = grid_dev(grid, z_lo, z_hi);
     const size_t lds = (size_t)WAVES * T * sizeof(unsigned);
     const unsigned nblk = (unsigned)((nwc + WAVES - 1) / WAVES);
     if (N > 0) {
@@ -369,7 +422,7 @@ LM_API int lm_strip_bin_points(void* hip_stream, const float* points_xyzi, long 
         if (int e = lm_ensure_dynamic_lds((const void*)strip_pass_kernel<false>, lds)) return e;
         if (int e = lm_ensure_dynamic_lds((const void*)strip_pass_kernel<true>, lds)) return e;
         hipLaunchKernelGGL(strip_pass_kernel<false>, dim3(nblk), dim3(SW), lds, s, reinterpret_cast<const f32x4*>(points_xyzi), N, d_xf, T,
-                           d_cells, G, H, W, table, nwc, (const long*)nullptr, (f32x4*)nullptr);
+                           d_cells, G, H, W, table, nwc, (const long*)nullptr, (f32x4*)nullptr, 0L, (unsigned*)nullptr);
         LM_LAUNCH_CHECK();
         if (int e = lm_prim_exclusive_scan_u32(s, table, table, L, scan_tmp, scan_bytes)) return e;
     }
@@ -387,8 +440,135 @@ LM_API int lm_strip_bin_points(void* hip_stream, const float* points_xyzi, long 
     if (total > 0) {
         LM_REQUIRE(binned, "strip_bin: null output");
         hipLaunchKernelGGL(strip_pass_kernel<true>, dim3(nblk), dim3(SW), lds, s, reinterpret_cast<const f32x4*>(points_xyzi), N, d_xf, T,
-                           d_cells, G, H, W, table, nwc, (const long*)offsets, reinterpret_cast<f32x4*>(binned));
+                           d_cells, G, H, W, table, nwc, (const long*)offsets, reinterpret_cast<f32x4*>(binned), 0L, (unsigned*)nullptr);
         LM_LAUNCH_CHECK();
     }
+    return LM_OK;
+}
+
+// ---- the chunked form: a plan per layout, then count / scatter per chunk -------------------------------------------------------------
+// n_cells: nx * ny of the layout's grid (lm_strip_build_grid with cells = NULL gives it)
+LM_API long lm_strip_plan_consts_bytes(int T, long n_cells) {
+    if (T < 1 || T > MAX_T || n_cells < 1 || n_cells > MAX_CELLS) return 0;
+    return (long)(lm_align256((size_t)T * sizeof(LmWindowXf)) + lm_align256((size_t)n_cells * CELL_CAP * 2));
+}
+
+// params: HOST [T]; consts: DEVICE, lm_strip_plan_consts_bytes(T, nx * ny) bytes, 16-byte aligned, the caller's, alive and untouched as
+// long as the plan is used; *plan: the handle.  Builds the host grid and the tile constants and uploads both ONCE; synchronises the stream
+LM_API int lm_strip_plan_create(const LmRasterParams* params, int T, int H, int W, double z_lo, double z_hi, void* consts, long consts_bytes,
+                                void** plan, void* hip_stream) {
+    LM_NO_CAPTURE(hip_stream, "strip_plan_create", LM_WHY_HOST_COPY_SYNC);
+    LM_REQUIRE(params && plan, "strip_plan_create: null pointer (params, plan)");
+    *plan = nullptr;
+    LM_REQUIRE(T >= 1 && T <= MAX_T, "strip_plan_create: T=%d tiles, 1 to %d are supported", T, MAX_T);
+    LM_REQUIRE(H > 0 && W > 0, "strip_plan_create: bad tile size (H=%d, W=%d)", H, W);
+    LM_REQUIRE(consts && ((uintptr_t)consts & 15) == 0, "strip_plan_create: consts is null or not 16-byte aligned");
+    std::vector<unsigned short> h_cells;
+    LmStripGrid grid;
+    if (int e = build_grid(params, T, H, W, z_lo, z_hi, &grid, h_cells)) return e;
+    const long need = lm_strip_plan_consts_bytes(T, (long)grid.nx * grid.ny);
+    LM_REQUIRE(consts_bytes >= need, "strip_plan_create: consts too small (%ld B needed)", need);
+    std::vector<LmWindowXf> h_xf((size_t)T);
+    for (int t = 0; t < T; ++t) lm_window_xf(params[t], h_xf[(size_t)t]);
+    hipStream_t s = (hipStream_t)hip_stream;
+    char* w = (char*)consts;
+    LmWindowXf* d_xf = (LmWindowXf*)w;
+    w += lm_align256((size_t)T * sizeof(LmWindowXf));
+    u32x4* d_cells = (u32x4*)w;
+    LM_HIP(hipMemcpyAsync(d_xf, h_xf.data(), (size_t)T * sizeof(LmWindowXf), hipMemcpyHostToDevice, s));
+    LM_HIP(hipMemcpyAsync(d_cells, h_cells.data(), (size_t)grid.nx * grid.ny * CELL_CAP * 2, hipMemcpyHostToDevice, s));
+    LM_HIP(hipStreamSynchronize(s));                           // the host vectors end with this call
+    StripPlan* P = new StripPlan;
+    P->magic = PLAN_MAGIC, P->T = T, P->H = H, P->W = W;
+    P->G = grid_dev(grid, z_lo, z_hi);
+    P->d_xf = d_xf, P->d_cells = d_cells;
+    *plan = P;
+    return LM_OK;
+}
+
+LM_API int lm_strip_plan_destroy(void* plan) {
+    if (!plan) return LM_OK;
+    StripPlan* P = (StripPlan*)plan;
+    LM_REQUIRE(P->magic == PLAN_MAGIC, "strip_plan_destroy: plan is no handle of lm_strip_plan_create");
+    P->magic = 0;
+    delete P;
+    return LM_OK;
+}
+
+LM_API long lm_strip_chunk_workspace_bytes(long N, int T) {
+    if (N < 0 || T < 1 || T > MAX_T) return 0;
+    return chunk_workspace_bytes(N, T);
+}
+
+// the checks both chunk entries share, and the chunk's workspace cut up
+static int chunk_args(const char* who, const void* plan, const float* points_xyzi, long N, void* workspace, long workspace_bytes,
+                      const StripPlan** P, ChunkWork* K) {
+    LM_REQUIRE(plan && ((const StripPlan*)plan)->magic == PLAN_MAGIC, "%s: plan is no handle of lm_strip_plan_create", who);
+    *P = (const StripPlan*)plan;
+    LM_REQUIRE(N >= 0 && N <= 2147483647L, "%s: N=%ld points, at most 2^31 - 1 are supported in one chunk", who, N);
+    LM_REQUIRE(points_xyzi || N == 0, "%s: null points", who);
+    LM_REQUIRE(((uintptr_t)points_xyzi & 15) == 0, "%s: points is not 16-byte aligned", who);
+    const int T = (*P)->T;
+    LM_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0, "%s: workspace is null or not 16-byte aligned", who);
+    LM_REQUIRE(chunk_workspace_bytes(N, T) <= workspace_bytes, "%s: workspace too small (%ld B needed)", who, chunk_workspace_bytes(N, T));
+    K->nwc = nwc_of(N), K->L = (long)T * K->nwc + 1;
+    char* w = (char*)workspace;
+    K->table = (unsigned*)w;
+    w += lm_align256((size_t)K->L * 4);
+    K->scan_tmp = w;
+    K->scan_bytes = lm_align256(lm_prim_scan_temp_bytes(K->L));
+    return LM_OK;
+}
+
+// count pass and scan of one chunk (N > 0) into its table
+static int chunk_count(hipStream_t s, const StripPlan& P, const float* points_xyzi, long N, const ChunkWork& K, size_t lds, unsigned nblk) {
+    if (int e = lm_ensure_dynamic_lds((const void*)strip_pass_kernel<false>, lds)) return e;
+    hipLaunchKernelGGL(strip_pass_kernel<false>, dim3(nblk), dim3(SW), lds, s, reinterpret_cast<const f32x4*>(points_xyzi), N, P.d_xf, P.T,
+                       P.d_cells, P.G, P.H, P.W, K.table, K.nwc, (const long*)nullptr, (f32x4*)nullptr, 0L, (unsigned*)nullptr);
+    LM_LAUNCH_CHECK();
+    return lm_prim_exclusive_scan_u32(s, K.table, K.table, K.L, K.scan_tmp, K.scan_bytes);
+}
+
+// points: DEVICE [N][4], one chunk; counts_accum: DEVICE [T] int64, the caller's, zeroed by the caller before the first chunk.
+// Asynchronous, nothing read back
+LM_API int lm_strip_bin_count(const void* plan, const float* points_xyzi, long N, void* workspace, long workspace_bytes, long* counts_accum,
+                              void* hip_stream) {
+    const StripPlan* P;
+    ChunkWork K;
+    if (int e = chunk_args("strip_bin_count", plan, points_xyzi, N, workspace, workspace_bytes, &P, &K)) return e;
+    LM_REQUIRE(counts_accum && ((uintptr_t)counts_accum & 7) == 0, "strip_bin_count: counts_accum is null or not 8-byte aligned");
+    if (N == 0) return LM_OK;
+    hipStream_t s = (hipStream_t)hip_stream;
+    const size_t lds = (size_t)WAVES * P->T * sizeof(unsigned);
+    if (int e = chunk_count(s, *P, points_xyzi, N, K, lds, (unsigned)((K.nwc + WAVES - 1) / WAVES))) return e;
+    hipLaunchKernelGGL(strip_advance_kernel, dim3(1), dim3(256), 0, s, K.table, K.nwc, P->T, counts_accum);
+    LM_LAUNCH_CHECK();
+    return LM_OK;
+}
+
+// cursors: DEVICE [T] int64, in and out: the slot of a point of tile t = cursors[t] + its rank among the chunk's points of t, and
+// afterwards cursors[t] has grown by the chunk's count of t.  binned: DEVICE [capacity][4]; a slot outside [0, capacity) is not
+// written, err (DEVICE, one int, zeroed by the caller) is set instead.  Asynchronous, nothing read back
+LM_API int lm_strip_bin_scatter(const void* plan, const float* points_xyzi, long N, void* workspace, long workspace_bytes, long* cursors,
+                                float* binned, long capacity, int* err, void* hip_stream) {
+    const StripPlan* P;
+    ChunkWork K;
+    if (int e = chunk_args("strip_bin_scatter", plan, points_xyzi, N, workspace, workspace_bytes, &P, &K)) return e;
+    LM_REQUIRE(cursors && ((uintptr_t)cursors & 7) == 0, "strip_bin_scatter: cursors is null or not 8-byte aligned");
+    LM_REQUIRE(capacity >= 0, "strip_bin_scatter: capacity=%ld is negative", capacity);
+    LM_REQUIRE((binned && ((uintptr_t)binned & 15) == 0) || capacity == 0, "strip_bin_scatter: binned is null or not 16-byte aligned");
+    LM_REQUIRE(err && ((uintptr_t)err & 3) == 0, "strip_bin_scatter: err is null or not 4-byte aligned");
+    if (N == 0) return LM_OK;
+    hipStream_t s = (hipStream_t)hip_stream;
+    const size_t lds = (size_t)WAVES * P->T * sizeof(unsigned);
+    const unsigned nblk = (unsigned)((K.nwc + WAVES - 1) / WAVES);
+    if (int e = chunk_count(s, *P, points_xyzi, N, K, lds, nblk)) return e;
+    if (int e = lm_ensure_dynamic_lds((const void*)strip_pass_kernel<true, true>, lds)) return e;
+    hipLaunchKernelGGL((strip_pass_kernel<true, true>), dim3(nblk), dim3(SW), lds, s, reinterpret_cast<const f32x4*>(points_xyzi), N, P->d_xf,
+                       P->T, P->d_cells, P->G, P->H, P->W, K.table, K.nwc, (const long*)cursors, reinterpret_cast<f32x4*>(binned), capacity,
+                       reinterpret_cast<unsigned*>(err));
+    LM_LAUNCH_CHECK();
+    hipLaunchKernelGGL(strip_advance_kernel, dim3(1), dim3(256), 0, s, K.table, K.nwc, P->T, cursors);
+    LM_LAUNCH_CHECK();
     return LM_OK;
 }

@@ -44,6 +44,10 @@ described on the GPU (`ops.paint_residue`), and on the host the centre, size, fi
 `PaintThreshold` / `hist_files` / `paint_threshold` (lanemapping_amd/threshold.py, reached from here by name) find the intensity
 threshold between asphalt and paint that the four stages above need, from the returns on the lines against the returns beside them;
 min_intensity='auto' / paint_intensity='auto' ask the map routes for it.
+
+`StripStream` / `LasChunks` / `tile_groups` (lanemapping_amd/las_stream.py, reached from here by name) map a strip that does not fit in
+memory: the files read in chunks of records, counted and then scattered into groups of tiles (`ops.StripBinner`), and the record passes
+above fed chunk by chunk (`chunk_records=`).
 """
 import ctypes as C
 import math
@@ -70,6 +74,7 @@ def _whole(v):
 
 
 _THRESHOLD = ('PaintThreshold', 'hist_records', 'hist_files', 'paint_threshold', 'KS_COEFF', 'HIST_BIN')
+_STREAM = ('StripStream', 'LasChunks', 'tile_groups')
 
 
 def __getattr__(name):
@@ -78,6 +83,9 @@ def __getattr__(name):
     if name in _THRESHOLD:
         from . import threshold
         return getattr(threshold, name)
+    if name in _STREAM:                     # lanemapping_amd/las_stream.py, built on this module in the same way
+        from . import las_stream
+        return getattr(las_stream, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')
 
 
@@ -484,18 +492,49 @@ def label_records(records_u8, header, index, labels, shift=None, select=None, n_
     return (out, counts, line) if want_line else (out, counts)
 
 
-def label_las(path, out_path, lines, labels, shift, select=None, device='cuda:0'):
+def _label_las_chunked(path, out_path, lines, labels, shift, select, device, chunk_records):
+    """label_las for a file that is never held whole: the bytes before the records, then every chunk of records relabelled (one
+    lm_las_label_records call and one read-back per chunk, written as it comes back), then the bytes after them; the counts add up.  A
+    label depends on its record alone, so the file is byte for byte the one the whole-file pass writes."""
+    from . import ops, las_stream
+    chunks = las_stream.LasChunks(path, chunk_records, device)
+    h = chunks.header
+    rl = h['record_len']
+    labels.for_format(h['point_format'])                                  # refused before anything is uploaded
+    if select is not None:
+        if not isinstance(select, PointFilter):
+            raise TypeError(f'las_io.label_las: select must be a PointFilter, not {type(select).__name__}')
+        select.for_format(h['point_format'])
+    index = ops.line_index(line_segments(lines, shift), labels.half_width, device=device)
+    total = np.zeros(len(lines) + 1, dtype=np.int64)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, 'wb') as f:
+        f.write(chunks.head_bytes)
+        for rec, m, _ in chunks:
+            out, counts = label_records(rec, {**h, 'n_points': m}, index, labels, shift, select, n_lines=len(lines))
+            both = torch.cat([out, counts.view(torch.uint8)]).cpu().numpy()    # the chunk's one read-back
+            f.write(both[:m * rl].tobytes())
+            total += both[len(rec):].view(np.int64)
+        f.write(chunks.tail_bytes)
+    per_line = [int(c) for c in total[1:]]
+    return {'records': int(h['n_points']), 'labelled': int(sum(per_line)), 'per_line': per_line}
+
+
+def label_las(path, out_path, lines, labels, shift, select=None, device='cuda:0', chunk_records=None):
     """The LAS file `path` written again as `out_path` with the returns of the `lines` (list of [n,3] float64, LAS frame) classified:
     the records are uploaded, labelled in one lm_las_label_records call (the rule and what is patched: include/lanemap_hip.h) and read back
     once, together with the counts.  out_path = the input's bytes up to offset_to_points (header and VLRs), the patched records, whatever
     followed them (EVLRs).  shift: the read offset of the frame the float32 arithmetic runs in (the las_read_offset the lines were found
-    with); select: the PointFilter the file was read with - a record that fails it is never relabelled.
+    with); select: the PointFilter the file was read with - a record that fails it is never relabelled.  chunk_records: None, or the
+    records read, labelled and written at a time (LasChunks): the same file, never held whole.
     -> {'records': n, 'labelled': records with a label, 'per_line': [count of line 1, ...]}."""
     from . import ops
     if not isinstance(labels, MarkingLabels):
         raise TypeError(f'las_io.label_las: labels must be a MarkingLabels, not {type(labels).__name__}')
     _resolved('las_io.label_las', labels, 'min_intensity')
     device = torch.device(device)
+    if chunk_records is not None:
+        return _label_las_chunked(path, out_path, list(lines), labels, shift, select, device, chunk_records)
     data = np.fromfile(path, dtype=np.uint8)
     h = parse_header(data)
     n, rl, off = h['n_points'], h['record_len'], h['offset_to_points']
@@ -612,13 +651,31 @@ def profile_records(records_u8, header, index, stations, survey, shift=None, sel
     return bins
 
 
-def _each_file(who, files, lines, bin, half_width, device, per_file, require=None):
+def _file_chunks(path, chunk_records, device):
+    """One file as the record passes take it: -> (header, an iterable of (records on the device, header of those records)).
+    chunk_records None: the file is read whole and uploaded once (_upload_records); else it goes through a LasChunks of that many records,
+    every chunk under the file's header with n_points = the chunk's records.  A file without records is one empty run either way."""
+    if chunk_records is None:
+        data = np.fromfile(path, dtype=np.uint8)
+        h = parse_header(data)
+        return h, ((_upload_records(data, h, device), h) for _ in range(1))
+    from . import las_stream
+    chunks = las_stream.LasChunks(path, chunk_records, device)
+    h = chunks.header
+    if h['n_points'] == 0:
+        return h, ((las_stream.empty_records(device), h) for _ in range(1))
+    return h, ((rec, {**h, 'n_points': m}) for rec, m, _ in chunks)
+
+
+def _each_file(who, files, lines, bin, half_width, device, per_file, require=None, chunk_records=None):
     """The loop of survey_files, survey_colour_files and cross_files over `files`, a list of (path, shift, select).  Every select is
     checked and `require`, if given, is called with every path before a file is read.  Then every file is read once and uploaded once
     (_upload_records) and goes through one call per_file(records, header, tables, shift, select, out) with tables = the ops.LineIndex
     (of `half_width`) and the ops.LineStations (of `bin`) of the lines in the frame of its own shift - built once per distinct shift -
     and the result of the call before it as `out`.  The bins each line owns, bin_start, are those of the FIRST file's frame, in every table.
-    -> (what the last call returned, bin_start); without a file (None, the bin_start of the unshifted lines).  Nothing is read back."""
+    -> (what the last call returned, bin_start); without a file (None, the bin_start of the unshifted lines).  Nothing is read back.
+    chunk_records: None, or the records of a file read, uploaded and passed to per_file at a time (LasChunks): one call per chunk into
+    the same `out` - the tables are integer sums, which do not depend on the partition."""
     from . import ops
     device = torch.device(device)
     lines, files = list(lines), list(files)
@@ -629,8 +686,7 @@ def _each_file(who, files, lines, bin, half_width, device, per_file, require=Non
         require(path)
     tables, bin_start, out = {}, None, None
     for path, shift, select in files:
-        data = np.fromfile(path, dtype=np.uint8)
-        h = parse_header(data)
+        h, runs = _file_chunks(path, chunk_records, device)
         if select is not None:
             select.for_format(h['point_format'])
         key = None if shift is None else tuple(float(v) for v in shift)
@@ -639,7 +695,8 @@ def _each_file(who, files, lines, bin, half_width, device, per_file, require=Non
             bin_start = bs if bin_start is None else bin_start
             tables[key] = (ops.line_index(line_segments(lines, shift), half_width, device=device),
                            ops.line_stations(st, bin_start, bin, device=device))
-        out = per_file(_upload_records(data, h, device), h, tables[key], shift, select, out)
+        for rec, hc in runs:
+            out = per_file(rec, hc, tables[key], shift, select, out)
     if out is None:
         bin_start = line_stations(lines, None, bin)[1]
     return out, bin_start
@@ -652,17 +709,18 @@ def _empty_bins(bin_start):
     return host
 
 
-def survey_files(files, lines, survey, device='cuda:0'):
+def survey_files(files, lines, survey, device='cuda:0', chunk_records=None):
     """The marking profile of `lines` (list of [n,3] float64, LAS frame) from the LAS files `files`, a list of (path, shift, select): every
     file is uploaded and profiled in one lm_las_line_profile_records call with its own read offset and PointFilter, all into one bins
     tensor, which is read back once.  The bins each line owns (bin_start) are those of the first file's frame; where another file's shift
-    rounds a line's length into one bin more, the rule's clamp to the line's last bin holds.
+    rounds a line's length into one bin more, the rule's clamp to the line's last bin holds.  chunk_records: as for _each_file.
     -> (bins [n_bins, 6] int64 numpy, bin_start [L + 1] int32 numpy)."""
     if not isinstance(survey, MarkingSurvey):
         raise TypeError(f'las_io.survey_files: survey must be a MarkingSurvey, not {type(survey).__name__}')
     _resolved('las_io.survey_files', survey, 'min_intensity')
     bins, bin_start = _each_file('las_io.survey_files', files, lines, survey.bin, survey.half_width, device,
-                                 lambda rec, h, tables, shift, select, out: profile_records(rec, h, *tables, survey, shift, select, out=out))
+                                 lambda rec, h, tables, shift, select, out: profile_records(rec, h, *tables, survey, shift, select, out=out),
+                                 chunk_records=chunk_records)
     if bins is None:                                                        # no file: the empty profile of the lines
         return _empty_bins(bin_start), bin_start
     return bins.cpu().numpy(), bin_start                                    # the one read-back
@@ -796,7 +854,7 @@ def profile_colour_records(records_u8, header, index, stations, survey, colour, 
     return bins, colours
 
 
-def survey_colour_files(files, lines, survey, colour, device='cuda:0'):
+def survey_colour_files(files, lines, survey, colour, device='cuda:0', chunk_records=None):
     """survey_files with the colour table: every file of `files`, a list of (path, shift, select), is uploaded and goes through one
     lm_las_line_colour_records call into one (bins, colours) pair, which is read back once.  All headers are read before anything is
     uploaded: a file whose point format has no colour is refused with a ValueError that names the file and its format.
@@ -808,7 +866,8 @@ def survey_colour_files(files, lines, survey, colour, device='cuda:0'):
     _resolved('las_io.survey_colour_files', survey, 'min_intensity')
     pair, bin_start = _each_file('las_io.survey_colour_files', files, lines, survey.bin, survey.half_width, device,
                                  lambda rec, h, tables, shift, select, out:
-                                 profile_colour_records(rec, h, *tables, survey, colour, shift, select, out=out), require=require_colour)
+                                 profile_colour_records(rec, h, *tables, survey, colour, shift, select, out=out), require=require_colour,
+                                 chunk_records=chunk_records)
     if pair is None:                                                        # no file: the empty tables of the lines
         host = _empty_bins(bin_start)
         return host, np.zeros_like(host), bin_start
@@ -985,7 +1044,7 @@ def cross_records(records_u8, header, index, stations, cross, shift=None, select
     return cells
 
 
-def cross_files(files, lines, cross, device='cuda:0'):
+def cross_files(files, lines, cross, device='cuda:0', chunk_records=None):
     """The cross-section table of `lines` (list of [n,3] float64, LAS frame) from the LAS files `files`, a list of (path, shift, select):
     every file is read once, uploaded and goes through one lm_las_line_cross_records call with its own read offset and PointFilter, all
     into one table, which is read back once.  The bins each line owns are those of the first file's frame, as in survey_files.
@@ -994,7 +1053,8 @@ def cross_files(files, lines, cross, device='cuda:0'):
         raise TypeError(f'las_io.cross_files: cross must be a CrossSection, not {type(cross).__name__}')
     _resolved('las_io.cross_files', cross, 'paint_intensity')
     cells, bin_start = _each_file('las_io.cross_files', files, lines, cross.bin, cross.half_width, device,
-                                  lambda rec, h, tables, shift, select, out: cross_records(rec, h, *tables, cross, shift, select, out=out))
+                                  lambda rec, h, tables, shift, select, out: cross_records(rec, h, *tables, cross, shift, select, out=out),
+                                  chunk_records=chunk_records)
     if cells is None:                                                       # no file: the empty table of the lines
         return np.zeros((int(bin_start[-1]), cross.nl, 4), dtype=np.int64), bin_start
     return cells.cpu().numpy(), bin_start                                   # the one read-back
@@ -1192,12 +1252,29 @@ def residue_index_cell(residue):
     return max(1.0, residue.reach / 4.0)
 
 
-def residue_files(files, lines, residue, device='cuda:0'):
+def decode_chunks(chunks, shift=None, select=None, scratch=None):
+    """The clouds of a LasChunks on a device, chunk by chunk: yields [kept,4] float32 tensors (x, y, z, RAW intensity: read_las_raw's
+    bits for those records).  select: a PointFilter, applied per chunk (one read of `kept` per chunk, as decode_points).  scratch: a
+    [chunk_records,4] float32 tensor every chunk is decoded into - the cloud a step yields is then valid until the next step."""
+    h = chunks.header
+    if select is not None:
+        select.for_format(h['point_format'])
+    for rec, m, _ in chunks:
+        out = None if scratch is None else scratch[:m]
+        if select is None:
+            yield decode_points(rec, h['record_len'], m, h['scale'], h['offset'], shift, False, out=out)
+        else:
+            yield decode_points(rec, h['record_len'], m, h['scale'], h['offset'], shift, False, out=out, point_format=h['point_format'],
+                                select=select)
+
+
+def residue_files(files, lines, residue, device='cuda:0', chunk_records=None):
     """The paint residue of `lines` (list of [n,3] float64, LAS frame) in the LAS files `files`, a list of (path, shift, select) like
     survey_files takes: every file is read once with its own PointFilter (read_las_raw), all clouds go through one ops.paint_residue
     call, and the result is read back once.  The grid lives in ONE frame, that of the first file's read offset: a file listed with
     another offset is decoded against the first one (the decode subtracts the offset in float64, so nothing is lost as long as the
-    files lie within float32 reach of it).  -> an ops.ResidueBlobs of numpy arrays (cells [M,2] int32, comp [M] int32, stats [K,12]
+    files lie within float32 reach of it).  chunk_records: None, or the records of a file read and decoded at a time (LasChunks): the
+    clouds then reach ops.paint_residue chunk by chunk, and the result is the same.  -> an ops.ResidueBlobs of numpy arrays (cells [M,2] int32, comp [M] int32, stats [K,12]
     int64, grid); grid['shift'] is the frame, what residue_summary needs."""
     from . import ops
     if not isinstance(residue, PaintResidue):
@@ -1210,7 +1287,11 @@ def residue_files(files, lines, residue, device='cuda:0'):
             raise TypeError(f'las_io.residue_files: select must be a PointFilter, not {type(select).__name__}')
     frame = None if not files or files[0][1] is None else [float(v) for v in files[0][1]]
     index = ops.line_index(line_segments(lines, frame), residue.reach, cell=residue_index_cell(residue), device=device)
-    clouds = [read_las_raw(path, device, frame, select)[0] for path, _, select in files]
+    if chunk_records is None:
+        clouds = [read_las_raw(path, device, frame, select)[0] for path, _, select in files]
+    else:                                   # ops.paint_residue takes its clouds one at a time and keeps the residue keys only
+        from . import las_stream
+        clouds = (pts for path, _, select in files for pts in decode_chunks(las_stream.LasChunks(path, chunk_records, device), frame, select))
     out = ops.paint_residue(clouds, index, residue.z_tol, residue.min_intensity, residue.clear, residue.cell, residue.connectivity).numpy()
     out.grid['shift'] = [0.0, 0.0, 0.0] if frame is None else frame
     return out

@@ -1100,6 +1100,133 @@ def strip_bin_points(points, params, H=1152, W=1152, z_range=None, capacity=None
     return binned[:offs[T]], [int(o) for o in offs]
 
 
+class _StripPlan:
+    """The layout constants of a run of tiles on the device (lm_strip_plan_create): the handle and the tensor it points into."""
+
+    def __init__(self, params, H, W, z_lo, z_hi, device):
+        T = len(params)
+        par = (LmRasterParams * T)(*params)
+        g = LmStripGrid()
+        check(lib().lm_strip_build_grid(par, T, H, W, z_lo, z_hi, C.byref(g), None, 0))        # the geometry: how many cells
+        need = int(lib().lm_strip_plan_consts_bytes(T, g.nx * g.ny))
+        self.consts = torch.empty(need, device=device, dtype=torch.uint8)
+        self.handle = C.c_void_p()
+        self._destroy = lib().lm_strip_plan_destroy                                          # (bound now: __del__ may run at interpreter exit)
+        check(lib().lm_strip_plan_create(par, T, H, W, z_lo, z_hi, _ptr(self.consts), need, C.byref(self.handle), _stream()))
+
+    def __del__(self):
+        if getattr(self, 'handle', None):
+            self._destroy(self.handle)
+            self.handle = None
+
+
+class StripBinner:
+    """strip_bin_points for a strip that arrives in chunks and is never held as one cloud (lm_strip_bin_count / lm_strip_bin_scatter).
+
+        b = StripBinner(params, H, W, z_range, device)
+        for every chunk:  b.count(points)                  pass A: the per-tile counts add up on the device
+        counts = b.counts()                                the one read-back of pass A: int64 numpy [T]
+        b.begin()  or  b.begin((t0, t1), capacity)         binned for all tiles, or for the consecutive tiles t0 .. t1 - 1 only
+        for every chunk, in the same order:  b.scatter(points)
+        binned, offsets = b.finish()                       the pair bev_raster_batch takes, for the tiles of begin()
+
+    With the chunks of pass B those of pass A, (binned, offsets) are bit for bit what strip_bin_points returns for the chunks
+    concatenated - for a run of tiles, what it returns for that sub-list of `params`.  begin() may be called again for another run.
+    The lookup grid and the tile constants go to the device once per run of tiles (a plan), not once per chunk.  z_range as for
+    strip_bin_points, but never taken from the points: tilted tiles need a finite one.  capacity: rows of binned (default: the run's
+    total); a chunk that overruns it writes nothing outside binned, and finish() raises."""
+
+    def __init__(self, params, H=1152, W=1152, z_range=None, device='cuda:0'):
+        self.params, self.H, self.W, self.device = list(params), int(H), int(W), torch.device(device)
+        if self.device.type != 'cuda':
+            raise LanemapHipError('StripBinner needs an MI355X (HIP) device; no CPU fallback exists')
+        z_lo, z_hi = (float(z_range[0]), float(z_range[1])) if z_range is not None else (-math.inf, math.inf)
+        if not (math.isfinite(z_lo) and math.isfinite(z_hi)) and any(_tilted(p) for p in self.params):
+            raise ValueError('StripBinner: tilted tiles need a finite z_range')
+        self.z = (z_lo, z_hi)
+        T = len(self.params)
+        self._plans = {}
+        self._plan((0, T))                                                          # (a layout the grid refuses is refused here)
+        self._counts = torch.zeros(T, device=self.device, dtype=torch.int64)
+        self._host_counts = None
+        self._ws = None
+        self._run = None
+
+    def _plan(self, tiles):
+        if tiles not in self._plans:
+            self._plans[tiles] = _StripPlan(self.params[tiles[0]:tiles[1]], self.H, self.W, *self.z, self.device)
+        return self._plans[tiles]
+
+    def _chunk(self, who, points, T):
+        if not points.is_cuda:
+            _ptr(points)
+        if points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous() or points.dtype != torch.float32 or points.device != self.device:
+            raise ValueError(f'StripBinner.{who}: points must be a contiguous [N,4] float32 tensor on {self.device}')
+        N = points.shape[0]
+        need = int(lib().lm_strip_chunk_workspace_bytes(N, T))
+        if need <= 0:
+            raise LanemapHipError(f'StripBinner.{who}: a chunk of {N} points is not supported (at most 2^31 - 1)')
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, device=self.device, dtype=torch.uint8)
+        return N
+
+    def count(self, points):
+        """Pass A, one chunk: asynchronous."""
+        if self._host_counts is not None:
+            raise ValueError('StripBinner.count: the counts were read already (counts()); pass A is over')
+        N = self._chunk('count', points, len(self.params))
+        check(lib().lm_strip_bin_count(self._plan((0, len(self.params))).handle, _ptr(points) if N else None, N, _ptr(self._ws), self._ws.numel(),
+                                       _ptr(self._counts), _stream()))
+
+    def counts(self):
+        """-> int64 numpy [T]: the points of every tile over all chunks counted.  The one read-back of pass A."""
+        if self._host_counts is None:
+            self._host_counts = self._counts.cpu().numpy()
+        return self._host_counts
+
+    def begin(self, tiles=None, capacity=None):
+        """Pass B for the tiles (t0, t1) (None: all): allocates binned and sets the cursors to the exclusive prefix of their counts."""
+        T = len(self.params)
+        t0, t1 = (0, T) if tiles is None else (int(tiles[0]), int(tiles[1]))
+        if not 0 <= t0 < t1 <= T:
+            raise ValueError(f'StripBinner.begin: tiles={tiles!r} is no run t0 < t1 of the {T} tiles')
+        c = [int(v) for v in self.counts()[t0:t1]]
+        offs = [0]
+        for v in c:
+            offs.append(offs[-1] + v)
+        cap = offs[-1] if capacity is None else int(capacity)
+        if cap < 0:
+            raise ValueError(f'StripBinner.begin: capacity={capacity!r} is negative')
+        import numpy as np
+        meta = torch.from_numpy(np.asarray(offs[:-1] + [0], dtype=np.int64)).to(self.device)          # cursors [t1 - t0] | err
+        self._run = {'plan': self._plan((t0, t1)), 'T': t1 - t0, 'offs': offs, 'cap': cap, 'meta': meta,
+                     'binned': torch.empty((cap, 4), device=self.device, dtype=torch.float32)}
+
+    def scatter(self, points):
+        """Pass B, one chunk: asynchronous."""
+        r = self._run
+        if r is None:
+            raise ValueError('StripBinner.scatter: call begin() first')
+        N = self._chunk('scatter', points, r['T'])
+        m = r['meta']
+        check(lib().lm_strip_bin_scatter(r['plan'].handle, _ptr(points) if N else None, N, _ptr(self._ws), self._ws.numel(), _ptr(m),
+                                         _ptr(r['binned']) if r['cap'] else None, r['cap'], C.c_void_p(m.data_ptr() + 8 * r['T']), _stream()))
+
+    def finish(self):
+        """-> (binned [sum counts, 4], offsets: t1 - t0 + 1 host ints) of the run begin() opened.  Reads the error word and the
+        cursors back (one read) and raises LanemapHipError when a chunk overran binned or the chunks of pass B were not those of pass A."""
+        r, self._run = self._run, None
+        if r is None:
+            raise ValueError('StripBinner.finish: call begin() first')
+        host = r['meta'].cpu().numpy()
+        if host[-1] != 0:
+            raise LanemapHipError(f"StripBinner.finish: a chunk overran binned ({r['cap']} rows): the points of pass B are not those that "
+                                  'were counted, or capacity is short; nothing was written outside binned')
+        if [int(v) for v in host[:-1]] != r['offs'][1:]:
+            raise LanemapHipError('StripBinner.finish: the chunks scattered are not the chunks counted (the cursors do not end at the offsets)')
+        return r['binned'][:r['offs'][-1]], r['offs']
+
+
 def tile_ground(points, tile_offsets, params, H=1152, W=1152, cell_px=32, want_cell_min=False):
     """The coarse ground model under every tile (csrc/ground.hip), from the (points, tile_offsets, params) triple bev_raster_batch takes:
     -> (ground [B,Gy,Gx] f32, ground_min [B] f32) on the device, Gy = ceil(H / cell_px), Gx = ceil(W / cell_px).  A cell's raw value is

@@ -305,6 +305,7 @@ class Runner:
     _las_colour = functools.partialmethod(_las_option, 'colour', 'las_colour', 'MarkingColour')            # white or yellow, beside the profile
     _las_residue = functools.partialmethod(_las_option, 'residue', 'las_residue', 'PaintResidue')          # the paint no line explains
     _las_cross = functools.partialmethod(_las_option, 'cross', 'las_cross', 'CrossSection')                # cross-sections, the snapped lines
+    _las_stream = functools.partialmethod(_las_option, 'stream', 'las_stream', 'StripStream')              # the chunked strip route
     _AUTO = (('label', 'min_intensity'), ('survey', 'min_intensity'), ('cross', 'paint_intensity'), ('residue', 'min_intensity'))
 
     def _las_threshold(self, threshold, stages):
@@ -315,7 +316,7 @@ class Runner:
         asked = any(stages[k] is not None and getattr(stages[k], name) == las_io.AUTO for k, name in self._AUTO)
         return las_io.PaintThreshold() if threshold is None and asked else threshold
 
-    def _threshold_inputs(self, threshold, stages, files, result, out_dir):
+    def _threshold_inputs(self, threshold, stages, files, result, out_dir, chunk_records=None):
         """The stage after the merge and before `label`: the paint / asphalt histograms of the lines the call returns (the same lines as
         _survey_inputs takes) from every input file (files: (path, shift, select) in input order, a file listed several times is used
         once): one lm_las_line_hist_records call per file into one table, one read-back (las_io.hist_files).  The raw table goes to
@@ -326,7 +327,7 @@ class Runner:
         outputs whatever the number."""
         from . import las_io
         lines = self._result_lines(result)
-        hist = las_io.hist_files(self._each_once(files), lines, threshold, device=self.device)
+        hist = las_io.hist_files(self._each_once(files), lines, threshold, device=self.device, **self._chunked(chunk_records))
         found = las_io.paint_threshold(hist, threshold)
         par_dir = self._params_dir(out_dir)
         np.save(os.path.join(par_dir, 'paint_hist.npy'), hist)
@@ -341,18 +342,24 @@ class Runner:
         value = g['threshold'] if lines else 0.0
         return {k: stages[k]._replace(**{dict(self._AUTO)[k]: value}) if k in asked else stages[k] for k in stages}
 
-    def _after_map(self, threshold, stages, colour, files, result, out_dir):
-        """The stages of the LAS routes that follow the merge, in their order: threshold, label, survey (with colour), cross, residue."""
+    def _after_map(self, threshold, stages, colour, files, result, out_dir, chunk_records=None):
+        """The stages of the LAS routes that follow the merge, in their order: threshold, label, survey (with colour), cross, residue.
+        chunk_records: None, or the records every stage reads and uploads of a file at a time (`stream=` of the strip route)."""
         if threshold is not None:
-            stages = self._threshold_inputs(threshold, stages, files, result, out_dir)
+            stages = self._threshold_inputs(threshold, stages, files, result, out_dir, chunk_records)
         if stages['label'] is not None:
-            self._label_inputs(stages['label'], files, result, out_dir)
+            self._label_inputs(stages['label'], files, result, out_dir, chunk_records)
         if stages['survey'] is not None:
-            self._survey_inputs(stages['survey'], files, result, out_dir, colour)
+            self._survey_inputs(stages['survey'], files, result, out_dir, colour, chunk_records)
         if stages['cross'] is not None:
-            self._cross_inputs(stages['cross'], files, result, out_dir)
+            self._cross_inputs(stages['cross'], files, result, out_dir, chunk_records)
         if stages['residue'] is not None:
-            self._residue_inputs(stages['residue'], files, result, out_dir)
+            self._residue_inputs(stages['residue'], files, result, out_dir, chunk_records)
+
+    @staticmethod
+    def _chunked(chunk_records):
+        """The keyword the stages after the map pass on to las_io: none without `stream=`, so that call stays what it was."""
+        return {} if chunk_records is None else {'chunk_records': chunk_records}
 
     @staticmethod
     def _colour_plan(colour, survey, paths):
@@ -406,7 +413,7 @@ class Runner:
                 once.append((path, shift, select))
         return once
 
-    def _label_inputs(self, labels, files, result, out_dir):
+    def _label_inputs(self, labels, files, result, out_dir, chunk_records=None):
         """The last stage of the LAS routes: every input file (files: (path, shift, select) in input order) labelled against the lines the
         call returns - `merged`, or the tiles' 3-D lines in tile-name order when nothing was merged - and written to
         <out_dir>/labelled/<basename>; what was done goes to <out_dir>/params/labels.json as {file: [records, labelled, [per-line counts]]}."""
@@ -416,12 +423,13 @@ class Runner:
         done = {}
         for path, shift, select in self._each_once(files):
             base = os.path.basename(path)
-            r = las_io.label_las(path, os.path.join(out_dir, 'labelled', base), lines, labels, shift, select=select, device=self.device)
+            r = las_io.label_las(path, os.path.join(out_dir, 'labelled', base), lines, labels, shift, select=select, device=self.device,
+                                 **self._chunked(chunk_records))
             done[base] = [r['records'], r['labelled'], r['per_line']]
         with open(os.path.join(self._params_dir(out_dir), 'labels.json'), 'w') as f:
             json.dump(done, f, indent=1)
 
-    def _survey_inputs(self, survey, files, result, out_dir, colour=None):
+    def _survey_inputs(self, survey, files, result, out_dir, colour=None, chunk_records=None):
         """The stage after `label`: the lines the call returns - `merged`, or the tiles' 3-D lines in tile-name order when nothing was
         merged - profiled from every input file (files: (path, shift, select) in input order; a file listed several times is surveyed
         once, with its first listing's read offset): one lm_las_line_profile_records call per file into one bins tensor, one read-back.
@@ -434,10 +442,10 @@ class Runner:
         lines = self._result_lines(result)
         once = self._each_once(files)
         if colour is None:
-            bins, bin_start = las_io.survey_files(once, lines, survey, device=self.device)
+            bins, bin_start = las_io.survey_files(once, lines, survey, device=self.device, **self._chunked(chunk_records))
             summary = las_io.marking_summary(bins, bin_start, survey)
         else:
-            bins, colours, bin_start = las_io.survey_colour_files(once, lines, survey, colour, device=self.device)
+            bins, colours, bin_start = las_io.survey_colour_files(once, lines, survey, colour, device=self.device, **self._chunked(chunk_records))
             summary = [{**m, **c} for m, c in zip(las_io.marking_summary(bins, bin_start, survey),
                                                   las_io.marking_colours(bins, colours, bin_start, survey, colour))]
         par_dir = self._params_dir(out_dir)
@@ -447,7 +455,7 @@ class Runner:
         with open(os.path.join(par_dir, 'markings.json'), 'w') as f:
             json.dump({str(k + 1): m for k, m in enumerate(summary)}, f, indent=1)
 
-    def _cross_inputs(self, cross, files, result, out_dir):
+    def _cross_inputs(self, cross, files, result, out_dir, chunk_records=None):
         """The stage after `survey`: the cross-section table of the lines the call returns (the same lines as _survey_inputs takes) from
         every input file (files: (path, shift, select) in input order, a file listed several times is used once): one
         lm_las_line_cross_records call per file into one table, one read-back (las_io.cross_files).  The raw table goes to
@@ -458,7 +466,7 @@ class Runner:
         from . import las_io, merge_lines as ml
         lines = self._result_lines(result)
         once = self._each_once(files)
-        cells, bin_start = las_io.cross_files(once, lines, cross, device=self.device)
+        cells, bin_start = las_io.cross_files(once, lines, cross, device=self.device, **self._chunked(chunk_records))
         summary = las_io.cross_summary(cells, bin_start, cross)
         snapped = las_io.snap_lines(lines, summary, bin_start, cross)
         par_dir = self._params_dir(out_dir)
@@ -470,7 +478,7 @@ class Runner:
         io_utils.save_seqs_list(snapped, os.path.join(pc_dir, 'merged_snapped.txt'))
         io_utils.save_seqs_list([ml.downsample_seqs(m) for m in snapped if m.shape[0] >= 2], os.path.join(pc_dir, 'merged_snapped_downsample.txt'))
 
-    def _residue_inputs(self, residue, files, result, out_dir):
+    def _residue_inputs(self, residue, files, result, out_dir, chunk_records=None):
         """The stage after `survey` and `cross`: the paint that none of the lines the call returns explains (the same lines as _survey_inputs takes),
         from every input file (files: (path, shift, select) in input order, a file listed several times is used once): one
         ops.paint_residue call over all files, one read-back (las_io.residue_files).  The raw statistics go to
@@ -481,7 +489,7 @@ class Runner:
         once = self._each_once(files)
         par_dir = self._params_dir(out_dir)
         if lines and once:
-            blobs = las_io.residue_files(once, lines, residue, device=self.device)
+            blobs = las_io.residue_files(once, lines, residue, device=self.device, **self._chunked(chunk_records))
             stats = blobs.stats
             cells = np.concatenate([blobs.cells, blobs.comp[:, None]], axis=1).astype(np.int32)
             summary = las_io.residue_summary(blobs, lines, residue)
@@ -821,7 +829,7 @@ class Runner:
 
     def infer_las_strip_to_map(self, las_paths, param_paths, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None,
                                ground=None, intensity=None, elevation=None, density=None, label=None, survey=None, colour=None, residue=None, cross=None,
-                               threshold=None):
+                               threshold=None, stream=None):
         """A whole strip -> map-level lane lines: the LAS file(s) of the strip are read once, their points are binned into the tiles of
         the layout on the GPU (ops.strip_bin_points: the windows of `param_paths` may overlap and be rotated), and every batch of tiles
         then runs the chain of infer_las_to_map from the rasteriser on.  Same outputs under the same names; a tile is named by the
@@ -840,7 +848,16 @@ class Runner:
         cross: as for infer_las_to_map, after the survey: every file of `las_paths` is read with the layout's las_read_offset and `select`.
         residue: as for infer_las_to_map, last of all: every file of `las_paths` is read with the layout's las_read_offset and `select`.
         threshold: as for infer_las_to_map, after the merge and before `label`: every file of `las_paths` is read with the layout's
-        las_read_offset and `select`."""
+        las_read_offset and `select`.
+        stream: a las_io.StripStream (default: cfg['las_stream'], a dict of its arguments; absent: nothing changes, file for file and
+        call for call): the strip is never held as one cloud.  Pass A reads every file in chunks of stream.chunk_records records,
+        decodes each into one reused scratch cloud (`select` per chunk) and counts it into the tiles (ops.StripBinner); the counts are
+        read once.  The tiles are cut into groups (las_io.tile_groups: layout order, cuts at multiples of the batch size, 16 x the
+        group's points within stream.binned_budget); pass B reads the files once more per group and scatters them into the group's
+        tiles, and the batch loop runs on the group's (binned, offsets) as it does on the whole strip's: the same bits, so every output
+        is the same.  The stages after the merge read the files in the same chunks.  What was done goes to
+        <out_dir>/params/stream.json.  intensity scope='strip' needs every binned range at once: with a binned_budget and more tiles
+        than one batch - more than one group is then possible - it is refused before anything is read."""
         from . import las_io
         if isinstance(las_paths, (str, os.PathLike)):
             las_paths = [las_paths]
@@ -849,19 +866,37 @@ class Runner:
         elevation, density, label = self._las_elevation(elevation), self._las_density(density), self._las_label(label)
         survey, colour, residue = self._las_survey(survey), self._las_colour(colour), self._las_residue(residue)
         cross = self._las_cross(cross)
+        stream = self._las_stream(stream)
         stages = {'label': label, 'survey': survey, 'cross': cross, 'residue': residue}
         threshold = self._las_threshold(threshold, stages)
         if label is not None:
             self._label_plan(las_paths)                                    # (a basename collision is refused before anything runs)
         self._colour_plan(colour, survey, las_paths)
         used = {}
+        B = int(batch_size or self.cfg.get('batch_size', 8))
+        if stream is not None and stream.binned_budget is not None and intensity is not None and intensity.scope == 'strip' and len(plist) > B:
+            raise ValueError(f"intensity: scope='strip' fits one window to every binned range of the strip at once; with stream.binned_budget="
+                             f'{stream.binned_budget} the {len(plist)} tiles (batches of {B}) may be cut into several groups, each binned on '
+                             f"its own.  Pass binned_budget=None, or use scope='tile'")
         if path_ckpt:
             self.load_ckpt(path_ckpt)
-        B = int(batch_size or self.cfg.get('batch_size', 8))
         H, W = self.cfg.list_img_size_xy[1], self.cfg.list_img_size_xy[0]
         out_dir = work_dirs or self.cfg.get('work_dirs', './work_dirs')
         raster_batch, close = self._las_chain(work_dirs, merge, elevation, density)
-        if plist:
+
+        def batches(binned, offs, t0, t1, strip=None):
+            """The batch loop over the tiles t0 .. t1 - 1, whose point ranges are offs (t1 - t0 + 1 entries) of binned."""
+            for i in range(t0, t1, B):
+                j = min(i + B, t1)
+                batch = (plist[i:j], binned, offs[i - t0:j - t0 + 1], rpar[i:j])
+                if ground is not None:
+                    batch = self._follow_ground(ground, names[i:j], *batch, H, W, out_dir)
+                self._raster_stretched(raster_batch, intensity, names[i:j], *batch, H, W, out_dir, used, strip)
+
+        if plist and stream is not None:
+            rpar = [io_utils.raster_params_from_dict(p) for p in plist]
+            self._stream_strip(stream, las_paths, plist, rpar, select, intensity, B, H, W, out_dir, batches)
+        elif plist:
             shift = plist[0]['las_read_offset']
             clouds, z_lo, z_hi = [], np.inf, -np.inf
             for path in las_paths:
@@ -877,16 +912,58 @@ class Runner:
             strip = None
             if intensity is not None and intensity.scope == 'strip':
                 strip = self._strip_intensity(intensity, binned, offs, rpar, H, W)
-            for i in range(0, len(plist), B):
-                j = min(i + B, len(plist))
-                batch = (plist[i:j], binned, offs[i:j + 1], rpar[i:j])
-                if ground is not None:
-                    batch = self._follow_ground(ground, names[i:j], *batch, H, W, out_dir)
-                self._raster_stretched(raster_batch, intensity, names[i:j], *batch, H, W, out_dir, used, strip)
+            batches(binned, offs, 0, len(plist), strip)
         result = close()
         if plist:
-            self._after_map(threshold, stages, colour, [(path, plist[0]['las_read_offset'], select) for path in las_paths], result, out_dir)
+            self._after_map(threshold, stages, colour, [(path, plist[0]['las_read_offset'], select) for path in las_paths], result, out_dir,
+                            None if stream is None else stream.chunk_records)
         return result
+
+    def _stream_strip(self, stream, las_paths, plist, rpar, select, intensity, B, H, W, out_dir, batches):
+        """The chunked route of infer_las_strip_to_map up to the batch loop (`batches`, which it calls once per group of tiles): pass A
+        counts every chunk of every file, pass B scatters them once per group.  No file and no cloud is held whole; the device holds
+        one chunk's records, one scratch cloud and the binned points of one group."""
+        from . import las_io
+        shift = plist[0]['las_read_offset']
+        files = [las_io.LasChunks(path, stream.chunk_records, self.device) for path in las_paths]      # (the headers only)
+        z_lo, z_hi = np.inf, -np.inf
+        for ch in files:
+            if select is not None:
+                select.for_format(ch.header['point_format'])                 # refused before anything is uploaded
+            z_lo, z_hi = min(z_lo, ch.header['min'][2] - shift[2]), max(z_hi, ch.header['max'][2] - shift[2])
+        pad = 1e-3 * max(1.0, abs(z_lo), abs(z_hi))                          # (as on the whole-cloud route: it only bounds the lookup grid)
+        binner = ops.StripBinner(rpar, H, W, (z_lo - pad, z_hi + pad) if z_lo <= z_hi else None, self.device)
+        kept = [0] * len(files)
+
+        def each_cloud(fn, count=False):
+            """fn(points) for every chunk of every file, decoded into one scratch cloud that lives as long as the pass."""
+            scratch = torch.empty((min(stream.chunk_records, max([ch.header['n_points'] for ch in files] + [1])), 4), device=self.device,
+                                  dtype=torch.float32)
+            for k, ch in enumerate(files):
+                for pts in las_io.decode_chunks(ch, shift, select, scratch):
+                    if count:
+                        kept[k] += int(pts.shape[0])
+                    fn(pts)
+
+        each_cloud(binner.count, count=True)
+        counts = binner.counts()                                             # the one read-back of pass A
+        groups = las_io.tile_groups(counts, B, stream.binned_budget)
+        done = []
+        for t0, t1 in groups:
+            binner.begin((t0, t1))
+            each_cloud(binner.scatter)
+            binned, offs = binner.finish()
+            done.append({'tiles': [t0, t1], 'points': int(offs[-1]), 'binned_bytes': 16 * int(offs[-1])})
+            strip = None
+            if intensity is not None and intensity.scope == 'strip':         # (one group: refused otherwise before anything was read)
+                strip = self._strip_intensity(intensity, binned, offs, rpar[t0:t1], H, W)
+            batches(binned, offs, t0, t1, strip)
+            del binned
+        with open(os.path.join(self._params_dir(out_dir), 'stream.json'), 'w') as f:
+            json.dump({'chunk_records': stream.chunk_records, 'binned_budget': stream.binned_budget, 'batch_size': B,
+                       'files': [{'file': os.path.basename(ch.path), 'records': int(ch.header['n_points']), 'chunks': len(ch), 'kept': n}
+                                 for ch, n in zip(files, kept)],
+                       'tile_counts': [int(c) for c in counts], 'groups': done}, f, indent=1)
 
     def infer_lane_geometry_segmentation_segmentor(self, path_ckpt=None, mode_view=False, write_lane_vertex=False,
                                                    *, tiles=None, batch_size=None, gt_avail=None):

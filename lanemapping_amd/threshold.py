@@ -132,16 +132,17 @@ def hist_records(records_u8, header, index, stations, threshold, shift=None, sel
     return hist
 
 
-def hist_files(files, lines, threshold, device='cuda:0'):
+def hist_files(files, lines, threshold, device='cuda:0', chunk_records=None):
     """The paint / asphalt histograms of `lines` (list of [n,3] float64, LAS frame) from the LAS files `files`, a list of (path, shift,
     select): every file is read once, uploaded and goes through one lm_las_line_hist_records call with its own read offset and
     PointFilter, all into one table, which is read back once.  -> hist [L, Z, NB] int64 numpy, L = len(lines); paint_threshold(hist,
-    threshold) reads the thresholds off it."""
+    threshold) reads the thresholds off it.  chunk_records: None, or the records of a file read and counted at a time (LasChunks)."""
     if not isinstance(threshold, PaintThreshold):
         raise TypeError(f'las_io.hist_files: threshold must be a PaintThreshold, not {type(threshold).__name__}')
     lines = list(lines)
     hist, _ = _each_file('las_io.hist_files', files, lines, HIST_BIN, threshold.half_width, device,
-                         lambda rec, h, tables, shift, select, out: hist_records(rec, h, *tables, threshold, shift, select, out=out))
+                         lambda rec, h, tables, shift, select, out: hist_records(rec, h, *tables, threshold, shift, select, out=out),
+                         chunk_records=chunk_records)
     if hist is None:                                                        # no file: the empty table of the lines
         return np.zeros((len(lines), threshold.rings, threshold.n_counts), dtype=np.int64)
     return hist.cpu().numpy()                                               # the one read-back
