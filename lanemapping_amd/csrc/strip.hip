@@ -23,7 +23,7 @@
 // same passes per chunk, the per-tile totals of every chunk added to a running int64 row by strip_advance_kernel - the counts in pass
 // A, the cursors in pass B, which the scatter reads where it reads offsets above (and checks against the capacity: they are the
 // caller's).  Chunks in cloud order give the bits of the whole-cloud call.  The grid and the tile constants go to the device once per
-// layout, in a plan, instead of once per call.
+// layout, in a plan, instead of once per call; the whole-cloud call fills a plan of its own, and both forms run on one host path.
 #include "common.h"
 #include "prim.h"
 #include "tile_points.h"
@@ -216,14 +216,24 @@ GridDev grid_dev(const LmStripGrid& grid, double z_lo, double z_hi) {
 
 constexpr unsigned PLAN_MAGIC = 0x4C4D5350u;   // 'LMSP'
 
-// What lm_strip_plan_create leaves behind for the chunked entries: the layout's constants, on the device once
+// The layout's constants on the device: what lm_strip_plan_create leaves behind for the chunked entries, once per layout, and what
+// lm_strip_bin_points fills on its stack, once per call
 struct StripPlan {
     unsigned magic;
     int T, H, W;
     GridDev G;
-    const LmWindowXf* d_xf;              // both inside the caller's `consts` buffer
+    const LmWindowXf* d_xf;              // both inside the caller's buffer (`consts`, or the head of the whole-cloud workspace)
     const u32x4* d_cells;
 };
+
+// ... and on the host, where plan_build leaves them and the uploads of plan_consts read them.  thread_local, no locals of an entry: an
+// early error return must not end vectors while a copy may still be in flight; they hold until the thread's next call
+thread_local std::vector<unsigned short> t_cells;              // [ny][nx][CELL_CAP]
+thread_local std::vector<LmWindowXf> t_xf;
+
+long consts_size(int T, long n_cells) {  // LmWindowXf[T] | cells
+    return (long)(lm_align256((size_t)T * sizeof(LmWindowXf)) + lm_align256((size_t)n_cells * CELL_CAP * 2));
+}
 
 struct ChunkWork {                       // the workspace of one chunk: its table and the scan's scratch
     unsigned* table;
@@ -235,6 +245,11 @@ struct ChunkWork {                       // the workspace of one chunk: its tabl
 long chunk_workspace_bytes(long N, int T) {
     const long L = (long)T * nwc_of(N) + 1;
     return (long)(lm_align256((size_t)L * 4) + lm_align256(lm_prim_scan_temp_bytes(L)));
+}
+
+ChunkWork chunk_work(void* workspace, long N, int T) {         // chunk_workspace_bytes(N, T) bytes cut up
+    const long nwc = nwc_of(N), L = (long)T * nwc + 1;
+    return {(unsigned*)workspace, (char*)workspace + lm_align256((size_t)L * 4), lm_align256(lm_prim_scan_temp_bytes(L)), nwc, L};
 }
 
 struct Footprint {                       // one tile on the host, in double, from the float constants the device uses
@@ -374,11 +389,42 @@ LM_API int lm_strip_build_grid(const LmRasterParams* params, int T, int H, int W
     return LM_OK;
 }
 
+// ---- the host path under both forms: the plan of a layout, its constants on the device, count and scan of a run of points -----------
+// A plan but for its device pointers: T, H, W, the grid as the kernels take it; the grid's cells and the tile constants into t_cells, t_xf
+static int plan_build(const LmRasterParams* params, int T, int H, int W, double z_lo, double z_hi, StripPlan* P) {
+    LmStripGrid grid;
+    if (int e = build_grid(params, T, H, W, z_lo, z_hi, &grid, t_cells)) return e;
+    t_xf.resize((size_t)T);
+    for (int t = 0; t < T; ++t) lm_window_xf(params[t], t_xf[(size_t)t]);
+    P->magic = PLAN_MAGIC, P->T = T, P->H = H, P->W = W;
+    P->G = grid_dev(grid, z_lo, z_hi);
+    return LM_OK;
+}
+
+// LmWindowXf[T] | cells laid out in `consts` (DEVICE, 16-byte aligned, consts_size(T, the grid's cells) bytes or more), the plan
+// pointed at them and, with `upload`, the two copies out of t_xf and t_cells enqueued
+static int plan_consts(hipStream_t s, void* consts, bool upload, StripPlan* P) {
+    P->d_xf = (const LmWindowXf*)consts;
+    P->d_cells = (const u32x4*)((char*)consts + lm_align256((size_t)P->T * sizeof(LmWindowXf)));
+    if (!upload) return LM_OK;
+    LM_HIP(hipMemcpyAsync((void*)P->d_xf, t_xf.data(), (size_t)P->T * sizeof(LmWindowXf), hipMemcpyHostToDevice, s));
+    LM_HIP(hipMemcpyAsync((void*)P->d_cells, t_cells.data(), t_cells.size() * 2, hipMemcpyHostToDevice, s));
+    return LM_OK;
+}
+
+// count pass and scan of N > 0 points (the whole cloud, or one chunk) into their table
+static int chunk_count(hipStream_t s, const StripPlan& P, const float* points_xyzi, long N, const ChunkWork& K, size_t lds, unsigned nblk) {
+    if (int e = lm_ensure_dynamic_lds((const void*)strip_pass_kernel<false>, lds)) return e;
+    hipLaunchKernelGGL(strip_pass_kernel<false>, dim3(nblk), dim3(SW), lds, s, reinterpret_cast<const f32x4*>(points_xyzi), N, P.d_xf, P.T,
+                       P.d_cells, P.G, P.H, P.W, K.table, K.nwc, (const long*)nullptr, (f32x4*)nullptr, 0L, (unsigned*)nullptr);
+    LM_LAUNCH_CHECK();
+    return lm_prim_exclusive_scan_u32(s, K.table, K.table, K.L, K.scan_tmp, K.scan_bytes);
+}
+
+// the constants, their cells region sized for the largest grid (the grid is not known before the call), then a chunk's workspace
 LM_API long lm_strip_bin_workspace_bytes(long N, int T) {
     if (N < 0 || T < 1 || T > MAX_T) return 0;
-    const long L = (long)T * nwc_of(N) + 1;
-    return (long)(lm_align256((size_t)T * sizeof(LmWindowXf)) + lm_align256((size_t)MAX_CELLS * CELL_CAP * 2) + lm_align256((size_t)L * 4) +
-                  lm_align256(lm_prim_scan_temp_bytes(L)));
+    return consts_size(T, MAX_CELLS) + chunk_workspace_bytes(N, T);
 }
 
 // points: device [N][4]; params: HOST [T]; counts [T], offsets [T+1]: device int64; offsets_host: HOST [T+1] (may be NULL);
@@ -394,39 +440,19 @@ LM_API int lm_strip_bin_points(void* hip_stream, const float* points_xyzi, long 
     LM_REQUIRE(H > 0 && W > 0, "strip_bin: bad tile size");
     LM_REQUIRE(lm_strip_bin_workspace_bytes(N, T) <= workspace_bytes, "strip_bin: workspace too small (%ld B needed)",
                lm_strip_bin_workspace_bytes(N, T));
-    static thread_local std::vector<unsigned short> h_cells;
-    static thread_local std::vector<LmWindowXf> h_xf;
     static thread_local std::vector<long> h_off;
-    LmStripGrid grid;
-    if (int e = build_grid(params, T, H, W, z_lo, z_hi, &grid, h_cells)) return e;
-    const long ncell = (long)grid.nx * grid.ny;
-    h_xf.resize((size_t)T);
-    for (int t = 0; t < T; ++t) lm_window_xf(params[t], h_xf[(size_t)t]);
+    StripPlan P;                                               // of this call alone: its constants lie at the head of the workspace
+    if (int e = plan_build(params, T, H, W, z_lo, z_hi, &P)) return e;
     hipStream_t s = (hipStream_t)hip_stream;
-    const long nwc = nwc_of(N), L = (long)T * nwc + 1;
-    char* w = (char*)workspace;
-    LmWindowXf* d_xf = (LmWindowXf*)w;
-    w += lm_align256((size_t)T * sizeof(LmWindowXf));
-    u32x4* d_cells = (u32x4*)w;
-    w += lm_align256((size_t)MAX_CELLS * CELL_CAP * 2);
-    unsigned* table = (unsigned*)w;
-    w += lm_align256((size_t)L * 4);
-    void* scan_tmp = w;
-    const size_t scan_bytes = lm_align256(lm_prim_scan_temp_bytes(L));
-    const GridDev G = grid_dev(grid, z_lo, z_hi);
+    const ChunkWork K = chunk_work((char*)workspace + consts_size(T, MAX_CELLS), N, T);
     const size_t lds = (size_t)WAVES * T * sizeof(unsigned);
-    const unsigned nblk = (unsigned)((nwc + WAVES - 1) / WAVES);
+    const unsigned nblk = (unsigned)((K.nwc + WAVES - 1) / WAVES);
+    if (int e = plan_consts(s, workspace, N > 0, &P)) return e;                    // (no points: nothing reads the constants)
     if (N > 0) {
-        LM_HIP(hipMemcpyAsync(d_xf, h_xf.data(), (size_t)T * sizeof(LmWindowXf), hipMemcpyHostToDevice, s));
-        LM_HIP(hipMemcpyAsync(d_cells, h_cells.data(), (size_t)ncell * CELL_CAP * 2, hipMemcpyHostToDevice, s));
-        if (int e = lm_ensure_dynamic_lds((const void*)strip_pass_kernel<false>, lds)) return e;
         if (int e = lm_ensure_dynamic_lds((const void*)strip_pass_kernel<true>, lds)) return e;
-        hipLaunchKernelGGL(strip_pass_kernel<false>, dim3(nblk), dim3(SW), lds, s, reinterpret_cast<const f32x4*>(points_xyzi), N, d_xf, T,
-                           d_cells, G, H, W, table, nwc, (const long*)nullptr, (f32x4*)nullptr, 0L, (unsigned*)nullptr);
-        LM_LAUNCH_CHECK();
-        if (int e = lm_prim_exclusive_scan_u32(s, table, table, L, scan_tmp, scan_bytes)) return e;
+        if (int e = chunk_count(s, P, points_xyzi, N, K, lds, nblk)) return e;
     }
-    hipLaunchKernelGGL(strip_offsets_kernel, dim3(1), dim3(256), 0, s, table, nwc, T, counts, offsets);
+    hipLaunchKernelGGL(strip_offsets_kernel, dim3(1), dim3(256), 0, s, K.table, K.nwc, T, counts, offsets);
     LM_LAUNCH_CHECK();
     h_off.resize((size_t)T + 1);
     long* hoff = offsets_host ? offsets_host : h_off.data();
@@ -439,8 +465,9 @@ LM_API int lm_strip_bin_points(void* hip_stream, const float* points_xyzi, long 
     }
     if (total > 0) {
         LM_REQUIRE(binned, "strip_bin: null output");
-        hipLaunchKernelGGL(strip_pass_kernel<true>, dim3(nblk), dim3(SW), lds, s, reinterpret_cast<const f32x4*>(points_xyzi), N, d_xf, T,
-                           d_cells, G, H, W, table, nwc, (const long*)offsets, reinterpret_cast<f32x4*>(binned), 0L, (unsigned*)nullptr);
+        hipLaunchKernelGGL(strip_pass_kernel<true>, dim3(nblk), dim3(SW), lds, s, reinterpret_cast<const f32x4*>(points_xyzi), N, P.d_xf, T,
+                           P.d_cells, P.G, H, W, K.table, K.nwc, (const long*)offsets, reinterpret_cast<f32x4*>(binned), 0L,
+                           (unsigned*)nullptr);
         LM_LAUNCH_CHECK();
     }
     return LM_OK;
@@ -450,7 +477,7 @@ LM_API int lm_strip_bin_points(void* hip_stream, const float* points_xyzi, long 
 // n_cells: nx * ny of the layout's grid (lm_strip_build_grid with cells = NULL gives it)
 LM_API long lm_strip_plan_consts_bytes(int T, long n_cells) {
     if (T < 1 || T > MAX_T || n_cells < 1 || n_cells > MAX_CELLS) return 0;
-    return (long)(lm_align256((size_t)T * sizeof(LmWindowXf)) + lm_align256((size_t)n_cells * CELL_CAP * 2));
+    return consts_size(T, n_cells);
 }
 
 // params: HOST [T]; consts: DEVICE, lm_strip_plan_consts_bytes(T, nx * ny) bytes, 16-byte aligned, the caller's, alive and untouched as
@@ -463,26 +490,14 @@ LM_API int lm_strip_plan_create(const LmRasterParams* params, int T, int H, int 
     LM_REQUIRE(T >= 1 && T <= MAX_T, "strip_plan_create: T=%d tiles, 1 to %d are supported", T, MAX_T);
     LM_REQUIRE(H > 0 && W > 0, "strip_plan_create: bad tile size (H=%d, W=%d)", H, W);
     LM_REQUIRE(consts && ((uintptr_t)consts & 15) == 0, "strip_plan_create: consts is null or not 16-byte aligned");
-    std::vector<unsigned short> h_cells;
-    LmStripGrid grid;
-    if (int e = build_grid(params, T, H, W, z_lo, z_hi, &grid, h_cells)) return e;
-    const long need = lm_strip_plan_consts_bytes(T, (long)grid.nx * grid.ny);
+    StripPlan built;
+    if (int e = plan_build(params, T, H, W, z_lo, z_hi, &built)) return e;
+    const long need = lm_strip_plan_consts_bytes(T, (long)(t_cells.size() / CELL_CAP));
     LM_REQUIRE(consts_bytes >= need, "strip_plan_create: consts too small (%ld B needed)", need);
-    std::vector<LmWindowXf> h_xf((size_t)T);
-    for (int t = 0; t < T; ++t) lm_window_xf(params[t], h_xf[(size_t)t]);
     hipStream_t s = (hipStream_t)hip_stream;
-    char* w = (char*)consts;
-    LmWindowXf* d_xf = (LmWindowXf*)w;
-    w += lm_align256((size_t)T * sizeof(LmWindowXf));
-    u32x4* d_cells = (u32x4*)w;
-    LM_HIP(hipMemcpyAsync(d_xf, h_xf.data(), (size_t)T * sizeof(LmWindowXf), hipMemcpyHostToDevice, s));
-    LM_HIP(hipMemcpyAsync(d_cells, h_cells.data(), (size_t)grid.nx * grid.ny * CELL_CAP * 2, hipMemcpyHostToDevice, s));
-    LM_HIP(hipStreamSynchronize(s));                           // the host vectors end with this call
-    StripPlan* P = new StripPlan;
-    P->magic = PLAN_MAGIC, P->T = T, P->H = H, P->W = W;
-    P->G = grid_dev(grid, z_lo, z_hi);
-    P->d_xf = d_xf, P->d_cells = d_cells;
-    *plan = P;
+    if (int e = plan_consts(s, consts, true, &built)) return e;
+    LM_HIP(hipStreamSynchronize(s));                           // the constants are on the device when the call returns
+    *plan = new StripPlan(built);
     return LM_OK;
 }
 
@@ -511,22 +526,8 @@ static int chunk_args(const char* who, const void* plan, const float* points_xyz
     const int T = (*P)->T;
     LM_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0, "%s: workspace is null or not 16-byte aligned", who);
     LM_REQUIRE(chunk_workspace_bytes(N, T) <= workspace_bytes, "%s: workspace too small (%ld B needed)", who, chunk_workspace_bytes(N, T));
-    K->nwc = nwc_of(N), K->L = (long)T * K->nwc + 1;
-    char* w = (char*)workspace;
-    K->table = (unsigned*)w;
-    w += lm_align256((size_t)K->L * 4);
-    K->scan_tmp = w;
-    K->scan_bytes = lm_align256(lm_prim_scan_temp_bytes(K->L));
+    *K = chunk_work(workspace, N, T);
     return LM_OK;
-}
-
-// count pass and scan of one chunk (N > 0) into its table
-static int chunk_count(hipStream_t s, const StripPlan& P, const float* points_xyzi, long N, const ChunkWork& K, size_t lds, unsigned nblk) {
-    if (int e = lm_ensure_dynamic_lds((const void*)strip_pass_kernel<false>, lds)) return e;
-    hipLaunchKernelGGL(strip_pass_kernel<false>, dim3(nblk), dim3(SW), lds, s, reinterpret_cast<const f32x4*>(points_xyzi), N, P.d_xf, P.T,
-                       P.d_cells, P.G, P.H, P.W, K.table, K.nwc, (const long*)nullptr, (f32x4*)nullptr, 0L, (unsigned*)nullptr);
-    LM_LAUNCH_CHECK();
-    return lm_prim_exclusive_scan_u32(s, K.table, K.table, K.L, K.scan_tmp, K.scan_bytes);
 }
 
 // points: DEVICE [N][4], one chunk; counts_accum: DEVICE [T] int64, the caller's, zeroed by the caller before the first chunk.

@@ -1058,6 +1058,19 @@ def _tilted(p):
     return p.quat[1] != 0.0 or p.quat[2] != 0.0
 
 
+def _strip_cloud(points):
+    """Both forms of the strip binning: a host tensor is refused (_ptr's message); -> whether it is a contiguous [N,4] float32 tensor."""
+    if not points.is_cuda:
+        _ptr(points)
+    return points.dim() == 2 and points.shape[1] == 4 and points.is_contiguous() and points.dtype == torch.float32
+
+
+def _strip_z(z_range, params):
+    """Both forms of the strip binning: -> (z_lo, z_hi, ok); None is the whole axis; ok: the range is finite, or no tile is tilted."""
+    z_lo, z_hi = (float(z_range[0]), float(z_range[1])) if z_range is not None else (-math.inf, math.inf)
+    return z_lo, z_hi, (math.isfinite(z_lo) and math.isfinite(z_hi)) or not any(_tilted(p) for p in params)
+
+
 def strip_bin_points(points, params, H=1152, W=1152, z_range=None, capacity=None):
     """points [N,4] f32 on device (one whole strip), params: list of T LmRasterParams -> (binned [sum counts, 4], offsets: T+1 host
     ints): the points of tile 0, then tile 1, ... in cloud order, exactly those the rasteriser keeps for each tile - the
@@ -1065,17 +1078,16 @@ def strip_bin_points(points, params, H=1152, W=1152, z_range=None, capacity=None
     tilted tiles; None: taken from the points when a tile is tilted (one more pass and sync).  One device-to-host read of the offsets;
     if the first guess of the output size was short, one second call.  Not inside a graph capture (the entry refuses a capturing
     stream by name)."""
-    if not points.is_cuda:
-        _ptr(points)
-    assert points.dim() == 2 and points.shape[1] == 4 and points.is_contiguous() and points.dtype == torch.float32
+    ok = _strip_cloud(points)
+    assert ok
     T, N = len(params), points.shape[0]
     par = (LmRasterParams * T)(*params)
     if z_range is None and N and any(_tilted(p) for p in params):
         z = points[:, 2]
         z = z[torch.isfinite(z)]
         z_range = (float(z.min()), float(z.max())) if z.numel() else (0.0, 0.0)
-    z_lo, z_hi = (float(z_range[0]), float(z_range[1])) if z_range is not None else (-math.inf, math.inf)
-    if not (math.isfinite(z_lo) and math.isfinite(z_hi)) and any(_tilted(p) for p in params):
+    z_lo, z_hi, ok = _strip_z(z_range, params)
+    if not ok:
         if N:
             raise ValueError('strip_bin_points: tilted tiles need a finite z_range (or None: it is then taken from the points)')
         z_lo, z_hi = 0.0, 0.0                                                   # no points: any range will do
@@ -1140,8 +1152,8 @@ class StripBinner:
         self.params, self.H, self.W, self.device = list(params), int(H), int(W), torch.device(device)
         if self.device.type != 'cuda':
             raise LanemapHipError('StripBinner needs an MI355X (HIP) device; no CPU fallback exists')
-        z_lo, z_hi = (float(z_range[0]), float(z_range[1])) if z_range is not None else (-math.inf, math.inf)
-        if not (math.isfinite(z_lo) and math.isfinite(z_hi)) and any(_tilted(p) for p in self.params):
+        z_lo, z_hi, ok = _strip_z(z_range, self.params)
+        if not ok:
             raise ValueError('StripBinner: tilted tiles need a finite z_range')
         self.z = (z_lo, z_hi)
         T = len(self.params)
@@ -1158,9 +1170,7 @@ class StripBinner:
         return self._plans[tiles]
 
     def _chunk(self, who, points, T):
-        if not points.is_cuda:
-            _ptr(points)
-        if points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous() or points.dtype != torch.float32 or points.device != self.device:
+        if not _strip_cloud(points) or points.device != self.device:
             raise ValueError(f'StripBinner.{who}: points must be a contiguous [N,4] float32 tensor on {self.device}')
         N = points.shape[0]
         need = int(lib().lm_strip_chunk_workspace_bytes(N, T))

@@ -68,6 +68,24 @@ def _prf(tp, dets, dg, gts):
     return pre, rec, f1
 
 
+# The stages of the LAS routes, in the order of their signatures: argument -> (cfg key, the options class of las_io).  Runner._las_<argument>
+# (the argument, else cfg[key], else none) is generated from a row; only _las_threshold, whose default depends on the stages, is written out.
+LAS_STAGES = {
+    'select': ('las_select', 'PointFilter'),              # the point filter of the readers
+    'ground': ('las_ground', 'GroundFilter'),             # the terrain following
+    'intensity': ('las_intensity', 'IntensityStretch'),   # the intensity window
+    'elevation': ('las_elevation', 'ElevationDrape'),     # the vertex heights
+    'density': ('las_density', 'GapFill'),                # the gap fill
+    'label': ('las_label', 'MarkingLabels'),              # the labelled LAS files
+    'survey': ('las_survey', 'MarkingSurvey'),            # the marking profile
+    'colour': ('las_colour', 'MarkingColour'),            # white or yellow, beside the profile
+    'residue': ('las_residue', 'PaintResidue'),           # the paint no line explains
+    'cross': ('las_cross', 'CrossSection'),               # cross-sections, the snapped lines
+    'threshold': ('las_threshold', 'PaintThreshold'),     # the paint / asphalt threshold 'auto' asks for
+    'stream': ('las_stream', 'StripStream'),              # the chunked strip route
+}
+
+
 class Runner:
     def __init__(self, cfg, device=None):
         self.cfg = cfg
@@ -295,26 +313,27 @@ class Runner:
             raise TypeError(f'{arg} must be a las_io.{cls.__name__}, not {type(value).__name__}')
         return value
 
-    _las_select = functools.partialmethod(_las_option, 'select', 'las_select', 'PointFilter')              # the point filter of the readers
-    _las_ground = functools.partialmethod(_las_option, 'ground', 'las_ground', 'GroundFilter')             # the terrain following
-    _las_intensity = functools.partialmethod(_las_option, 'intensity', 'las_intensity', 'IntensityStretch')  # the intensity window
-    _las_elevation = functools.partialmethod(_las_option, 'elevation', 'las_elevation', 'ElevationDrape')  # the vertex heights
-    _las_density = functools.partialmethod(_las_option, 'density', 'las_density', 'GapFill')               # the gap fill
-    _las_label = functools.partialmethod(_las_option, 'label', 'las_label', 'MarkingLabels')               # the labelled LAS files
-    _las_survey = functools.partialmethod(_las_option, 'survey', 'las_survey', 'MarkingSurvey')            # the marking profile
-    _las_colour = functools.partialmethod(_las_option, 'colour', 'las_colour', 'MarkingColour')            # white or yellow, beside the profile
-    _las_residue = functools.partialmethod(_las_option, 'residue', 'las_residue', 'PaintResidue')          # the paint no line explains
-    _las_cross = functools.partialmethod(_las_option, 'cross', 'las_cross', 'CrossSection')                # cross-sections, the snapped lines
-    _las_stream = functools.partialmethod(_las_option, 'stream', 'las_stream', 'StripStream')              # the chunked strip route
     _AUTO = (('label', 'min_intensity'), ('survey', 'min_intensity'), ('cross', 'paint_intensity'), ('residue', 'min_intensity'))
 
     def _las_threshold(self, threshold, stages):
         """`threshold=` of the LAS routes: the argument, else cfg['las_threshold'] (a dict of las_io.PaintThreshold's arguments), else
         PaintThreshold() when a stage of `stages` ({'label': ..., 'survey': ..., 'cross': ..., 'residue': ...}) asks for 'auto', else none."""
         from . import las_io
-        threshold = self._las_option('threshold', 'las_threshold', 'PaintThreshold', threshold)
+        threshold = self._las_option('threshold', *LAS_STAGES['threshold'], threshold)
         asked = any(stages[k] is not None and getattr(stages[k], name) == las_io.AUTO for k, name in self._AUTO)
         return las_io.PaintThreshold() if threshold is None and asked else threshold
+
+    def _las_options(self, given, las_paths):
+        """What both LAS routes do with their stage arguments before anything runs.  given: {argument: value} in the order of LAS_STAGES
+        (`stream` only on the strip route), each resolved by its Runner._las_<argument>, `threshold` last: its 'auto' rule reads the
+        stages; then _label_plan and _colour_plan over `las_paths`.  -> ({argument: options object or None}, the `stages` of _after_map)."""
+        opt = {arg: getattr(self, '_las_' + arg)(value) for arg, value in given.items() if arg != 'threshold'}
+        stages = {k: opt[k] for k, _ in self._AUTO}
+        opt['threshold'] = self._las_threshold(given['threshold'], stages)
+        if opt['label'] is not None:
+            self._label_plan(las_paths)                                    # (a basename collision is refused before anything runs)
+        self._colour_plan(opt['colour'], opt['survey'], las_paths)
+        return opt, stages
 
     def _threshold_inputs(self, threshold, stages, files, result, out_dir, chunk_records=None):
         """The stage after the merge and before `label`: the paint / asphalt histograms of the lines the call returns (the same lines as
@@ -651,15 +670,10 @@ class Runner:
         cross, residue.
         Single rank (the merge is sequential over the sorted tiles)."""
         from . import las_io
-        select, ground, intensity = self._las_select(select), self._las_ground(ground), self._las_intensity(intensity)
-        elevation, density, label = self._las_elevation(elevation), self._las_density(density), self._las_label(label)
-        survey, colour, residue = self._las_survey(survey), self._las_colour(colour), self._las_residue(residue)
-        cross = self._las_cross(cross)
-        stages = {'label': label, 'survey': survey, 'cross': cross, 'residue': residue}
-        threshold = self._las_threshold(threshold, stages)
-        if label is not None:
-            self._label_plan([p for p, _ in las_and_params])              # (a basename collision is refused before anything runs)
-        self._colour_plan(colour, survey, [p for p, _ in las_and_params])
+        opt, stages = self._las_options(dict(select=select, ground=ground, intensity=intensity, elevation=elevation, density=density,
+                                             label=label, survey=survey, colour=colour, residue=residue, cross=cross, threshold=threshold),
+                                        [p for p, _ in las_and_params])
+        select, ground, intensity, elevation, density = (opt[k] for k in ('select', 'ground', 'intensity', 'elevation', 'density'))
         if intensity is not None and intensity.scope == 'strip':
             raise ValueError("intensity: scope='strip' needs the whole strip in one cloud (infer_las_strip_to_map); infer_las_to_map reads "
                              "its tiles file by file, use scope='tile'")
@@ -688,7 +702,7 @@ class Runner:
                 plist, pts, offs, rpar = self._follow_ground(ground, names, plist, pts, offs, rpar, H, W, out_dir)
             self._raster_stretched(raster_batch, intensity, names, plist, pts, offs, rpar, H, W, out_dir, used)
         result = close()
-        self._after_map(threshold, stages, colour, inputs, result, out_dir)
+        self._after_map(opt['threshold'], stages, opt['colour'], inputs, result, out_dir)
         return result
 
     def _las_chain(self, work_dirs, merge, elevation=None, density=None):
@@ -827,6 +841,15 @@ class Runner:
             plist.append(params)
         return names, plist
 
+    @staticmethod
+    def _strip_z_range(headers, shift):
+        """The z range of the strip binning's lookup grid: the min / max z of the file headers (las_io.parse_header's dicts) minus `shift`,
+        widened by a float ulp's worth - it only bounds the grid, never the result.  None where the headers hold no range."""
+        z_lo = min([np.inf] + [h['min'][2] - shift[2] for h in headers])
+        z_hi = max([-np.inf] + [h['max'][2] - shift[2] for h in headers])
+        pad = 1e-3 * max(1.0, abs(z_lo), abs(z_hi))
+        return (z_lo - pad, z_hi + pad) if z_lo <= z_hi else None
+
     def infer_las_strip_to_map(self, las_paths, param_paths, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None,
                                ground=None, intensity=None, elevation=None, density=None, label=None, survey=None, colour=None, residue=None, cross=None,
                                threshold=None, stream=None):
@@ -862,16 +885,11 @@ class Runner:
         if isinstance(las_paths, (str, os.PathLike)):
             las_paths = [las_paths]
         names, plist = self._strip_layout(list(param_paths))
-        select, ground, intensity = self._las_select(select), self._las_ground(ground), self._las_intensity(intensity)
-        elevation, density, label = self._las_elevation(elevation), self._las_density(density), self._las_label(label)
-        survey, colour, residue = self._las_survey(survey), self._las_colour(colour), self._las_residue(residue)
-        cross = self._las_cross(cross)
-        stream = self._las_stream(stream)
-        stages = {'label': label, 'survey': survey, 'cross': cross, 'residue': residue}
-        threshold = self._las_threshold(threshold, stages)
-        if label is not None:
-            self._label_plan(las_paths)                                    # (a basename collision is refused before anything runs)
-        self._colour_plan(colour, survey, las_paths)
+        opt, stages = self._las_options(dict(select=select, ground=ground, intensity=intensity, elevation=elevation, density=density,
+                                             label=label, survey=survey, colour=colour, residue=residue, cross=cross, threshold=threshold,
+                                             stream=stream), las_paths)
+        select, ground, intensity, elevation, density, stream = (opt[k] for k in ('select', 'ground', 'intensity', 'elevation', 'density',
+                                                                                  'stream'))
         used = {}
         B = int(batch_size or self.cfg.get('batch_size', 8))
         if stream is not None and stream.binned_budget is not None and intensity is not None and intensity.scope == 'strip' and len(plist) > B:
@@ -898,16 +916,14 @@ class Runner:
             self._stream_strip(stream, las_paths, plist, rpar, select, intensity, B, H, W, out_dir, batches)
         elif plist:
             shift = plist[0]['las_read_offset']
-            clouds, z_lo, z_hi = [], np.inf, -np.inf
+            clouds, headers = [], []
             for path in las_paths:
                 p, h = las_io.read_las_raw(path, self.device, shift=shift, select=select)
                 clouds.append(p)
-                z_lo, z_hi = min(z_lo, h['min'][2] - shift[2]), max(z_hi, h['max'][2] - shift[2])
+                headers.append(h)
             cloud = clouds[0] if len(clouds) == 1 else torch.cat(clouds)
             rpar = [io_utils.raster_params_from_dict(p) for p in plist]
-            # (the header's z range, widened by a float ulp's worth: it only bounds the lookup grid, never the result)
-            pad = 1e-3 * max(1.0, abs(z_lo), abs(z_hi))
-            binned, offs = ops.strip_bin_points(cloud, rpar, H, W, z_range=(z_lo - pad, z_hi + pad) if z_lo <= z_hi else None)
+            binned, offs = ops.strip_bin_points(cloud, rpar, H, W, z_range=self._strip_z_range(headers, shift))
             del cloud, clouds
             strip = None
             if intensity is not None and intensity.scope == 'strip':
@@ -915,8 +931,8 @@ class Runner:
             batches(binned, offs, 0, len(plist), strip)
         result = close()
         if plist:
-            self._after_map(threshold, stages, colour, [(path, plist[0]['las_read_offset'], select) for path in las_paths], result, out_dir,
-                            None if stream is None else stream.chunk_records)
+            self._after_map(opt['threshold'], stages, opt['colour'], [(path, plist[0]['las_read_offset'], select) for path in las_paths], result,
+                            out_dir, None if stream is None else stream.chunk_records)
         return result
 
     def _stream_strip(self, stream, las_paths, plist, rpar, select, intensity, B, H, W, out_dir, batches):
@@ -926,13 +942,9 @@ class Runner:
         from . import las_io
         shift = plist[0]['las_read_offset']
         files = [las_io.LasChunks(path, stream.chunk_records, self.device) for path in las_paths]      # (the headers only)
-        z_lo, z_hi = np.inf, -np.inf
-        for ch in files:
-            if select is not None:
-                select.for_format(ch.header['point_format'])                 # refused before anything is uploaded
-            z_lo, z_hi = min(z_lo, ch.header['min'][2] - shift[2]), max(z_hi, ch.header['max'][2] - shift[2])
-        pad = 1e-3 * max(1.0, abs(z_lo), abs(z_hi))                          # (as on the whole-cloud route: it only bounds the lookup grid)
-        binner = ops.StripBinner(rpar, H, W, (z_lo - pad, z_hi + pad) if z_lo <= z_hi else None, self.device)
+        for ch in files if select is not None else ():
+            select.for_format(ch.header['point_format'])                     # refused before anything is uploaded
+        binner = ops.StripBinner(rpar, H, W, self._strip_z_range([ch.header for ch in files], shift), self.device)
         kept = [0] * len(files)
 
         def each_cloud(fn, count=False):
@@ -1016,3 +1028,8 @@ class Runner:
                 for k, v in self.metrics.items():
                     print(f'{k}={v}')
         return res
+
+
+for _arg, _row in LAS_STAGES.items():
+    if _arg != 'threshold':
+        setattr(Runner, '_las_' + _arg, functools.partialmethod(Runner._las_option, _arg, *_row))

@@ -252,7 +252,7 @@ def test_header_declares_the_entry_with_hip_stream_and_the_inventories_hold():
     assert re.search(r'^def test_select_guards\(', gpu, flags=re.M) and 'lm_las_decode_select(' in gpu
 
 
-# ------------------------------------------------------------------------------------------------ the ten option classes
+# ------------------------------------------------------------------------------------------------ the twelve option classes
 OPTION_CASES = [
     (las_io.PointFilter, dict(classes=[11, 2], drop_keypoint=True, returns='last', z_range=(-1, 2.5))),
     (las_io.GroundFilter, dict(height_range=(-0.5, 1), cell_px=16, datum=False, datum_margin=0.5)),
@@ -264,18 +264,40 @@ OPTION_CASES = [
     (las_io.MarkingColour, dict(yellow_ratio=0.5, yellow_share=0.25, min_coloured=3)),
     (las_io.CrossSection, dict(paint_intensity=9000)),
     (las_io.PaintResidue, dict(min_intensity=9000)),
+    (las_io.PaintThreshold, dict(half_width=0.5, ring=0.03125, inner=0.0625, outer=0.25, z_tol=1, bin_shift=4, min_returns=10,
+                                 min_separation=0.1, tolerance_shift=3)),
+    (las_io.StripStream, dict(chunk_records=512, binned_budget=1 << 20)),
 ]
 
 
 def test_the_option_case_list_names_every_option_class():
-    """Every class of las_io that declares __slots__ of its own is in OPTION_CASES: a new stage's options get the same checks."""
-    slotted = {c for c in vars(las_io).values() if isinstance(c, type) and c.__module__ == las_io.__name__ and c.__dict__.get('__slots__')}
-    assert slotted == {c for c, _ in OPTION_CASES} and len(OPTION_CASES) == 10
+    """Every class of las_options that declares __slots__ of its own is in OPTION_CASES: a new stage's options get the same checks.
+    las_io hands each of them on under its name."""
+    from lanemapping_amd import las_options
+    slotted = {c for c in vars(las_options).values()
+               if isinstance(c, type) and c.__module__ == las_options.__name__ and c.__dict__.get('__slots__')}
+    assert slotted == {c for c, _ in OPTION_CASES} and len(OPTION_CASES) == 12
+    for c in slotted:
+        assert getattr(las_io, c.__name__) is c, c.__name__
+
+
+def test_las_io_hands_on_every_name_it_once_fetched_on_demand():
+    """The names las_io used to fetch from two other modules on first use are plain attributes of it, and the options module stands on
+    its own: importing it in a fresh interpreter loads neither torch nor las_io."""
+    import subprocess
+    import sys
+    for name in ('PaintThreshold', 'hist_records', 'hist_files', 'paint_threshold', 'KS_COEFF', 'HIST_BIN', 'StripStream', 'LasChunks',
+                 'tile_groups'):
+        assert name in vars(las_io), name
+    code = ("import sys, lanemapping_amd.las_options\n"
+            "print(int('torch' in sys.modules), int('lanemapping_amd.las_io' in sys.modules))")
+    out = subprocess.run([sys.executable, '-c', code], cwd=ROOT, capture_output=True, text=True, check=True).stdout
+    assert out.split() == ['0', '0'], out
 
 
 @pytest.mark.parametrize('cls, kwargs', OPTION_CASES, ids=[c.__name__ for c, _ in OPTION_CASES])
 def test_option_classes_are_values(cls, kwargs):
-    """What the ten option classes share: repr round-trips, equality and hash by value within the class only, no assignment, no deletion,
+    """What the twelve option classes share: repr round-trips, equality and hash by value within the class only, no assignment, no deletion,
     no instance dictionary, the arguments in __slots__ order."""
     name = cls.__name__
     x = cls(**kwargs)

@@ -84,7 +84,6 @@ def test_a_truncated_file_is_refused_with_both_byte_counts(tmp_path):
 def test_more_records_than_one_call_takes_are_accepted(tmp_path, monkeypatch):
     """A LAS 1.4 header that announces 2^31 + 5 records, over a file the file system reports long enough (64 GB are not written here):
     the object is built and its chunks are counted; the same header over the file as it is, is a truncated file."""
-    from lanemapping_amd import las_stream
     n = (1 << 31) + 5
     _write(tmp_path / 'e.las', 4, 6, 0)
     with open(tmp_path / 'e.las', 'r+b') as f:
@@ -92,7 +91,7 @@ def test_more_records_than_one_call_takes_are_accepted(tmp_path, monkeypatch):
         f.write(np.array([n], dtype='<u8').tobytes())
     with pytest.raises(LanemapHipError, match=rf'truncated.*{375 + n * 30} bytes.*{375 + 4 * 30}'):
         las_io.LasChunks(tmp_path / 'e.las', 1 << 24)
-    monkeypatch.setattr(las_stream.os.path, 'getsize', lambda p: 375 + n * 30)
+    monkeypatch.setattr(las_io.os.path, 'getsize', lambda p: 375 + n * 30)
     chunks = las_io.LasChunks(tmp_path / 'e.las', 1 << 24)
     assert chunks.header['n_points'] == n and len(chunks) == 129 and chunks.record_bytes == n * 30
 
