@@ -786,6 +786,96 @@ int lm_las_line_hist_records(const unsigned char* records, int record_len, int p
                              const LmLineGrid* grid, const int* cell_start, const int* cell_segs, float half_width, const float* stations,
                              int L, float z_tol, int ring_q, int bin_shift, int accumulate, long* hist, long n_hist, void* hip_stream);
 
+/* ---- paint thresholds per line and station window (csrc/profile.hip, label.hip, residue.hip).  A scanner's intensity falls with range:
+ * the paint of an outer lane is routinely darker than the asphalt of the lane under the scanner, and no single number separates the two
+ * on such a strip.  So the threshold is a TABLE, one value per station window of every line, read off WINDOWED histograms by the host
+ * policy (las_io.hist_window_files, las_io.paint_table) and looked up on the device for every return by the stages that take it.
+ * THE WINDOWS.  win_start [L + 1] int32 is a CSR table: line k (from 1) owns the rows win_start[k-1] .. win_start[k] - 1, nw_k of them.
+ * It is the bin_start of the marking profile for bin = window (las_io.line_stations(lines, shift, bin=window)).  For a return whose winner
+ * (the labelling rule's: smallest d2, ties to the smaller line, then to the smaller segment index) is segment s of line k at the clamped
+ * t, with the stations row s0, len of that segment, plain f32, no contraction:
+ *     st  = s0 + t len                                         the marking profile's station
+ *     w   = min((int)(st inv_window), nw_k - 1)                inv_window = (f32)(1 / window)
+ *     row = win_start[k-1] + w
+ * A line per row ("scope = line") is the same table with a window longer than every line: no second code path.
+ * THE WINDOWED HISTOGRAM.  las_line_hist_window_records: the histogram rule above with the row taken per window instead of per line:
+ *     hist[(row Z + r) NB + ib] += 1                           r, ib, Z, NB as above; hist [R][Z][NB] int64, R = win_start_host[L]
+ *         The arguments of lm_las_line_hist_records, then win_start (DEVICE [L + 1]), win_start_host (its HOST copy, what the call checks:
+ *         from 0, not descending - the table travels twice, as bin_start does) and window (metres, finite, > 0); n_hist = R Z NB.  One more
+ *         instantiation of las_profile_kernel: the records are read once and only read.  accumulate, the asynchrony and the edge sizes
+ *         (n = 0, S = 0, R = 0: LM_OK after the initialisation) are lm_las_line_hist_records'.  One window per line gives bit for bit its
+ *         table, and the windows of a line summed give it as well.  TRUST: whatever the device tables hold, win_start is read only in
+ *         [0, L] and hist is written only in [0, n_hist).  Refused, by the argument's name, before anything is launched or written: what
+ *         lm_las_line_hist_records refuses; a null or misaligned win_start; a null win_start_host, one that does not start at 0 or
+ *         descends; window <= 0 or not finite; R Z NB > 2^27; n_hist != R Z NB.
+ * THE RULE OF THE STAGES (one definition: this text; table_row / table_pass in csrc/label_rule.h and tests/local_ref.py restate it).
+ *     1. The winner (line k, segment s, t) is the labelling rule's, taken WITHOUT a min_intensity.
+ *     2. row as above.
+ *     3. A return PASSES when i >= thr_min && i >= thr[row], in plain f32; a NaN intensity fails.  In the cross entry, which counts
+ *        every finite return, nothing is filtered: a return is paint when iq >= paint_iq[row].
+ *     4. A return that does not pass is treated exactly as the scalar rule treats a return below min_intensity: label 0 and not counted
+ *        as labelled; not added to any bin or colour row; no residue (key -1, iq 0).
+ * thr_min keeps the early exit of dark waves - a wave of asphalt leaves before the search.  The host wrappers pass min(thr); whatever a
+ * caller passes, the rule above is what happens (a thr_min above a row's threshold raises that row's threshold to it).  A table whose
+ * rows all equal T, with thr_min = T, gives bit for bit what the scalar entry gives with min_intensity = T (paint_iq: with the scalar
+ * paint_iq in every row): eligibility by intensity does not depend on the winner.
+ * THE ENTRIES.  Each takes its scalar entry's arguments with `const LmPaintTable* table` (HOST) in place of min_intensity / paint_iq,
+ * and is that entry's kernel with one more template parameter, not a copy of it:
+ *     lm_las_label_records_local, lm_las_line_profile_records_local, lm_las_line_colour_records_local, lm_las_line_cross_records_local
+ *     and lm_residue_keys_local (the points entry: the residue route decodes first).
+ * table->stations is the station table of the segments the index was built from; the label and residue entries take no station table
+ * otherwise and get it here (lm_residue_keys_local also takes L, the lines of win_start, which its scalar entry has no use for).  n = 0, S = 0 and n_rows = 0 are LM_OK after the initialisation (no row: nothing passes).
+ * TRUST: whatever the device tables hold, thr and paint_iq are read only in [0, n_rows), win_start only in [0, L], and the outputs are
+ * written only where the scalar entry writes them.
+ * Refused with LM_ERR_ARG and a message that names the argument ("table.thr", ...), before anything is launched or written: what the
+ * scalar entry refuses; a null table; a null table member the entry reads (thr in all but the cross entry, paint_iq in the cross entry,
+ * win_start and stations with S > 0, win_start_host always); a misaligned member (thr, paint_iq, win_start: 4 bytes, stations: 16);
+ * n_rows != win_start_host[L]; a win_start_host that does not start at 0 or descends; a window that is not finite or not positive; a
+ * thr_min that is not finite; paint_iq given to an entry that does not read it, or missing from the cross entry.
+ * NOT HERE: points entries for label, profile, cross and the windowed histogram - the map routes run these stages on the records.
+ * NOTE on the place of `hip_stream`: LAST, as for lm_line_hist_points above and for the same reason; the cases the literal tables would
+ * name - guarded buffers, a side stream, graph replay, poisoned LDS - are in tests/test_gpu_threshold_local.py.  The new instantiations keep
+ * the kernel names las_profile_kernel and las_label_kernel, and residue_keys_kernel declares no __shared__. */
+typedef struct {
+    const float* thr;            /* DEVICE [n_rows] f32 */
+    const int*   paint_iq;       /* DEVICE [n_rows] int32 in 0 .. 65536: the cross entry reads this one, the others NULL */
+    const int*   win_start;      /* DEVICE [L + 1] */
+    const int*   win_start_host; /* HOST copy, what the call checks: from 0, not descending, win_start_host[L] == n_rows */
+    const float* stations;       /* DEVICE [S][4] f32, 16-byte aligned: s0, len, rlen of the segment table */
+    double window;               /* metres, finite, > 0 */
+    float  thr_min;              /* the early-exit pre-filter, see the rule */
+    long   n_rows;
+} LmPaintTable;
+int lm_las_line_hist_window_records(const unsigned char* records, int record_len, int point_format, long n, const double* scale,
+                                    const double* offset, const double* shift, const LmLasSelect* select, const float* segments, long S,
+                                    const LmLineGrid* grid, const int* cell_start, const int* cell_segs, float half_width,
+                                    const float* stations, int L, float z_tol, int ring_q, int bin_shift, int accumulate, long* hist,
+                                    long n_hist, const int* win_start, const int* win_start_host, double window, void* hip_stream);
+int lm_las_label_records_local(const unsigned char* records, int record_len, int point_format, long n, const double* scale,
+                               const double* offset, const double* shift, const LmLasSelect* select, const float* segments, long S,
+                               const LmLineGrid* grid, const int* cell_start, const int* cell_segs, float half_width, float z_tol,
+                               const LmPaintTable* table, int marking_class, int write_line_id, unsigned char* records_out, int* line,
+                               unsigned long* counts, int L, void* hip_stream);
+int lm_las_line_profile_records_local(const unsigned char* records, int record_len, int point_format, long n, const double* scale,
+                                      const double* offset, const double* shift, const LmLasSelect* select, const float* segments, long S,
+                                      const LmLineGrid* grid, const int* cell_start, const int* cell_segs, float half_width,
+                                      const float* stations, const int* bin_start, const int* bin_start_host, int L, double bin, float z_tol,
+                                      const LmPaintTable* table, int accumulate, long* bins, long n_bins, void* hip_stream);
+int lm_las_line_colour_records_local(const unsigned char* records, int record_len, int point_format, long n, const double* scale,
+                                     const double* offset, const double* shift, const LmLasSelect* select, const float* segments, long S,
+                                     const LmLineGrid* grid, const int* cell_start, const int* cell_segs, float half_width,
+                                     const float* stations, const int* bin_start, const int* bin_start_host, int L, double bin, float z_tol,
+                                     const LmPaintTable* table, int blue_q, int accumulate, long* bins, long* colours, long n_bins,
+                                     void* hip_stream);
+int lm_las_line_cross_records_local(const unsigned char* records, int record_len, int point_format, long n, const double* scale,
+                                    const double* offset, const double* shift, const LmLasSelect* select, const float* segments, long S,
+                                    const LmLineGrid* grid, const int* cell_start, const int* cell_segs, float half_width,
+                                    const float* stations, const int* bin_start, const int* bin_start_host, int L, double bin, float z_tol,
+                                    int lateral_q, const LmPaintTable* table, int accumulate, long* cells, long n_cells, void* hip_stream);
+int lm_residue_keys_local(const float* points_xyzi, long N, const float* segments, long S, const LmLineGrid* grid, const int* cell_start,
+                          const int* cell_segs, float half_width, float z_tol, const LmPaintTable* table, int L, float clear, double cell,
+                          int nx, int ny, long* key, int* iq, void* hip_stream);
+
 /* ---- the paint no lane line explains (csrc/residue.hip): stop bars, crossing bars, arrows, hatching, chevrons and lines the network
  * missed are bright paint in the same returns as the lines, and label, profile and colour above see only paint that lies ON a line.  This
  * stage takes the strip's returns and the lines the call returns, keeps the bright road-level returns that no line explains (the RESIDUE),

@@ -43,6 +43,12 @@ class LmLineGrid(C.Structure):
                 ('max_line', C.c_int), ('n_segments', C.c_long), ('n_entries', C.c_long), ('half_width', C.c_float)]
 
 
+class LmPaintTable(C.Structure):
+    """A paint threshold per station window of every line, as the _local entries take it (include/lanemap_hip.h)."""
+    _fields_ = [('thr', C.c_void_p), ('paint_iq', C.c_void_p), ('win_start', C.c_void_p), ('win_start_host', C.c_void_p),
+                ('stations', C.c_void_p), ('window', C.c_double), ('thr_min', C.c_float), ('n_rows', C.c_long)]
+
+
 # name -> (restype, argtypes); every entry must be declared in include/lanemap_hip.h
 SIGNATURES = {
     'lm_abi_version': (i32, []),
@@ -178,6 +184,23 @@ SIGNATURES = {
     'lm_las_line_hist_records': (i32, [vp, i32, i32, i64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                        C.POINTER(LmLasSelect), vp, i64, C.POINTER(LmLineGrid), vp, vp, f32, vp, i32, f32, i32, i32, i32, vp,
                                        i64, vp]),
+    'lm_las_line_hist_window_records': (i32, [vp, i32, i32, i64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                              C.POINTER(LmLasSelect), vp, i64, C.POINTER(LmLineGrid), vp, vp, f32, vp, i32, f32, i32, i32, i32,
+                                              vp, i64, vp, vp, C.c_double, vp]),
+    'lm_las_label_records_local': (i32, [vp, i32, i32, i64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                         C.POINTER(LmLasSelect), vp, i64, C.POINTER(LmLineGrid), vp, vp, f32, f32, C.POINTER(LmPaintTable), i32, i32,
+                                         vp, vp, vp, i32, vp]),
+    'lm_las_line_profile_records_local': (i32, [vp, i32, i32, i64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                C.POINTER(LmLasSelect), vp, i64, C.POINTER(LmLineGrid), vp, vp, f32, vp, vp, vp, i32, C.c_double,
+                                                f32, C.POINTER(LmPaintTable), i32, vp, i64, vp]),
+    'lm_las_line_colour_records_local': (i32, [vp, i32, i32, i64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                               C.POINTER(LmLasSelect), vp, i64, C.POINTER(LmLineGrid), vp, vp, f32, vp, vp, vp, i32, C.c_double,
+                                               f32, C.POINTER(LmPaintTable), i32, i32, vp, vp, i64, vp]),
+    'lm_las_line_cross_records_local': (i32, [vp, i32, i32, i64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                              C.POINTER(LmLasSelect), vp, i64, C.POINTER(LmLineGrid), vp, vp, f32, vp, vp, vp, i32, C.c_double,
+                                              f32, i32, C.POINTER(LmPaintTable), i32, vp, i64, vp]),
+    'lm_residue_keys_local': (i32, [vp, i64, vp, i64, C.POINTER(LmLineGrid), vp, vp, f32, f32, C.POINTER(LmPaintTable), i32, f32, C.c_double, i32,
+                                    i32, vp, vp, vp]),
     'lm_residue_keys': (i32, [vp, vp, i64, vp, i64, C.POINTER(LmLineGrid), vp, vp, f32, f32, f32, f32, C.c_double, i32, i32, vp, vp]),
     'lm_cell_components': (i32, [vp, vp, i64, i32, i32, i32, vp, vp]),
     'lm_residue_stats': (i32, [vp, vp, vp, i32, i32, vp, vp, i64, i64, vp]),

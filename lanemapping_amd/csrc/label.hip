@@ -24,6 +24,7 @@
 #include "las_record.h"
 
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -63,11 +64,15 @@ __global__ __launch_bounds__(256) void label_points_kernel(const lab_f32x4* __re
 }
 
 // grid: min(blocks of 256 records, the workgroups resident at once) workgroups; dynamic LDS = 256 records.  Per block: stage, decode + label + patch the staged
-// record, store the staged words back.  counts: labels below HIST in an LDS histogram, flushed once per workgroup.
+// record, store the staged words back.  counts: labels below HIST in an LDS histogram, flushed once per workgroup.  LOCAL: I.min_inten is
+// the paint table's thr_min, the search also yields the winner's segment and t, and a return below its row's threshold (table_pass,
+// label_rule.h) gets label 0 like one below min_intensity; T is the last argument, so the others keep their places.
+struct NoTable {};
+template <bool LOCAL>
 __global__ __launch_bounds__(256) void las_label_kernel(const unsigned* rec, int record_len, long n, long nblk, LasXf X, LasSel S,
                                                         int use_sel, IndexDev I, int fmt6, unsigned marking_class, int write_id,
                                                         unsigned* out, int* __restrict__ line, unsigned long long* __restrict__ counts,
-                                                        int L) {                                         // (out may be rec: no restrict)
+                                                        int L, std::conditional_t<LOCAL, TableDev, NoTable> T) {   // (out may be rec: no restrict)
     extern __shared__ unsigned lab_stage[];
     __shared__ unsigned hist[HIST];
     if (counts)
@@ -87,7 +92,16 @@ __global__ __launch_bounds__(256) void las_label_kernel(const unsigned* rec, int
         }
         float best;
         int ln = 0;
-        if (__ballot(b > a)) ln = label_search(p, I, a, b, best);
+        if constexpr (LOCAL) {
+            if (__ballot(b > a)) {
+                int s;
+                float t;
+                ln = label_search_t<true>(p, I, a, b, best, s, t);
+                if (ln > 0 && !table_pass(T, p.w, ln, s, t)) ln = 0;
+            }
+        } else {
+            if (__ballot(b > a)) ln = label_search(p, I, a, b, best);
+        }
         if (ln > 0) {                                                      // this lane's own bytes of the stage
             if (fmt6) r[16] = (unsigned char)marking_class;
             else r[15] = (unsigned char)((r[15] & 0xE0u) | marking_class);
@@ -248,30 +262,38 @@ LM_API int lm_label_points(void* hip_stream, const float* points_xyzi, long N, c
     return LM_OK;
 }
 
-// records / records_out: DEVICE, n record_len bytes rounded up to a multiple of 4, 4-byte aligned; records_out == records is allowed, any
-// other overlap is not.  line [n] int32 or NULL; counts: DEVICE [L + 1] u64 or NULL, zeroed by the call on the stream.
-LM_API int lm_las_label_records(void* hip_stream, const unsigned char* records, int record_len, int point_format, long n,
-                                const double* scale, const double* offset, const double* shift, const LmLasSelect* select,
-                                const float* segments, long S, const LmLineGrid* grid, const int* cell_start, const int* cell_segs,
-                                float half_width, float z_tol, float min_intensity, int marking_class, int write_line_id,
-                                unsigned char* records_out, int* line, unsigned long* counts, int L) {
-    if (int e = las_check_records("las_label_records", point_format, record_len, n)) return e;
+namespace {
+
+// The two record entries.  LOCAL: `table` (the paint table, checked after everything the scalar entry refuses) takes the place of
+// min_intensity.
+template <bool LOCAL>
+int las_label_records(const char* who, void* hip_stream, const unsigned char* records, int record_len, int point_format, long n,
+                      const double* scale, const double* offset, const double* shift, const LmLasSelect* select, const float* segments, long S,
+                      const LmLineGrid* grid, const int* cell_start, const int* cell_segs, float half_width, float z_tol, float min_intensity,
+                      const LmPaintTable* table, int marking_class, int write_line_id, unsigned char* records_out, int* line,
+                      unsigned long* counts, int L) {
+    if (int e = las_check_records(who, point_format, record_len, n)) return e;
     LM_REQUIRE(marking_class >= 0 && marking_class <= (point_format >= 6 ? 255 : 31),
-               "las_label_records: marking_class=%d does not fit format %d (0 .. %d)", marking_class, point_format, point_format >= 6 ? 255 : 31);
-    LM_REQUIRE(L >= 0, "las_label_records: L=%d lines", L);
-    LM_REQUIRE(!(write_line_id && L > 65535), "las_label_records: write_line_id with L=%d lines: the point source ID holds 16 bits", L);
+               "%s: marking_class=%d does not fit format %d (0 .. %d)", who, marking_class, point_format, point_format >= 6 ? 255 : 31);
+    LM_REQUIRE(L >= 0, "%s: L=%d lines", who, L);
+    LM_REQUIRE(!(write_line_id && L > 65535), "%s: write_line_id with L=%d lines: the point source ID holds 16 bits", who, L);
     IndexDev I;
-    if (int e = check_index("las_label_records", grid, S, segments, cell_start, cell_segs, half_width, z_tol, I)) return e;
-    LM_REQUIRE(S == 0 || (grid->min_line >= 1 && grid->max_line <= L), "las_label_records: segments carry lines %d .. %d, outside 1 .. L=%d",
+    if (int e = check_index(who, grid, S, segments, cell_start, cell_segs, half_width, z_tol, I)) return e;
+    LM_REQUIRE(S == 0 || (grid->min_line >= 1 && grid->max_line <= L), "%s: segments carry lines %d .. %d, outside 1 .. L=%d", who,
                S ? grid->min_line : 0, S ? grid->max_line : 0, L);
-    LM_REQUIRE(scale && offset && (n == 0 || (records && records_out)), "las_label_records: null pointer (scale, offset, records, records_out)");
-    LM_REQUIRE(((uintptr_t)records & 3) == 0, "las_label_records: records is not 4-byte aligned");
-    LM_REQUIRE(((uintptr_t)records_out & 3) == 0, "las_label_records: records_out is not 4-byte aligned");
-    LM_REQUIRE(((uintptr_t)line & 3) == 0, "las_label_records: line is not 4-byte aligned");
-    LM_REQUIRE(((uintptr_t)counts & 7) == 0, "las_label_records: counts is not 8-byte aligned");
+    LM_REQUIRE(scale && offset && (n == 0 || (records && records_out)), "%s: null pointer (scale, offset, records, records_out)", who);
+    LM_REQUIRE(((uintptr_t)records & 3) == 0, "%s: records is not 4-byte aligned", who);
+    LM_REQUIRE(((uintptr_t)records_out & 3) == 0, "%s: records_out is not 4-byte aligned", who);
+    LM_REQUIRE(((uintptr_t)line & 3) == 0, "%s: line is not 4-byte aligned", who);
+    LM_REQUIRE(((uintptr_t)counts & 7) == 0, "%s: counts is not 8-byte aligned", who);
     LasSel Sel;
-    if (int e = las_check_select("las_label_records", "select ", select, point_format, Sel)) return e;
+    if (int e = las_check_select(who, "select ", select, point_format, Sel)) return e;
     I.min_inten = min_intensity;
+    std::conditional_t<LOCAL, TableDev, NoTable> T{};
+    if constexpr (LOCAL) {
+        if (int e = check_table(who, table, L, S, true, false, T)) return e;
+        I.min_inten = table->thr_min;
+    }
     hipStream_t s = (hipStream_t)hip_stream;
     const long nblk = (n + 255) / 256;
     const size_t lds = las_stage_bytes(record_len);
@@ -279,14 +301,39 @@ LM_API int lm_las_label_records(void* hip_stream, const unsigned char* records, 
     // the others are half way through (registers and LDS decide how many that is)
     long resident = 0;
     if (n > 0)
-        if (int e = resident_groups(las_label_kernel, lds, resident)) return e;
+        if (int e = resident_groups(las_label_kernel<LOCAL>, lds, resident)) return e;
     if (counts) LM_HIP(lm_zero_async(counts, ((size_t)L + 1) * sizeof(unsigned long), s));
     if (n == 0) return LM_OK;
     const LasXf X = las_xf(scale, offset, shift, 0.f, 1.f, 0);         // raw intensity
     const unsigned groups = (unsigned)(nblk < resident ? nblk : resident);
-    hipLaunchKernelGGL(las_label_kernel, dim3(groups), dim3(256), lds, s, reinterpret_cast<const unsigned*>(records), record_len, n, nblk, X,
+    hipLaunchKernelGGL(las_label_kernel<LOCAL>, dim3(groups), dim3(256), lds, s, reinterpret_cast<const unsigned*>(records), record_len, n, nblk, X,
                        Sel, select ? 1 : 0, I, point_format >= 6 ? 1 : 0, (unsigned)marking_class, write_line_id ? 1 : 0,
-                       reinterpret_cast<unsigned*>(records_out), line, reinterpret_cast<unsigned long long*>(counts), L);
+                       reinterpret_cast<unsigned*>(records_out), line, reinterpret_cast<unsigned long long*>(counts), L, T);
     LM_LAUNCH_CHECK();
     return LM_OK;
+}
+
+}  // namespace
+
+// records / records_out: DEVICE, n record_len bytes rounded up to a multiple of 4, 4-byte aligned; records_out == records is allowed, any
+// other overlap is not.  line [n] int32 or NULL; counts: DEVICE [L + 1] u64 or NULL, zeroed by the call on the stream.
+LM_API int lm_las_label_records(void* hip_stream, const unsigned char* records, int record_len, int point_format, long n,
+                                const double* scale, const double* offset, const double* shift, const LmLasSelect* select,
+                                const float* segments, long S, const LmLineGrid* grid, const int* cell_start, const int* cell_segs,
+                                float half_width, float z_tol, float min_intensity, int marking_class, int write_line_id,
+                                unsigned char* records_out, int* line, unsigned long* counts, int L) {
+    return las_label_records<false>("las_label_records", hip_stream, records, record_len, point_format, n, scale, offset, shift, select, segments,
+                                    S, grid, cell_start, cell_segs, half_width, z_tol, min_intensity, nullptr, marking_class, write_line_id,
+                                    records_out, line, counts, L);
+}
+
+// as above with the paint table (the rule: include/lanemap_hip.h) in place of min_intensity; the stream comes LAST.
+LM_API int lm_las_label_records_local(const unsigned char* records, int record_len, int point_format, long n, const double* scale,
+                                      const double* offset, const double* shift, const LmLasSelect* select, const float* segments, long S,
+                                      const LmLineGrid* grid, const int* cell_start, const int* cell_segs, float half_width, float z_tol,
+                                      const LmPaintTable* table, int marking_class, int write_line_id, unsigned char* records_out, int* line,
+                                      unsigned long* counts, int L, void* hip_stream) {
+    return las_label_records<true>("las_label_records_local", hip_stream, records, record_len, point_format, n, scale, offset, shift, select,
+                                   segments, S, grid, cell_start, cell_segs, half_width, z_tol, NAN, table, marking_class, write_line_id,
+                                   records_out, line, counts, L);
 }

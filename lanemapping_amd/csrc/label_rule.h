@@ -94,6 +94,65 @@ inline int check_index(const char* who, const LmLineGrid* grid, long S, const vo
     return LM_OK;
 }
 
+// The paint table on the device (LmPaintTable, the rule: include/lanemap_hip.h): a threshold per station window of every line, looked up
+// for a return once its winner is known.  What the _local entries and the windowed histogram take beside the index.
+struct TableDev {
+    const float* thr;                    // [n_rows], or null in the entries that do not read it
+    const int* paint_iq;                 // [n_rows], the cross entry alone
+    const int* win_start;                // [L + 1]
+    const float4* stations;              // [S]: s0 len rlen 0
+    float inv_window;
+    int L, n_rows;
+};
+
+// the row of the table for a point whose winner is segment s of line ln at t, -1: none.  The station and its window are the marking
+// profile's st and b with bin = window.  win_start and stations are device tables the host cannot see: whatever they hold, a row outside
+// [0, n_rows) is never returned and win_start is never read outside [0, L].
+__device__ __forceinline__ int table_row(const TableDev& T, int ln, int s, float t) {
+    if (ln <= 0 || ln > T.L) return -1;
+    const int base = T.win_start[ln - 1], nw = T.win_start[ln] - base;
+    if (base < 0 || nw <= 0 || nw > T.n_rows - base) return -1;
+    const float4 St = T.stations[s];
+    const float st = St.x + t * St.y;
+    int w = (int)(st * T.inv_window);
+    w = w < nw - 1 ? w : nw - 1;
+    w = w > 0 ? w : 0;
+    return base + w;
+}
+
+// whether a return of intensity i whose winner is (ln, s, t) passes its row's threshold: i >= thr[row], plain f32, a NaN fails; without a
+// row nothing passes.  (i >= thr_min is label_range's test, with min_inten = thr_min.)
+__device__ __forceinline__ bool table_pass(const TableDev& T, float i, int ln, int s, float t) {
+    const int row = table_row(T, ln, s, t);
+    return row >= 0 && i >= T.thr[row];
+}
+
+// an LmPaintTable checked on the host before anything is launched -> D.  THR: the entry reads thr (every stage but the cross-sections);
+// IQ: it reads paint_iq (the cross-sections); neither: the windowed histogram, which reads the windows alone.
+inline int check_table(const char* who, const LmPaintTable* T, int L, long S, bool THR, bool IQ, TableDev& D) {
+    LM_REQUIRE(T, "%s: null pointer (table)", who);
+    LM_REQUIRE(T->window > 0 && T->window < HUGE_VAL, "%s: table.window=%g must be a finite length > 0", who, T->window);
+    LM_REQUIRE(std::fabs(T->thr_min) < INFINITY, "%s: table.thr_min=%g must be a finite number", who, (double)T->thr_min);
+    LM_REQUIRE(L >= 0, "%s: L=%d lines", who, L);
+    LM_REQUIRE(T->win_start_host, "%s: null pointer (table.win_start_host)", who);
+    LM_REQUIRE(T->win_start_host[0] == 0, "%s: table.win_start[0]=%d must be 0", who, T->win_start_host[0]);
+    for (int k = 0; k < L; ++k)
+        LM_REQUIRE(T->win_start_host[k + 1] >= T->win_start_host[k], "%s: table.win_start[%d]=%d is below table.win_start[%d]=%d", who, k + 1,
+                   T->win_start_host[k + 1], k, T->win_start_host[k]);
+    LM_REQUIRE(T->n_rows == (long)T->win_start_host[L], "%s: table.n_rows=%ld, but table.win_start[L]=%d", who, T->n_rows, T->win_start_host[L]);
+    LM_REQUIRE(S == 0 || (T->win_start && T->stations), "%s: null pointer (table.win_start, table.stations)", who);
+    LM_REQUIRE(!THR || T->n_rows == 0 || T->thr, "%s: null pointer (table.thr)", who);
+    LM_REQUIRE(!IQ || T->n_rows == 0 || T->paint_iq, "%s: null pointer (table.paint_iq): the cross-sections read it", who);
+    LM_REQUIRE(IQ || !T->paint_iq, "%s: table.paint_iq is given, but only the cross-sections read it", who);
+    LM_REQUIRE(((uintptr_t)T->thr & 3) == 0, "%s: table.thr is not 4-byte aligned", who);
+    LM_REQUIRE(((uintptr_t)T->paint_iq & 3) == 0, "%s: table.paint_iq is not 4-byte aligned", who);
+    LM_REQUIRE(((uintptr_t)T->win_start & 3) == 0, "%s: table.win_start is not 4-byte aligned", who);
+    LM_REQUIRE(((uintptr_t)T->stations & 15) == 0, "%s: table.stations is not 16-byte aligned", who);
+    D = TableDev{THR ? T->thr : nullptr, IQ ? T->paint_iq : nullptr, T->win_start, reinterpret_cast<const float4*>(T->stations),
+                 (float)(1.0 / T->window), L, (int)T->n_rows};
+    return LM_OK;
+}
+
 // the cloud of an entry whose only per-point buffer is points_xyzi (lm_label_points and lm_residue_keys name a second one in the same
 // refusal: their checks stay with them)
 inline int check_points(const char* who, const float* points_xyzi, long N) {

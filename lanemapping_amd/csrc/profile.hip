@@ -44,6 +44,12 @@
 // return.  hist_cell is the one device function for the per-point terms; hist_points_kernel has cross_points_kernel's streaming shape and
 // no LDS, las_profile_kernel<false, false, true> is the record kernel's fourth instantiation - the other three compile to the
 // instructions they had before it existed.  How a wave's counts go to memory was measured both ways: one atomic per hit lane won (hist_add).
+//
+// Paint thresholds per line and station window (the rule: include/lanemap_hip.h; table_row and table_pass: label_rule.h).  LOCAL is a
+// fourth template parameter of las_profile_kernel: the instantiation's argument is its kind's with the paint table appended
+// (WithTable), so the layouts of the four older instantiations do not move and they compile to the instructions they had.  Profile and
+// colour: a return that fails its row's threshold lands in no bin; cross: a return is paint by its row's paint_iq; histogram
+// (lm_las_line_hist_window_records): the row is the return's station window instead of its line.
 #include "common.h"
 #include "label_rule.h"
 #include "las_record.h"
@@ -84,8 +90,15 @@ struct HistDev {                         // what las_profile_kernel<false, false
     int L, hq, ring_q, Z, bin_shift;     // ceil(half_width 1024); the ring width in 1/1024 m; hq / ring_q + 1 rings; NB = 65536 >> bin_shift
 };
 
+template <class Base>
+struct WithTable : Base {                // what a LOCAL instantiation takes: its kind's arguments, then the paint table (label_rule.h)
+    TableDev T;
+};
+
 template <bool COLOUR, bool CROSS = false, bool HIST = false>
-using ProfArg = std::conditional_t<HIST, HistDev, std::conditional_t<CROSS, CrossDev, std::conditional_t<COLOUR, ColourDev, ProfDev>>>;
+using ProfBase = std::conditional_t<HIST, HistDev, std::conditional_t<CROSS, CrossDev, std::conditional_t<COLOUR, ColourDev, ProfDev>>>;
+template <bool COLOUR, bool CROSS = false, bool HIST = false, bool LOCAL = false>
+using ProfArg = std::conditional_t<LOCAL, WithTable<ProfBase<COLOUR, CROSS, HIST>>, ProfBase<COLOUR, CROSS, HIST>>;
 
 // the bin (absolute, -1: none), q and iq of a point whose winner is segment s of line ln at t.  bin_start and stations are device tables
 // the host cannot see: whatever they hold, a bin outside [0, n_bins) is never returned and bin_start is never read outside [0, L].
@@ -207,11 +220,12 @@ __device__ __forceinline__ int cross_row(const float4 p, const IndexDev& I, cons
 
 // Wave-uniform like profile_merge: every lane of the wave calls it, row = -1 where the lane has nothing.  Per distinct row of the wave the
 // two counts by ballots and the two sums by cross-lane adds, then lanes 0 .. 3 issue the row's four 64-bit atomics (32 contiguous bytes;
-// an add of 0 is left out).  A row held by one lane alone skips the reduction.  The plain form - every hit lane adding its own four
+// an add of 0 is left out).  A row held by one lane alone skips the reduction.  LOCAL: the return is paint by its row of the paint table (table_paint), not by P.paint_iq.  The plain form - every hit lane adding its own four
 // values, zeros left out - was measured beside this one and is slower wherever a wave's lanes share rows (profiles/cross_section.txt).
-__device__ __forceinline__ void cross_add(const CrossDev& P, int row, unsigned iq, int zq) {
+template <bool LOCAL = false>
+__device__ __forceinline__ void cross_add(const CrossDev& P, int row, unsigned iq, int zq, bool table_paint = false) {
     long long* __restrict__ cells = P.bins;
-    const bool paint = iq >= P.paint_iq;
+    const bool paint = LOCAL ? table_paint : iq >= P.paint_iq;
     const int lane = (int)__lane_id();
     unsigned long long todo = __ballot(row >= 0);
     while (todo) {
@@ -244,8 +258,8 @@ __device__ __forceinline__ void cross_add(const CrossDev& P, int row, unsigned i
 // ln: -> its cell in the table, -1: none.  q and iq are profile_bin's expressions, unchanged.  The ring r <= hq / ring_q = Z - 1 by the clamp
 // of |q|, ib <= 65535 >> bin_shift = NB - 1 by the clamp of iq and ln <= L is checked: whatever the device tables hold, a cell outside
 // [0, L Z NB) is never returned.
-__device__ __forceinline__ int hist_cell(const float4 p, const IndexDev& I, const HistDev& H, int ln, int s) {
-    if (ln <= 0 || ln > H.L) return -1;
+// hist_cell_at: the same for row `row` of the table, which the caller has checked - line ln - 1, or a window's row.
+__device__ __forceinline__ int hist_cell_at(const float4 p, const IndexDev& I, const HistDev& H, int row, int s) {
     const float4 A = I.seg[2 * s], D = I.seg[2 * s + 1];
     const float rlen = H.stations[4 * (long)s + 2];
     const float px = p.x - A.x, py = p.y - A.y;
@@ -255,7 +269,11 @@ __device__ __forceinline__ int hist_cell(const float4 p, const IndexDev& I, cons
     unsigned aq = q < 0 ? 0u - (unsigned)q : (unsigned)q;              // |q|, also of -2^31
     aq = aq < (unsigned)H.hq ? aq : (unsigned)H.hq;
     const int r = (int)(aq / (unsigned)H.ring_q), NB = 65536 >> H.bin_shift;
-    return ((ln - 1) * H.Z + r) * NB + (int)(iq >> H.bin_shift);
+    return (row * H.Z + r) * NB + (int)(iq >> H.bin_shift);
+}
+__device__ __forceinline__ int hist_cell(const float4 p, const IndexDev& I, const HistDev& H, int ln, int s) {
+    if (ln <= 0 || ln > H.L) return -1;
+    return hist_cell_at(p, I, H, ln - 1, s);
 }
 
 // One no-return 64-bit atomic add per hit lane (cell = -1: the lane has nothing).  Unlike the rows of cross_add a hit here is one count in
@@ -363,10 +381,12 @@ __global__ __launch_bounds__(256) void hist_points_kernel(const lab_f32x4* __res
 // registers, barrier (the stage is free again), search and accumulate.  The records are only read.  COLOUR: P is a ColourDev, the lane also
 // takes the R, G, B of its own staged record into registers before the barrier, and the colour row is merged after the profile's.  CROSS: P
 // is a CrossDev, and after the search the cross-section's cell is accumulated instead of the profile's bin.  HIST: P is a HistDev, and the
-// histogram's cell takes its place.
-template <bool COLOUR, bool CROSS = false, bool HIST = false>
+// histogram's cell takes its place.  LOCAL: P ends in the paint table P.T (the rule: include/lanemap_hip.h).  Profile and colour: I.min_inten is
+// thr_min and a return below its row's threshold lands in no bin; cross: a return is paint by its row's paint_iq; HIST: the histogram's row
+// is the return's window instead of its line.  The four instantiations without LOCAL compile to the instructions they had before it.
+template <bool COLOUR, bool CROSS = false, bool HIST = false, bool LOCAL = false>
 __global__ __launch_bounds__(256) void las_profile_kernel(const unsigned* __restrict__ rec, int record_len, long n, long nblk, LasXf X, LasSel S,
-                                                          int use_sel, IndexDev I, ProfArg<COLOUR, CROSS, HIST> P) {
+                                                          int use_sel, IndexDev I, ProfArg<COLOUR, CROSS, HIST, LOCAL> P) {
     extern __shared__ unsigned prof_stage[];
     for (long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
         const int cnt = las_stage_block(rec, record_len, n, blk, prof_stage);
@@ -390,17 +410,27 @@ __global__ __launch_bounds__(256) void las_profile_kernel(const unsigned* __rest
         float best, t;
         int s;
         const int ln = label_search_t<true>(p, I, a, b, best, s, t);
-        if constexpr (HIST) {
+        if constexpr (HIST && LOCAL) {
+            const int w = ln > 0 && ln <= P.L ? table_row(P.T, ln, s, t) : -1;
+            hist_add(P, w >= 0 ? hist_cell_at(p, I, P, w, s) : -1);
+        } else if constexpr (HIST) {
             hist_add(P, ln > 0 ? hist_cell(p, I, P, ln, s) : -1);
         } else if constexpr (CROSS) {
             int row = -1, zq = 0;
             unsigned iq = 0u;
             if (ln > 0) row = cross_row(p, I, P, ln, s, t, iq, zq);
-            cross_add(P, row, iq, zq);
+            if constexpr (LOCAL) {
+                const int w = row >= 0 ? table_row(P.T, ln, s, t) : -1;
+                cross_add<true>(P, row, iq, zq, w >= 0 && (int)iq >= P.T.paint_iq[w]);
+            } else {
+                cross_add(P, row, iq, zq);
+            }
         } else {
             int q = 0, B = -1;
             unsigned iq = 0u;
             if (ln > 0) B = profile_bin(p, I, P, ln, s, t, q, iq);
+            if constexpr (LOCAL)
+                if (B >= 0 && !table_pass(P.T, p.w, ln, s, t)) B = -1;
             profile_merge(P.bins, B, q, iq);
             if constexpr (COLOUR) colour_merge(P.colours, B, cr, cg, cb, P.blue_q);
         }
@@ -441,6 +471,9 @@ struct TableArgs {                       // where the result goes: an entry sets
     long* hist;                          // histograms
     long n_hist;
     int ring_q, bin_shift;
+    const LmPaintTable* table;           // the _local entries: the paint table in place of min_intensity / paint_iq
+    const int *win_start, *win_start_host;   // the windowed histogram: its rows
+    double window;
 };
 
 // the lines, up to the host copy of the bin table -> I, and P but for its table
@@ -507,8 +540,8 @@ int check_cross(const char* who, const LineArgs& A, int lateral_q, int paint_iq,
 }
 
 // the arguments of the two histogram entries, checked likewise: what the cross entries refuse of the arguments they share (no bin, no
-// bin_start), then the histogram's own; fills I and H
-int check_hist(const char* who, const LineArgs& A, int ring_q, int bin_shift, long* hist, long n_hist, IndexDev& I, HistDev& H) {
+// bin_start), then the histogram's own; fills I and H.  rows: L, or (windows) the rows of the windowed histogram
+int check_hist(const char* who, const LineArgs& A, int ring_q, int bin_shift, long* hist, long n_hist, long rows, bool windows, IndexDev& I, HistDev& H) {
     if (int e = check_index(who, A.grid, A.S, A.segments, A.cell_start, A.cell_segs, A.half_width, A.z_tol, I)) return e;
     LM_REQUIRE(A.half_width <= MAX_HALF_WIDTH, "%s: half_width=%g, at most %g m is supported (the offsets are taken in 1/1024 m)", who,
                (double)A.half_width, (double)MAX_HALF_WIDTH);
@@ -525,10 +558,11 @@ int check_hist(const char* who, const LineArgs& A, int ring_q, int bin_shift, lo
     H = HistDev{};
     H.stations = A.stations, H.L = A.L, H.hq = (int)std::ceil((double)A.half_width * 1024.0);   // <= 16384
     H.ring_q = ring_q, H.Z = H.hq / ring_q + 1, H.bin_shift = bin_shift;
-    const long NB = 65536L >> bin_shift, cells = (long)A.L * H.Z * NB;                           // < 2^31 2^15 2^16
-    LM_REQUIRE(cells <= MAX_HIST_CELLS, "%s: L=%d lines of Z=%d rings of NB=%ld counts are %ld, at most 2^27 are supported (choose a larger "
-               "ring_q or bin_shift)", who, A.L, H.Z, NB, cells);
-    LM_REQUIRE(n_hist == cells, "%s: n_hist=%ld, but L=%d lines of Z=%d rings of NB=%ld counts are %ld", who, n_hist, A.L, H.Z, NB, cells);
+    const long NB = 65536L >> bin_shift, cells = rows * H.Z * NB;                                // < 2^31 2^15 2^16
+    const char* unit = windows ? "windows" : "lines";
+    LM_REQUIRE(cells <= MAX_HIST_CELLS, "%s: n_hist: %ld %s of Z=%d rings of NB=%ld counts are %ld, at most 2^27 are supported (choose a larger "
+               "ring_q or bin_shift%s)", who, rows, unit, H.Z, NB, cells, windows ? ", or a longer window" : "");
+    LM_REQUIRE(n_hist == cells, "%s: n_hist=%ld, but %ld %s of Z=%d rings of NB=%ld counts are %ld", who, n_hist, rows, unit, H.Z, NB, cells);
     LM_REQUIRE(n_hist == 0 || hist, "%s: null pointer (hist)", who);
     H.hist = reinterpret_cast<long long*>(hist);
     return LM_OK;
@@ -577,20 +611,41 @@ LM_API int lm_line_profile_points(void* hip_stream, const float* points_xyzi, lo
 
 namespace {
 
-// The four record entries.  COLOUR: blue_q and colours are checked after everything the profile entry refuses, both tensors are initialised,
+// the windows of the windowed histogram, checked like the bin table of check_lines; -> the rows, and D (the windows alone: no thr)
+int check_windows(const char* who, const LineArgs& A, const TableArgs& T, TableDev& D, long& rows) {
+    LM_REQUIRE(T.window > 0 && T.window < HUGE_VAL, "%s: window=%g must be a finite length > 0", who, T.window);
+    LM_REQUIRE(A.L >= 0, "%s: L=%d lines", who, A.L);
+    LM_REQUIRE(T.win_start_host, "%s: null pointer (win_start_host)", who);
+    LM_REQUIRE(T.win_start_host[0] == 0, "%s: win_start[0]=%d must be 0", who, T.win_start_host[0]);
+    for (int k = 0; k < A.L; ++k)
+        LM_REQUIRE(T.win_start_host[k + 1] >= T.win_start_host[k], "%s: win_start[%d]=%d is below win_start[%d]=%d", who, k + 1,
+                   T.win_start_host[k + 1], k, T.win_start_host[k]);
+    LM_REQUIRE(A.S == 0 || T.win_start, "%s: null pointer (win_start)", who);
+    LM_REQUIRE(((uintptr_t)T.win_start & 3) == 0, "%s: win_start is not 4-byte aligned", who);
+    rows = T.win_start_host[A.L];
+    D = TableDev{nullptr, nullptr, T.win_start, reinterpret_cast<const float4*>(A.stations), (float)(1.0 / T.window), A.L, (int)rows};
+    return LM_OK;
+}
+
+// The record entries.  COLOUR: blue_q and colours are checked after everything the profile entry refuses, both tensors are initialised,
 // and las_profile_kernel<true> fills both in its one pass over the records.  CROSS: the cells take the place of the bins.  HIST: the
-// histograms do.
-template <bool COLOUR, bool CROSS, bool HIST = false>
+// histograms do.  LOCAL: the paint table T.table is checked after the scalar entry's arguments and rides at the end of P; with HIST the
+// table is the windows alone and the histogram has a row per window.
+template <bool COLOUR, bool CROSS, bool HIST = false, bool LOCAL = false>
 int las_profile_records(const char* who, void* hip_stream, const RecordArgs& R, const LineArgs& A, const TableArgs& T) {
     static const int rgb_off[11] = {-1, -1, 20, 28, -1, 28, -1, 30, 30, -1, 30};      // rgb_off + 6 <= las_min_len wherever there is colour
     if (int e = las_check_records(who, R.point_format, R.record_len, R.n)) return e;
     IndexDev I;
-    ProfArg<COLOUR, CROSS, HIST> P;
+    ProfArg<COLOUR, CROSS, HIST, LOCAL> P;
     long n_table;                                                      // the table's rows: without one there is nothing to launch
-    if constexpr (HIST) {
-        if (int e = check_hist(who, A, T.ring_q, T.bin_shift, T.hist, T.n_hist, I, P)) return e;
+    if constexpr (HIST && LOCAL) {
+        long rows = 0;
+        if (int e = check_windows(who, A, T, P.T, rows)) return e;
+        if (int e = check_hist(who, A, T.ring_q, T.bin_shift, T.hist, T.n_hist, rows, true, I, P)) return e;
+    } else if constexpr (HIST) {
+        if (int e = check_hist(who, A, T.ring_q, T.bin_shift, T.hist, T.n_hist, A.L, false, I, P)) return e;
     } else if constexpr (CROSS) {
-        if (int e = check_cross(who, A, T.lateral_q, T.paint_iq, T.cells, T.n_cells, I, P)) return e;
+        if (int e = check_cross(who, A, T.lateral_q, LOCAL ? 0 : T.paint_iq, T.cells, T.n_cells, I, P)) return e;
     } else {
         if (int e = check_profile(who, A, T.bins, T.n_bins, I, P)) return e;
     }
@@ -610,13 +665,20 @@ int las_profile_records(const char* who, void* hip_stream, const RecordArgs& R, 
         P.colours = reinterpret_cast<long long*>(T.colours), P.rgb_off = rgb_off[R.point_format], P.blue_q = (unsigned)T.blue_q;
     }
     I.min_inten = T.min_intensity;
+    if constexpr (LOCAL && !HIST) {
+        if (int e = check_table(who, T.table, A.L, A.S, !CROSS, CROSS, P.T)) return e;
+        if constexpr (!CROSS) {
+            I.min_inten = T.table->thr_min;
+            if (P.T.n_rows == 0) n_table = 0;                           // no row: nothing passes - the initialised table
+        }
+    }
     hipStream_t s = (hipStream_t)hip_stream;
     const bool work = R.n > 0 && A.S > 0 && n_table > 0;
     const long nblk = (R.n + 255) / 256;
     const size_t lds = las_stage_bytes(R.record_len);
     long resident = 0;
     if (work)
-        if (int e = resident_groups(las_profile_kernel<COLOUR, CROSS, HIST>, lds, resident)) return e;
+        if (int e = resident_groups(las_profile_kernel<COLOUR, CROSS, HIST, LOCAL>, lds, resident)) return e;
     if (!A.accumulate) {
         if constexpr (HIST) {
             LM_HIP(lm_zero_async(P.hist, (size_t)T.n_hist * sizeof(long long), s));
@@ -631,7 +693,7 @@ int las_profile_records(const char* who, void* hip_stream, const RecordArgs& R, 
     if (!work) return LM_OK;
     const LasXf X = las_xf(R.scale, R.offset, R.shift, 0.f, 1.f, 0);  // raw intensity
     const unsigned groups = (unsigned)(nblk < resident ? nblk : resident);
-    hipLaunchKernelGGL((las_profile_kernel<COLOUR, CROSS, HIST>), dim3(groups), dim3(256), lds, s, reinterpret_cast<const unsigned*>(R.records),
+    hipLaunchKernelGGL((las_profile_kernel<COLOUR, CROSS, HIST, LOCAL>), dim3(groups), dim3(256), lds, s, reinterpret_cast<const unsigned*>(R.records),
                        R.record_len, R.n, nblk, X, Sel, R.select ? 1 : 0, I, P);
     LM_LAUNCH_CHECK();
     return LM_OK;
@@ -710,7 +772,7 @@ LM_API int lm_line_hist_points(const float* points_xyzi, long N, const float* se
     IndexDev I;
     HistDev H;
     const LineArgs A{segments, S, grid, cell_start, cell_segs, half_width, z_tol, stations, nullptr, nullptr, L, 0.0, accumulate};
-    if (int e = check_hist("line_hist_points", A, ring_q, bin_shift, hist, n_hist, I, H)) return e;
+    if (int e = check_hist("line_hist_points", A, ring_q, bin_shift, hist, n_hist, L, false, I, H)) return e;
     if (int e = check_points("line_hist_points", points_xyzi, N)) return e;
     I.min_inten = NAN;
     hipStream_t s = (hipStream_t)hip_stream;
@@ -734,4 +796,60 @@ LM_API int lm_las_line_hist_records(const unsigned char* records, int record_len
     TableArgs T{};
     T.min_intensity = NAN, T.hist = hist, T.n_hist = n_hist, T.ring_q = ring_q, T.bin_shift = bin_shift;
     return las_profile_records<false, false, true>("las_line_hist_records", hip_stream, R, A, T);
+}
+
+// The windowed histogram (the rule: include/lanemap_hip.h): lm_las_line_hist_records with a row per station window of every line instead
+// of one per line.  hist DEVICE [R][Z][NB] int64, R = win_start_host[L].  las_profile_kernel<false, false, true, true>.
+LM_API int lm_las_line_hist_window_records(const unsigned char* records, int record_len, int point_format, long n, const double* scale,
+                                           const double* offset, const double* shift, const LmLasSelect* select, const float* segments,
+                                           long S, const LmLineGrid* grid, const int* cell_start, const int* cell_segs, float half_width,
+                                           const float* stations, int L, float z_tol, int ring_q, int bin_shift, int accumulate, long* hist,
+                                           long n_hist, const int* win_start, const int* win_start_host, double window, void* hip_stream) {
+    const RecordArgs R{records, record_len, point_format, n, scale, offset, shift, select};
+    const LineArgs A{segments, S, grid, cell_start, cell_segs, half_width, z_tol, stations, nullptr, nullptr, L, 0.0, accumulate};
+    TableArgs T{};
+    T.min_intensity = NAN, T.hist = hist, T.n_hist = n_hist, T.ring_q = ring_q, T.bin_shift = bin_shift;
+    T.win_start = win_start, T.win_start_host = win_start_host, T.window = window;
+    return las_profile_records<false, false, true, true>("las_line_hist_window_records", hip_stream, R, A, T);
+}
+
+// The three _local record entries of this file (the rule: include/lanemap_hip.h): the scalar entry's arguments with the paint table in
+// place of min_intensity / paint_iq, and the scalar entry's kernel with LOCAL set.
+LM_API int lm_las_line_profile_records_local(const unsigned char* records, int record_len, int point_format, long n, const double* scale,
+                                             const double* offset, const double* shift, const LmLasSelect* select, const float* segments,
+                                             long S, const LmLineGrid* grid, const int* cell_start, const int* cell_segs, float half_width,
+                                             const float* stations, const int* bin_start, const int* bin_start_host, int L, double bin,
+                                             float z_tol, const LmPaintTable* table, int accumulate, long* bins, long n_bins,
+                                             void* hip_stream) {
+    const RecordArgs R{records, record_len, point_format, n, scale, offset, shift, select};
+    const LineArgs A{segments, S, grid, cell_start, cell_segs, half_width, z_tol, stations, bin_start, bin_start_host, L, bin, accumulate};
+    TableArgs T{};
+    T.min_intensity = NAN, T.bins = bins, T.n_bins = n_bins, T.table = table;
+    return las_profile_records<false, false, false, true>("las_line_profile_records_local", hip_stream, R, A, T);
+}
+
+LM_API int lm_las_line_colour_records_local(const unsigned char* records, int record_len, int point_format, long n, const double* scale,
+                                            const double* offset, const double* shift, const LmLasSelect* select, const float* segments,
+                                            long S, const LmLineGrid* grid, const int* cell_start, const int* cell_segs, float half_width,
+                                            const float* stations, const int* bin_start, const int* bin_start_host, int L, double bin,
+                                            float z_tol, const LmPaintTable* table, int blue_q, int accumulate, long* bins, long* colours,
+                                            long n_bins, void* hip_stream) {
+    const RecordArgs R{records, record_len, point_format, n, scale, offset, shift, select};
+    const LineArgs A{segments, S, grid, cell_start, cell_segs, half_width, z_tol, stations, bin_start, bin_start_host, L, bin, accumulate};
+    TableArgs T{};
+    T.min_intensity = NAN, T.bins = bins, T.n_bins = n_bins, T.colours = colours, T.blue_q = blue_q, T.table = table;
+    return las_profile_records<true, false, false, true>("las_line_colour_records_local", hip_stream, R, A, T);
+}
+
+LM_API int lm_las_line_cross_records_local(const unsigned char* records, int record_len, int point_format, long n, const double* scale,
+                                           const double* offset, const double* shift, const LmLasSelect* select, const float* segments,
+                                           long S, const LmLineGrid* grid, const int* cell_start, const int* cell_segs, float half_width,
+                                           const float* stations, const int* bin_start, const int* bin_start_host, int L, double bin,
+                                           float z_tol, int lateral_q, const LmPaintTable* table, int accumulate, long* cells, long n_cells,
+                                           void* hip_stream) {
+    const RecordArgs R{records, record_len, point_format, n, scale, offset, shift, select};
+    const LineArgs A{segments, S, grid, cell_start, cell_segs, half_width, z_tol, stations, bin_start, bin_start_host, L, bin, accumulate};
+    TableArgs T{};
+    T.min_intensity = NAN, T.cells = cells, T.n_cells = n_cells, T.lateral_q = lateral_q, T.table = table;
+    return las_profile_records<false, true, false, true>("las_line_cross_records_local", hip_stream, R, A, T);
 }

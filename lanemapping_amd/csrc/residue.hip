@@ -36,6 +36,7 @@
 #include "label_rule.h"
 
 #include <cmath>
+#include <type_traits>
 
 namespace {
 
@@ -50,9 +51,13 @@ struct ResDev {
     int nx, ny;
 };
 
-// grid: ceil(N / 1024) workgroups
+// grid: ceil(N / 1024) workgroups.  LOCAL: I.min_inten is the paint table's thr_min, the search also yields the winner's segment and t, and
+// a return below its row's threshold (table_pass, label_rule.h) is no residue, like one below min_intensity; T is the last argument.
+struct NoTable {};
+template <bool LOCAL>
 __global__ __launch_bounds__(256) void residue_keys_kernel(const lab_f32x4* __restrict__ pts, long N, IndexDev I, ResDev R,
-                                                           long long* __restrict__ key, int* __restrict__ iq) {
+                                                           long long* __restrict__ key, int* __restrict__ iq,
+                                                           std::conditional_t<LOCAL, TableDev, NoTable> T) {
     const long first = (long)blockIdx.x * CHUNK;
     const long left = N - first;                               // >= 1
     float4 p[PER];
@@ -70,7 +75,16 @@ __global__ __launch_bounds__(256) void residue_keys_kernel(const lab_f32x4* __re
         if (valid) label_range(p[j], I, a, b);
         float best = INFINITY;
         int ln = 0;
-        if (__ballot(b > a)) ln = label_search(p[j], I, a, b, best);       // wave-uniform: a wave beside the lines leaves here
+        if constexpr (LOCAL) {
+            if (__ballot(b > a)) {
+                int s;
+                float t;
+                ln = label_search_t<true>(p[j], I, a, b, best, s, t);
+                if (ln > 0 && !table_pass(T, p[j].w, ln, s, t)) ln = 0;
+            }
+        } else {
+            if (__ballot(b > a)) ln = label_search(p[j], I, a, b, best);   // wave-uniform: a wave beside the lines leaves here
+        }
         long long k = -1;
         int q = 0;
         if (ln > 0 && best > R.clear2) {
@@ -253,33 +267,62 @@ int check_side(const char* who, int nx, int ny) {
 
 }  // namespace
 
+namespace {
+
+// The two key entries.  LOCAL: `table` (the paint table of L lines, checked after everything the scalar entry refuses) takes the place
+// of min_intensity.
+template <bool LOCAL>
+int residue_keys(const char* who, void* hip_stream, const float* points_xyzi, long N, const float* segments, long S, const LmLineGrid* grid,
+                 const int* cell_start, const int* cell_segs, float half_width, float z_tol, float min_intensity, const LmPaintTable* table,
+                 int L, float clear, double cell, int nx, int ny, long* key, int* iq) {
+    IndexDev I;
+    if (int e = check_index(who, grid, S, segments, cell_start, cell_segs, half_width, z_tol, I)) return e;
+    LM_REQUIRE(half_width <= MAX_REACH, "%s: half_width=%g (the reach), at most %g m is supported", who, (double)half_width, (double)MAX_REACH);
+    LM_REQUIRE(LOCAL || std::fabs(min_intensity) < INFINITY, "%s: min_intensity=%g must be a finite number (without one the whole road is one blob)",
+               who, (double)min_intensity);
+    LM_REQUIRE(clear >= 0.f && clear < half_width, "%s: clear=%g must lie in 0 <= clear < half_width=%g (the reach)", who, (double)clear,
+               (double)half_width);
+    LM_REQUIRE(cell > 0 && cell < HUGE_VAL, "%s: cell=%g must be a finite size > 0", who, cell);
+    if (int e = check_side(who, nx, ny)) return e;
+    LM_REQUIRE(S == 0 || (nx >= 1 && ny >= 1), "%s: nx=%d, ny=%d: a grid of at least one cell is needed", who, nx, ny);
+    LM_REQUIRE(N >= 0 && N <= 2147483647L, "%s: N=%ld points, at most 2^31 - 1 are supported", who, N);
+    LM_REQUIRE(N == 0 || (points_xyzi && key), "%s: null pointer (points_xyzi, key)", who);
+    LM_REQUIRE(((uintptr_t)points_xyzi & 15) == 0, "%s: points_xyzi is not 16-byte aligned", who);
+    LM_REQUIRE(((uintptr_t)key & 7) == 0, "%s: key is not 8-byte aligned", who);
+    LM_REQUIRE(((uintptr_t)iq & 3) == 0, "%s: iq is not 4-byte aligned", who);
+    I.min_inten = min_intensity;
+    std::conditional_t<LOCAL, TableDev, NoTable> T{};
+    if constexpr (LOCAL) {
+        LM_REQUIRE(S == 0 || (grid->min_line >= 1 && grid->max_line <= L), "%s: segments carry lines %d .. %d, outside 1 .. L=%d", who,
+                   S ? grid->min_line : 0, S ? grid->max_line : 0, L);
+        if (int e = check_table(who, table, L, S, true, false, T)) return e;
+        I.min_inten = table->thr_min;
+    }
+    if (N == 0) return LM_OK;
+    const ResDev R{clear * clear, (float)(1.0 / cell), nx, ny};
+    hipLaunchKernelGGL(residue_keys_kernel<LOCAL>, dim3((unsigned)lm_cdivl(N, CHUNK)), dim3(256), 0, (hipStream_t)hip_stream,
+                       reinterpret_cast<const lab_f32x4*>(points_xyzi), N, I, R, reinterpret_cast<long long*>(key), iq, T);
+    LM_LAUNCH_CHECK();
+    return LM_OK;
+}
+
+}  // namespace
+
 // points_xyzi: DEVICE [N][4] f32; the index arguments of lm_label_points, half_width = the reach the grid was built for.  key [N] int64,
 // iq [N] int32 or NULL.  Asynchronous, no workspace, nothing read back.
 LM_API int lm_residue_keys(void* hip_stream, const float* points_xyzi, long N, const float* segments, long S, const LmLineGrid* grid,
                            const int* cell_start, const int* cell_segs, float half_width, float z_tol, float min_intensity, float clear,
                            double cell, int nx, int ny, long* key, int* iq) {
-    IndexDev I;
-    if (int e = check_index("residue_keys", grid, S, segments, cell_start, cell_segs, half_width, z_tol, I)) return e;
-    LM_REQUIRE(half_width <= MAX_REACH, "residue_keys: half_width=%g (the reach), at most %g m is supported", (double)half_width, (double)MAX_REACH);
-    LM_REQUIRE(std::fabs(min_intensity) < INFINITY, "residue_keys: min_intensity=%g must be a finite number (without one the whole road is one blob)",
-               (double)min_intensity);
-    LM_REQUIRE(clear >= 0.f && clear < half_width, "residue_keys: clear=%g must lie in 0 <= clear < half_width=%g (the reach)", (double)clear,
-               (double)half_width);
-    LM_REQUIRE(cell > 0 && cell < HUGE_VAL, "residue_keys: cell=%g must be a finite size > 0", cell);
-    if (int e = check_side("residue_keys", nx, ny)) return e;
-    LM_REQUIRE(S == 0 || (nx >= 1 && ny >= 1), "residue_keys: nx=%d, ny=%d: a grid of at least one cell is needed", nx, ny);
-    LM_REQUIRE(N >= 0 && N <= 2147483647L, "residue_keys: N=%ld points, at most 2^31 - 1 are supported", N);
-    LM_REQUIRE(N == 0 || (points_xyzi && key), "residue_keys: null pointer (points_xyzi, key)");
-    LM_REQUIRE(((uintptr_t)points_xyzi & 15) == 0, "residue_keys: points_xyzi is not 16-byte aligned");
-    LM_REQUIRE(((uintptr_t)key & 7) == 0, "residue_keys: key is not 8-byte aligned");
-    LM_REQUIRE(((uintptr_t)iq & 3) == 0, "residue_keys: iq is not 4-byte aligned");
-    I.min_inten = min_intensity;
-    if (N == 0) return LM_OK;
-    const ResDev R{clear * clear, (float)(1.0 / cell), nx, ny};
-    hipLaunchKernelGGL(residue_keys_kernel, dim3((unsigned)lm_cdivl(N, CHUNK)), dim3(256), 0, (hipStream_t)hip_stream,
-                       reinterpret_cast<const lab_f32x4*>(points_xyzi), N, I, R, reinterpret_cast<long long*>(key), iq);
-    LM_LAUNCH_CHECK();
-    return LM_OK;
+    return residue_keys<false>("residue_keys", hip_stream, points_xyzi, N, segments, S, grid, cell_start, cell_segs, half_width, z_tol,
+                               min_intensity, nullptr, 0, clear, cell, nx, ny, key, iq);
+}
+
+// as above with the paint table of L lines (the rule: include/lanemap_hip.h) in place of min_intensity; the stream comes LAST.
+LM_API int lm_residue_keys_local(const float* points_xyzi, long N, const float* segments, long S, const LmLineGrid* grid,
+                                 const int* cell_start, const int* cell_segs, float half_width, float z_tol, const LmPaintTable* table, int L,
+                                 float clear, double cell, int nx, int ny, long* key, int* iq, void* hip_stream) {
+    return residue_keys<true>("residue_keys_local", hip_stream, points_xyzi, N, segments, S, grid, cell_start, cell_segs, half_width, z_tol,
+                              NAN, table, L, clear, cell, nx, ny, key, iq);
 }
 
 // keys: DEVICE [M] int64, ascending and distinct (what the host cannot check: anything else gives garbage inside root[0, M)); root DEVICE

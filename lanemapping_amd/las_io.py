@@ -48,6 +48,11 @@ the threshold that best separates the returns ON the lines from those BESIDE the
 `StripStream` / `LasChunks` / `tile_groups` map a strip that does not fit in memory: the files read in chunks of records, counted and
 then scattered into groups of tiles (`ops.StripBinner`), and the record passes above fed chunk by chunk (`chunk_records=`).
 
+`PaintThreshold(scope='line' | 'window')` / `hist_window_files` / `paint_table` / `PaintTable` make the threshold a table, one value per
+line or per station window along every line, for strips whose intensity falls with range: the histograms are taken per window
+(`lm_las_line_hist_window_records`), a window without support takes its line's threshold and a line without support the strip's, and the
+four stages look the value up for every return on the GPU (the `_local` entries) where their option holds the table.
+
 The option classes are defined in las_options.py and imported here (`las_io.<name>` is the same object); the readers, the passes over
 the records and the policy functions that take an options object are here.
 """
@@ -61,7 +66,8 @@ import torch
 from ._lib import lib, check, LmLasHeader, LanemapHipError
 from .las_options import (AUTO, CHUNK_MULTIPLE, DROP_KEYPOINT, DROP_OVERLAP, DROP_SYNTHETIC, DROP_WITHHELD, RETURNS, CrossSection,
                           ElevationDrape, GapFill, GroundFilter, IntensityStretch, MarkingColour, MarkingLabels, MarkingSurvey, PaintResidue,
-                          PaintThreshold, PointFilter, StripStream, _Options, _check_chunk_records, _is_auto, _number, _resolved, _whole)
+                          PaintThreshold, PointFilter, StripStream, THRESHOLD_SCOPES, _Options, _Table, _check_chunk_records, _is_auto, _is_table,
+                          _number, _resolved, _whole, paint_iq_of)
 
 INTEN_MIN, INTEN_MAX = 800.0, 33000.0
 
@@ -183,9 +189,27 @@ def _records_args(who, records_u8, header, shift, select, index, stations, asker
             C.byref(sel) if sel is not None else None, *index.args(), *(stations.args() if bin is not None else ())), dev
 
 
-def label_records(records_u8, header, index, labels, shift=None, select=None, n_lines=None, want_line=False):
+def _paint_rows(who, table, stations, n_lines, cross=False):
+    """The PaintTable of a stage option on the device of `stations` (the [S,4] f32 tensor of the segments' ops.LineStations), checked
+    against the lines: -> an ops.PaintRows.  cross: with the cross-sections' integer of every row."""
+    from . import ops
+    if len(table.win_start) != n_lines + 1:
+        raise ValueError(f'{who}: the paint table was cut for {len(table.win_start) - 1} lines, the call has {n_lines}')
+    key = (table, stations.data_ptr(), str(stations.device), bool(cross))
+    if _ROWS[:1] != [key]:                  # the chunks of a file, and the files of a frame, come with the same tables: uploaded once
+        _ROWS[:] = [key, ops.paint_rows(table.thr, table.win_start, table.window, stations,
+                                        paint_iq=np.array([paint_iq_of(float(v)) for v in table.thr], dtype=np.int32) if cross else None)]
+    return _ROWS[1]
+
+
+_ROWS = []                          # the last (key, ops.PaintRows) of _paint_rows
+
+
+def label_records(records_u8, header, index, labels, shift=None, select=None, n_lines=None, want_line=False, stations=None):
     """One lm_las_label_records call on the DEVICE records of a file (padded to a multiple of 4 bytes; `header`: parse_header's dict)
-    against an ops.line_index: -> (patched records, counts [n_lines + 1] int64 device tensor[, line [n] int32]).  Asynchronous."""
+    against an ops.line_index: -> (patched records, counts [n_lines + 1] int64 device tensor[, line [n] int32]).  Asynchronous.
+    Where labels.min_intensity is a PaintTable the call is lm_las_label_records_local, and `stations` - the ops.LineStations of the same
+    segments, any bin - is required: the table's rows are looked up with it."""
     if not isinstance(labels, MarkingLabels):
         raise TypeError(f'las_io.label_records: labels must be a MarkingLabels, not {type(labels).__name__}')
     args, dev = _records_args('las_io.label_records', records_u8, header, shift, select, index, None, 'labels ask', labels.half_width)
@@ -195,10 +219,24 @@ def label_records(records_u8, header, index, labels, shift=None, select=None, n_
     counts = torch.empty((L + 1,), device=dev, dtype=torch.int64)
     line = torch.empty((header['n_points'],), device=dev, dtype=torch.int32) if want_line else None
     mi = _resolved('las_io.label_records', labels, 'min_intensity')
-    mi = math.nan if mi is None else mi
-    check(lib().lm_las_label_records(*args, labels.z_tol, mi, cls, int(labels.line_ids), C.c_void_p(out.data_ptr()),
-                                     C.c_void_p(line.data_ptr()) if want_line else None, C.c_void_p(counts.data_ptr()), L))
+    tail = (cls, int(labels.line_ids), C.c_void_p(out.data_ptr()), C.c_void_p(line.data_ptr()) if want_line else None,
+            C.c_void_p(counts.data_ptr()), L)
+    if _is_table(mi):
+        if stations is None or stations.n_segments != index.n_segments:
+            raise ValueError('las_io.label_records: a PaintTable needs stations=, the ops.LineStations of the index\' segments')
+        table = _paint_rows('las_io.label_records', mi, stations.stations, L).struct()
+        check(lib().lm_las_label_records_local(*args[1:], labels.z_tol, C.byref(table), *tail, args[0]))
+    else:
+        check(lib().lm_las_label_records(*args, labels.z_tol, math.nan if mi is None else mi, *tail))
     return (out, counts, line) if want_line else (out, counts)
+
+
+def _label_stations(lines, labels, shift, device):
+    """The station table label_las needs beside its index when labels.min_intensity is a PaintTable (else None)."""
+    from . import ops
+    if not _is_table(labels.min_intensity):
+        return None
+    return ops.line_stations(*line_stations(lines, shift, labels.min_intensity.window), labels.min_intensity.window, device=device)
 
 
 def _label_las_chunked(path, out_path, lines, labels, shift, select, device, chunk_records):
@@ -215,12 +253,13 @@ def _label_las_chunked(path, out_path, lines, labels, shift, select, device, chu
             raise TypeError(f'las_io.label_las: select must be a PointFilter, not {type(select).__name__}')
         select.for_format(h['point_format'])
     index = ops.line_index(line_segments(lines, shift), labels.half_width, device=device)
+    stations = _label_stations(lines, labels, shift, device)
     total = np.zeros(len(lines) + 1, dtype=np.int64)
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
     with open(out_path, 'wb') as f:
         f.write(chunks.head_bytes)
         for rec, m, _ in chunks:
-            out, counts = label_records(rec, {**h, 'n_points': m}, index, labels, shift, select, n_lines=len(lines))
+            out, counts = label_records(rec, {**h, 'n_points': m}, index, labels, shift, select, n_lines=len(lines), stations=stations)
             both = torch.cat([out, counts.view(torch.uint8)]).cpu().numpy()    # the chunk's one read-back
             f.write(both[:m * rl].tobytes())
             total += both[len(rec):].view(np.int64)
@@ -256,7 +295,7 @@ def label_las(path, out_path, lines, labels, shift, select=None, device='cuda:0'
     index = ops.line_index(line_segments(lines, shift), labels.half_width, device=device)
     nbytes = n * rl
     rec = _upload_records(data, h, device)
-    out, counts = label_records(rec, h, index, labels, shift, select, n_lines=len(lines))
+    out, counts = label_records(rec, h, index, labels, shift, select, n_lines=len(lines), stations=_label_stations(lines, labels, shift, device))
     both = torch.cat([out, counts.view(torch.uint8)]).cpu().numpy()        # the one read-back
     counts = both[len(rec):].view(np.int64)
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
@@ -315,8 +354,12 @@ def profile_records(records_u8, header, index, stations, survey, shift=None, sel
     nb = stations.n_bins
     bins = ops._table_out(who, (nb, 6), out, dev)
     mi = _resolved(who, survey, 'min_intensity')
-    mi = math.nan if mi is None else mi
-    check(lib().lm_las_line_profile_records(*args, survey.z_tol, mi, int(out is not None), C.c_void_p(bins.data_ptr()) if nb else None, nb))
+    tail = (int(out is not None), C.c_void_p(bins.data_ptr()) if nb else None, nb)
+    if _is_table(mi):
+        table = _paint_rows(who, mi, stations.stations, stations.n_lines).struct()
+        check(lib().lm_las_line_profile_records_local(*args[1:], survey.z_tol, C.byref(table), *tail, args[0]))
+    else:
+        check(lib().lm_las_line_profile_records(*args, survey.z_tol, math.nan if mi is None else mi, *tail))
     return bins
 
 
@@ -614,9 +657,12 @@ def profile_colour_records(records_u8, header, index, stations, survey, colour, 
     bins = ops._table_out(who, (nb, 6), None if out is None else out[0], dev)
     colours = ops._table_out(who, (nb, 6), None if out is None else out[1], dev)
     mi = _resolved(who, survey, 'min_intensity')
-    mi = math.nan if mi is None else mi
-    check(lib().lm_las_line_colour_records(*args, survey.z_tol, mi, colour.blue_q, int(out is not None),
-                                           C.c_void_p(bins.data_ptr()) if nb else None, C.c_void_p(colours.data_ptr()) if nb else None, nb))
+    tail = (colour.blue_q, int(out is not None), C.c_void_p(bins.data_ptr()) if nb else None, C.c_void_p(colours.data_ptr()) if nb else None, nb)
+    if _is_table(mi):
+        table = _paint_rows(who, mi, stations.stations, stations.n_lines).struct()
+        check(lib().lm_las_line_colour_records_local(*args[1:], survey.z_tol, C.byref(table), *tail, args[0]))
+    else:
+        check(lib().lm_las_line_colour_records(*args, survey.z_tol, math.nan if mi is None else mi, *tail))
     return bins, colours
 
 
@@ -725,8 +771,12 @@ def cross_records(records_u8, header, index, stations, cross, shift=None, select
     nl = cross.nl
     cells = ops._table_out(who, (stations.n_bins, nl, 4), out, dev)
     n_cells = stations.n_bins * nl
-    check(lib().lm_las_line_cross_records(*args, cross.z_tol, cross.lateral_q, cross.paint_iq, int(out is not None),
-                                          C.c_void_p(cells.data_ptr()) if n_cells else None, n_cells))
+    tail = (int(out is not None), C.c_void_p(cells.data_ptr()) if n_cells else None, n_cells)
+    if _is_table(_resolved(who, cross, 'paint_intensity')):
+        table = _paint_rows(who, cross.paint_intensity, stations.stations, stations.n_lines, cross=True).struct(cross=True)
+        check(lib().lm_las_line_cross_records_local(*args[1:], cross.z_tol, cross.lateral_q, C.byref(table), *tail, args[0]))
+    else:
+        check(lib().lm_las_line_cross_records(*args, cross.z_tol, cross.lateral_q, cross.paint_iq, *tail))
     return cells
 
 
@@ -980,6 +1030,177 @@ def paint_threshold(hist, threshold):
     return {'strip': group(inner.sum(axis=0), outer.sum(axis=0)), 'lines': {k + 1: group(inner[k], outer[k]) for k in range(len(hist))}}
 
 
+SOURCES = ('window', 'line', 'strip')            # PaintTable.source: whose group a row's threshold was read off
+
+
+class PaintTable(_Table):
+    """A paint threshold per line or per station window along every line (immutable): what paint_table reads off the windowed
+    histograms, and what MarkingLabels.min_intensity, MarkingSurvey.min_intensity, CrossSection.paint_intensity and
+    PaintResidue.min_intensity take wherever they take a number or 'auto'.  The stages then look the value up for every return on the GPU
+    (the rule: include/lanemap_hip.h).
+
+      thr         float32 [R], every value finite: the threshold of every row
+      win_start   int32 [L + 1], a CSR table from 0, not descending, ending in R: line k (from 1) owns the rows win_start[k-1] ..
+                  win_start[k] - 1, its station windows in order - line_stations(lines, shift, bin=window)'s bin_start
+      window      metres (finite, > 0): the length of a window.  One row per line with a window longer than every line is
+                  PaintThreshold's scope='line': the same table, not a second code path
+      source      uint8 [R]: 0 the window's own group gave the threshold, 1 the line's, 2 the strip's (SOURCES)
+    The arrays are copied and read-only; two tables are equal when all four hold the same values."""
+    __slots__ = ('thr', 'win_start', 'window', 'source')
+
+    def __init__(self, thr, win_start, window, source=None):
+        thr = np.array(thr, dtype=np.float32, order='C', copy=True)
+        ws = np.array(win_start, order='C', copy=True)
+        if thr.ndim != 1 or not np.isfinite(thr).all():
+            raise ValueError(f'PaintTable: thr must be a [R] array of finite numbers, not {thr.shape}' + ('' if thr.ndim != 1 else ' with a '
+                             'value that is not finite'))
+        if ws.ndim != 1 or len(ws) < 1 or ws.dtype.kind not in 'iu' or ws[0] != 0 or (np.diff(ws.astype(np.int64)) < 0).any() \
+                or int(ws[-1]) != len(thr):
+            raise ValueError(f'PaintTable: win_start must be a [L + 1] table of whole numbers from 0, not descending, ending in R={len(thr)}, '
+                             f'not {ws.tolist() if ws.ndim == 1 and len(ws) < 8 else ws.shape}')
+        if not _number(window) or not (0.0 < float(window) < math.inf):
+            raise ValueError(f'PaintTable: window={window!r} must be a finite length > 0')
+        src = np.zeros(len(thr), np.uint8) if source is None else np.array(source, order='C', copy=True)
+        if src.shape != thr.shape or src.dtype.kind not in 'iu' or (src.astype(np.int64) > 2).any() or (src.astype(np.int64) < 0).any():
+            raise ValueError(f'PaintTable: source must be a [R={len(thr)}] array of 0 (window), 1 (line), 2 (strip), not {src.shape} {src.dtype}')
+        ws, src = ws.astype(np.int32), src.astype(np.uint8)
+        for a in (thr, ws, src):
+            a.setflags(write=False)
+        self._set(thr=thr, win_start=ws, window=float(window), source=src)
+
+    def _key(self):
+        return (self.thr.tobytes(), self.win_start.tobytes(), self.window, self.source.tobytes())
+
+    def __eq__(self, other):
+        return type(other) is type(self) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return f'PaintTable(thr={self.thr.tolist()!r}, win_start={self.win_start.tolist()!r}, window={self.window!r}, source={self.source.tolist()!r})'
+
+
+def save_paint_table(path, table):
+    """A PaintTable as one float64 array [4, max(R, L + 1)] in a .npy file: row 0 thr, row 1 source, row 2 win_start, row 3 the window
+    length, each padded with NaN (float64 holds every value exactly)."""
+    R, n = len(table.thr), len(table.win_start)
+    a = np.full((4, max(R, n)), np.nan)
+    a[0, :R], a[1, :R], a[2, :n], a[3, 0] = table.thr, table.source, table.win_start, table.window
+    np.save(path, a)
+
+
+def load_paint_table(path):
+    """-> the PaintTable save_paint_table wrote."""
+    a = np.load(path)
+    n = int(np.isfinite(a[2]).sum())
+    R = int(a[2, n - 1])
+    return PaintTable(a[0, :R].astype(np.float32), a[2, :n].astype(np.int32), float(a[3, 0]), a[1, :R].astype(np.uint8))
+
+
+def threshold_window(lines, shift, threshold):
+    """The window length a PaintThreshold's scope cuts the lines with, metres: threshold.window for 'window'; for 'line' (and 'strip') a
+    length beyond every line in the frame of `shift` - twice the longest, at least 1 m - so that every line owns one row."""
+    if threshold.scope == 'window':
+        return threshold.window
+    seg = line_segments(lines, shift)
+    if not len(seg):
+        return 1.0
+    of_line = np.ascontiguousarray(seg[:, 7]).view(np.int32)
+    d = seg[:, 3:5].astype(np.float64)
+    total = np.bincount(of_line, weights=np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]))
+    return max(1.0, 2.0 * float(total.max()))
+
+
+def hist_window_records(records_u8, header, index, stations, threshold, shift=None, select=None, out=None):
+    """One lm_las_line_hist_window_records call on the DEVICE records of a file, as hist_records: -> hist [R, Z, NB] int64 device tensor,
+    a histogram per station window of every line and lateral ring (the rule: include/lanemap_hip.h).  stations: the ops.LineStations cut
+    with bin = the window length - its bin_start is the table of the windows, R = stations.n_bins.  out: the table of an earlier call to
+    add to.  Asynchronous."""
+    from . import ops
+    who = 'las_io.hist_window_records'
+    if not isinstance(threshold, PaintThreshold):
+        raise TypeError(f'{who}: threshold must be a PaintThreshold, not {type(threshold).__name__}')
+    if not isinstance(index, ops.LineIndex) or not isinstance(stations, ops.LineStations):
+        raise TypeError(f'{who}: index must be an ops.LineIndex and stations an ops.LineStations')
+    if stations.n_segments != index.n_segments:
+        raise ValueError(f'{who}: stations hold {stations.n_segments} rows, the index {index.n_segments} segments')
+    args, dev = _records_args(who, records_u8, header, shift, select, index, None, 'the threshold asks', threshold.half_width)
+    st, ws, ws_host, L, window = stations.args()
+    R, Z, NB = stations.n_bins, threshold.rings, threshold.n_counts
+    hist = ops._table_out(who, (R, Z, NB), out, dev)
+    n_hist = R * Z * NB
+    check(lib().lm_las_line_hist_window_records(*args[1:], st, L, threshold.z_tol, threshold.ring_q, threshold.bin_shift, int(out is not None),
+                                                C.c_void_p(hist.data_ptr()) if n_hist else None, n_hist, ws, ws_host, window, args[0]))
+    return hist
+
+
+def hist_window_files(files, lines, threshold, window=None, device='cuda:0', chunk_records=None):
+    """hist_files with a histogram per station window: every file of `files`, a list of (path, shift, select), is read once and goes through
+    one lm_las_line_hist_window_records call per file (or chunk, chunk_records as for hist_files) into one table, which is read back once.
+    window: the window length in metres; None: threshold_window(lines, the first file's shift, threshold) - threshold.window for
+    scope='window', one window per line otherwise.  The windows each line owns are those of the first file's frame, as the bins of
+    survey_files.  -> (hist [R, Z, NB] int64 numpy, win_start [L + 1] int32 numpy, window); summed over the windows of a line it is
+    hist_files' table."""
+    if not isinstance(threshold, PaintThreshold):
+        raise TypeError(f'las_io.hist_window_files: threshold must be a PaintThreshold, not {type(threshold).__name__}')
+    lines, files = list(lines), list(files)
+    if window is None:
+        window = threshold_window(lines, files[0][1] if files else None, threshold)
+    hist, win_start = _each_file('las_io.hist_window_files', files, lines, window, threshold.half_width, device,
+                                 lambda rec, h, tables, shift, select, out: hist_window_records(rec, h, *tables, threshold, shift, select, out=out),
+                                 chunk_records=chunk_records)
+    if hist is None:                                                        # no file: the empty table of the lines
+        return np.zeros((int(win_start[-1]), threshold.rings, threshold.n_counts), dtype=np.int64), win_start, float(window)
+    return hist.cpu().numpy(), win_start, float(window)                      # the one read-back
+
+
+def line_hist_of_windows(hist_w, win_start):
+    """The per-line table [L, Z, NB] of a windowed one [R, Z, NB]: the sum of every line's windows - hist_files' table."""
+    hist_w, ws = np.asarray(hist_w), np.asarray(win_start, dtype=np.int64)
+    out = np.zeros((len(ws) - 1,) + hist_w.shape[1:], dtype=np.int64)
+    for k in range(len(ws) - 1):
+        out[k] = hist_w[ws[k]:ws[k + 1]].sum(axis=0)
+    return out
+
+
+def paint_table(hist_w, win_start, threshold, window=None):
+    """The paint table read off the windowed histograms (host, Python integers and float64): hist_w [R, Z, NB] int64 and win_start [L + 1]
+    (hist_window_files) -> (PaintTable, {'strip': group, 'lines': {k: group}, 'windows': {k: [group, ...]}}).  _threshold_group, unchanged,
+    on three kinds of group: every window; every line, the sum of its windows; the strip, the sum of all.  thr[row] is the window's
+    threshold where its group is supported, else its line's where that is supported, else the strip's - PaintTable.source says which (0,
+    1, 2).  A strip that is not supported is a ValueError, as it is where 'auto' asks for the strip's one number.  No smoothing between
+    neighbouring windows.  window: the window length the table was cut with; None: threshold.window."""
+    if not isinstance(threshold, PaintThreshold):
+        raise TypeError(f'paint_table: threshold must be a las_io.PaintThreshold, not {type(threshold).__name__}')
+    hist_w, ws = np.asarray(hist_w), np.asarray(win_start)
+    Z, NB = threshold.rings, threshold.n_counts
+    if hist_w.ndim != 3 or hist_w.dtype != np.int64 or hist_w.shape[1:] != (Z, NB) or (hist_w < 0).any():
+        raise ValueError(f'paint_table: hist_w must be an [R, {Z}, {NB}] int64 table of counts, not {hist_w.dtype} {hist_w.shape}')
+    if ws.ndim != 1 or len(ws) < 1 or ws[0] != 0 or (np.diff(ws.astype(np.int64)) < 0).any() or int(ws[-1]) != len(hist_w):
+        raise ValueError(f'paint_table: win_start must be a CSR table from 0 ending in R={len(hist_w)}, not {ws.tolist() if len(ws) < 8 else ws.shape}')
+    inner = hist_w[:, threshold.inner_rings, :].sum(axis=1)                 # [R, NB]
+    outer = hist_w[:, threshold.outer_rings, :].sum(axis=1)
+    group = lambda A, O: _threshold_group([int(v) for v in A], [int(v) for v in O], threshold)
+    strip = group(inner.sum(axis=0), outer.sum(axis=0))
+    lines, windows = {}, {}
+    for k in range(len(ws) - 1):
+        a, b = int(ws[k]), int(ws[k + 1])
+        lines[k + 1] = group(inner[a:b].sum(axis=0), outer[a:b].sum(axis=0))
+        windows[k + 1] = [group(inner[r], outer[r]) for r in range(a, b)]
+    found = {'strip': strip, 'lines': lines, 'windows': windows}
+    if not strip['supported'] and len(hist_w):
+        raise ValueError(f"paint_table: the strip's returns support no threshold between asphalt and paint: separation "
+                         f"{strip['separation']:.4f} with {strip['inner_returns']} returns on the lines and {strip['outer_returns']} beside them")
+    thr, source = np.zeros(len(hist_w), np.float32), np.zeros(len(hist_w), np.uint8)
+    for k in range(len(ws) - 1):
+        for j, g in enumerate(windows[k + 1]):
+            src = 0 if g['supported'] else 1 if lines[k + 1]['supported'] else 2
+            thr[int(ws[k]) + j] = (g, lines[k + 1], strip)[src]['threshold']
+            source[int(ws[k]) + j] = src
+    return PaintTable(thr, ws, threshold.window if window is None else window, source), found
+
+
 def residue_index_cell(residue):
     """The cell of the line index residue_files builds, metres.  The index' default, max(1 m, 2 half_width), is sized for the narrow band
     of the labelling; with half_width = reach it lists every segment within reach + a cell's diagonal of the cell, so a large cell
@@ -1026,7 +1247,11 @@ def residue_files(files, lines, residue, device='cuda:0', chunk_records=None):
         clouds = [read_las_raw(path, device, frame, select)[0] for path, _, select in files]
     else:                                   # ops.paint_residue takes its clouds one at a time and keeps the residue keys only
         clouds = (pts for path, _, select in files for pts in decode_chunks(LasChunks(path, chunk_records, device), frame, select))
-    out = ops.paint_residue(clouds, index, residue.z_tol, residue.min_intensity, residue.clear, residue.cell, residue.connectivity).numpy()
+    mi = residue.min_intensity
+    if _is_table(mi):                       # the rows are looked up with the station table of the index' own segments, in its frame
+        st = ops.line_stations(*line_stations(lines, frame, mi.window), mi.window, device=device)
+        mi = _paint_rows('las_io.residue_files', mi, st.stations, len(lines))
+    out = ops.paint_residue(clouds, index, residue.z_tol, mi, residue.clear, residue.cell, residue.connectivity).numpy()
     out.grid['shift'] = [0.0, 0.0, 0.0] if frame is None else frame
     return out
 

@@ -43,6 +43,16 @@ def _resolved(who, options, name):
     return v
 
 
+def _is_table(v):
+    """A las_io.PaintTable: a threshold per line or station window, which min_intensity / paint_intensity take wherever they take 'auto'."""
+    return isinstance(v, _Table)
+
+
+def paint_iq_of(p):
+    """The integer the cross-section entries compare iq with: ceil(p), clamped into 0 .. 65536 (65536: nothing is paint)."""
+    return 65536 if p > 65535.0 else 0 if p <= 0.0 else int(math.ceil(p))
+
+
 def _check_chunk_records(who, chunk_records):
     if not _whole(chunk_records) or int(chunk_records) <= 0 or int(chunk_records) % CHUNK_MULTIPLE:
         raise ValueError(f'{who}: chunk_records={chunk_records!r} must be a positive multiple of {CHUNK_MULTIPLE}')
@@ -53,14 +63,20 @@ class _Options:
     """What the option classes of this module share: a value that cannot be changed, compared, hashed and printed by the __slots__ of its
     class, in their order.  A class validates its arguments in __init__ and stores them with _set."""
     __slots__ = ()
+    _later = {}                         # arguments a class took on after its __slots__ were what callers compare with: {name: default};
+    #                                     they are kept in the slots of a base class, compared and hashed like the others, and printed
+    #                                     where they differ from the default - so a value without them prints as it always did
 
     def _set(self, **values):
         for k, v in values.items():
             object.__setattr__(self, k, v)
 
+    def _fields(self):
+        return tuple(self.__slots__) + tuple(self._later)
+
     def _replace(self, **changes):
         """A copy with some arguments changed, validated again (for the classes whose __slots__ are their constructor's arguments)."""
-        return type(self)(**{**{k: getattr(self, k) for k in self.__slots__}, **changes})
+        return type(self)(**{**{k: getattr(self, k) for k in self._fields()}, **changes})
 
     def __setattr__(self, name, value):
         raise AttributeError(f'{type(self).__name__} is immutable')
@@ -69,13 +85,24 @@ class _Options:
         raise AttributeError(f'{type(self).__name__} is immutable')
 
     def __repr__(self):
-        return type(self).__name__ + '(' + ', '.join(f'{k}={getattr(self, k)!r}' for k in self.__slots__) + ')'
+        shown = tuple(self.__slots__) + tuple(k for k, d in self._later.items() if getattr(self, k) != d)
+        return type(self).__name__ + '(' + ', '.join(f'{k}={getattr(self, k)!r}' for k in shown) + ')'
 
     def __eq__(self, other):
-        return type(other) is type(self) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
+        return type(other) is type(self) and all(getattr(self, k) == getattr(other, k) for k in self._fields())
 
     def __hash__(self):
-        return hash(tuple(getattr(self, k) for k in self.__slots__))
+        return hash(tuple(getattr(self, k) for k in self._fields()))
+
+
+def _later_slots(*names):
+    """-> a base class that holds the `_later` arguments of an options class in slots of its own, so that the class keeps its __slots__."""
+    return type('_LaterSlots', (_Options,), {'__slots__': names})
+
+
+class _Table(_Options):
+    """The base of las_io.PaintTable, here so that the stage options can tell one without importing las_io."""
+    __slots__ = ()
 
 
 class PointFilter(_Options):
@@ -264,8 +291,8 @@ class MarkingLabels(_Options):
 
       half_width      metres (finite, >= 0): half the width of the band around a line in which a return counts as its paint
       z_tol           metres (>= 0, may be infinite): the height band; it only keeps a carriageway from labelling the one under or over it
-      min_intensity   None, the smallest raw intensity a labelled return has (paint is bright), or 'auto': the threshold the map routes
-                      find in the strip's own returns (PaintThreshold)
+      min_intensity   None, the smallest raw intensity a labelled return has (paint is bright), 'auto': the threshold the map routes
+                      find in the strip's own returns (PaintThreshold), or a las_io.PaintTable: a threshold per line or station window
       marking_class   the classification a labelled record gets, 0..255; None: 64 on point formats 6-10 (the first user-definable class of
                       LAS 1.4), 31 on formats 0-5 (the largest class their five bits hold)
       line_ids        True: the point source ID of a labelled record becomes its line number (at most 65535 lines)
@@ -277,9 +304,9 @@ class MarkingLabels(_Options):
             raise ValueError(f'MarkingLabels: half_width={half_width!r} must be a finite number >= 0')
         if not _number(z_tol) or not float(z_tol) >= 0.0:
             raise ValueError(f'MarkingLabels: z_tol={z_tol!r} must be a number >= 0')
-        if min_intensity is not None and not _is_auto(min_intensity):
+        if min_intensity is not None and not _is_auto(min_intensity) and not _is_table(min_intensity):
             if not _number(min_intensity) or math.isnan(float(min_intensity)):
-                raise ValueError(f"MarkingLabels: min_intensity={min_intensity!r} must be None, a number or 'auto'")
+                raise ValueError(f"MarkingLabels: min_intensity={min_intensity!r} must be None, a number, 'auto' or a PaintTable")
             min_intensity = float(min_intensity)
         if marking_class is not None:
             if not _whole(marking_class) or not 0 <= int(marking_class) <= 255:
@@ -327,9 +354,9 @@ class MarkingSurvey(_Options):
             raise ValueError(f'MarkingSurvey: half_width={half_width!r} must be a number in 0 .. 16 (metres)')
         if not _number(z_tol) or not float(z_tol) >= 0.0:
             raise ValueError(f'MarkingSurvey: z_tol={z_tol!r} must be a number >= 0')
-        if min_intensity is not None and not _is_auto(min_intensity):
+        if min_intensity is not None and not _is_auto(min_intensity) and not _is_table(min_intensity):
             if not _number(min_intensity) or math.isnan(float(min_intensity)):
-                raise ValueError(f"MarkingSurvey: min_intensity={min_intensity!r} must be None, a number or 'auto'")
+                raise ValueError(f"MarkingSurvey: min_intensity={min_intensity!r} must be None, a number, 'auto' or a PaintTable")
             min_intensity = float(min_intensity)
         if not _whole(min_points) or int(min_points) < 1:
             raise ValueError(f'MarkingSurvey: min_points={min_points!r} must be a whole number >= 1')
@@ -400,8 +427,9 @@ class CrossSection(_Options):
 
     def __init__(self, paint_intensity, bin=0.5, half_width=0.625, lateral=0.03125, z_tol=0.5, min_points=3, paint_share=0.5, max_hole=1,
                  min_stripe=0.05, smooth=2.0, min_stations=2, max_shift=0.3):
-        if not _is_auto(paint_intensity) and (not _number(paint_intensity) or math.isnan(float(paint_intensity))):
-            raise ValueError(f"CrossSection: paint_intensity={paint_intensity!r} must be a number or 'auto'")
+        given = _is_auto(paint_intensity) or _is_table(paint_intensity)
+        if not given and (not _number(paint_intensity) or math.isnan(float(paint_intensity))):
+            raise ValueError(f"CrossSection: paint_intensity={paint_intensity!r} must be a number, 'auto' or a PaintTable")
         if not _number(bin) or not (0.0 < float(bin) < math.inf):
             raise ValueError(f'CrossSection: bin={bin!r} must be a finite length > 0')
         if not _number(half_width) or not (0.0 <= float(half_width) <= 16.0):
@@ -424,7 +452,7 @@ class CrossSection(_Options):
             raise ValueError(f'CrossSection: min_stations={min_stations!r} must be a whole number >= 1')
         if not _number(max_shift) or not (0.0 <= float(max_shift) < math.inf):
             raise ValueError(f'CrossSection: max_shift={max_shift!r} must be a finite length >= 0')
-        self._set(paint_intensity=AUTO if _is_auto(paint_intensity) else float(paint_intensity), bin=float(bin), half_width=float(half_width),
+        self._set(paint_intensity=paint_intensity if given else float(paint_intensity), bin=float(bin), half_width=float(half_width),
                   lateral=float(lateral),
                   z_tol=float(z_tol), min_points=int(min_points), paint_share=float(paint_share), max_hole=int(max_hole),
                   min_stripe=float(min_stripe), smooth=float(smooth), min_stations=int(min_stations), max_shift=float(max_shift))
@@ -436,9 +464,9 @@ class CrossSection(_Options):
 
     @property
     def paint_iq(self):
-        """The integer the device entries take: ceil(paint_intensity), clamped into 0 .. 65536."""
+        """The integer the device entries take: ceil(paint_intensity), clamped into 0 .. 65536; of a PaintTable, that of every row."""
         p = _resolved('CrossSection.paint_iq', self, 'paint_intensity')
-        return 65536 if p > 65535.0 else 0 if p <= 0.0 else int(math.ceil(p))
+        return np.array([paint_iq_of(float(v)) for v in p.thr], dtype=np.int32) if _is_table(p) else paint_iq_of(p)
 
     @property
     def hq(self):
@@ -476,9 +504,10 @@ class PaintResidue(_Options):
 
     def __init__(self, min_intensity, clear=0.3, reach=6.0, z_tol=0.5, cell=0.1, connectivity=8, min_cells=20, min_points=20, elongated=2.0,
                  angle_tol_deg=30.0):
-        if not _is_auto(min_intensity) and (not _number(min_intensity) or not math.isfinite(float(min_intensity))):
-            raise ValueError(f"PaintResidue: min_intensity={min_intensity!r} must be a finite number or 'auto' (without one the whole road is "
-                             f"one blob)")
+        given = _is_auto(min_intensity) or _is_table(min_intensity)
+        if not given and (not _number(min_intensity) or not math.isfinite(float(min_intensity))):
+            raise ValueError(f"PaintResidue: min_intensity={min_intensity!r} must be a finite number, 'auto' or a PaintTable (without one the "
+                             f"whole road is one blob)")
         if not _number(reach) or not (0.0 < float(reach) <= 16.0):
             raise ValueError(f'PaintResidue: reach={reach!r} must be a number with 0 < reach <= 16 (metres)')
         if not _number(clear) or not (0.0 <= float(clear) < float(reach)):
@@ -496,12 +525,15 @@ class PaintResidue(_Options):
             raise ValueError(f'PaintResidue: elongated={elongated!r} must be a finite ratio >= 1')
         if not _number(angle_tol_deg) or not (0.0 <= float(angle_tol_deg) <= 45.0):
             raise ValueError(f'PaintResidue: angle_tol_deg={angle_tol_deg!r} must be a number in 0 .. 45 (degrees)')
-        self._set(min_intensity=AUTO if _is_auto(min_intensity) else float(min_intensity), clear=float(clear), reach=float(reach), z_tol=float(z_tol), cell=float(cell),
+        self._set(min_intensity=min_intensity if given else float(min_intensity), clear=float(clear), reach=float(reach), z_tol=float(z_tol), cell=float(cell),
                   connectivity=int(connectivity), min_cells=int(min_cells), min_points=int(min_points), elongated=float(elongated),
                   angle_tol_deg=float(angle_tol_deg))
 
 
-class PaintThreshold(_Options):
+THRESHOLD_SCOPES = ('strip', 'line', 'window')
+
+
+class PaintThreshold(_later_slots('scope', 'window')):
     """How the LAS -> map routes find the intensity threshold between asphalt and paint in the strip's own returns (immutable;
     Runner.infer_las_strip_to_map / infer_las_to_map, `threshold=`; hist_files, paint_threshold) - the number MarkingLabels, MarkingSurvey
     and PaintResidue take as min_intensity and CrossSection as paint_intensity, which they ask for with 'auto'.  Every finite return the
@@ -521,11 +553,24 @@ class PaintThreshold(_Options):
       min_separation  ... and a separation D (paint_threshold) of at least this, 0 .. 1
       tolerance_shift whole number 1 .. 30: the threshold is the middle of the plateau on which J stays within M >> tolerance_shift of its
                       maximum M
-    Apart from the derived KS_COEFF = 1.95 of the support test, the defaults are plain defaults, not tuned values."""
+      scope           'strip': one threshold for the strip, which replaces every 'auto' (the default, and all there was before `scope`);
+                      'line': one per line; 'window': one per station window of `window` metres along every line.  With 'line' and 'window'
+                      the histograms are taken per window (hist_window_files), paint_table reads a las_io.PaintTable off them - a window
+                      without support takes its line's threshold, a line without support the strip's - and every 'auto' becomes that table,
+                      looked up for each return on the GPU.  A scanner's intensity falls with range, so the paint of an outer lane is
+                      routinely darker than the asphalt under the scanner: no single number serves such a strip
+      window          metres (finite, > 0): the length of a station window; only read with scope='window'
+    Apart from the derived KS_COEFF = 1.95 of the support test, the defaults - scope and window = 50 m among them - are plain defaults, not
+    tuned values."""
     __slots__ = ('half_width', 'ring', 'inner', 'outer', 'z_tol', 'bin_shift', 'min_returns', 'min_separation', 'tolerance_shift')
+    _later = {'scope': 'strip', 'window': 50.0}
 
     def __init__(self, half_width=0.625, ring=0.0625, inner=0.125, outer=0.375, z_tol=0.5, bin_shift=6, min_returns=1000,
-                 min_separation=0.05, tolerance_shift=5):
+                 min_separation=0.05, tolerance_shift=5, scope='strip', window=50.0):
+        if not (isinstance(scope, str) and scope in THRESHOLD_SCOPES):
+            raise ValueError(f"PaintThreshold: scope={scope!r} must be 'strip', 'line' or 'window'")
+        if not _number(window) or not (0.0 < float(window) < math.inf):
+            raise ValueError(f'PaintThreshold: window={window!r} must be a finite length > 0')
         if not _number(half_width) or not (0.0 <= float(half_width) <= 16.0):
             raise ValueError(f'PaintThreshold: half_width={half_width!r} must be a number in 0 .. 16 (metres)')
         if not _number(ring) or not (0.0 < float(ring) < math.inf):
@@ -549,7 +594,7 @@ class PaintThreshold(_Options):
             raise ValueError(f'PaintThreshold: tolerance_shift={tolerance_shift!r} must be a whole number in 1 .. 30')
         self._set(half_width=float(half_width), ring=float(ring), inner=float(inner), outer=float(outer), z_tol=float(z_tol),
                   bin_shift=int(bin_shift), min_returns=int(min_returns), min_separation=float(min_separation),
-                  tolerance_shift=int(tolerance_shift))
+                  tolerance_shift=int(tolerance_shift), scope=scope, window=float(window))
         if not self.inner_rings:
             raise ValueError(f'PaintThreshold: no ring of {self.ring_q}/1024 m lies within inner={inner!r}: the inner set is empty')
         if not self.outer_rings:

@@ -11,7 +11,7 @@ import math
 
 import torch
 
-from ._lib import lib, check, LmRasterParams, LmStripGrid, LmLineGrid, LanemapHipError
+from ._lib import lib, check, LmRasterParams, LmStripGrid, LmLineGrid, LmPaintTable, LanemapHipError
 
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
 
@@ -856,6 +856,51 @@ def line_stations(stations, bin_start, bin, device='cuda:0'):
     return LineStations(torch.from_numpy(st.copy()).to(device), torch.from_numpy(bs).to(device), bs, bin)
 
 
+class PaintRows:
+    """A paint table (las_io.PaintTable: a threshold per station window of every line) on the device, beside the station table of the
+    segments it is looked up with: what the _local entries take in place of a min_intensity (the rule: include/lanemap_hip.h).  thr [R]
+    f32, paint_iq [R] int32 (the cross-sections' integer of every row) and win_start [L + 1] int32 are device tensors, win_start_host
+    the same table as a numpy array, stations the [S,4] f32 device tensor of an ops.LineStations of the same segments, window the window
+    length in metres; thr_min = min(thr), the pre-filter that lets a wave of asphalt leave before the search (0 without rows)."""
+
+    def __init__(self, thr, paint_iq, win_start, win_start_host, stations, window, thr_min):
+        self.thr, self.paint_iq, self.win_start, self.win_start_host, self.stations = thr, paint_iq, win_start, win_start_host, stations
+        self.window, self.thr_min = float(window), float(thr_min)
+        self.n_lines, self.n_rows, self.n_segments = int(win_start_host.shape[0]) - 1, int(win_start_host[-1]), int(stations.shape[0])
+
+    def struct(self, cross=False):
+        """-> the LmPaintTable of one call: the cross-section entry reads paint_iq and no thr, the others thr and no paint_iq."""
+        t = LmPaintTable()
+        p = lambda x, on: x.data_ptr() if on and x.numel() else None
+        t.thr, t.paint_iq = p(self.thr, not cross), p(self.paint_iq, cross)
+        t.win_start, t.win_start_host = self.win_start.data_ptr(), self.win_start_host.ctypes.data
+        t.stations, t.window, t.thr_min, t.n_rows = p(self.stations, True), self.window, self.thr_min, self.n_rows
+        t.rows = self                                                       # (the struct holds addresses: the tensors live as long as it)
+        return t
+
+
+def paint_rows(thr, win_start, window, stations, paint_iq=None):
+    """(thr [R] float32, win_start [L + 1] int32) numpy, as a las_io.PaintTable holds them, the window length and the [S,4] f32 device
+    tensor of the station table (ops.LineStations.stations) -> a PaintRows on that tensor's device.  paint_iq: [R] int32 numpy, the
+    cross-sections' integer per row; None: not uploaded (zeros)."""
+    import numpy as np
+    thr = np.ascontiguousarray(thr, dtype=np.float32)
+    ws = np.array(win_start, dtype=np.int32, order='C', copy=True)
+    if thr.ndim != 1 or ws.ndim != 1 or ws.shape[0] < 1 or int(ws[-1]) != thr.shape[0] or not np.isfinite(thr).all():
+        raise ValueError(f'paint_rows: thr must be [R] finite float32 and win_start [L + 1] int32 ending in R, not {thr.shape} and {ws.shape}')
+    if not (math.isfinite(float(window)) and float(window) > 0.0):
+        raise ValueError(f'paint_rows: window={window!r} must be a finite length > 0')
+    if not stations.is_cuda:
+        raise LanemapHipError('lanemapping_amd ops need tensors on an MI355X (HIP) device; no CPU fallback exists')
+    assert stations.dim() == 2 and stations.shape[1] == 4 and stations.is_contiguous() and stations.dtype == torch.float32
+    dev = stations.device
+    iq = np.zeros(thr.shape, np.int32) if paint_iq is None else np.ascontiguousarray(paint_iq, dtype=np.int32)
+    if iq.shape != thr.shape or (iq < 0).any() or (iq > 65536).any():
+        raise ValueError(f'paint_rows: paint_iq must be [R] int32 in 0 .. 65536, not {iq.shape}')
+    return PaintRows(torch.from_numpy(thr.copy()).to(dev), torch.from_numpy(iq.copy()).to(dev), torch.from_numpy(ws).to(dev), ws, stations,
+                     window, float(thr.min()) if thr.size else 0.0)
+
+
 def line_profile(points, index, stations, z_tol, min_intensity=None, out=None):
     """points [N,4] f32 on device -> bins [n_bins, 6] int64 on device: per station bin of every line the columns n, sum iq, sum q,
     sum q^2, min q, max q over the points the labelling rule gives that line (the rule: include/lanemap_hip.h; q the lateral offset in
@@ -952,7 +997,8 @@ def residue_grid(index, cell=0.1):
 def residue_keys(points, index, z_tol, min_intensity, clear, grid, want_iq=True):
     """points [N,4] f32 on device -> (key [N] int64, iq [N] int32 or None): the residue cell of every point on `grid` (residue_grid), -1
     where the point is no residue - not within the index' half_width (the reach) and z_tol of a line, below min_intensity, or within
-    `clear` of its nearest line (the rule: include/lanemap_hip.h).  No synchronisation."""
+    `clear` of its nearest line (the rule: include/lanemap_hip.h).  min_intensity: a number, or a PaintRows (paint_rows) of the same
+    segments: the threshold of the return's own line and station window (lm_residue_keys_local).  No synchronisation."""
     if not points.is_cuda:
         raise LanemapHipError('lanemapping_amd ops need tensors on an MI355X (HIP) device; no CPU fallback exists')
     assert points.dim() == 2 and points.shape[1] == 4 and points.is_contiguous() and points.dtype == torch.float32
@@ -961,9 +1007,16 @@ def residue_keys(points, index, z_tol, min_intensity, clear, grid, want_iq=True)
     N = int(points.shape[0])
     key = torch.empty((N,), device=points.device, dtype=torch.int64)
     iq = torch.empty((N,), device=points.device, dtype=torch.int32) if want_iq else None
-    check(lib().lm_residue_keys(_stream(), _ptr(points) if N else None, N, *index.args(), float(z_tol), float(min_intensity), float(clear),
-                                float(grid['cell']), int(grid['nx']), int(grid['ny']), _ptr(key) if N else None,
-                                _ptr(iq) if (want_iq and N) else None))
+    tail = (float(clear), float(grid['cell']), int(grid['nx']), int(grid['ny']), _ptr(key) if N else None, _ptr(iq) if (want_iq and N) else None)
+    if isinstance(min_intensity, PaintRows):
+        if min_intensity.n_segments != index.n_segments:
+            raise ValueError(f'residue_keys: the paint table looks rows up in {min_intensity.n_segments} station rows, the index holds '
+                             f'{index.n_segments} segments')
+        table = min_intensity.struct()
+        check(lib().lm_residue_keys_local(_ptr(points) if N else None, N, *index.args(), float(z_tol), C.byref(table), min_intensity.n_lines,
+                                          *tail, _stream()))
+    else:
+        check(lib().lm_residue_keys(_stream(), _ptr(points) if N else None, N, *index.args(), float(z_tol), float(min_intensity), *tail))
     return key, iq
 
 

@@ -343,22 +343,46 @@ class Runner:
         {'strip': group, 'lines': {line number: group}}.  -> `stages` with every 'auto' replaced by the strip's threshold, on copies of the
         option objects.  A stage that asked for 'auto' of a strip whose group is not supported is a ValueError, raised after the files are
         written and before any stage runs.  Without lines both files are empty, and 'auto' becomes 0.0: every stage then writes its empty
-        outputs whatever the number."""
+        outputs whatever the number.
+        threshold.scope 'line' or 'window': ONE windowed pass (las_io.hist_window_files: lm_las_line_hist_window_records, a histogram per
+        station window of every line; one window per line for 'line') takes the place of the per-line pass.  The per-line table is the sum
+        of its windows, so paint_hist.npy and the 'strip' and 'lines' of the JSON are computed from it and are what the strip scope writes.
+        In addition: paint_hist_windows.npy ([R, Z, NB] int64), paint_table.npy (thr, source and win_start in one array:
+        las_io.save_paint_table) and a 'windows' key in the JSON, {line number: [[start_m, end_m, threshold, source, supported,
+        separation], ...]}, source one of 'window', 'line', 'strip'.  Every 'auto' then becomes the las_io.PaintTable (las_io.paint_table:
+        a window without support takes its line's threshold, a line without support the strip's), which the stages look up per return
+        on the GPU."""
         from . import las_io
         lines = self._result_lines(result)
-        hist = las_io.hist_files(self._each_once(files), lines, threshold, device=self.device, **self._chunked(chunk_records))
-        found = las_io.paint_threshold(hist, threshold)
         par_dir = self._params_dir(out_dir)
-        np.save(os.path.join(par_dir, 'paint_hist.npy'), hist)
-        with open(os.path.join(par_dir, 'paint_threshold.json'), 'w') as f:
-            json.dump({'strip': found['strip'], 'lines': {str(k): g for k, g in found['lines'].items()}}, f, indent=1)
         asked = [k for k, name in self._AUTO if stages[k] is not None and getattr(stages[k], name) == las_io.AUTO]
+        local = threshold.scope != 'strip'
+        if local:
+            hist_w, win_start, window = las_io.hist_window_files(self._each_once(files), lines, threshold, device=self.device,
+                                                                 **self._chunked(chunk_records))
+            hist = las_io.line_hist_of_windows(hist_w, win_start)
+        else:
+            hist = las_io.hist_files(self._each_once(files), lines, threshold, device=self.device, **self._chunked(chunk_records))
+        found = las_io.paint_threshold(hist, threshold)
+        np.save(os.path.join(par_dir, 'paint_hist.npy'), hist)
+        report = {'strip': found['strip'], 'lines': {str(k): g for k, g in found['lines'].items()}}
+        table = None
+        if local:
+            np.save(os.path.join(par_dir, 'paint_hist_windows.npy'), hist_w)
+            if found['strip']['supported'] or not lines:
+                table, groups = las_io.paint_table(hist_w, win_start, threshold, window)
+                las_io.save_paint_table(os.path.join(par_dir, 'paint_table.npy'), table)
+                report['windows'] = {str(k): [[j * window, (j + 1) * window, float(table.thr[win_start[k - 1] + j]),
+                                               las_io.SOURCES[int(table.source[win_start[k - 1] + j])], g['supported'], g['separation']]
+                                              for j, g in enumerate(gs)] for k, gs in groups['windows'].items()}
+        with open(os.path.join(par_dir, 'paint_threshold.json'), 'w') as f:
+            json.dump(report, f, indent=1)
         g = found['strip']
         if asked and lines and not g['supported']:
             raise ValueError(f"{', '.join(asked)}: 'auto' needs a threshold between asphalt and paint, and the strip's returns do not support "
                              f"one: separation {g['separation']:.4f} with {g['inner_returns']} returns on the lines and "
                              f"{g['outer_returns']} beside them (las_io.paint_threshold; {os.path.join(par_dir, 'paint_threshold.json')})")
-        value = g['threshold'] if lines else 0.0
+        value = table if local else g['threshold'] if lines else 0.0
         return {k: stages[k]._replace(**{dict(self._AUTO)[k]: value}) if k in asked else stages[k] for k in stages}
 
     def _after_map(self, threshold, stages, colour, files, result, out_dir, chunk_records=None):
