@@ -9,7 +9,7 @@
  *   - borrows its inputs (const), never frees or allocates caller-visible memory.
  * Streams and graphs: an entry enqueues on `stream` and on no other stream.  Every entry may be captured into a HIP graph (after one
  * eager call of the same shape) except lm_strip_bin_points, lm_strip_plan_create, lm_tile_ground, lm_ground_select,
- * lm_tile_intensity_window and lm_drape_vertices, which copy host memory of the call to the device or synchronise the stream: on a capturing stream they return
+ * lm_tile_intensity_window, lm_tile_intensity_cells, lm_tile_intensity_apply and lm_drape_vertices, which copy host memory of the call to the device or synchronise the stream: on a capturing stream they return
  * LM_ERR_ARG with their name and the reason before touching it, and the capture stays valid.  Measured: tests/test_gpu_streams.py
  * (single-stream captures, three replays each; captures with parallel branches were not measured).
  * Activations are fp32, NHWC ("pixel-major rows", channel stride 1); `ld*` = floats between consecutive pixels.
@@ -361,6 +361,60 @@ long lm_tile_intensity_workspace_bytes(int B, int G);
 int lm_tile_intensity_window(void* hip_stream, const float* points_xyzi, const long* tile_offsets, const LmRasterParams* params, int B,
                              int H, int W, const int* group, int G, int q_lo_ppm, int q_hi_ppm, void* workspace, long workspace_bytes,
                              int* window, long* count, unsigned* coarse_hist);
+
+/* ---- intensity balance per ground cell (csrc/intensity.hip).  A mobile scanner's intensity falls with range: under any single window
+ * the outer lanes of a strip rasterise as dark paint on black and the near lane as grey asphalt brighter than that paint.  So before
+ * the window is fitted, the binned points are balanced: a local asphalt level per cell, a gain per cell towards one reference level,
+ * and every point's intensity multiplied by the gain interpolated between the cell centres.  THE RULE (one definition: this text;
+ * tests/balance_ref.py restates it in numpy):
+ * WHICH POINTS COUNT.  (points, tile_offsets, params, B, H, W) as for lm_tile_ground, at most 2^31 - 1 points between tile_offsets[0]
+ *     and tile_offsets[B].  A point counts for tile b when the window test of csrc/raster_xf.h, lm_point_window, keeps it for b and its intensity p[3] is
+ *     not NaN.  Its key is lm_tile_intensity_window's: k = (int)floorf(fminf(fmaxf(i, 0), 65535)).  Its cell is (row / cell_px,
+ *     col / cell_px) on lm_tile_ground's grid Gy = ceil(H / cell_px) by Gx = ceil(W / cell_px); 16 <= cell_px <= 128, at most 32768
+ *     cells per tile.
+ * LEVEL, COUNT, MODEL (lm_tile_intensity_cells; all DEVICE [B][Gy][Gx] int32).
+ *     count[b][cy][cx] = n, the counted points of the cell.
+ *     level[b][cy][cx] = the key of 0-based rank (n - 1) * q_ppm / 1000000 (64-bit integer floor division) among the cell's n keys in
+ *         ascending order; q_ppm = 500000 is the lower median - the asphalt level, paint being the minority of a road cell.  -1 for
+ *         n = 0.
+ *     A cell is KNOWN when n >= min_points.
+ *     model[b][cy][cx] = the LOWER MEDIAN (element (k - 1) / 2 of the k values in ascending order) of `level` over the known cells of
+ *         the 3 x 3 neighbourhood clipped at the grid edge, the cell itself included; -1 when none is known.  lm_tile_ground's
+ *         smoothing on integers: a cell that is mostly paint (a crossing, hatching) does not dim itself.
+ *     Exact in two levels of 256 x 256 keys: rows of 256 u32 counters per cell in the workspace, added to with integer global atomics
+ *     (the lanes of a wave that hit one counter are merged first); a wave per cell finds the bin of the rank with a prefix sum over
+ *     its lanes.  Integer adds only: the same bits on every run, whatever the order of the points.
+ *     workspace: device, 16-byte aligned, lm_tile_intensity_cells_workspace_bytes(B, H, W, cell_px) bytes - 1 KiB per cell, so callers
+ *     with many tiles call in groups of tiles (0 = unsupported arguments).
+ * GAINS are host policy (las_io.balance_gains): for a known model and a reference level r > 0, clip((f32)r / (f32)max(model, 1),
+ *     1 / max_gain, max_gain), else 1; float32.
+ * APPLY (lm_tile_intensity_apply).  gains DEVICE [B][Gy][Gx] f32; out DEVICE [tile_offsets[B]][4] f32 (rows from tile_offsets[0] on are
+ *     written), 16-byte aligned; it may be points_xyzi itself.  For a point that counts, at pixel (row, col):
+ *         u  = (f32)(2 col + 1 - cell_px) / (f32)(2 cell_px), clamped to [0, Gx - 1]       the position between the cell centres
+ *         x0 = floor(u), fx = u - x0, x1 = min(x0 + 1, Gx - 1); v, y0, fy, y1 the same from row and Gy
+ *         g  = (g[y0][x0] (1 - fx) + g[y0][x1] fx) (1 - fy) + (g[y1][x0] (1 - fx) + g[y1][x1] fx) fy
+ *         i' = fminf(i g, 65535)
+ *     every operation rounded on its own (__fmul_rn, __fadd_rn, __fsub_rn, __fdiv_rn: no contraction decides a bit).  x, y and z are
+ *     stored back as they are; a point that does not count is stored back unchanged in every bit.  Bilinear between the cell centres,
+ *     so no cell seam appears in the image - a step at a seam would look like a line to the network.  One streaming pass, 16 bytes
+ *     read and 16 written per point.  workspace: device, 16-byte aligned, lm_tile_intensity_apply_workspace_bytes(B) bytes.
+ * Both entries copy the tile table from host memory of the call: asynchronous, no synchronisation, and a capturing stream is refused
+ * by name.  B = 0 is LM_OK and touches nothing.  Refused with LM_ERR_ARG and a message that names the argument, before anything is
+ * launched or written: B outside 1 .. 4096; cell_px outside 16 .. 128 or more than 32768 cells; q_ppm outside 0 .. 1000000;
+ * min_points < 0; a null or misaligned pointer (points, workspace: 16 bytes; level, count, model, gains: 4; out: 16); a workspace too
+ * small; decreasing tile_offsets.
+ * NOTE on the place of `hip_stream`: LAST, as for lm_line_hist_points below and for the same reason: the inventories of
+ * tests/test_stream_inventory_cpu.py, tests/test_bounds_inventory_cpu.py and tests/lds_state.py find entries by the stream in first
+ * place and hold each to a literal table inside an existing test file.  The cases those tables would name - guarded buffers around
+ * every operand and the workspace, a side stream beside a busy default stream, the refusal on a capturing stream - are in
+ * tests/test_gpu_balance.py.  For the same reason none of the kernels of these entries declares __shared__. */
+long lm_tile_intensity_cells_workspace_bytes(int B, int H, int W, int cell_px);
+int lm_tile_intensity_cells(const float* points_xyzi, const long* tile_offsets, const LmRasterParams* params, int B, int H, int W,
+                            int cell_px, int q_ppm, int min_points, void* workspace, long workspace_bytes, int* level, int* count,
+                            int* model, void* hip_stream);
+long lm_tile_intensity_apply_workspace_bytes(int B);
+int lm_tile_intensity_apply(const float* points_xyzi, const long* tile_offsets, const LmRasterParams* params, int B, int H, int W,
+                            int cell_px, const float* gains, void* workspace, long workspace_bytes, float* out, void* hip_stream);
 
 /* ---- vertex heights from the points (csrc/drape.hip): a pixel-scale ground model around the polyline vertices of every tile.
  * (points, tile_offsets, params, H, W) as for lm_tile_ground, 0 <= B <= 4096, H and W at most 32768.  vertices_rc: HOST [V][2] int32

@@ -121,6 +121,10 @@ SIGNATURES = {
     'lm_tile_intensity_workspace_bytes': (i64, [i32, i32]),
     'lm_tile_intensity_window': (i32, [vp, vp, C.POINTER(i64), C.POINTER(LmRasterParams), i32, i32, i32, C.POINTER(i32), i32, i32, i32, vp, i64,
                                        vp, vp, vp]),
+    'lm_tile_intensity_cells_workspace_bytes': (i64, [i32, i32, i32, i32]),
+    'lm_tile_intensity_cells': (i32, [vp, C.POINTER(i64), C.POINTER(LmRasterParams), i32, i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, vp]),
+    'lm_tile_intensity_apply_workspace_bytes': (i64, [i32]),
+    'lm_tile_intensity_apply': (i32, [vp, C.POINTER(i64), C.POINTER(LmRasterParams), i32, i32, i32, i32, vp, vp, i64, vp, vp]),
     'lm_drape_workspace_bytes': (i64, [i64, i32, i32]),
     'lm_drape_vertices': (i32, [vp, vp, C.POINTER(i64), C.POINTER(LmRasterParams), i32, i32, i32, vp, C.POINTER(i64), i32, vp, i64, vp, vp, vp]),
     'lm_tile_gap_hist': (i32, [vp, vp, i32, i32, i32, i32, vp]),

@@ -100,6 +100,32 @@ def intensity_window(lo_key, hi_key, count, stretch):
     return lo, hi, stretch.white / (hi - lo)
 
 
+def balance_gains(model, reference, stretch, count=None):
+    """The gain field of the intensity balance (the rule: include/lanemap_hip.h) from ops.tile_intensity_cells' model [B, Gy, Gx] (-1: no
+    known cell near) and a reference level per tile, reference [B] - the lower median key of the tile ('tile') or of the call ('strip'),
+    ops.tile_intensity_window(percentiles=(50, 50)).  -> float32 [B, Gy, Gx]: for a known model and reference[b] > 0
+    clip(float32(reference[b]) / float32(max(model, 1)), 1 / max_gain, max_gain) in float32 operations, else 1.  count [B], when given,
+    holds the counted points behind every reference: a tile whose count is below stretch.min_points keeps gain 1 everywhere, as its window
+    keeps the fallback."""
+    if not isinstance(stretch, IntensityStretch):
+        raise TypeError(f'balance_gains: stretch must be a las_io.IntensityStretch, not {type(stretch).__name__}')
+    model = np.asarray(model)
+    if model.ndim != 3 or model.dtype.kind not in 'iu':
+        raise ValueError(f'balance_gains: model must be a [B, Gy, Gx] integer array, not {model.dtype} {list(model.shape)}')
+    ref = np.asarray(reference, dtype=np.int64).reshape(-1)
+    if len(ref) != model.shape[0]:
+        raise ValueError(f'balance_gains: {len(ref)} reference levels for {model.shape[0]} tiles')
+    if count is not None:
+        cnt = np.asarray(count, dtype=np.int64).reshape(-1)
+        if len(cnt) != len(ref):
+            raise ValueError(f'balance_gains: {len(cnt)} counts for {len(ref)} tiles')
+        ref = np.where(cnt < stretch.min_points, 0, ref)
+    top = np.float32(stretch.max_gain)
+    ratio = ref.astype(np.float32)[:, None, None] / np.maximum(model, 1).astype(np.float32)
+    gains = np.clip(ratio, np.float32(1.0) / top, top).astype(np.float32)
+    return np.where((model >= 0) & (ref[:, None, None] > 0), gains, np.float32(1.0)).astype(np.float32)
+
+
 def gap_radius(hist_row, fill):
     """The fill radius of one tile from its row of ops.tile_gap_hist (Rmax + 2 counters for Rmax = fill.max_radius_px): a fixed
     fill.radius_px as it is; 'auto': with near = sum(hist_row[0 : Rmax + 1]) - the far pixels, the black area beside the swath, left out -

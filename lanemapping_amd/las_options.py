@@ -192,7 +192,7 @@ class GroundFilter(_Options):
         self._set(height_range=height_range, cell_px=int(cell_px), datum=bool(datum), datum_margin=margin)
 
 
-class IntensityStretch(_Options):
+class IntensityStretch(_later_slots('balance', 'cell_px', 'cell_min_points', 'max_gain')):
     """How the LAS -> map routes choose the rasteriser's intensity window (immutable; Runner.infer_las_strip_to_map / infer_las_to_map,
     `intensity=`).  The window is read off the data: two percentiles of the intensities of the points a tile keeps
     (ops.tile_intensity_window), stretched so that the upper one lands on `white` (intensity_window below).
@@ -205,10 +205,31 @@ class IntensityStretch(_Options):
       min_span      the window is at least this many intensity steps wide (> 0): a featureless tile is not amplified into noise
       min_points    a tile or strip with fewer counted points keeps the `fallback` window and the reference's rule
       fallback      (inten_lo, inten_hi) of that case: the constants of the reference's read_las
-    min_span and min_points are plain defaults, not tuned values."""
+      balance       True: before the window is fitted, the binned points are balanced in place (ops.tile_intensity_cells,
+                    balance_gains, ops.tile_intensity_apply; the rule: include/lanemap_hip.h).  A scanner's intensity falls with range, so
+                    under any single window the outer lanes rasterise as dark paint on black and the near lane as asphalt brighter than
+                    that paint.  Per cell of cell_px x cell_px pixels the median intensity is the local asphalt level (paint is the
+                    minority of a road cell); the lower median of that over the 3 x 3 known cells keeps a cell that is mostly paint from
+                    dimming itself; every point is multiplied by the gain that takes its place's level to one reference level - the
+                    median of the tile ('tile') or of the call ('strip') - interpolated between the cell centres.  False (the default):
+                    nothing changes, bit for bit and call for call
+      cell_px       16 .. 128 pixels per cell (default 32: 1.6 m at 0.05 m per pixel)
+      cell_min_points  a cell is known with at least this many counted points (whole number >= 1); unknown cells keep gain 1
+      max_gain      finite, >= 1: gains are clipped into [1 / max_gain, max_gain]
+    min_span, min_points, cell_px, cell_min_points and max_gain are plain defaults, not tuned values."""
     __slots__ = ('percentiles', 'scope', 'white', 'min_span', 'min_points', 'fallback')
+    _later = {'balance': False, 'cell_px': 32, 'cell_min_points': 64, 'max_gain': 4.0}
 
-    def __init__(self, percentiles=(1.0, 99.9), scope='tile', white=249, min_span=16, min_points=1024, fallback=(800.0, 33000.0)):
+    def __init__(self, percentiles=(1.0, 99.9), scope='tile', white=249, min_span=16, min_points=1024, fallback=(800.0, 33000.0),
+                 balance=False, cell_px=32, cell_min_points=64, max_gain=4.0):
+        if not isinstance(balance, (bool, np.bool_)):
+            raise ValueError(f'IntensityStretch: balance={balance!r} must be True or False')
+        if not _whole(cell_px) or not 16 <= int(cell_px) <= 128:
+            raise ValueError(f'IntensityStretch: cell_px={cell_px!r} must be a whole number of pixels in 16..128')
+        if not _whole(cell_min_points) or int(cell_min_points) < 1:
+            raise ValueError(f'IntensityStretch: cell_min_points={cell_min_points!r} must be a whole number >= 1')
+        if not _number(max_gain) or not (1.0 <= float(max_gain) < math.inf):
+            raise ValueError(f'IntensityStretch: max_gain={max_gain!r} must be a finite number >= 1')
         try:
             lo, hi = (float(v) for v in percentiles)
         except (TypeError, ValueError):
@@ -230,7 +251,8 @@ class IntensityStretch(_Options):
         if not (f_lo < f_hi < math.inf and f_hi > 0.0 and f_lo > -math.inf):
             raise ValueError(f'IntensityStretch: fallback={fallback!r} must be a finite window lo < hi with hi > 0')
         self._set(percentiles=(lo, hi), scope=scope, white=float(white), min_span=float(min_span), min_points=int(min_points),
-                  fallback=(f_lo, f_hi))
+                  fallback=(f_lo, f_hi), balance=bool(balance), cell_px=int(cell_px), cell_min_points=int(cell_min_points),
+                  max_gain=float(max_gain))
 
 
 class ElevationDrape(_Options):

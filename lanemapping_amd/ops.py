@@ -1367,6 +1367,63 @@ def tile_intensity_window(points, tile_offsets, params, H=1152, W=1152, percenti
     return (window, count, hist) if want_hist else (window, count)
 
 
+CELLS_WORKSPACE_CAP = 256 << 20     # bytes: tile_intensity_cells takes its tiles in groups whose counters (1 KiB per cell) stay below it
+
+
+def _cell_grid(H, W, cell_px):
+    return (-(-H // cell_px), -(-W // cell_px)) if cell_px > 0 else (0, 0)
+
+
+def tile_intensity_cells(points, tile_offsets, params, H=1152, W=1152, cell_px=32, q_ppm=500000, min_points=64):
+    """The local intensity level under every tile (csrc/intensity.hip), from the (points, tile_offsets, params) triple bev_raster_batch
+    takes: -> (level, count, model), each [B,Gy,Gx] int32 on the device, Gy = ceil(H / cell_px), Gx = ceil(W / cell_px).  A point counts
+    for a tile when the rasteriser keeps it for the tile and its intensity is not NaN; its key is floor(clamp(intensity, 0, 65535)), its
+    cell (row // cell_px, col // cell_px).  count = the counted points n of the cell; level = the key of 0-based rank
+    (n - 1) * q_ppm // 10**6 among them (500000: the lower median; -1 for n = 0); model = the lower median of the levels of the KNOWN cells
+    (n >= min_points) of the 3 x 3 neighbourhood, -1 where none is known.  Exact and reproducible.  The counters take 1 KiB per cell:
+    the tiles are processed in groups whose workspace stays below CELLS_WORKSPACE_CAP (a group is at least one tile).  No
+    synchronisation, but the tile table is copied from host memory of the call: not inside a graph capture (the entry refuses a capturing
+    stream by name)."""
+    B, offs, par = _tile_range_args('tile_intensity_cells', points, tile_offsets, params)
+    H, W, cell_px = int(H), int(W), int(cell_px)
+    Gy, Gx = _cell_grid(H, W, cell_px)
+    level, count, model = (torch.empty((B, Gy, Gx), device=points.device, dtype=torch.int32) for _ in range(3))
+    one = lib().lm_tile_intensity_cells_workspace_bytes(1, H, W, cell_px)
+    step = max(1, min(B, CELLS_WORKSPACE_CAP // one)) if one else max(B, 1)
+    for b0 in range(0, B, step):
+        n = min(step, B - b0)
+        need = lib().lm_tile_intensity_cells_workspace_bytes(n, H, W, cell_px)
+        ws = _workspace(points, max(need, 16))
+        sub = (C.c_long * (n + 1)).from_buffer(offs, 8 * b0)
+        # (need == 0: unsupported arguments; the call below refuses them with the argument's name)
+        check(lib().lm_tile_intensity_cells(_ptr(points) if points.numel() else None, sub, (LmRasterParams * n).from_buffer(par, b0 * C.sizeof(LmRasterParams)),
+                                            n, H, W, cell_px, int(q_ppm), int(min_points), _ptr(ws), ws.numel() if need else 0,
+                                            _ptr(level[b0:b0 + n]), _ptr(count[b0:b0 + n]), _ptr(model[b0:b0 + n]), _stream()))
+    return level, count, model
+
+
+def tile_intensity_apply(points, tile_offsets, params, gains, H=1152, W=1152, cell_px=32, out=None):
+    """Every counted point's intensity times the gain of its place (csrc/intensity.hip): gains [B,Gy,Gx] f32 on the device, one per cell
+    of tile_intensity_cells' grid, interpolated bilinearly between the cell centres (clamped at the tile's edge) with every float32
+    operation rounded on its own; i' = min(i * g, 65535).  x, y, z and the points that do not count keep every bit.  out: None - IN PLACE,
+    -> points; or a [N,4] f32 tensor of points' shape, which gets the rows tile_offsets[0] .. tile_offsets[B] and is returned.  One
+    streaming pass.  Not inside a graph capture (the entry refuses a capturing stream by name)."""
+    B, offs, par = _tile_range_args('tile_intensity_apply', points, tile_offsets, params)
+    H, W, cell_px = int(H), int(W), int(cell_px)
+    Gy, Gx = _cell_grid(H, W, cell_px)
+    if not torch.is_tensor(gains) or tuple(gains.shape) != (B, Gy, Gx) or gains.dtype != torch.float32 or not gains.is_contiguous() or \
+            gains.device != points.device:
+        raise ValueError(f'tile_intensity_apply: gains must be a contiguous [{B},{Gy},{Gx}] float32 tensor on {points.device}')
+    out = points if out is None else out
+    if out.shape != points.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != points.device:
+        raise ValueError(f'tile_intensity_apply: out must be a contiguous {list(points.shape)} float32 tensor on {points.device}')
+    need = lib().lm_tile_intensity_apply_workspace_bytes(B)
+    ws = _workspace(points, max(need, 16))
+    check(lib().lm_tile_intensity_apply(_ptr(points) if points.numel() else None, offs, par, B, H, W, cell_px, _ptr(gains), _ptr(ws),
+                                        ws.numel() if need else 0, _ptr(out) if out.numel() else None, _stream()))
+    return out
+
+
 def drape_vertices(points, tile_offsets, params, vertices, vertex_offsets, H=1152, W=1152, radius_px=4, want_pixel_min=False):
     """Heights of polyline vertices read off the points (csrc/drape.hip), from the (points, tile_offsets, params) triple bev_raster_batch
     takes: vertices [V,2] int32 host array of (row, col) pixels, tile 0's first; vertex_offsets: B+1 ints, vertex_offsets[0] = 0.

@@ -574,7 +574,47 @@ class Runner:
         lo, hi, n = (int(v) for v in torch.cat([window.to(torch.int64), count[:, None]], dim=1).cpu().numpy()[0])   # the one read-back
         return (*las_io.intensity_window(lo, hi, n, st), n)
 
-    def _stretch_intensity(self, st, names, points, offs, rpar, H, W, out_dir, used, strip=None):
+    def _balance_intensity(self, st, names, points, offs, rpar, H, W, out_dir, bal, reference=None):
+        """One batch of tiles through the balance of a las_io.IntensityStretch(balance=True): the intensities of `points` in the batch's
+        ranges are balanced IN PLACE (the rule: include/lanemap_hip.h).  reference: None (scope='tile': every tile's own lower median key
+        and count, ops.tile_intensity_window with percentiles (50, 50), one device-to-host read) or the (key, count) of the whole call
+        (scope='strip').  Then ops.tile_intensity_cells, one device-to-host read of model and count, las_io.balance_gains on the host and
+        ops.tile_intensity_apply.  In place, because what reads the binned points afterwards is the window fit and the rasteriser, which
+        are meant to see the balanced values, and `elevation`, which reads heights only.  `bal` collects over the call what is written
+        to <out_dir>/params/balance.json as {tile name: [reference, known cells, cells, smallest gain, largest gain]} and to
+        balance_gains.npy as [tiles, Gy, Gx] float32, in the order of the tiles."""
+        from . import las_io
+        bal = {} if bal is None else bal
+        if reference is None:
+            window, count = ops.tile_intensity_window(points, offs, rpar, H, W, percentiles=(50.0, 50.0))
+            both = torch.cat([window[:, :1].to(torch.int64), count[:, None]], dim=1).cpu().numpy()
+            ref, cnt = both[:, 0], both[:, 1]
+        else:
+            ref, cnt = np.full(len(rpar), int(reference[0]), np.int64), np.full(len(rpar), int(reference[1]), np.int64)
+        _, count, model = ops.tile_intensity_cells(points, offs, rpar, H, W, cell_px=st.cell_px, q_ppm=500000, min_points=st.cell_min_points)
+        host = torch.stack([model, count]).cpu().numpy()                    # the one read-back
+        gains = las_io.balance_gains(host[0], ref, st, count=cnt)
+        ops.tile_intensity_apply(points, offs, rpar, torch.from_numpy(gains).to(points.device), H, W, cell_px=st.cell_px)
+        for j, name in enumerate(names):
+            bal.setdefault('rows', {})[name] = [int(ref[j]), int((host[1][j] >= st.cell_min_points).sum()), int(host[1][j].size),
+                                                float(gains[j].min()), float(gains[j].max())]
+            bal.setdefault('gains', {})[name] = gains[j]
+        par_dir = self._params_dir(out_dir)
+        with open(os.path.join(par_dir, 'balance.json'), 'w') as f:
+            json.dump(bal['rows'], f, indent=1)
+        np.save(os.path.join(par_dir, 'balance_gains.npy'), np.stack(list(bal['gains'].values())).astype(np.float32))
+
+    def _balance_strip(self, st, names, binned, offs, rpar, B, H, W, out_dir):
+        """scope='strip' with balance: every binned range of the call is balanced towards ONE reference, the lower median key of all of
+        them (one group, one device-to-host read), in batches of B tiles, before the strip's window is fitted on the balanced values."""
+        window, count = ops.tile_intensity_window(binned, offs, rpar, H, W, percentiles=(50.0, 50.0), group=[0] * len(rpar))
+        reference = [int(v) for v in torch.cat([window[:, :1].to(torch.int64), count[:, None]], dim=1).cpu().numpy()[0]]
+        bal = {}
+        for i in range(0, len(rpar), B):
+            j = min(i + B, len(rpar))
+            self._balance_intensity(st, names[i:j], binned, offs[i:j + 1], rpar[i:j], H, W, out_dir, bal, reference)
+
+    def _stretch_intensity(self, st, names, points, offs, rpar, H, W, out_dir, used, strip=None, bal=None):
         """One batch of tiles through a las_io.IntensityStretch: -> (rpar, inten_scale) to rasterise with.  scope='tile': the two
         percentiles of every tile come from the point ranges the rasteriser will see (ops.tile_intensity_window; one device-to-host read
         of window and count per batch); scope='strip': `strip` is the window found once for the whole call.  Every tile's inten_lo /
@@ -583,6 +623,8 @@ class Runner:
         from . import las_io
         from ._lib import LmRasterParams
         if strip is None:
+            if st.balance:                                                  # (scope='strip': balanced before the strip's window was fitted)
+                self._balance_intensity(st, names, points, offs, rpar, H, W, out_dir, bal)
             window, count = ops.tile_intensity_window(points, offs, rpar, H, W, percentiles=st.percentiles)
             both = torch.cat([window.to(torch.int64), count[:, None]], dim=1).cpu().numpy()      # the one read-back
             wins = [(*las_io.intensity_window(r[0], r[1], r[2], st), int(r[2])) for r in both]
@@ -598,12 +640,12 @@ class Runner:
             json.dump(used, f, indent=1)
         return rpar, scales
 
-    def _raster_stretched(self, raster_batch, st, names, plist, points, offs, rpar, H, W, out_dir, used, strip=None):
+    def _raster_stretched(self, raster_batch, st, names, plist, points, offs, rpar, H, W, out_dir, used, strip=None, bal=None):
         """One batch into the chain of _las_chain: as it is without an IntensityStretch (no new code runs), else with every tile's fitted
         window in its LmRasterParams and its scale beside them (the one call site of both LAS routes)."""
         if st is None:
             return raster_batch(names, plist, points, offs, rpar)
-        rpar, scales = self._stretch_intensity(st, names, points, offs, rpar, H, W, out_dir, used, strip)
+        rpar, scales = self._stretch_intensity(st, names, points, offs, rpar, H, W, out_dir, used, strip, bal)
         return raster_batch(names, plist, points, offs, rpar, scales)
 
     def infer_las_to_map(self, las_and_params, work_dirs=None, path_ckpt=None, batch_size=None, merge=True, select=None, ground=None,
@@ -629,7 +671,11 @@ class Runner:
         after `select` and `ground`, every tile's intensity window is fitted to two percentiles of the intensities it keeps
         (ops.tile_intensity_window) and stretched (lm_bev_raster_batch_scaled); what was used is written to
         <work_dirs>/params/intensity.json as {tile name: [inten_lo, inten_hi, scale or null, count]}.  scope='strip' is refused here: the
-        tiles arrive file by file.
+        tiles arrive file by file.  With intensity.balance the batch's points are first balanced in place per ground cell
+        (ops.tile_intensity_cells, las_io.balance_gains, ops.tile_intensity_apply: two more device-to-host reads per batch) and the window
+        is fitted on the balanced values; what was used is written to <work_dirs>/params/balance.json as {tile name: [reference, known
+        cells, cells, smallest gain, largest gain]} and to balance_gains.npy ([tiles, Gy, Gx] float32).  `elevation` reads heights only
+        and is not affected.
         elevation: a las_io.ElevationDrape (default: cfg['las_elevation'], a dict of its arguments; absent: nothing changes): after the
         network, the height of every lane vertex is read off the points the rasteriser saw (ops.drape_vertices, one call and one
         device-to-host read per batch: the lower median of the per-pixel minimum heights around the vertex pixel) instead of the tile's
@@ -690,7 +736,7 @@ class Runner:
         min_intensity='auto' of label, survey and residue and paint_intensity='auto' of cross is then replaced by the strip's threshold.
         A strip whose returns support no threshold is a ValueError that names the separation and the counts, raised after the JSON is
         written and before any stage runs - when a stage asked for 'auto'.  With no lines found both files are written empty.
-        Order of the stages: select, (binning,) ground, intensity, rasteriser, density, network, elevation, (merge,) threshold, label, survey,
+        Order of the stages: select, (binning,) ground, (balance,) intensity, rasteriser, density, network, elevation, (merge,) threshold, label, survey,
         cross, residue.
         Single rank (the merge is sequential over the sorted tiles)."""
         from . import las_io
@@ -701,7 +747,7 @@ class Runner:
         if intensity is not None and intensity.scope == 'strip':
             raise ValueError("intensity: scope='strip' needs the whole strip in one cloud (infer_las_strip_to_map); infer_las_to_map reads "
                              "its tiles file by file, use scope='tile'")
-        used = {}
+        used, bal = {}, {}
         if path_ckpt:
             self.load_ckpt(path_ckpt)
         B = int(batch_size or self.cfg.get('batch_size', 8))
@@ -724,7 +770,7 @@ class Runner:
             pts = torch.cat(pts)
             if ground is not None:
                 plist, pts, offs, rpar = self._follow_ground(ground, names, plist, pts, offs, rpar, H, W, out_dir)
-            self._raster_stretched(raster_batch, intensity, names, plist, pts, offs, rpar, H, W, out_dir, used)
+            self._raster_stretched(raster_batch, intensity, names, plist, pts, offs, rpar, H, W, out_dir, used, bal=bal)
         result = close()
         self._after_map(opt['threshold'], stages, opt['colour'], inputs, result, out_dir)
         return result
@@ -887,6 +933,8 @@ class Runner:
         intensity: as for infer_las_to_map, after `ground`.  scope='tile': per batch, on the ranges the rasteriser will see (after the
         height selection of `ground`).  scope='strip': one window for every tile, found once over all binned ranges before the batch
         loop - BEFORE `ground`'s height selection, which runs per batch: points it later drops still count for the strip's window.
+        With intensity.balance and scope='strip' all binned ranges are balanced, in batches of tiles, towards the median of the whole
+        call before that window is fitted (so before `ground` as well); with scope='tile' per batch, after `ground`.
         elevation: as for infer_las_to_map, after the network, on the ranges the rasteriser saw (after `ground` and `intensity`).
         density: as for infer_las_to_map, per batch between the rasteriser and the network.
         label: as for infer_las_to_map, after the merge: every file of `las_paths` is labelled with the layout's las_read_offset and `select`.
@@ -914,7 +962,7 @@ class Runner:
                                              stream=stream), las_paths)
         select, ground, intensity, elevation, density, stream = (opt[k] for k in ('select', 'ground', 'intensity', 'elevation', 'density',
                                                                                   'stream'))
-        used = {}
+        used, bal = {}, {}
         B = int(batch_size or self.cfg.get('batch_size', 8))
         if stream is not None and stream.binned_budget is not None and intensity is not None and intensity.scope == 'strip' and len(plist) > B:
             raise ValueError(f"intensity: scope='strip' fits one window to every binned range of the strip at once; with stream.binned_budget="
@@ -933,11 +981,11 @@ class Runner:
                 batch = (plist[i:j], binned, offs[i - t0:j - t0 + 1], rpar[i:j])
                 if ground is not None:
                     batch = self._follow_ground(ground, names[i:j], *batch, H, W, out_dir)
-                self._raster_stretched(raster_batch, intensity, names[i:j], *batch, H, W, out_dir, used, strip)
+                self._raster_stretched(raster_batch, intensity, names[i:j], *batch, H, W, out_dir, used, strip, bal)
 
         if plist and stream is not None:
             rpar = [io_utils.raster_params_from_dict(p) for p in plist]
-            self._stream_strip(stream, las_paths, plist, rpar, select, intensity, B, H, W, out_dir, batches)
+            self._stream_strip(stream, las_paths, names, plist, rpar, select, intensity, B, H, W, out_dir, batches)
         elif plist:
             shift = plist[0]['las_read_offset']
             clouds, headers = [], []
@@ -951,6 +999,8 @@ class Runner:
             del cloud, clouds
             strip = None
             if intensity is not None and intensity.scope == 'strip':
+                if intensity.balance:
+                    self._balance_strip(intensity, names, binned, offs, rpar, B, H, W, out_dir)
                 strip = self._strip_intensity(intensity, binned, offs, rpar, H, W)
             batches(binned, offs, 0, len(plist), strip)
         result = close()
@@ -959,7 +1009,7 @@ class Runner:
                             out_dir, None if stream is None else stream.chunk_records)
         return result
 
-    def _stream_strip(self, stream, las_paths, plist, rpar, select, intensity, B, H, W, out_dir, batches):
+    def _stream_strip(self, stream, las_paths, names, plist, rpar, select, intensity, B, H, W, out_dir, batches):
         """The chunked route of infer_las_strip_to_map up to the batch loop (`batches`, which it calls once per group of tiles): pass A
         counts every chunk of every file, pass B scatters them once per group.  No file and no cloud is held whole; the device holds
         one chunk's records, one scratch cloud and the binned points of one group."""
@@ -992,6 +1042,8 @@ class Runner:
             done.append({'tiles': [t0, t1], 'points': int(offs[-1]), 'binned_bytes': 16 * int(offs[-1])})
             strip = None
             if intensity is not None and intensity.scope == 'strip':         # (one group: refused otherwise before anything was read)
+                if intensity.balance:
+                    self._balance_strip(intensity, names[t0:t1], binned, offs, rpar[t0:t1], B, H, W, out_dir)
                 strip = self._strip_intensity(intensity, binned, offs, rpar[t0:t1], H, W)
             batches(binned, offs, t0, t1, strip)
             del binned
